@@ -9,7 +9,7 @@ on 1024 parallel 2.4 MS/s u8 IQ streams per GPU, synthetic i.i.d. uniform u8 (SU
 signal"), inputs resident in HBM before the timed region.  One step = one block of 2344*1024 = 2 400 256 complex
 samples (1.0001 s of signal) of every stream through the whole chain (state carried from step to step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--block T] [--no-cpu-baseline] [--verify | --no-verify] [--no-other-configs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--block T] [--no-cpu-baseline] [--verify | --no-verify] [--no-other-configs] [--dump-outputs DIR]
 
 The line checks itself: four rows of the batch carry a real FM signal (put there BEFORE the timed loop) and are held to +-1 LSB on every sample against the CPU
 oracle after it, and 16 rows of the noise batch spread over all stream blocks go through the statistical gate of tests/verify_configs.py ("verify", default;
@@ -26,7 +26,9 @@ Prints ONE JSON line on rank 0.
 Before the W warm-up steps the bench runs untimed steps for --spinup-ms (default 60 ms, reported as "spinup_steps_before_warmup"): after idle the GPU
 takes about 25 launches to reach its running clocks (the chain kernel's first launches measure 990-1175 us, then settle at ~905: profiles/r3_notes.md),
 and the metric is a stream's steady-state rate.  The K timed steps are untouched: every one runs the whole chain on the whole batch.  --spinup-ms 0
-gives the cold number (about 3 % lower at --steps 20 --warmup 5).
+gives the cold number (about 3 % lower at --steps 20 --warmup 5).  The chain is reset to a stream start after the spin-up, so that what the W + K steps compute
+does not depend on how many spin-up steps the clocks took; --dump-outputs DIR writes the audio of the last timed step (dump_outputs) for output-for-output comparison
+of two builds.
 """
 import argparse
 import ctypes as C
@@ -43,6 +45,21 @@ import bench_common as bc
 
 ALGO_BYTES_PER_SAMPLE = 2.0 + 2.0 / 50.0      # u8 IQ in + s16 audio out per complex input sample
 HBM_PEAK_GBS = bc.HBM_PEAK_GBS                 # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
+DUMP_BYTES_MAX = 64 << 20                      # --dump-outputs: all files together
+
+
+def dump_outputs(d, out_s16, n):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last step, the s16 audio rows [:n] of csdr_amd_wfm_process, as
+    DIR/audio_s16.npy (float32, exact) for a fixed seeded sample of the streams in ascending order (all streams when they fit DUMP_BYTES_MAX)."""
+    import numpy as np
+    import torch
+    S = out_s16.shape[0]
+    k = max(1, min(S, (DUMP_BYTES_MAX - 4096) // (4 * max(n, 1))))
+    rows = np.arange(S) if k == S else np.sort(np.random.default_rng(0).choice(S, k, replace=False))
+    a = out_s16[torch.from_numpy(rows).to(out_s16.device), :n].float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "audio_s16.npy"), a)
+    return {"dir": d, "files": {"audio_s16": list(a.shape)}, "streams": "all" if k == S else "%d of %d, seeded sample" % (k, S)}
 
 
 def cpu_baseline():
@@ -221,7 +238,11 @@ def main():
                          "buffers; four planted FM rows held to +-1 LSB and <= 1e-5 on every sample and 16 full audio rows of the noise batch spread over all stream "
                          "blocks under the statistical gate of tests/verify_configs.py, all against the CPU oracle on the same bytes")
     ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the short legs of the other BASELINE configs and the short-block operating points")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the s16 audio of the last one as DIR/audio_s16.npy (float32; a seeded sample of "
+                                                         "the streams, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -286,6 +307,8 @@ def main():
         step()
     ctx.sync(); cold_ms = (time.perf_counter() - tc0) / max(cold_k, 1) * 1e3
     spin_steps = bc.spinup(step, ctx.sync, args.spinup_ms)
+    if L.csdr_amd_wfm_reset(w):                  # a stream start: the W + K steps below compute the same whatever the number of spin-up steps
+        raise SystemExit("wfm_reset: " + ctx.err())
     for _ in range(args.warmup):
         step()
     ctx.sync(); torch.cuda.synchronize()
@@ -296,7 +319,8 @@ def main():
     ctx.timer_start()
     audio = 0
     for _ in range(args.steps):
-        audio += step()
+        n_last = step()
+        audio += n_last
     ev_ms = ctx.timer_stop_ms()                  # HIP events on the kernels' own stream (includes the sync)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
@@ -308,6 +332,7 @@ def main():
     kms = C.c_double(0); kl = C.c_long(0)
     L.csdr_amd_wfm_kernel_time(w, C.byref(kms), C.byref(kl))
     kernel_name = L.csdr_amd_wfm_kernel_name(w).decode()
+    dumped = dump_outputs(args.dump_outputs, out_s16, n_last) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         samples_per_step_gpu = S * T
@@ -336,6 +361,8 @@ def main():
                          "hip_event_ms_per_step_all_kernels": round(ev_ms / args.steps, 4)},
             "audio_samples_per_step_per_stream": audio // max(args.steps, 1),
         }
+        if dumped:
+            res["dump_outputs"] = dumped
         tr = pmc_traffic(kernel_name, S, T)
         if tr:
             res["roofline"]["traffic"] = tr[0]

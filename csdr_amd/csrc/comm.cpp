@@ -384,8 +384,21 @@ csdr_amd_comm *csdr_amd_comm_create_loopback(csdr_amd_ctx *ctx, csdr_amd_loopbac
     return c;
 }
 
-/* Ranks as processes on one box, any devices (in the tests: all on device 0).  path_prefix: a filesystem path all ranks see; rank r listens on "<prefix>.<r>" and
- * connects to every lower rank (60 s for the peers to appear).  Collective. */
+/* The socket of rank r: "<prefix>.<r>" in the file system.  A name that does not fit sun_path (108 bytes: a deep temporary directory, and every dup adds
+ * ".dup<k>") goes to the abstract namespace instead, under a hash of the whole name (FNV-1a 64), the same on every rank.  Returns the address length. */
+static socklen_t ipc_addr(const std::string &prefix, int r, sockaddr_un &a)
+{
+    memset(&a, 0, sizeof a); a.sun_family = AF_UNIX;
+    const std::string name = prefix + "." + std::to_string(r);
+    if (name.size() < sizeof a.sun_path) { memcpy(a.sun_path, name.c_str(), name.size() + 1); return (socklen_t)sizeof a; }
+    unsigned long long h = 1469598103934665603ull;
+    for (unsigned char ch : name) { h ^= ch; h *= 1099511628211ull; }
+    const int n = snprintf(a.sun_path + 1, sizeof a.sun_path - 1, "csdr_amd.comm.%016llx", h);      // leading NUL: no file system entry
+    return (socklen_t)(offsetof(sockaddr_un, sun_path) + 1 + n);
+}
+
+/* Ranks as processes on one box, any devices (in the tests: all on device 0).  path_prefix: a filesystem path all ranks see; rank r listens on "<prefix>.<r>" (ipc_addr)
+ * and connects to every lower rank (60 s for the peers to appear).  Collective. */
 csdr_amd_comm *csdr_amd_comm_create_ipc(csdr_amd_ctx *ctx, const char *path_prefix, int rank, int world)
 {
     if (!path_prefix || world < 1 || world > 64 || rank < 0 || rank >= world) { fail_msg(-3, "ipc comm: bad rank %d of %d", rank, world); return nullptr; }
@@ -394,19 +407,17 @@ csdr_amd_comm *csdr_amd_comm_create_ipc(csdr_amd_ctx *ctx, const char *path_pref
     c->ddc.rank = rank; c->ddc.world = world; c->ddc.impl = c;
     c->ddc.group_start = i_group_start; c->ddc.group_end = i_group_end; c->ddc.send = i_send; c->ddc.recv = i_recv; c->ddc.all_gather = i_all_gather;
     c->peer_fd.assign(world, -1);
-    auto addr_of = [&](int r, sockaddr_un &a) { memset(&a, 0, sizeof a); a.sun_family = AF_UNIX; snprintf(a.sun_path, sizeof a.sun_path, "%s.%d", path_prefix, r); };
     auto bail = [&](const char *what) { i_fail(what); csdr_amd_comm_destroy(c); return (csdr_amd_comm *)nullptr; };
-    sockaddr_un me_a; addr_of(rank, me_a);
-    if (strlen(path_prefix) + 8 >= sizeof me_a.sun_path) { fail_msg(-3, "ipc comm: path too long"); csdr_amd_comm_destroy(c); return nullptr; }
+    sockaddr_un me_a; const socklen_t me_len = ipc_addr(c->ipc_prefix, rank, me_a);
     c->listen_fd = socket(AF_UNIX, SOCK_STREAM, 0);
-    (void)unlink(me_a.sun_path);
-    if (c->listen_fd < 0 || bind(c->listen_fd, (sockaddr *)&me_a, sizeof me_a) || listen(c->listen_fd, world)) return bail("listen");
+    if (me_a.sun_path[0]) (void)unlink(me_a.sun_path);
+    if (c->listen_fd < 0 || bind(c->listen_fd, (sockaddr *)&me_a, me_len) || listen(c->listen_fd, world)) return bail("listen");
     for (int p = 0; p < rank; p++) {                                   // connect to the lower ranks ...
-        sockaddr_un a; addr_of(p, a);
+        sockaddr_un a; const socklen_t a_len = ipc_addr(c->ipc_prefix, p, a);
         int fd = -1;
         for (int tries = 0; tries < 6000; tries++) {
             fd = socket(AF_UNIX, SOCK_STREAM, 0);
-            if (fd >= 0 && connect(fd, (sockaddr *)&a, sizeof a) == 0) break;
+            if (fd >= 0 && connect(fd, (sockaddr *)&a, a_len) == 0) break;
             if (fd >= 0) close(fd);
             fd = -1; usleep(10000);
         }
@@ -444,7 +455,7 @@ void csdr_amd_comm_destroy(csdr_amd_comm *c)
     if (c->ipc) {
         for (auto &kv : c->ipc_open) (void)hipIpcCloseMemHandle(kv.second);
         for (int fd : c->peer_fd) if (fd >= 0) close(fd);
-        if (c->listen_fd >= 0) { close(c->listen_fd); char path[160]; snprintf(path, sizeof path, "%s.%d", c->ipc_prefix.c_str(), c->ddc.rank); (void)unlink(path); }
+        if (c->listen_fd >= 0) { close(c->listen_fd); sockaddr_un a; ipc_addr(c->ipc_prefix, c->ddc.rank, a); if (a.sun_path[0]) (void)unlink(a.sun_path); }
     }
     if (c->dup_parent && c->dup_index >= 0) {                         // the child group's place is free again for this rank
         std::lock_guard<std::mutex> lk(c->dup_parent->mu);

@@ -111,8 +111,6 @@ def test_reference_client_links_against_our_library(libpath, tmp_path):
                         os.path.join(ROOT, "tests", "data", "dropin_client.c"), "-L", os.path.dirname(libpath), "-l:libcsdr_amd.so",
                         "-Wl,-rpath," + os.path.dirname(libpath), "-o", exe, "-lm"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    import shutil
-    shutil.copy(exe, os.path.join(ROOT, "tests", "data", "dropin_client.bin"))      # travels to the GPU box for the -m gpu run
 
 
 def test_reference_fft_malloc_macro_needs_no_fftw(libpath, tmp_path):

@@ -187,67 +187,97 @@ def fm_iq(rng, n):
     return np.clip(np.round(127.5 * (iq + 1)), 0, 255).astype(np.uint8)
 
 
-def wfm_pipeline(cli, iq, block=None, env_extra=None, stderr_dir=None):
-    stages = [["convert_u8_f"], ["shift_addition_cc", "-0.085"], ["fir_decimate_cc", "10", "0.05", "HAMMING"], ["fmdemod_quadri_cf"],
+WFM_STAGES = [["convert_u8_f"], ["shift_addition_cc", "-0.085"], ["fir_decimate_cc", "10", "0.05", "HAMMING"], ["fmdemod_quadri_cf"],
               ["fractional_decimator_ff", "5"], ["deemphasis_wfm_ff", "48000", "50e-6"], ["convert_f_s16"]]
-    env = dict(os.environ)
-    if block:
-        env["CSDR_AMD_BLOCK"] = str(block)
-    env.update(env_extra or {})
+# At most this many of our csdr processes are alive at once (each one holds the GPU); with the test process itself that is 6.
+GPU_PROCS_MAX = 5
+
+
+def shell_pipeline(cli, stages, data, env, err_paths):
+    """`cli stages[0] | cli stages[1] | ...` with `data` on the first stdin; the last stdout is returned, stderr of stage i goes to err_paths[i] (None: dropped)."""
     procs = []
     prev = subprocess.PIPE
     for i, st in enumerate(stages):
-        err = open(os.path.join(stderr_dir, "err%d.txt" % i), "wb") if stderr_dir else subprocess.DEVNULL
+        err = open(err_paths[i], "wb") if err_paths[i] else subprocess.DEVNULL
         p = subprocess.Popen([cli] + st, stdin=prev if i else subprocess.PIPE, stdout=subprocess.PIPE, stderr=err, env=env)
         if i:
             procs[-1].stdout.close()
         prev = p.stdout
         procs.append(p)
     import threading
-    t = threading.Thread(target=lambda: (procs[0].stdin.write(iq.tobytes()), procs[0].stdin.close()))
+    t = threading.Thread(target=lambda: (procs[0].stdin.write(data), procs[0].stdin.close()))
     t.start()
     out = procs[-1].stdout.read()
     t.join()
     for p in procs:
         p.wait(timeout=60)
-    return np.frombuffer(out, np.int16)
+    return out
+
+
+def wfm_pipeline(cli, iq, block=None, env_extra=None, stderr_dir=None, split=4):
+    """README.md:66 as a shell pipeline.  Our CLI runs it as two pipelines one after the other, WFM_STAGES[:split] then WFM_STAGES[split:], joined by the bytes
+    the first one writes (so that no more than GPU_PROCS_MAX csdr processes hold the GPU at once); the reference CLI (CPU only) runs all seven stages at once.
+    stderr_dir: stage i's stderr in err<i>.txt."""
+    env = dict(os.environ)
+    if block:
+        env["CSDR_AMD_BLOCK"] = str(block)
+    env.update(env_extra or {})
+    cuts = [0, split, len(WFM_STAGES)] if cli == CLI else [0, len(WFM_STAGES)]
+    data = iq.tobytes()
+    for a, b in zip(cuts, cuts[1:]):
+        assert cli != CLI or b - a <= GPU_PROCS_MAX
+        errs = [os.path.join(stderr_dir, "err%d.txt" % i) if stderr_dir else None for i in range(a, b)]
+        data = shell_pipeline(cli, WFM_STAGES[a:b], data, env, errs)
+    return np.frombuffer(data, np.int16)
 
 
 def test_cli_device_handoff_between_processes(port, tmp_path):
-    """north_star: "the stdin->stdout pipe never round-trips to host between stages".  The unchanged seven-process shell pipeline of README.md:66: adjacent
-    csdr processes find each other through a socket named after the pipe between them and hand blocks over in HBM (HIP IPC ring + tokens; csdr_cli.cpp "device
-    hand-off"); the first process still reads bytes from a foreign producer, the last still writes bytes.  Same samples as with CSDR_AMD_IPC=0, bit for bit, and
-    as the oracle's chain; every inner link reports the hand-off (or, where HIP IPC is not available to the container, its refusal and the byte fallback)."""
+    """north_star: "the stdin->stdout pipe never round-trips to host between stages".  The seven stages of README.md:66 as csdr processes joined by pipes:
+    adjacent csdr processes find each other through a socket named after the pipe between them and hand blocks over in HBM (HIP IPC ring + tokens; csdr_cli.cpp
+    "device hand-off"); the first process of a pipeline still reads bytes from a foreign producer, the last still writes bytes.  The chain runs as two pipelines
+    (wfm_pipeline: at most GPU_PROCS_MAX GPU processes at once), split once after stage 4 and once after stage 3, so that every link of the chain lies inside a
+    pipeline in one of the runs.  Same samples as with CSDR_AMD_IPC=0, bit for bit, and as the oracle's chain; every inner link reports the hand-off (or, where
+    HIP IPC is not available to the container, its refusal and the byte fallback)."""
     iq = fm_iq(np.random.default_rng(19), 1200000)
     want_s16, _ = port.wfm_chain(iq, -0.085, 10, port.firdes_lowpass_f(port.firdes_filter_len(0.05), 0.05))
-    d1 = tmp_path / "on"; d1.mkdir()
-    on = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC_VERBOSE": "1", "CSDR_AMD_IPC_WAIT_MS": "3000"}, str(d1))     # (a loaded box may start a consumer late: look for its socket for 3 s)
     off = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC": "0"})
-    assert np.array_equal(on, off)
-    m = min(on.size, want_s16.size)
-    assert m >= want_s16.size - 2
-    d = np.abs(on[:m].astype(np.int32) - want_s16[:m].astype(np.int32))
-    assert d.max() <= 1 and np.mean(d != 0) < 0.01
-    errs = [open(d1 / ("err%d.txt" % i)).read() for i in range(7)]
-    handed = [("output leaves by device hand-off" in errs[i], "input arrives by device hand-off" in errs[i + 1]) for i in range(6)]
-    refused = ["refused" in e for e in errs]
-    assert all(a == b for a, b in handed), errs
-    assert all(a for a, _ in handed) or any(refused), errs         # every link hands over in HBM, or says why not
-    assert "hand-off" not in errs[0].split("output leaves")[0] and "output leaves" not in errs[6]      # the ends of the pipeline talk bytes
-    if not all(a for a, _ in handed):
-        pytest.xfail("HIP IPC refused on this box (the byte fallback gave the same samples): " + " | ".join(e.strip() for e in errs if "refused" in e))
+    all_handed = True
+    refusals = []
+    for split in (4, 3):
+        d1 = tmp_path / ("on%d" % split); d1.mkdir()
+        on = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC_VERBOSE": "1", "CSDR_AMD_IPC_WAIT_MS": "3000"}, str(d1), split)     # (a loaded box may start a consumer late: look for its socket for 3 s)
+        assert np.array_equal(on, off)
+        m = min(on.size, want_s16.size)
+        assert m >= want_s16.size - 2
+        d = np.abs(on[:m].astype(np.int32) - want_s16[:m].astype(np.int32))
+        assert d.max() <= 1 and np.mean(d != 0) < 0.01
+        errs = [open(d1 / ("err%d.txt" % i)).read() for i in range(7)]
+        handed = [("output leaves by device hand-off" in errs[i], "input arrives by device hand-off" in errs[i + 1]) for i in range(6)]
+        inner = [handed[i] for i in range(6) if i != split - 1]
+        refused = ["refused" in e for e in errs]
+        assert all(a == b for a, b in handed), errs
+        assert all(a for a, _ in inner) or any(refused), errs          # every link inside a pipeline hands over in HBM, or says why not
+        for first, last in ((0, split - 1), (split, 6)):                 # the ends of each pipeline talk bytes
+            assert "hand-off" not in errs[first].split("output leaves")[0] and "output leaves" not in errs[last], errs
+        all_handed = all_handed and all(a for a, _ in inner)
+        refusals += [e.strip() for e in errs if "refused" in e]
+    if not all_handed:
+        pytest.xfail("HIP IPC refused on this box (the byte fallback gave the same samples): " + " | ".join(refusals))
 
 
 def test_cli_device_handoff_refused_falls_back_to_bytes(tmp_path):
     """The other half of the negotiation: the producer connects, the consumer cannot take the handle (another device, HIP IPC not available to it: forced here with
-    CSDR_AMD_IPC_TEST_NAK) and answers NAK -- both sides go on with bytes through the pipe they already share; same samples as without any hand-off."""
+    CSDR_AMD_IPC_TEST_NAK) and answers NAK -- both sides go on with bytes through the pipe they already share; same samples as without any hand-off.  Split as in
+    test_cli_device_handoff_between_processes, so that every link of the chain is refused inside a pipeline in one of the two runs."""
     iq = fm_iq(np.random.default_rng(20), 300000)
-    d1 = tmp_path / "nak"; d1.mkdir()
-    nak = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC_VERBOSE": "1", "CSDR_AMD_IPC_WAIT_MS": "3000", "CSDR_AMD_IPC_TEST_NAK": "1"}, str(d1))
     off = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC": "0"})
-    assert nak.size > 5000 and np.array_equal(nak, off)
-    errs = [open(d1 / ("err%d.txt" % i)).read() for i in range(7)]
-    assert all("hand-off to the next process refused" in errs[i] and "hand-off from the previous process refused" in errs[i + 1] for i in range(6)), errs
+    for split in (4, 3):
+        d1 = tmp_path / ("nak%d" % split); d1.mkdir()
+        nak = wfm_pipeline(CLI, iq, 65536, {"CSDR_AMD_IPC_VERBOSE": "1", "CSDR_AMD_IPC_WAIT_MS": "3000", "CSDR_AMD_IPC_TEST_NAK": "1"}, str(d1), split)
+        assert nak.size > 5000 and np.array_equal(nak, off)
+        errs = [open(d1 / ("err%d.txt" % i)).read() for i in range(7)]
+        assert all("hand-off to the next process refused" in errs[i] and "hand-off from the previous process refused" in errs[i + 1]
+                   for i in range(6) if i != split - 1), errs
 
 
 def test_cli_device_handoff_consumer_dies_midstream():
@@ -915,6 +945,19 @@ def test_cli_fastddc_bank_as_separate_processes(tmp_path, world, shard):
     (CSDR_AMD_COMM=ipc: unix sockets + HIP IPC; RCCL refuses two ranks per device): per-rank bootstrap, the per-batch header broadcast with a retune in it, each rank opening
     only its clients' outputs, both schedules (channel shards with the spectrum exchange, time slices with the output exchange; "auto" = the library's choice for the
     world size).  Every channel's file must hold what the single-process command writes."""
+    bank_as_separate_processes(tmp_path, world, shard, str(tmp_path / "comm"))
+
+
+def test_cli_fastddc_bank_ipc_long_comm_path(tmp_path):
+    """The sockets of the inter-process transport are named after CSDR_AMD_COMM_FILE, and the time-sliced schedule's second communicator adds ".dup0" to that name:
+    a prefix longer than a unix socket path can hold (108 bytes; deep temporary directories get there) must still join the ranks (comm.cpp: ipc_addr)."""
+    d = tmp_path / ("d" * 60) / ("e" * 60); d.mkdir(parents=True)
+    comm = str(d / "comm")
+    assert len(comm) > 120
+    bank_as_separate_processes(tmp_path, 2, "blocks", comm)
+
+
+def bank_as_separate_processes(tmp_path, world, shard, comm):
     rng = np.random.default_rng(28)
     D, tbw, nch, nblk = 256, 0.001, 7, 6
     inp = 57344
@@ -934,7 +977,10 @@ def test_cli_fastddc_bank_as_separate_processes(tmp_path, world, shard):
             procs.append(subprocess.Popen([CLI] + [str(a) for a in args], stdin=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env))
         ctl = open(fifo, "w")
         ctl.write("3 0.25\n5 -0.125\n"); ctl.flush()                    # applied before the first batch, by every rank
-        procs[0].stdin.write(x.tobytes()); procs[0].stdin.close()
+        try:
+            procs[0].stdin.write(x.tobytes()); procs[0].stdin.close()
+        except BrokenPipeError:                                        # rank 0 ended early: its and the other ranks' stderr say why
+            pass
         errs = []
         for pr in procs:
             rc = pr.wait(timeout=180)
@@ -944,7 +990,6 @@ def test_cli_fastddc_bank_as_separate_processes(tmp_path, world, shard):
         return [np.fromfile(o, c64) for o in outs], errs
 
     want, _ = run_one("plain", [{}])
-    comm = str(tmp_path / "comm")
     envs = [{"CSDR_AMD_RANK": str(r), "CSDR_AMD_WORLD": str(world), "CSDR_AMD_COMM": "ipc", "CSDR_AMD_COMM_FILE": comm, **({} if shard == "auto" else {"CSDR_AMD_SHARD": shard})} for r in range(world)]
     got, errs = run_one("w%d_%s" % (world, shard), envs)
     expect = {"channels": "channel shards", "blocks": "time slices", "auto": "time slices" if world > 2 else "channel shards"}[shard]

@@ -436,13 +436,13 @@ def test_wfm_chain_full_size_properties(gpu, port):
 
 
 def test_dropin_client_binary(gpu):
-    """The client of tests/data/dropin_client.c (compiled against the reference's headers on the build host, linked against
-    libcsdr_amd.so) runs on the GPU and reproduces the reference's results."""
+    """The client of tests/data/dropin_client.c (compiled against the reference's headers into oracle/_ref/dropin_client by build() on the
+    build host, linked against libcsdr_amd.so) runs on the GPU and reproduces the reference's results."""
     import os, re, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "tests", "data", "dropin_client.bin")
+    exe = os.path.join(root, "oracle", "_ref", "dropin_client")
     if not os.path.exists(exe):
-        pytest.skip("dropin_client.bin not built (needs the reference headers on the build host)")
+        pytest.skip("oracle/_ref/dropin_client not built (needs the reference headers on the build host)")
     env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(root, "csdr_amd") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
     assert out.returncode == 0, out.stderr
