@@ -97,6 +97,16 @@ def lib():
     L.csdr_amd_encode_ima_adpcm_i16_u8.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_decode_ima_adpcm_u8_i16.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_compress_fft_adpcm_f_u8.argtypes = [vp, vp, vp, i, i]
+    L.csdr_amd_waterfall_create.restype = vp; L.csdr_amd_waterfall_create.argtypes = [vp, i, i, i, i, fl, i, i, i, sz]
+    L.csdr_amd_waterfall_process.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(i)]
+    L.csdr_amd_waterfall_reset.argtypes = [vp]
+    L.csdr_amd_waterfall_kernel_name.restype = C.c_char_p; L.csdr_amd_waterfall_kernel_name.argtypes = [vp]
+    L.csdr_amd_waterfall_force_generic.argtypes = [vp, i]
+    L.csdr_amd_waterfall_destroy.argtypes = [vp]; L.csdr_amd_waterfall_destroy.restype = None
+    L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
+    L.csdr_amd_fft_exchange_sides_ff.argtypes = [vp, vp, vp, i, i]
+    L.csdr_amd_accumulate_power_cf.argtypes = [vp, vp, vp, sz]
+    L.csdr_amd_log_ff.argtypes = [vp, vp, vp, sz, fl]
     L.csdr_amd_timer_start.argtypes = [vp]
     L.csdr_amd_timer_stop_ms.argtypes = [vp, C.POINTER(fl)]
     L.csdr_amd_firdes_filter_len.argtypes = [fl]
@@ -264,6 +274,72 @@ class DevBuf:
 
     def at(self, byte_offset):
         return C.c_void_p(self.ptr + int(byte_offset))
+
+
+class Waterfall:
+    """csdr_amd_waterfall: n_streams streams in lockstep -> rows of fft_size float dB values (out_format "db") or (fft_size+10)/2 ADPCM bytes ("adpcm")."""
+
+    def __init__(self, ctx, fft_size, every_n, avgnumber, add_db, window, in_format, out_format, n_streams, max_samples_per_call):
+        self.ctx, self.fft, self.every, self.avg, self.n_streams, self.max_in = ctx, fft_size, every_n, avgnumber, n_streams, int(max_samples_per_call)
+        self.in_format, self.out_format = in_format, out_format
+        self.h = ctx.L.csdr_amd_waterfall_create(ctx.h, fft_size, every_n, WINDOWS[window], avgnumber, add_db, 1 if in_format == "u8" else 0,
+                                                 1 if out_format == "adpcm" else 0, n_streams, self.max_in)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+        self.row_bytes = 4 * fft_size if out_format == "db" else (fft_size + 10) // 2
+
+    def max_rows(self, n_in):
+        return (n_in + self.fft) // self.every + 2
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch):
+        """device pointers: n_in new samples per stream (in_pitch samples apart) -> rows per stream written at d_out (out_pitch bytes apart)"""
+        rows = C.c_int(0)
+        self.ctx.check(self.ctx.L.csdr_amd_waterfall_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, C.byref(rows)), "waterfall_process")
+        return rows.value
+
+    def process(self, x, calls=None):
+        """x: [n_streams, ...] host samples (u8 IQ bytes or complex64); calls: list of per-call sample counts (default one call) -> [n_streams, rows, ...]"""
+        x = np.ascontiguousarray(x, np.uint8 if self.in_format == "u8" else c64)
+        if x.ndim == 1:
+            x = x[None]
+        n = x.shape[1] // 2 if self.in_format == "u8" else x.shape[1]
+        eb = 2 if self.in_format == "u8" else 8
+        calls = [n] if calls is None else list(calls)
+        di = self.ctx.upload(x)
+        opitch = (self.max_rows(max(calls)) * self.row_bytes + 255) // 256 * 256
+        do = self.ctx.alloc(opitch * self.n_streams + 256)
+        out = [[] for _ in range(self.n_streams)]
+        at = 0
+        for k in calls:
+            r = self.process_dev(di.at(eb * at), k, n, do.ptr, opitch)
+            if r:
+                y = self.ctx.download(do, np.uint8, opitch * self.n_streams).reshape(self.n_streams, opitch)[:, :r * self.row_bytes]
+                for s in range(self.n_streams):
+                    out[s].append(y[s].copy())
+            at += k
+        dt = f32 if self.out_format == "db" else np.uint8
+        per = self.fft if self.out_format == "db" else self.row_bytes
+        return np.stack([np.concatenate(o).view(dt).reshape(-1, per) if o else np.zeros((0, per), dt) for o in out])
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_waterfall_kernel_name(self.h).decode()
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_waterfall_force_generic(self.h, int(on)), "waterfall_force_generic")
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_waterfall_reset(self.h), "waterfall_reset")
+
+    def close(self):
+        if self.h:
+            self.ctx.L.csdr_amd_waterfall_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -502,6 +578,24 @@ class Context:
         self.L.csdr_amd_fftcc_destroy(f)
         return y
 
+
+    # ---- the waterfall (waterfall.hip)
+    def waterfall(self, fft_size, every_n, avgnumber, add_db=0.0, window="HAMMING", in_format="u8", out_format="db", n_streams=1, max_samples_per_call=1 << 20):
+        """A batched `[convert_u8_f |] fft_cc | logaveragepower_cf | fft_exchange_sides_ff [| compress_fft_adpcm_f_u8]` object (csdr_amd_waterfall)."""
+        return Waterfall(self, fft_size, every_n, avgnumber, add_db, window, in_format, out_format, n_streams, max_samples_per_call)
+
+    def logaveragepower_cf(self, x, fft_size, avgnumber, add_db=0.0):
+        """x: n_rows*avgnumber spectra of fft_size bins -> [n_rows, fft_size] dB rows (csdr.c:1663-1695)"""
+        x = np.ascontiguousarray(x, c64).ravel(); rows = x.size // (fft_size * avgnumber)
+        di = self.upload(x); do = self.alloc(4 * rows * fft_size + 64)
+        self.check(self.L.csdr_amd_logaveragepower_cf(self.h, di.ptr, do.ptr, rows, fft_size, avgnumber, add_db), "logaveragepower_cf")
+        return self.download(do, f32, rows * fft_size).reshape(rows, fft_size)
+
+    def fft_exchange_sides_ff(self, x, fft_size):
+        x = np.ascontiguousarray(x, f32).ravel(); rows = x.size // fft_size
+        di = self.upload(x); do = self.alloc(4 * rows * fft_size + 64)
+        self.check(self.L.csdr_amd_fft_exchange_sides_ff(self.h, di.ptr, do.ptr, rows, fft_size), "fft_exchange_sides_ff")
+        return self.download(do, f32, rows * fft_size).reshape(rows, fft_size)
 
     # ---- f3: IMA ADPCM
     def encode_ima_adpcm_i16_u8(self, x, state=None, calls=1):

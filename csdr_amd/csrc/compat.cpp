@@ -461,6 +461,18 @@ void logpower_cf(complexf *in, float *out, int n, float add_db)
     cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); float *dout = stage_out<float>(5, n);
     MUST(csdr_amd_logpower_cf(ctx(), (const csdr_complexf *)din, dout, n, add_db)); fetch(out, dout, n);
 }
+void accumulate_power_cf(complexf *in, float *out, int n)
+{
+    if (n <= 0) return;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); float *dacc = stage_in<float>(5, out, n);
+    MUST(csdr_amd_accumulate_power_cf(ctx(), (const csdr_complexf *)din, dacc, n)); fetch(out, dacc, n);
+}
+void log_ff(float *in, float *out, int n, float add_db)
+{
+    if (n <= 0) return;
+    float *din = stage_in<float>(4, in, n); float *dout = stage_out<float>(5, n);
+    MUST(csdr_amd_log_ff(ctx(), din, dout, n, add_db)); fetch(out, dout, n);
+}
 float fmdemod_atan_cf(complexf *in, float *out, int n, float last_phase)
 {
     if (n <= 0) return last_phase;

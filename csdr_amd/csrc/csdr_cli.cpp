@@ -553,6 +553,52 @@ struct CompressFft : Stage {
     }
 };
 
+// ------------------------------------------------------------------ the waterfall (csdr.c:1663-1714; waterfall.hip)
+struct LogAvgPower : Stage {   // csdr.c:1663-1695: avgnumber spectra in, one row out; reads no preamble and sends none
+    int fft, avg; float add_db;
+    LogAvgPower(int f, int a, float db) : fft(f), avg(a), add_db(db) { in_elem = 8; out_elem = 4; granule = (size_t)f * a; flush_partial = false; }
+    int next_bufsize(int) override { return -1; }
+    size_t out_capacity(size_t n) override { return (n / granule + 1) * (size_t)fft; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        const int nr = (int)(n / granule); *cons = (size_t)nr * granule;
+        if (nr) MUST(csdr_amd_logaveragepower_cf(c, (const csdr_complexf *)i, (float *)o, nr, fft, avg, add_db));
+        return (long)nr * fft;
+    }
+};
+struct ExchangeSides : Stage {   // csdr.c:1697-1714
+    int fft;
+    ExchangeSides(int f) : fft(f) { granule = f; flush_partial = false; }
+    int next_bufsize(int) override { return fft; }                   // csdr.c:1705
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        const int nr = (int)(n / fft); *cons = (size_t)nr * fft;
+        if (nr) MUST(csdr_amd_fft_exchange_sides_ff(c, (const float *)i, (float *)o, nr, fft));
+        return (long)nr * fft;
+    }
+};
+// `[convert_u8_f |] fft_cc N E [window] | logaveragepower_cf A N AVG | fft_exchange_sides_ff N [| compress_fft_adpcm_f_u8 N]` as ONE command (extension):
+//   csdr waterfall_u8 | waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>
+struct WaterfallStage : Stage {
+    csdr_amd_waterfall *w; int fft, every, avg; bool adpcm;
+    WaterfallStage(csdr_amd_ctx *c, bool u8, int f, int e, int window, float add_db, int a, bool ad, size_t block) : fft(f), every(e), avg(a), adpcm(ad)
+    {
+        in_elem = u8 ? 2 : 8; out_elem = ad ? 1 : 4;
+        w = csdr_amd_waterfall_create(c, f, e, window, a, add_db, u8 ? CSDR_AMD_WF_IN_U8 : CSDR_AMD_WF_IN_CF32, ad ? CSDR_AMD_WF_OUT_ADPCM : CSDR_AMD_WF_OUT_DB, 1, block + 64);
+        if (!w) die("waterfall_create");
+    }
+    size_t row_elems() const { return adpcm ? (size_t)(fft + 10) / 2 : (size_t)fft; }
+    size_t out_capacity(size_t n) override { return ((n + fft) / every / avg + 2) * row_elems(); }
+    int next_bufsize(int) override { return adpcm ? fft + 10 : fft; }  // what the last stage of the pattern sends (csdr.c:1752, 1705)
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;                                                    // overlap, skip and partial row stay in the object
+        int rows = 0;
+        MUST(csdr_amd_waterfall_process(w, i, n, n, o, 0, &rows));
+        return (long)((size_t)rows * row_elems());
+    }
+};
+
 // ------------------------------------------------------------------ wire protocol (csdr.c:325-419)
 int g_dynamic = 0, g_fixed = 1024, g_fixed_big = 16384, g_print = 0;
 void parse_env()
@@ -1034,7 +1080,7 @@ int run(csdr_amd_ctx *c, std::vector<Stage *> &stages, std::vector<size_t> &caps
         }
     }
     io.sink_bufs = hout;
-    send_bufsize(out_bufsize);                                       // csdr.c:375-391, through the pipe itself in either mode
+    if (out_bufsize >= 0) send_bufsize(out_bufsize);                 // csdr.c:375-391, through the pipe itself in either mode (< 0: the command sends none)
     for (int k = 0; k < NBUF; k++) {
         hin[k].cap = io.max_bytes + 64; hout[k].cap = cap_out * last->out_elem; hout[k].slot = k;
         if ((!io.src && hipHostMalloc((void **)&hin[k].p, hin[k].cap, hipHostMallocDefault) != hipSuccess) ||
@@ -1390,6 +1436,60 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, bool nfm)
     return 0;
 }
 
+// csdr waterfall_bank_u8 <fft> <every_n> <window> <add_db> <avg> <db|adpcm> <in_0> <out_0> [<in_1> <out_1> ...]: N u8 IQ streams through ONE waterfall object
+// (the batch API from the command line).  Lockstep like wfm_bank_u8_s16: every pass reads CSDR_AMD_BANK_BLOCK samples (default 262144) from every input; the
+// pass in which the first stream ends is the last one.  Each output gets the rows of its stream, byte-identical to `csdr waterfall_u8` on that input alone.
+int run_waterfall_bank(csdr_amd_ctx *c, int argc, char **argv)
+{
+    if (argc < 10 || (argc - 8) % 2) return badsyntax("usage: <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm> <in_0> <out_0> [<in_k> <out_k> ...]   (paths, fifos or fd:<n>)");
+    int fft = 0, every = 0, avg = 0; float add_db = 0;
+    sscanf(argv[2], "%d", &fft); sscanf(argv[3], "%d", &every); sscanf(argv[5], "%g", &add_db); sscanf(argv[6], "%d", &avg);
+    if (csdr_amd_log2n(fft) < 1 || every <= 0 || avg <= 0) return badsyntax("fft_size must be a power of two >= 2, every_n and avgnumber positive");
+    const bool adpcm = !strcmp(argv[7], "adpcm");
+    const int S = (argc - 8) / 2;
+    auto open_fd = [](const char *spec, int flags) { int fd = -1; if (!strncmp(spec, "fd:", 3)) sscanf(spec + 3, "%d", &fd); else fd = open(spec, flags, 0644); return fd; };
+    std::vector<int> in_fd(S), out_fd(S);
+    for (int k = 0; k < S; k++) {
+        in_fd[k] = open_fd(argv[8 + 2 * k], O_RDONLY); out_fd[k] = open_fd(argv[9 + 2 * k], O_WRONLY | O_CREAT | O_TRUNC);
+        if (in_fd[k] < 0 || out_fd[k] < 0) { fprintf(stderr, "csdr %s: cannot open %s / %s\n", g_cmd, argv[8 + 2 * k], argv[9 + 2 * k]); return -1; }
+    }
+    size_t T = 262144; if (const char *e = getenv("CSDR_AMD_BANK_BLOCK")) { long v = atol(e); if (v >= 1024) T = (size_t)v; }
+    csdr_amd_waterfall *w = csdr_amd_waterfall_create(c, fft, every, window_from(argv[4]), avg, add_db, CSDR_AMD_WF_IN_U8, adpcm ? CSDR_AMD_WF_OUT_ADPCM : CSDR_AMD_WF_OUT_DB, S, T);
+    if (!w) die("waterfall_create");
+    const size_t row_bytes = adpcm ? (size_t)(fft + 10) / 2 : 4 * (size_t)fft;
+    const size_t in_pitch = 2 * T, out_pitch = ((T + fft) / every / avg + 2) * row_bytes;
+    uint8_t *h_in = nullptr, *h_out = nullptr;
+    if (hipHostMalloc((void **)&h_in, (size_t)S * in_pitch, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&h_out, (size_t)S * out_pitch, hipHostMallocDefault) != hipSuccess) die("pinned buffers");
+    uint8_t *d_in = (uint8_t *)csdr_amd_malloc(c, (size_t)S * in_pitch + 256), *d_out = (uint8_t *)csdr_amd_malloc(c, (size_t)S * out_pitch + 256);
+    if (!d_in || !d_out) die("device buffers");
+    fprintf(stderr, "csdr %s: %d streams, %zu samples per stream and pass\n", g_cmd, S, T);
+    for (;;) {
+        size_t got_min = T;
+        for (int k = 0; k < S; k++) {
+            size_t have = 0;
+            while (have < in_pitch) { ssize_t r = read(in_fd[k], h_in + (size_t)k * in_pitch + have, in_pitch - have); if (r < 0 && errno == EINTR) continue; if (r <= 0) break; have += (size_t)r; }
+            if (have / 2 < got_min) got_min = have / 2;
+        }
+        if (got_min) {
+            MUST(csdr_amd_h2d(c, d_in, h_in, (size_t)S * in_pitch));
+            int rows = 0;
+            MUST(csdr_amd_waterfall_process(w, d_in, got_min, T, d_out, out_pitch, &rows));
+            if (rows > 0) {
+                MUST(csdr_amd_d2h(c, h_out, d_out, (size_t)S * out_pitch));
+                for (int k = 0; k < S; k++) {
+                    if (out_fd[k] < 0) continue;
+                    size_t done = 0; const size_t bytes = (size_t)rows * row_bytes; const char *src = (const char *)(h_out + (size_t)k * out_pitch);
+                    while (done < bytes) { ssize_t r = write(out_fd[k], src + done, bytes - done); if (r < 0) { if (errno == EINTR) continue; close(out_fd[k]); out_fd[k] = -1; break; } done += (size_t)r; }
+                }
+            }
+        }
+        if (got_min < T) break;                                      // the first stream has ended: the lockstep streams end here
+    }
+    for (int k = 0; k < S; k++) { if (out_fd[k] >= 0) close(out_fd[k]); close(in_fd[k]); }
+    csdr_amd_waterfall_destroy(w);
+    return 0;
+}
+
 // Build the operator for one command line.  `block` = the largest input this stage will be handed in one call.
 // ctl: opened when the command line carries --fifo/--fd (single-command mode only).  Returns nullptr after printing why.
 Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control *ctl, int the_bufsize)
@@ -1515,6 +1615,26 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         if (fft <= 0 || (fft & 1)) { badsyntax("fft_size must be positive and even"); return nullptr; }
         return new CompressFft(fft);
     }
+    if (cmd == "logaveragepower_cf") {
+        if (argc <= 4) { badsyntax("need required parameters (add_db, fft_size, avgnumber)"); return nullptr; }
+        float add_db = 0; int fft = 0, avg = 0;
+        sscanf(argv[2], "%g", &add_db); sscanf(argv[3], "%d", &fft); sscanf(argv[4], "%d", &avg);
+        if (csdr_amd_log2n(fft) < 1 || avg <= 0) { badsyntax("fft_size must be a power of two >= 2 and avgnumber positive"); return nullptr; }
+        return new LogAvgPower(fft, avg, add_db);
+    }
+    if (cmd == "fft_exchange_sides_ff") {
+        if (argc <= 2) { badsyntax("need required parameters (fft_size)"); return nullptr; }
+        int fft = 0; sscanf(argv[2], "%d", &fft);
+        if (csdr_amd_log2n(fft) < 1) { badsyntax("fft_size must be a power of two >= 2"); return nullptr; }
+        return new ExchangeSides(fft);
+    }
+    if (cmd == "waterfall_u8" || cmd == "waterfall_cc") {
+        if (argc <= 7) { badsyntax("need required parameters (fft_size, every_n, window, add_db, avgnumber, db|adpcm)"); return nullptr; }
+        int fft = 0, every = 0, avg = 0; float add_db = 0;
+        sscanf(argv[2], "%d", &fft); sscanf(argv[3], "%d", &every); sscanf(argv[5], "%g", &add_db); sscanf(argv[6], "%d", &avg);
+        if (csdr_amd_log2n(fft) < 1 || every <= 0 || avg <= 0) { badsyntax("fft_size must be a power of two >= 2, every_n and avgnumber positive"); return nullptr; }
+        return new WaterfallStage(c, cmd == "waterfall_u8", fft, every, window_from(argv[4]), add_db, avg, !strcmp(argv[7], "adpcm"), block);
+    }
     // the fused commands: `--fifo <path>` / `--fd <n>` stand where the shift rate stands, as in shift_addition_cc (csdr.c:881-893); the first rate is waited for
     if (cmd == "ddc_u8_cc" || cmd == "nfm_chain_u8_s16" || cmd == "wfm_chain_u8_s16") {
         float shift = 0;
@@ -1594,6 +1714,30 @@ bool is_nfm_pattern(const std::vector<std::vector<std::string>> &cmds, std::vect
     return shift_rate_args(cmds[1], rate_args);
 }
 
+// [convert_u8_f |] fft_cc N E [window] | logaveragepower_cf A N AVG | fft_exchange_sides_ff N [| compress_fft_adpcm_f_u8 N], one N throughout -> waterfall_u8 / waterfall_cc
+bool is_waterfall_pattern(const std::vector<std::vector<std::string>> &cmds, std::vector<std::string> *fused)
+{
+    size_t k = 0;
+    const bool u8 = !cmds.empty() && cmds[0].size() == 2 && cmds[0][1] == "convert_u8_f";
+    if (u8) k = 1;
+    if (cmds.size() < k + 3 || cmds.size() > k + 4) return false;
+    const auto &f = cmds[k], &l = cmds[k + 1], &x = cmds[k + 2];
+    if (f.size() < 4 || f.size() > 5 || f[1] != "fft_cc" || l.size() != 5 || l[1] != "logaveragepower_cf" || x.size() != 3 || x[1] != "fft_exchange_sides_ff") return false;
+    const std::string &N = f[2];
+    if (l[3] != N || x[2] != N) return false;
+    bool adpcm = false;
+    if (cmds.size() == k + 4) {
+        const auto &a = cmds[k + 3];
+        if (a.size() != 3 || a[1] != "compress_fft_adpcm_f_u8" || a[2] != N) return false;
+        adpcm = true;
+    }
+    int n = 0, e = 0, avg = 0; float db = 0;
+    if (sscanf(N.c_str(), "%d", &n) != 1 || csdr_amd_log2n(n) < 1 || sscanf(f[3].c_str(), "%d", &e) != 1 || e <= 0 ||
+        sscanf(l[2].c_str(), "%g", &db) != 1 || sscanf(l[4].c_str(), "%d", &avg) != 1 || avg <= 0) return false;
+    *fused = {"csdr", u8 ? "waterfall_u8" : "waterfall_cc", N, f[3], f.size() == 5 ? f[4] : "HAMMING", l[2], l[4], adpcm ? "adpcm" : "db"};
+    return true;
+}
+
 // convert_u8_f | shift_addition_cc r | fir_decimate_cc D [tbw [window]] at the head of a chain -> one ddc_u8_cc command
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
 {
@@ -1622,8 +1766,10 @@ int main(int argc, char **argv)
                         "convert_f_s24 convert_s24_f shift_math_cc shift_addition_cc shift_addition_fc shift_table_cc shift_addfast_cc shift_unroll_cc "
                         "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff deemphasis_wfm_ff "
                         "deemphasis_nfm_ff limit_ff fastagc_ff bandpass_fir_fft_cc fastddc_fwd_cc fastddc_inv_cc firdes_lowpass_f firdes_bandpass_c "
-                        "amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf fft_cc encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
-                        "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], chain \"<cmd> <args> | <cmd> <args> ...\"\n");
+                        "amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
+                        "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
+                        "waterfall_u8 / waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>, "
+                        "waterfall_bank_u8 <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm> <in_0> <out_0> [<in_k> <out_k> ...], chain \"<cmd> <args> | <cmd> <args> ...\"\n");
         return -1;
     }
     g_cmd = argv[1];
@@ -1663,13 +1809,14 @@ int main(int argc, char **argv)
     if (cmd == "fractional_decimator_ff" && argc > 2) { float r = 0; sscanf(argv[2], "%g", &r); if (r == 1) return passthrough(true, 0); }   // csdr.c:1494
     // device hand-off from the previous process of the shell pipeline (the streaming commands only): listen before anything slow -- the producer looks for this
     // socket when its first block is ready
-    if (cmd != "fastddc_bank_cc" && cmd != "wfm_bank_u8_s16" && cmd != "nfm_bank_u8_s16") ipc_listen_on_stdin();
+    if (cmd != "fastddc_bank_cc" && cmd != "wfm_bank_u8_s16" && cmd != "nfm_bank_u8_s16" && cmd != "waterfall_bank_u8") ipc_listen_on_stdin();
     const char *dev = getenv("CSDR_AMD_DEVICE");
     csdr_amd_ctx *c = csdr_amd_ctx_create(dev ? atoi(dev) : 0, nullptr);
     if (!c) { fprintf(stderr, "csdr %s: %s\n", g_cmd, csdr_amd_last_error()); return 3; }
     size_t block = block_elems();
     if (cmd == "fastddc_bank_cc") return run_bank(c, argc, argv, block);
     if (cmd == "wfm_bank_u8_s16" || cmd == "nfm_bank_u8_s16") return run_stream_bank(c, argc, argv, cmd[0] == 'n');
+    if (cmd == "waterfall_bank_u8") return run_waterfall_bank(c, argc, argv);
     std::vector<Stage *> stages; std::vector<size_t> caps;
     std::vector<std::vector<std::string>> cmds;
     if (cmd == "chain") {
@@ -1684,6 +1831,9 @@ int main(int argc, char **argv)
             fprintf(stderr, "csdr chain: NFM receive pattern recognised -> fused chain (matrix-core front end and de-emphasis)\n");
             std::vector<std::string> fused = {"csdr", "nfm_chain_u8_s16"}; fused.insert(fused.end(), rate_args.begin(), rate_args.end());
             cmds.assign(1, fused);
+        } else if (std::vector<std::string> wf; !g_dynamic && is_waterfall_pattern(cmds, &wf)) {   // (the unfused pipeline's preambles are not modelled)
+            fprintf(stderr, "csdr chain: waterfall pattern recognised -> %s (one-pass spectrum rows)\n", wf[1].c_str());
+            cmds.assign(1, wf);
         } else if (fuse_front_end(cmds)) {
             fprintf(stderr, "csdr chain: convert_u8_f | shift_addition_cc | fir_decimate_cc recognised -> fused matrix-core front end\n");
         }
@@ -1691,7 +1841,9 @@ int main(int argc, char **argv)
         cmds.assign(1, std::vector<std::string>(argv, argv + argc));
     }
     if (g_dynamic) ipc_source_decide(dev ? atoi(dev) : 0);           // (before the preamble is read: a producer of ours connects first, then writes it)
-    const int in_bufsize = get_bufsize(cmds[0].size() > 1 && (cmds[0][1] == "shift_addition_cc" || cmds[0][1] == "decimating_shift_addition_cc" || cmds[0][1] == "shift_addition_fc"));
+    // (logaveragepower_cf reads no preamble: csdr.c:1663-1695 never calls getbufsize())
+    const int in_bufsize = cmds[0].size() > 1 && cmds[0][1] == "logaveragepower_cf" ? unitround(g_dynamic ? 1024 : g_fixed)
+                         : get_bufsize(cmds[0].size() > 1 && (cmds[0][1] == "shift_addition_cc" || cmds[0][1] == "decimating_shift_addition_cc" || cmds[0][1] == "shift_addition_fc"));
     int out_bufsize = in_bufsize;
     // every command may have its control channel, also inside `chain` (fusion and retune together): the newest complete line is applied in front of a pass
     std::vector<Control> ctls(cmds.size());

@@ -194,6 +194,33 @@ csdr_amd_fftcc *csdr_amd_fftcc_create(csdr_amd_ctx *ctx, int fft_size, int every
 void csdr_amd_fftcc_destroy(csdr_amd_fftcc *f);
 int  csdr_amd_fftcc_process(csdr_amd_fftcc *f, const csdr_complexf *in, size_t n_in, csdr_complexf *out, size_t *consumed);
 
+/* ------------------------------------------------------------------ the waterfall: `[convert_u8_f |] fft_cc N E [window] | logaveragepower_cf A N AVG |
+ * fft_exchange_sides_ff N [| compress_fft_adpcm_f_u8 N]` (csdr.c:1569-1641, 1663-1714, 1745-1768) for n_streams streams per call.
+ * fft_size 1024 / 2048 / 4096 / 8192: one kernel per row that reads the input once (k_wf_onepass); any other power of two >= 2: framing + hipFFT + one
+ * post-FFT kernel.  The frame schedule is fft_cc's; the overlap history, the samples still to skip and the partial row are carried per stream between calls,
+ * and only complete rows are written: rows of fft_size float dB values (CSDR_AMD_WF_OUT_DB, halves exchanged) or of (fft_size+10)/2 ADPCM bytes
+ * (CSDR_AMD_WF_OUT_ADPCM, compress_fft_adpcm_f_u8 of the dB row).  add_db' = (float)(add_db - 10 log10(avgnumber)) as csdr.c:1678 forms it. */
+typedef struct csdr_amd_waterfall csdr_amd_waterfall;
+enum { CSDR_AMD_WF_IN_CF32 = 0, CSDR_AMD_WF_IN_U8 = 1 };
+enum { CSDR_AMD_WF_OUT_DB = 0, CSDR_AMD_WF_OUT_ADPCM = 1 };
+csdr_amd_waterfall *csdr_amd_waterfall_create(csdr_amd_ctx *ctx, int fft_size, int every_n_samples, int window, int avgnumber,
+                                              float add_db, int in_format, int out_format, int n_streams, size_t max_samples_per_call);
+/* n_in new samples for every stream (device, in_pitch samples apart); writes *rows_out rows per stream (out_pitch bytes apart).  Returns the rows or < 0. */
+int  csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_in, size_t in_pitch, void *out, size_t out_pitch, int *rows_out);
+int  csdr_amd_waterfall_reset(csdr_amd_waterfall *w);
+/* what the last call ran: "k_wf_onepass (u8)" / "k_wf_onepass (cf32)" or "k_wf_post (generic: framing + hipFFT)" */
+const char *csdr_amd_waterfall_kernel_name(const csdr_amd_waterfall *w);
+/* on != 0: the one-pass sizes take the generic path too (A/B comparisons) */
+int  csdr_amd_waterfall_force_generic(csdr_amd_waterfall *w, int on);
+void csdr_amd_waterfall_destroy(csdr_amd_waterfall *w);
+/* stand-alone stages (device, n_rows independent rows): logaveragepower_cf reads n_rows*avgnumber spectra, writes n_rows rows (csdr.c:1663-1695);
+ * fft_exchange_sides_ff swaps the halves of every row (csdr.c:1697-1714) */
+int  csdr_amd_logaveragepower_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, int n_rows, int fft_size, int avgnumber, float add_db);
+int  csdr_amd_fft_exchange_sides_ff(csdr_amd_ctx *ctx, const float *in, float *out, int n_rows, int fft_size);
+/* accumulate_power_cf / log_ff (libcsdr.c:1305-1314), device arrays: acc_io[i] += |in[i]|^2; out[i] = 10 log10(in[i]) + add_db */
+int  csdr_amd_accumulate_power_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *acc_io, size_t n);
+int  csdr_amd_log_ff(csdr_amd_ctx *ctx, const float *in, float *out, size_t n, float add_db);
+
 /* ------------------------------------------------------------------ f3: IMA ADPCM (ima_adpcm.c:110-174), bit exact.
  * A serial state machine per stream: one lane per stream.  state_io: device int32[2*n_streams] = {index, previousValue} (ima_adpcm_state_t).
  * encode: n int16 samples per stream -> n/2 bytes (low nibble first; an odd last sample is dropped like the reference does);
@@ -547,6 +574,11 @@ int  csdr_amd_debug_ddc_chain(int mode, float rate2, int post_in, int post_dec, 
 /* Test hook: one tile (16 outputs from 256 limited samples) of the NFM chain's matrix-core de-emphasis FIR on the CPU: digit planes,
  * Toeplitz digit table and accumulator classes as k_nfm_deemph_mfma combines them. */
 int csdr_amd_debug_nfm_deemph_tile(int audio_rate, float max_amp, const float *x, float *out16);
+/* Test hook: the one-pass waterfall kernel's stages (k_wf_onepass) on the CPU for the first row of a fresh stream (fft_size 1024 / 2048 / 4096 / 8192):
+ * in holds n_in samples (cf32 or u8 IQ pairs) from the stream's start.  db_row: the row as the object writes it (halves exchanged); power_row (may be null):
+ * the summed |X|^2 in the same order.  Returns 0, or -3 when the row's frames are not all within n_in. */
+int csdr_amd_debug_waterfall_row(int fft_size, int every_n_samples, int window, int avgnumber, float add_db, int in_format, const void *in, long long n_in,
+                                 float *db_row, float *power_row);
 #ifdef __cplusplus
 }
 #endif

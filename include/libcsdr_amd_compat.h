@@ -106,6 +106,8 @@ float *precalculate_window(int size, window_t window);
 void apply_window_c(complexf *input, complexf *output, int size, window_t window);
 void apply_precalculated_window_c(complexf *input, complexf *output, int size, float *windowt);
 void logpower_cf(complexf *input, float *output, int size, float add_db);
+void accumulate_power_cf(complexf *input, float *output, int size);
+void log_ff(float *input, float *output, int size, float add_db);
 float agc_ff(float *input, float *output, int input_size, float reference, float attack_rate, float decay_rate, float max_gain,
              short hang_time, short attack_wait_time, float gain_filter_alpha, float last_gain);
 
