@@ -312,8 +312,8 @@ struct csdr_amd_fracdec {
     float plan_where; int plan_n; bool plan_valid; int plan_outputs, plan_processed; float plan_where_after;
     int cli_bufsize, plan_bufsize;   // > 0: replay the CLI's loop over the_bufsize-sample windows (csdr.c:1511-1524) instead of one call over the whole array
     std::vector<int> lo; std::vector<float> frac;      // per output: first input sample of its window, fractional position (the coefficients are the kernel's)
-    int *d_lo; float *d_frac; float *d_denom; float *d_taps; size_t d_cap;
-    FdWin *d_win; size_t win_cap;                       // exact rates: the windows of the plan (the outputs' positions are evaluated on the device)
+    DevBuf<int> d_lo; DevBuf<float> d_frac, d_denom, d_taps; size_t d_cap;
+    DevBuf<FdWin> d_win; size_t win_cap;                      // exact rates: the windows of the plan (the outputs' positions are evaluated on the device)
 };
 
 extern "C" {
@@ -425,7 +425,7 @@ csdr_amd_fracdec *csdr_amd_fracdec_create(float rate, int num_poly_points, const
     d->where = (float)(-d->xifirst); d->rate = rate; d->input_processed = 0;
     d->taps_length = host_taps ? taps_length : 0;
     if (d->taps_length) d->taps.assign(host_taps, host_taps + taps_length);
-    d->plan_valid = false; d->d_lo = nullptr; d->d_frac = nullptr; d->d_denom = nullptr; d->d_taps = nullptr; d->d_cap = 0; d->cli_bufsize = 0; d->plan_bufsize = 0; d->d_win = nullptr; d->win_cap = 0;
+    d->plan_valid = false; d->d_cap = 0; d->cli_bufsize = 0; d->plan_bufsize = 0; d->win_cap = 0;
     return d;
 }
 
@@ -435,12 +435,6 @@ float csdr_amd_fracdec_get_where(const csdr_amd_fracdec *d) { return d->where; }
 
 void csdr_amd_fracdec_destroy(csdr_amd_fracdec *d)
 {
-    if (!d) return;
-    if (d->d_lo) (void)hipFree(d->d_lo);
-    if (d->d_frac) (void)hipFree(d->d_frac);
-    if (d->d_denom) (void)hipFree(d->d_denom);
-    if (d->d_taps) (void)hipFree(d->d_taps);
-    if (d->d_win) (void)hipFree(d->d_win);
     delete d;
 }
 
@@ -508,44 +502,43 @@ int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const
         const size_t need = (size_t)d->plan_outputs + 1;
         if (need > d->d_cap) {
             CSDR_HIP(hipStreamSynchronize(c->stream));
-            if (d->d_lo) (void)hipFree(d->d_lo);
-            if (d->d_frac) (void)hipFree(d->d_frac);
+            d->d_lo.reset(); d->d_frac.reset();
             d->d_cap = need + need / 2;
-            CSDR_HIP(hipMalloc((void **)&d->d_lo, sizeof(int) * d->d_cap));
-            CSDR_HIP(hipMalloc((void **)&d->d_frac, sizeof(float) * d->d_cap));
+            CSDR_HIP(dev_alloc(d->d_lo, sizeof(int) * d->d_cap));
+            CSDR_HIP(dev_alloc(d->d_frac, sizeof(float) * d->d_cap));
         }
         if (!d->d_denom) {
-            CSDR_HIP(hipMalloc((void **)&d->d_denom, sizeof(float) * d->denom.size()));
-            CSDR_HIP(hipMemcpy(d->d_denom, d->denom.data(), sizeof(float) * d->denom.size(), hipMemcpyHostToDevice));
+            CSDR_HIP(dev_alloc(d->d_denom, sizeof(float) * d->denom.size()));
+            CSDR_HIP(hipMemcpy(d->d_denom.get(), d->denom.data(), sizeof(float) * d->denom.size(), hipMemcpyHostToDevice));
         }
         if (d->taps_length && !d->d_taps) {
-            CSDR_HIP(hipMalloc((void **)&d->d_taps, sizeof(float) * d->taps_length));
-            CSDR_HIP(hipMemcpy(d->d_taps, d->taps.data(), sizeof(float) * d->taps_length, hipMemcpyHostToDevice));
+            CSDR_HIP(dev_alloc(d->d_taps, sizeof(float) * d->taps_length));
+            CSDR_HIP(hipMemcpy(d->d_taps.get(), d->taps.data(), sizeof(float) * d->taps_length, hipMemcpyHostToDevice));
         }
         if (d->plan_outputs && exact) {
             // stream ordered: the window table through the context's pinned staging (an earlier launch that still reads the old plan is in front of it on the stream)
             if (wins.size() > d->win_cap) {
                 CSDR_HIP(hipStreamSynchronize(c->stream));
-                if (d->d_win) (void)hipFree(d->d_win);
+                d->d_win.reset();
                 d->win_cap = wins.size() + wins.size() / 2 + 16;
-                CSDR_HIP(hipMalloc((void **)&d->d_win, sizeof(FdWin) * d->win_cap));
+                CSDR_HIP(dev_alloc(d->d_win, sizeof(FdWin) * d->win_cap));
             }
             FdWin *hw = (FdWin *)c->pinned_acquire(sizeof(FdWin) * wins.size());
             if (!hw) return -2;
             memcpy(hw, wins.data(), sizeof(FdWin) * wins.size());
-            const int urc = c->pinned_upload(d->d_win, sizeof(FdWin) * wins.size()); if (urc) return urc;
-            hipLaunchKernelGGL(k_fracdec_plan, dim3(cdiv(d->plan_outputs, 256)), dim3(256), 0, c->stream, d->d_win, (int)wins.size(), d->plan_outputs, d->rate, d->d_lo, d->d_frac);
+            const int urc = c->pinned_upload(d->d_win.get(), sizeof(FdWin) * wins.size()); if (urc) return urc;
+            hipLaunchKernelGGL(k_fracdec_plan, dim3(cdiv(d->plan_outputs, 256)), dim3(256), 0, c->stream, d->d_win.get(), (int)wins.size(), d->plan_outputs, d->rate, d->d_lo.get(), d->d_frac.get());
             CSDR_LAUNCH_CHECK();
         } else if (d->plan_outputs) {
             CSDR_HIP(hipStreamSynchronize(c->stream));     // previous launch may still read the old plan
-            CSDR_HIP(hipMemcpy(d->d_lo, d->lo.data(), sizeof(int) * d->lo.size(), hipMemcpyHostToDevice));
-            CSDR_HIP(hipMemcpy(d->d_frac, d->frac.data(), sizeof(float) * d->frac.size(), hipMemcpyHostToDevice));
+            CSDR_HIP(hipMemcpy(d->d_lo.get(), d->lo.data(), sizeof(int) * d->lo.size(), hipMemcpyHostToDevice));
+            CSDR_HIP(hipMemcpy(d->d_frac.get(), d->frac.data(), sizeof(float) * d->frac.size(), hipMemcpyHostToDevice));
         }
         d->plan_valid = true;
     }
     if (d->plan_outputs && n_streams > 0) {
         hipLaunchKernelGGL(k_fracdec, dim3(cdiv(d->plan_outputs, 256), n_streams), dim3(256), 0, c->stream, in, out, d->plan_outputs,
-                           in_pitch, out_pitch, d->d_lo, d->d_frac, P, d->xifirst, d->d_denom, d->d_taps, d->taps_length);
+                           in_pitch, out_pitch, d->d_lo.get(), d->d_frac.get(), P, d->xifirst, d->d_denom.get(), d->d_taps.get(), d->taps_length);
         CSDR_LAUNCH_CHECK();
     }
     d->input_processed = d->plan_processed;

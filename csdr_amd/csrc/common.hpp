@@ -1,9 +1,13 @@
 // common.hpp -- shared host-side plumbing for libcsdr_amd.so (MI355X / gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hipfft/hipfft.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/csdr_amd.h"
 
@@ -22,6 +26,66 @@ static const float PI_F = (float)3.14159265358979323846;
 
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// ---- owners of HIP resources.  A member frees its resource when its object goes; members go in reverse declaration order, so a resource
+// is declared in front of everything that uses it (a stream in front of its events, buffers and hipFFT plans).
+template <auto Release> struct Del { template <class P> void operator()(P p) const { (void)Release(p); } };
+template <class T = void> using DevBuf = std::unique_ptr<T, Del<hipFree>>;        // hipMalloc
+template <class T = void> using HostBuf = std::unique_ptr<T, Del<hipHostFree>>;   // hipHostMalloc (pinned)
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Del<hipEventDestroy>>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, Del<hipStreamDestroy>>;
+using FftPlan = std::unique_ptr<std::remove_pointer_t<hipfftHandle>, Del<hipfftDestroy>>;
+template <class T, auto Destroy> using Owned = std::unique_ptr<T, Del<Destroy>>;      // a library object, released by its destroy function
+
+// (re)allocate: an owner that holds a buffer frees it first
+template <class T> hipError_t dev_alloc(DevBuf<T> &p, size_t bytes)
+{
+    p.reset(); void *q = nullptr; const hipError_t e = hipMalloc(&q, bytes); p.reset(static_cast<T *>(q)); return e;
+}
+template <class T> hipError_t host_alloc(HostBuf<T> &p, size_t bytes, unsigned flags = hipHostMallocDefault)
+{
+    p.reset(); void *q = nullptr; const hipError_t e = hipHostMalloc(&q, bytes, flags); p.reset(static_cast<T *>(q)); return e;
+}
+static inline hipError_t event_create(Event &ev, unsigned flags = hipEventDefault)
+{
+    hipEvent_t e = nullptr; const hipError_t r = hipEventCreateWithFlags(&e, flags); ev.reset(e); return r;
+}
+static inline hipError_t stream_create(Stream &st, unsigned flags = hipStreamNonBlocking)
+{
+    hipStream_t s = nullptr; const hipError_t r = hipStreamCreateWithFlags(&s, flags); st.reset(s); return r;
+}
+
+// HIP-event timing of chosen kernels: a pool of (start, end) event pairs that grows on demand.  resolve() synchronises each end event recorded since the
+// last resolve(), adds the pairs' elapsed times to *ms and their count to *launches, and starts over.
+class KernelTimer {
+    std::vector<std::pair<Event, Event>> pool_;
+    size_t used_ = 0;
+public:
+    // the next pair, for the caller to record (e.g. as a launch's own start and completion signals)
+    int take(hipEvent_t *start, hipEvent_t *end)
+    {
+        if (used_ == pool_.size()) {
+            Event a, b; CSDR_HIP(event_create(a)); CSDR_HIP(event_create(b));
+            pool_.emplace_back(std::move(a), std::move(b));
+        }
+        *start = pool_[used_].first.get(); *end = pool_[used_].second.get(); used_++;
+        return 0;
+    }
+    // the next pair, its start recorded on st; end() records its end
+    int begin(hipStream_t st) { hipEvent_t a, b; const int rc = take(&a, &b); if (rc) return rc; CSDR_HIP(hipEventRecord(a, st)); return 0; }
+    int end(hipStream_t st) { CSDR_HIP(hipEventRecord(pool_[used_ - 1].second.get(), st)); return 0; }
+    int resolve(double *ms, long *launches)
+    {
+        for (size_t k = 0; k < used_; k++) {
+            CSDR_HIP(hipEventSynchronize(pool_[k].second.get()));
+            float t = 0; CSDR_HIP(hipEventElapsedTime(&t, pool_[k].first.get(), pool_[k].second.get()));
+            *ms += t; ++*launches;
+        }
+        used_ = 0;
+        return 0;
+    }
+    void reset() { used_ = 0; }
+};
+
 enum { SCRATCH_SLOTS = 8 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (current device, kernel): the attribute is per device, contexts may live on several
@@ -35,26 +99,28 @@ void drop_fft_plans(hipStream_t st);      // fftpath.hip
 int fastagc_ff_s16(struct ::csdr_amd_ctx *c, const float *in, float *out, int16_t *out_s16, int n_streams, int n_blocks, int block,
                    size_t in_pitch, size_t out_pitch, size_t s16_pitch, float reference, float *state_io, bool have_peaks = false);
 float *fastagc_peaks_buffer(struct ::csdr_amd_ctx *c, int n_streams, int n_blocks);      // [n_streams][n_blocks + 2]; entries 2.. = peak |x| of the call's new blocks
+struct ShiftAhead;                                                   // shift.hip
+struct ShiftAheadDel { void operator()(ShiftAhead *a) const; };
 
 } // namespace csdr_amd
 
 struct csdr_amd_ctx {
     int device;
     hipStream_t stream;
-    bool own_stream;
+    csdr_amd::Stream own_stream;      // set when the context created `stream`
     std::string arch;
-    void *scratch[csdr_amd::SCRATCH_SLOTS];
-    size_t scratch_bytes[csdr_amd::SCRATCH_SLOTS];
-    hipEvent_t ev0, ev1;
-    // returns a device buffer of at least `bytes` that stays valid until the next request on the same slot
-    void *get_scratch(int slot, size_t bytes);
     // pinned host staging for small host-computed tables (phase sequences, plans): acquire() waits until the
     // previous upload from the buffer has completed, upload() queues the async copy on the context's stream
-    void *pinned; size_t pinned_bytes; hipEvent_t pinned_ev; bool pinned_in_flight;
+    csdr_amd::HostBuf<> pinned; size_t pinned_bytes; csdr_amd::Event pinned_ev; bool pinned_in_flight;
     void *pinned_acquire(size_t bytes);
     int pinned_upload(void *dst_dev, size_t bytes);
+    csdr_amd::Event ev0, ev1;
+    csdr_amd::DevBuf<> scratch[csdr_amd::SCRATCH_SLOTS];
+    size_t scratch_bytes[csdr_amd::SCRATCH_SLOTS];
+    // returns a device buffer of at least `bytes` that stays valid until the next request on the same slot
+    void *get_scratch(int slot, size_t bytes);
     // shift_math_cc / shift_table_cc: the per-sample phase scan of the NEXT call, running on a helper thread while this call's kernels run (shift.hip: ShiftAhead)
-    void *shift_ahead; void (*shift_ahead_free)(void *);
+    std::unique_ptr<csdr_amd::ShiftAhead, csdr_amd::ShiftAheadDel> shift_ahead;
 };
 
 // ---- LDS-DMA row-step shared by the ring kernels (wfm_mfma.hip, ddc_mfma.hip).  Device code only.

@@ -50,32 +50,30 @@ using namespace csdr_amd;
 
 void *csdr_amd_ctx::get_scratch(int slot, size_t bytes)
 {
-    if (bytes <= scratch_bytes[slot] && scratch[slot]) return scratch[slot];
-    if (scratch[slot]) { (void)hipStreamSynchronize(stream); (void)hipFree(scratch[slot]); scratch[slot] = nullptr; scratch_bytes[slot] = 0; }
+    if (bytes <= scratch_bytes[slot] && scratch[slot]) return scratch[slot].get();
+    if (scratch[slot]) { (void)hipStreamSynchronize(stream); scratch[slot].reset(); scratch_bytes[slot] = 0; }
     size_t want = bytes + bytes / 4 + 4096;
-    void *p = nullptr;
-    if (hipMalloc(&p, want) != hipSuccess) { fail_msg(-2, "scratch allocation of %zu bytes failed", want); return nullptr; }
-    scratch[slot] = p; scratch_bytes[slot] = want;
-    return p;
+    if (dev_alloc(scratch[slot], want) != hipSuccess) { fail_msg(-2, "scratch allocation of %zu bytes failed", want); return nullptr; }
+    scratch_bytes[slot] = want;
+    return scratch[slot].get();
 }
 
 void *csdr_amd_ctx::pinned_acquire(size_t bytes)
 {
-    if (pinned_in_flight) { (void)hipEventSynchronize(pinned_ev); pinned_in_flight = false; }
+    if (pinned_in_flight) { (void)hipEventSynchronize(pinned_ev.get()); pinned_in_flight = false; }
     if (bytes > pinned_bytes) {
-        if (pinned) (void)hipHostFree(pinned);
-        pinned = nullptr; pinned_bytes = 0;
+        pinned_bytes = 0;
         const size_t want = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc(&pinned, want, hipHostMallocDefault) != hipSuccess) { fail_msg(-2, "pinned allocation of %zu bytes failed", want); return nullptr; }
+        if (host_alloc(pinned, want) != hipSuccess) { fail_msg(-2, "pinned allocation of %zu bytes failed", want); return nullptr; }
         pinned_bytes = want;
     }
-    return pinned;
+    return pinned.get();
 }
 
 int csdr_amd_ctx::pinned_upload(void *dst_dev, size_t bytes)
 {
-    CSDR_HIP(hipMemcpyAsync(dst_dev, pinned, bytes, hipMemcpyHostToDevice, stream));
-    CSDR_HIP(hipEventRecord(pinned_ev, stream));
+    CSDR_HIP(hipMemcpyAsync(dst_dev, pinned.get(), bytes, hipMemcpyHostToDevice, stream));
+    CSDR_HIP(hipEventRecord(pinned_ev.get(), stream));
     pinned_in_flight = true;
     return 0;
 }
@@ -101,18 +99,15 @@ csdr_amd_ctx *csdr_amd_ctx_create(int device, void *hip_stream)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { fail_msg(-1, "hipGetDeviceProperties failed"); return nullptr; }
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { fail_msg(-1, "device %d is %s; libcsdr_amd is built for gfx950 (MI355X) only", device, prop.gcnArchName); return nullptr; }
-    csdr_amd_ctx *c = new csdr_amd_ctx();
+    std::unique_ptr<csdr_amd_ctx> c(new csdr_amd_ctx());
     c->device = device; c->arch = prop.gcnArchName;
-    for (int i = 0; i < SCRATCH_SLOTS; i++) { c->scratch[i] = nullptr; c->scratch_bytes[i] = 0; }
-    if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
+    if (hip_stream) c->stream = (hipStream_t)hip_stream;
     else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { fail_msg(-1, "hipStreamCreate failed"); delete c; return nullptr; }
-        c->own_stream = true;
+        if (stream_create(c->own_stream) != hipSuccess) { fail_msg(-1, "hipStreamCreate failed"); return nullptr; }
+        c->stream = c->own_stream.get();
     }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreateWithFlags(&c->pinned_ev, hipEventDisableTiming) != hipSuccess) { fail_msg(-1, "hipEventCreate failed"); delete c; return nullptr; }
-    c->pinned = nullptr; c->pinned_bytes = 0; c->pinned_in_flight = false;
-    c->shift_ahead = nullptr; c->shift_ahead_free = nullptr;
-    return c;
+    if (event_create(c->ev0) != hipSuccess || event_create(c->ev1) != hipSuccess || event_create(c->pinned_ev, hipEventDisableTiming) != hipSuccess) { fail_msg(-1, "hipEventCreate failed"); return nullptr; }
+    return c.release();
 }
 
 void csdr_amd_ctx_destroy(csdr_amd_ctx *c)
@@ -121,11 +116,6 @@ void csdr_amd_ctx_destroy(csdr_amd_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     drop_fft_plans(c->stream);
-    if (c->shift_ahead && c->shift_ahead_free) c->shift_ahead_free(c->shift_ahead);
-    for (int i = 0; i < SCRATCH_SLOTS; i++) if (c->scratch[i]) (void)hipFree(c->scratch[i]);
-    (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1); (void)hipEventDestroy(c->pinned_ev);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -167,12 +157,12 @@ int csdr_amd_memset(csdr_amd_ctx *c, void *dst, int value, size_t bytes)
     CSDR_HIP(hipMemsetAsync(dst, value, bytes, c->stream));
     return 0;
 }
-int csdr_amd_timer_start(csdr_amd_ctx *c) { CSDR_HIP(hipEventRecord(c->ev0, c->stream)); return 0; }
+int csdr_amd_timer_start(csdr_amd_ctx *c) { CSDR_HIP(hipEventRecord(c->ev0.get(), c->stream)); return 0; }
 int csdr_amd_timer_stop_ms(csdr_amd_ctx *c, float *ms)
 {
-    CSDR_HIP(hipEventRecord(c->ev1, c->stream));
-    CSDR_HIP(hipEventSynchronize(c->ev1));
-    CSDR_HIP(hipEventElapsedTime(ms, c->ev0, c->ev1));
+    CSDR_HIP(hipEventRecord(c->ev1.get(), c->stream));
+    CSDR_HIP(hipEventSynchronize(c->ev1.get()));
+    CSDR_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
     return 0;
 }
 

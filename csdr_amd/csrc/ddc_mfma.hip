@@ -818,19 +818,20 @@ struct csdr_amd_ddc {
     int n_streams, D, L;
     float shift_rate;
     size_t max_block;
-    float *d_taps; uint8_t *d_hist[2]; int hflip;
-    void *d_frags; float *d_cum; float2 *d_dtab, *d_ctab, *d_corr; size_t ctab_cap; bool need_corr;
+    DevBuf<float> d_taps; DevBuf<uint8_t> d_hist[2]; int hflip;
+    DevBuf<> d_frags; DevBuf<float> d_cum; DevBuf<float2> d_dtab, d_ctab, d_corr; size_t ctab_cap; bool need_corr;
     float scale; int nk_used;
     bool use_mfma, ended, whole_off;
     float phase; float2 c_prev;
     long long tab_first; bool tab_valid;      // the device tables of chunk seeds (and drift corrections) cover chunks [tab_first, tab_first + ctab_cap)
     long long B, next_k;
     std::string kernel_name;
-    bool profiling; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool; size_t ev_used; double prof_ms; long prof_launches;
+    bool profiling; KernelTimer timer; double prof_ms; long prof_launches;
     // a shift rate per stream (csdr_amd_ddc_create_rates)
-    bool ps; std::vector<float> rates, h_taps; csdr_amd::SeedTables *seeds; float *d_scales;
-    float2 *d_dtab_old, *d_corr_old; int *d_list; std::vector<int> retuned;      // streams retuned since the last call: their first outputs straddle two rates (lead fix-up)
+    bool ps; std::vector<float> rates, h_taps; DevBuf<float> d_scales;
+    DevBuf<float2> d_dtab_old, d_corr_old; DevBuf<int> d_list; std::vector<int> retuned;      // streams retuned since the last call: their first outputs straddle two rates (lead fix-up)
     int fallback;                                                     // 1: the last call ran outside the matrix-core kernel (csdr_amd_ddc_fallback)
+    Owned<csdr_amd::SeedTables, seeds_destroy> seeds;                 // (reads d_dtab on its side stream)
 };
 
 // tables of ONE stream of a per-stream object: weights, prefix sums, scale, D^k
@@ -839,13 +840,13 @@ static int ddc_upload_stream_tables(csdr_amd_ddc *d, int s, float rate)
     if (d->use_mfma) {
         DdcTable t;
         ddc_build_table(d->D, d->L, rate, d->h_taps.data(), t);
-        CSDR_HIP(hipMemcpy((uint8_t *)d->d_frags + (size_t)s * t.frags.size(), t.frags.data(), t.frags.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(d->d_cum + (size_t)s * t.cum.size(), t.cum.data(), t.cum.size() * sizeof(float), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(d->d_dtab + (size_t)s * DDC_DTAB, t.dtab.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(d->d_scales + s, &t.scale, sizeof(float), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy((uint8_t *)d->d_frags.get() + (size_t)s * t.frags.size(), t.frags.data(), t.frags.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d->d_cum.get() + (size_t)s * t.cum.size(), t.cum.data(), t.cum.size() * sizeof(float), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d->d_dtab.get() + (size_t)s * DDC_DTAB, t.dtab.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d->d_scales.get() + s, &t.scale, sizeof(float), hipMemcpyHostToDevice));
     } else {
         std::vector<float2> dt; ddc_build_dtab(rate, dt);
-        CSDR_HIP(hipMemcpy(d->d_dtab + (size_t)s * DDC_DTAB, dt.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d->d_dtab.get() + (size_t)s * DDC_DTAB, dt.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -859,68 +860,64 @@ static csdr_amd_ddc *ddc_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
     if (taps_length - 1 > DDC_HIST) { fail_msg(-3, "ddc_create: %d taps exceed the %d-sample history", taps_length, DDC_HIST + 1); return nullptr; }
     if (max_block_samples < 1024) max_block_samples = 1024;
     const float shift_rate = rates[0];
-    csdr_amd_ddc *d = new csdr_amd_ddc();
+    Owned<csdr_amd_ddc, csdr_amd_ddc_destroy> d(new csdr_amd_ddc());
     d->ctx = ctx; d->n_streams = n_streams; d->D = decimation; d->L = taps_length; d->shift_rate = shift_rate; d->max_block = max_block_samples;
-    d->d_taps = nullptr; d->d_hist[0] = d->d_hist[1] = nullptr; d->d_frags = nullptr; d->d_cum = nullptr; d->d_dtab = nullptr; d->d_ctab = nullptr; d->d_corr = nullptr;
-    d->profiling = false; d->ev_used = 0; d->prof_ms = 0; d->prof_launches = 0;
-    d->ps = ps; d->seeds = nullptr; d->d_scales = nullptr; d->d_dtab_old = nullptr; d->d_corr_old = nullptr; d->d_list = nullptr; d->fallback = 0;
+    d->ps = ps;
     d->ctab_cap = 16 * (max_block_samples / 1024 + 8);                 // seeds for 16 calls of the largest block ahead (see ddc_process_fused)
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    auto alloc = [&](auto &p, size_t bytes) { if (e == hipSuccess) e = dev_alloc(p, bytes); };
     const size_t nt = ps ? (size_t)n_streams : 1;                      // table sets
-    alloc((void **)&d->d_taps, sizeof(float) * taps_length);
-    alloc((void **)&d->d_hist[0], (size_t)2 * DDC_HIST * n_streams);
-    alloc((void **)&d->d_hist[1], (size_t)2 * DDC_HIST * n_streams);
-    alloc((void **)&d->d_dtab, sizeof(float2) * DDC_DTAB * nt);
-    if (!ps) alloc((void **)&d->d_ctab, sizeof(float2) * d->ctab_cap);
+    alloc(d->d_taps, sizeof(float) * taps_length);
+    alloc(d->d_hist[0], (size_t)2 * DDC_HIST * n_streams);
+    alloc(d->d_hist[1], (size_t)2 * DDC_HIST * n_streams);
+    alloc(d->d_dtab, sizeof(float2) * DDC_DTAB * nt);
+    if (!ps) alloc(d->d_ctab, sizeof(float2) * d->ctab_cap);
     const char *ce = getenv("CSDR_AMD_DDC_CORR");                     // 0 = never, 1 = always, default = only for rates whose float recurrence drifts (model deviation > 2e-6 RMS)
     auto drifts = [&](float r) { return ce ? atoi(ce) != 0 : ddc_rotator_model_rms(r) > 2e-6; };
     d->need_corr = false;
     if (!ps) {
         d->need_corr = drifts(shift_rate);
-        if (d->need_corr) alloc((void **)&d->d_corr, sizeof(float2) * d->ctab_cap * 32);
+        if (d->need_corr) alloc(d->d_corr, sizeof(float2) * d->ctab_cap * 32);
     }
-    if (e == hipSuccess) e = hipMemcpy(d->d_taps, host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d->d_taps.get(), host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice);
     const char *force = getenv("CSDR_AMD_DDC_PATH");                  // "direct" forces the plain kernel (A/B comparisons)
     d->use_mfma = ddc_mfma_supported(decimation, taps_length) && !(force && !strcmp(force, "direct"));
     d->whole_off = getenv("CSDR_AMD_DDC_WHOLE") && atoi(getenv("CSDR_AMD_DDC_WHOLE")) == 0;      // A/B: interior tiles only, the edges on k_ddc_direct (round 2's split)
     d->scale = 0; d->nk_used = 0;
     if (ps) {
         d->rates.assign(rates, rates + n_streams); d->h_taps.assign(host_taps, host_taps + taps_length);
-        alloc((void **)&d->d_scales, sizeof(float) * n_streams);
+        alloc(d->d_scales, sizeof(float) * n_streams);
         if (d->use_mfma) {
             d->nk_used = (2 * (7 * decimation + taps_length) + 63) / 64;
-            alloc(&d->d_frags, (size_t)DDC_NKT * 3 * 64 * 16 * nt);
-            alloc((void **)&d->d_cum, (size_t)DDC_NGRAN * 16 * sizeof(float) * nt);
+            alloc(d->d_frags, (size_t)DDC_NKT * 3 * 64 * 16 * nt);
+            alloc(d->d_cum, (size_t)DDC_NGRAN * 16 * sizeof(float) * nt);
         }
-        for (int s = 0; s < n_streams && e == hipSuccess; s++) {
-            const int rc = ddc_upload_stream_tables(d, s, rates[s]);
-            if (rc) { csdr_amd_ddc_destroy(d); return nullptr; }
-        }
+        for (int s = 0; s < n_streams && e == hipSuccess; s++)
+            if (ddc_upload_stream_tables(d.get(), s, rates[s])) return nullptr;
         if (e == hipSuccess) {
-            d->seeds = seeds_create(ctx, n_streams, rates, d->d_dtab, DDC_DTAB, max_block_samples);
-            if (!d->seeds) { csdr_amd_ddc_destroy(d); return nullptr; }
+            d->seeds.reset(seeds_create(ctx, n_streams, rates, d->d_dtab.get(), DDC_DTAB, max_block_samples));
+            if (!d->seeds) return nullptr;
             std::vector<char> dr(n_streams);
             for (int s = 0; s < n_streams; s++) dr[s] = drifts(rates[s]) ? 1 : 0;
-            if (seeds_set_drift(d->seeds, dr)) { csdr_amd_ddc_destroy(d); return nullptr; }
+            if (seeds_set_drift(d->seeds.get(), dr)) return nullptr;
         }
     } else if (d->use_mfma) {
         DdcTable t;
         ddc_build_table(decimation, taps_length, shift_rate, host_taps, t);
         d->scale = t.scale; d->nk_used = (2 * (7 * decimation + taps_length) + 63) / 64;
-        alloc(&d->d_frags, t.frags.size());
-        alloc((void **)&d->d_cum, t.cum.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(d->d_frags, t.frags.data(), t.frags.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d->d_cum, t.cum.data(), t.cum.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d->d_dtab, t.dtab.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice);
+        alloc(d->d_frags, t.frags.size());
+        alloc(d->d_cum, t.cum.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(d->d_frags.get(), t.frags.data(), t.frags.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d->d_cum.get(), t.cum.data(), t.cum.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d->d_dtab.get(), t.dtab.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice);
     } else {
         std::vector<float2> dt; ddc_build_dtab(shift_rate, dt);
-        if (e == hipSuccess) e = hipMemcpy(d->d_dtab, dt.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d->d_dtab.get(), dt.data(), sizeof(float2) * DDC_DTAB, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) { fail(e, "hipMalloc/hipMemcpy(ddc state)", __FILE__, __LINE__); csdr_amd_ddc_destroy(d); return nullptr; }
+    if (e != hipSuccess) { fail(e, "hipMalloc/hipMemcpy(ddc state)", __FILE__, __LINE__); return nullptr; }
     d->kernel_name = d->use_mfma ? "k_ddc_mfma" : "k_ddc_direct";
-    if (csdr_amd_ddc_reset(d)) { csdr_amd_ddc_destroy(d); return nullptr; }
-    return d;
+    if (csdr_amd_ddc_reset(d.get())) return nullptr;
+    return d.release();
 }
 
 csdr_amd_ddc *csdr_amd_ddc_create(csdr_amd_ctx *ctx, int n_streams, float shift_rate, int decimation, const float *host_taps, int taps_length,
@@ -944,25 +941,25 @@ int csdr_amd_ddc_set_rate(csdr_amd_ddc *d, int stream, float shift_rate)
     if (stream < 0 || stream >= d->n_streams) return fail_msg(-3, "ddc_set_rate: stream %d out of range", stream);
     if (d->rates[stream] == shift_rate) return 0;
     CSDR_HIP(hipStreamSynchronize(d->ctx->stream));                   // calls in flight read this stream's tables
-    if (!d->d_dtab_old) CSDR_HIP(hipMalloc((void **)&d->d_dtab_old, sizeof(float2) * DDC_DTAB * (size_t)d->n_streams));
-    if (!d->d_corr_old) CSDR_HIP(hipMalloc((void **)&d->d_corr_old, sizeof(float2) * 32 * (size_t)d->n_streams));
+    if (!d->d_dtab_old) CSDR_HIP(dev_alloc(d->d_dtab_old, sizeof(float2) * DDC_DTAB * (size_t)d->n_streams));
+    if (!d->d_corr_old) CSDR_HIP(dev_alloc(d->d_corr_old, sizeof(float2) * 32 * (size_t)d->n_streams));
     bool listed = false;
     for (int v : d->retuned) listed |= v == stream;
     if (!listed) {                                                    // (two retunes between calls: the history was rotated at the first old rate)
-        CSDR_HIP(hipMemcpy(d->d_dtab_old + (size_t)stream * DDC_DTAB, d->d_dtab + (size_t)stream * DDC_DTAB, sizeof(float2) * DDC_DTAB, hipMemcpyDeviceToDevice));
+        CSDR_HIP(hipMemcpy(d->d_dtab_old.get() + (size_t)stream * DDC_DTAB, d->d_dtab.get() + (size_t)stream * DDC_DTAB, sizeof(float2) * DDC_DTAB, hipMemcpyDeviceToDevice));
         // ... and the old rate's drift corrections for the chunk in front of the next block
-        const float2 *co = seeds_corr_entry(d->seeds, stream, d->B / 1024 - 1);
-        if (co) CSDR_HIP(hipMemcpy(d->d_corr_old + (size_t)stream * 32, co, sizeof(float2) * 32, hipMemcpyDeviceToDevice));
+        const float2 *co = seeds_corr_entry(d->seeds.get(), stream, d->B / 1024 - 1);
+        if (co) CSDR_HIP(hipMemcpy(d->d_corr_old.get() + (size_t)stream * 32, co, sizeof(float2) * 32, hipMemcpyDeviceToDevice));
         else {
             float2 one[32]; for (int i = 0; i < 32; i++) one[i] = make_float2(1.f, 0.f);
-            CSDR_HIP(hipMemcpy(d->d_corr_old + (size_t)stream * 32, one, sizeof one, hipMemcpyHostToDevice));
+            CSDR_HIP(hipMemcpy(d->d_corr_old.get() + (size_t)stream * 32, one, sizeof one, hipMemcpyHostToDevice));
         }
         d->retuned.push_back(stream);
     }
     const int rc = ddc_upload_stream_tables(d, stream, shift_rate); if (rc) return rc;
     d->rates[stream] = shift_rate;
     const char *ce = getenv("CSDR_AMD_DDC_CORR");
-    return seeds_set_rate(d->seeds, stream, shift_rate, ce ? atoi(ce) != 0 : ddc_rotator_model_rms(shift_rate) > 2e-6);
+    return seeds_set_rate(d->seeds.get(), stream, shift_rate, ce ? atoi(ce) != 0 : ddc_rotator_model_rms(shift_rate) > 2e-6);
 }
 
 float csdr_amd_ddc_get_rate(const csdr_amd_ddc *d, int stream)
@@ -977,10 +974,6 @@ void csdr_amd_ddc_destroy(csdr_amd_ddc *d)
 {
     if (!d) return;
     (void)hipStreamSynchronize(d->ctx->stream);
-    if (d->seeds) seeds_destroy(d->seeds);
-    (void)hipFree(d->d_taps); (void)hipFree(d->d_hist[0]); (void)hipFree(d->d_hist[1]); (void)hipFree(d->d_frags); (void)hipFree(d->d_cum);
-    (void)hipFree(d->d_dtab); (void)hipFree(d->d_ctab); (void)hipFree(d->d_corr); (void)hipFree(d->d_scales); (void)hipFree(d->d_dtab_old); (void)hipFree(d->d_corr_old); (void)hipFree(d->d_list);
-    for (auto &pr : d->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     delete d;
 }
 
@@ -988,9 +981,9 @@ int csdr_amd_ddc_reset(csdr_amd_ddc *d)
 {
     d->phase = 0.f; d->c_prev = make_float2(1.f, 0.f); d->B = 0; d->next_k = 0; d->ended = false; d->hflip = 0; d->tab_valid = false; d->tab_first = 0;
     d->retuned.clear();
-    if (d->seeds) { const int rc = seeds_reset(d->seeds); if (rc) return rc; }
-    CSDR_HIP(hipMemsetAsync(d->d_hist[0], 0x80, (size_t)2 * DDC_HIST * d->n_streams, d->ctx->stream));
-    CSDR_HIP(hipMemsetAsync(d->d_hist[1], 0x80, (size_t)2 * DDC_HIST * d->n_streams, d->ctx->stream));
+    if (d->seeds) { const int rc = seeds_reset(d->seeds.get()); if (rc) return rc; }
+    CSDR_HIP(hipMemsetAsync(d->d_hist[0].get(), 0x80, (size_t)2 * DDC_HIST * d->n_streams, d->ctx->stream));
+    CSDR_HIP(hipMemsetAsync(d->d_hist[1].get(), 0x80, (size_t)2 * DDC_HIST * d->n_streams, d->ctx->stream));
     return 0;
 }
 
@@ -998,18 +991,14 @@ const char *csdr_amd_ddc_kernel_name(const csdr_amd_ddc *d) { return d->kernel_n
 
 int csdr_amd_ddc_set_profiling(csdr_amd_ddc *d, int on)
 {
-    d->profiling = on != 0; d->ev_used = 0; d->prof_ms = 0; d->prof_launches = 0;
+    d->profiling = on != 0; d->timer.reset(); d->prof_ms = 0; d->prof_launches = 0;
     return 0;
 }
 
 int csdr_amd_ddc_kernel_time(csdr_amd_ddc *d, double *total_ms, long *launches)
 {
     CSDR_HIP(hipStreamSynchronize(d->ctx->stream));
-    for (size_t i = 0; i < d->ev_used; i++) {
-        float ms = 0; CSDR_HIP(hipEventElapsedTime(&ms, d->ev_pool[i].first, d->ev_pool[i].second));
-        d->prof_ms += ms; d->prof_launches++;
-    }
-    d->ev_used = 0;
+    if (const int rc = d->timer.resolve(&d->prof_ms, &d->prof_launches)) return rc;
     if (total_ms) *total_ms = d->prof_ms;
     if (launches) *launches = d->prof_launches;
     return 0;
@@ -1046,7 +1035,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
     SeedView sv; memset(&sv, 0, sizeof sv);
     if (d->ps) {
         // a rate per stream: the same bookkeeping, one lane per stream on a side stream, a few calls ahead (seeds.hip)
-        rc = seeds_acquire(d->seeds, first, nch + 3, (T % 1024) ? 0 : nch, &sv); if (rc) return rc;
+        rc = seeds_acquire(d->seeds.get(), first, nch + 3, (T % 1024) ? 0 : nch, &sv); if (rc) return rc;
     } else
     if (!d->tab_valid || first < d->tab_first || first + (long long)nch + 3 > d->tab_first + (long long)d->ctab_cap) {
         float2 *hc = (float2 *)c->pinned_acquire(sizeof(float2) * d->ctab_cap);
@@ -1060,15 +1049,15 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             while (nx < -PI_F) nx += 2 * PI_F;
             ph = nx;
         }
-        rc = c->pinned_upload(d->d_ctab, sizeof(float2) * d->ctab_cap); if (rc) return rc;
+        rc = c->pinned_upload(d->d_ctab.get(), sizeof(float2) * d->ctab_cap); if (rc) return rc;
         if (d->need_corr) {
-            hipLaunchKernelGGL(k_ddc_corr, dim3(cdiv(d->ctab_cap, 64)), dim3(64), 0, st, d->d_ctab, d->d_dtab, d->d_corr, (int)d->ctab_cap, (float)cos((double)inc), (float)sin((double)inc));
+            hipLaunchKernelGGL(k_ddc_corr, dim3(cdiv(d->ctab_cap, 64)), dim3(64), 0, st, d->d_ctab.get(), d->d_dtab.get(), d->d_corr.get(), (int)d->ctab_cap, (float)cos((double)inc), (float)sin((double)inc));
             CSDR_LAUNCH_CHECK();
         }
         d->tab_first = first; d->tab_valid = true;
     }
-    const float2 *ctab = d->ps ? sv.ctab : d->d_ctab + (first - d->tab_first);
-    const float2 *corr = d->ps ? sv.corr : d->need_corr ? d->d_corr + (first - d->tab_first) * 32 : nullptr;
+    const float2 *ctab = d->ps ? sv.ctab : d->d_ctab.get() + (first - d->tab_first);
+    const float2 *corr = d->ps ? sv.corr : d->need_corr ? d->d_corr.get() + (first - d->tab_first) * 32 : nullptr;
     if (!d->ps) {   // the stream's phase behind this block (and the seed of its last chunk, for a table rebuilt at the next call)
         float ph = d->phase;
         for (size_t m = 0; m < nch; m++) {
@@ -1092,10 +1081,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
         if ((size_t)n_out > out_pitch && d->n_streams > 1) return fail_msg(-3, "ddc: out_pitch %zu smaller than the %ld outputs of this block", out_pitch, n_out);
         const long long k_first = d->next_k;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (d->profiling) {
-            if (d->ev_used == d->ev_pool.size()) { hipEvent_t a, b; CSDR_HIP(hipEventCreate(&a)); CSDR_HIP(hipEventCreate(&b)); d->ev_pool.emplace_back(a, b); }
-            e0 = d->ev_pool[d->ev_used].first; e1 = d->ev_pool[d->ev_used].second; d->ev_used++;
-        }
+        if (d->profiling) { if (const int trc = d->timer.take(&e0, &e1)) return trc; }
         // whole tiles (8 outputs) whose window lies inside this block, fetched as 1-KiB runs of whole lines
         long long ta = 0, tb = -1;
         const long long tstride = 16LL * d->D;
@@ -1121,8 +1107,8 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             DdcParams p;
             memset(&p, 0, sizeof p);
             p.n_streams = d->n_streams; p.B = d->B; p.tile_first = ta; p.n_tiles = (int)(tb - ta + 1); p.k_out0 = k_first; p.D = d->D; p.nk_used = d->nk_used; p.scale = d->scale;
-            p.two_T = 2LL * T; p.hist_out = (T >= DDC_HIST && (T & 7) == 0) ? d->d_hist[d->hflip ^ 1] : nullptr; hist_saved = p.hist_out != nullptr;
-            p.n_out = (int)n_out; p.hist_in = whole ? d->d_hist[d->hflip] : nullptr;
+            p.two_T = 2LL * T; p.hist_out = (T >= DDC_HIST && (T & 7) == 0) ? d->d_hist[d->hflip ^ 1].get() : nullptr; hist_saved = p.hist_out != nullptr;
+            p.n_out = (int)n_out; p.hist_in = whole ? d->d_hist[d->hflip].get() : nullptr;
             const int n_wsb = (d->n_streams + 15) / 16;
             // 8 KiB ring per stream (window 2304 B + the next group's bytes + 1-KiB fetch granularity on both sides need > 4 KiB), one workgroup per CU.
             // Two teams (512 threads, two waves per SIMD) when the ring also holds a second tile per group: 3 * 16 D <= 3842.
@@ -1148,7 +1134,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
                 gx = d->n_streams; gy = (n_cols + 15) / 16;
                 p.col_bytes = (long long)p.tiles_per_seg * tstride; p.col_chunks = (int)(p.col_bytes / 2048);
                 p.frag_stride = (size_t)DDC_NKT * 3 * 64; p.tab_pitch = sv.pitch; p.tab_len = sv.n_entries;
-                p.scales = d->d_scales; p.corr_row = sv.corr_row; p.corr_chunks = sv.corr_chunks;
+                p.scales = d->d_scales.get(); p.corr_row = sv.corr_row; p.corr_chunks = sv.corr_chunks;
             }
             p.n_lead_store = (fuse && n_fix > 0) ? (int)n_fix + 1 : 0;
             const size_t lds = (size_t)16 * ((1u << rbl) + DDC_RING_PAD) + (size_t)2 * nt * DDC_WPT * 64 * sizeof(float4) + DDC_NGRAN * 16 * sizeof(float) + 2 * 16 * sizeof(float2)
@@ -1157,7 +1143,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
 #define DDC_LAUNCH(NTV, FV, PSV, THREADS) do {                                                                                                             \
                 const int arc = lds_attr_once((const void *)k_ddc_mfma<rbl, NTV, FV, PSV>, lds); if (arc) return arc;                                         \
                 if (e0) CSDR_HIP(hipEventRecord(e0, st));                                                                                                      \
-                hipLaunchKernelGGL((k_ddc_mfma<rbl, NTV, FV, PSV>), dim3(gx, gy), dim3(THREADS), lds, st, in, in_pitch, (const v4i *)d->d_frags, d->d_cum, d->d_dtab, ctab, \
+                hipLaunchKernelGGL((k_ddc_mfma<rbl, NTV, FV, PSV>), dim3(gx, gy), dim3(THREADS), lds, st, in, in_pitch, (const v4i *)d->d_frags.get(), d->d_cum.get(), d->d_dtab.get(), ctab, \
                                    corr, reinterpret_cast<float2 *>(out), out_pitch, p, fz); } while (0)
             if (d->ps) {
                 if (fuse) { if (nt == 2) DDC_LAUNCH(2, true, true, 128 * DDC_WPT); else DDC_LAUNCH(1, true, true, 64 * DDC_WPT); }
@@ -1187,7 +1173,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
         else { q.ka0 = k_first; q.na = (int)n_out; q.kb0 = 0; q.nb = 0; }
         if (q.na + q.nb > 0) {
             if (tb < ta && e0) CSDR_HIP(hipEventRecord(e0, st));
-            hipLaunchKernelGGL(k_ddc_direct, dim3(cdiv(q.na + q.nb, 4), d->n_streams), dim3(256), 0, st, in, in_pitch, d->d_hist[d->hflip], d->d_taps, d->d_dtab, ctab, corr,
+            hipLaunchKernelGGL(k_ddc_direct, dim3(cdiv(q.na + q.nb, 4), d->n_streams), dim3(256), 0, st, in, in_pitch, d->d_hist[d->hflip].get(), d->d_taps.get(), d->d_dtab.get(), ctab, corr,
                                reinterpret_cast<float2 *>(out), out_pitch, q);
             CSDR_LAUNCH_CHECK();
             if (tb < ta && e1) CSDR_HIP(hipEventRecord(e1, st));
@@ -1196,20 +1182,20 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
         if (n_fix > 0) {
             // the first outputs of the streams retuned since the last call, with the old rate's table for the samples in front of the block
             const int nr = (int)d->retuned.size();
-            if (!d->d_list) CSDR_HIP(hipMalloc((void **)&d->d_list, sizeof(int) * d->n_streams));
+            if (!d->d_list) CSDR_HIP(dev_alloc(d->d_list, sizeof(int) * d->n_streams));
             int *hl = (int *)c->pinned_acquire(sizeof(int) * nr); if (!hl) return -2;
             memcpy(hl, d->retuned.data(), sizeof(int) * nr);
-            rc = c->pinned_upload(d->d_list, sizeof(int) * nr); if (rc) return rc;
+            rc = c->pinned_upload(d->d_list.get(), sizeof(int) * nr); if (rc) return rc;
             DirectParams f = q;
-            f.ka0 = k_first; f.na = (int)n_fix; f.kb0 = 0; f.nb = 0; f.list = d->d_list; f.dtab_old = d->d_dtab_old; f.corr_old = d->d_corr_old;
-            hipLaunchKernelGGL(k_ddc_direct, dim3(cdiv(f.na, 4), nr), dim3(256), 0, st, in, in_pitch, d->d_hist[d->hflip], d->d_taps, d->d_dtab, ctab, corr,
+            f.ka0 = k_first; f.na = (int)n_fix; f.kb0 = 0; f.nb = 0; f.list = d->d_list.get(); f.dtab_old = d->d_dtab_old.get(); f.corr_old = d->d_corr_old.get();
+            hipLaunchKernelGGL(k_ddc_direct, dim3(cdiv(f.na, 4), nr), dim3(256), 0, st, in, in_pitch, d->d_hist[d->hflip].get(), d->d_taps.get(), d->d_dtab.get(), ctab, corr,
                                reinterpret_cast<float2 *>(out), out_pitch, f);
             CSDR_LAUNCH_CHECK();
         }
     }
     if (n_out > 0) d->retuned.clear();
     // 3. history for the next block (the matrix-core kernel's last segment has done it when it ran on a whole block)
-    if (!hist_saved) hipLaunchKernelGGL(k_ddc_save_hist, dim3(d->n_streams), dim3(256), 0, st, in, in_pitch, T, d->d_hist[d->hflip], d->d_hist[d->hflip ^ 1]);
+    if (!hist_saved) hipLaunchKernelGGL(k_ddc_save_hist, dim3(d->n_streams), dim3(256), 0, st, in, in_pitch, T, d->d_hist[d->hflip].get(), d->d_hist[d->hflip ^ 1].get());
     CSDR_LAUNCH_CHECK();
     d->hflip ^= 1;
     if (T % 1024) d->ended = true;

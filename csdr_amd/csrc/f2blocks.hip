@@ -295,7 +295,7 @@ inline unsigned grid1(size_t n) { size_t g = (n + 255) / 256; if (g < 1) g = 1; 
 } // namespace
 
 struct csdr_amd_fftcc {
-    csdr_amd_ctx *c; int fft, every, max_frames; float *d_w; cf32 *d_hist[2]; int cur; cf32 *d_frames; std::map<int, hipfftHandle> plans;
+    csdr_amd_ctx *c; int fft, every, max_frames; DevBuf<float> d_w; DevBuf<cf32> d_hist[2]; int cur; DevBuf<cf32> d_frames; std::map<int, FftPlan> plans;
 };
 
 extern "C" {
@@ -385,23 +385,22 @@ void csdr_amd_precalculate_window(float *windowt, int size, int window)
 csdr_amd_fftcc *csdr_amd_fftcc_create(csdr_amd_ctx *c, int fft_size, int every_n_samples, int window, int max_frames)
 {
     if (fft_size <= 0 || (fft_size & (fft_size - 1)) || every_n_samples <= 0 || max_frames <= 0) { fail_msg(-3, "fft_cc: fft_size must be a power of two, every_n and max_frames positive"); return nullptr; }
-    csdr_amd_fftcc *f = new csdr_amd_fftcc();
+    std::unique_ptr<csdr_amd_fftcc> f(new csdr_amd_fftcc());
     f->c = c; f->fft = fft_size; f->every = every_n_samples; f->max_frames = max_frames; f->cur = 0;
     const int H = fft_size > every_n_samples ? fft_size - every_n_samples : 0;
-    f->d_w = (float *)csdr_amd_malloc(c, 4 * (size_t)fft_size);
-    f->d_hist[0] = (cf32 *)csdr_amd_malloc(c, 8 * (size_t)(H + 1)); f->d_hist[1] = (cf32 *)csdr_amd_malloc(c, 8 * (size_t)(H + 1));
-    f->d_frames = (cf32 *)csdr_amd_malloc(c, 8 * (size_t)fft_size * max_frames);
-    if (!f->d_w || !f->d_hist[0] || !f->d_hist[1] || !f->d_frames) { delete f; return nullptr; }
+    f->d_w.reset((float *)csdr_amd_malloc(c, 4 * (size_t)fft_size));
+    f->d_hist[0].reset((cf32 *)csdr_amd_malloc(c, 8 * (size_t)(H + 1))); f->d_hist[1].reset((cf32 *)csdr_amd_malloc(c, 8 * (size_t)(H + 1)));
+    f->d_frames.reset((cf32 *)csdr_amd_malloc(c, 8 * (size_t)fft_size * max_frames));
+    if (!f->d_w || !f->d_hist[0] || !f->d_hist[1] || !f->d_frames) return nullptr;
     std::vector<float> w(fft_size); csdr_amd_precalculate_window(w.data(), fft_size, window);
-    csdr_amd_h2d(c, f->d_w, w.data(), 4 * (size_t)fft_size);
-    csdr_amd_memset(c, f->d_hist[0], 0, 8 * (size_t)(H + 1));     // the sliding buffer starts empty (the reference's fresh allocation)
-    return f;
+    csdr_amd_h2d(c, f->d_w.get(), w.data(), 4 * (size_t)fft_size);
+    csdr_amd_memset(c, f->d_hist[0].get(), 0, 8 * (size_t)(H + 1));     // the sliding buffer starts empty (the reference's fresh allocation)
+    return f.release();
 }
 void csdr_amd_fftcc_destroy(csdr_amd_fftcc *f)
 {
     if (!f) return;
-    for (auto &kv : f->plans) hipfftDestroy(kv.second);
-    csdr_amd_free(f->c, f->d_w); csdr_amd_free(f->c, f->d_hist[0]); csdr_amd_free(f->c, f->d_hist[1]); csdr_amd_free(f->c, f->d_frames);
+    (void)hipSetDevice(f->c->device);
     delete f;
 }
 // in: n_in new samples (device).  Emits floor(n_in / every_n) spectra of fft_size bins into out; *consumed = frames * every_n.
@@ -413,11 +412,11 @@ int csdr_amd_fftcc_process(csdr_amd_fftcc *f, const csdr_complexf *in, size_t n_
     if (consumed) *consumed = (size_t)n_frames * f->every;
     if (n_frames <= 0) return 0;
     const int H = f->fft > f->every ? f->fft - f->every : 0;
-    hipLaunchKernelGGL(k_fft_frame, dim3(cdiv(f->fft, 256) > 64 ? 64 : cdiv(f->fft, 256), (unsigned)n_frames), dim3(256), 0, c->stream, (const cf32 *)in, f->d_hist[f->cur],
-                       f->d_w, f->d_frames, f->fft, f->every, n_frames);
+    hipLaunchKernelGGL(k_fft_frame, dim3(cdiv(f->fft, 256) > 64 ? 64 : cdiv(f->fft, 256), (unsigned)n_frames), dim3(256), 0, c->stream, (const cf32 *)in, f->d_hist[f->cur].get(),
+                       f->d_w.get(), f->d_frames.get(), f->fft, f->every, n_frames);
     CSDR_LAUNCH_CHECK();
     if (H) {
-        hipLaunchKernelGGL(k_fft_hist, dim3(cdiv(H, 256) > 64 ? 64 : cdiv(H, 256)), dim3(256), 0, c->stream, (const cf32 *)in, f->d_hist[f->cur], f->d_hist[f->cur ^ 1], H,
+        hipLaunchKernelGGL(k_fft_hist, dim3(cdiv(H, 256) > 64 ? 64 : cdiv(H, 256)), dim3(256), 0, c->stream, (const cf32 *)in, f->d_hist[f->cur].get(), f->d_hist[f->cur ^ 1].get(), H,
                            (long)n_frames * f->every);
         CSDR_LAUNCH_CHECK();
         f->cur ^= 1;
@@ -425,10 +424,10 @@ int csdr_amd_fftcc_process(csdr_amd_fftcc *f, const csdr_complexf *in, size_t n_
     if (!f->plans.count(n_frames)) {
         hipfftHandle h; int n[1] = {f->fft};
         if (hipfftPlanMany(&h, 1, n, nullptr, 1, f->fft, nullptr, 1, f->fft, HIPFFT_C2C, n_frames) != HIPFFT_SUCCESS) return fail_msg(-5, "fft_cc: hipfftPlanMany(%d x %d) failed", f->fft, n_frames);
+        f->plans[n_frames].reset(h);
         hipfftSetStream(h, c->stream);
-        f->plans[n_frames] = h;
     }
-    if (hipfftExecC2C(f->plans[n_frames], (hipfftComplex *)f->d_frames, (hipfftComplex *)out, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "fft_cc: hipfftExecC2C failed");
+    if (hipfftExecC2C(f->plans[n_frames].get(), (hipfftComplex *)f->d_frames.get(), (hipfftComplex *)out, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "fft_cc: hipfftExecC2C failed");
     return n_frames;
 }
 

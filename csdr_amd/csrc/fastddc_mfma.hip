@@ -39,46 +39,37 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct DdcMfma {
     csdr_amd_ctx *ctx;
+    Stream side;                                                       // (synchronised by ddc_mfma_destroy, the last to go)
     int fft, inv, pre, G, C, Cpad, nbp, scrap, post_in, post_dec, kmax, rpitch, max_blocks;
-    float *d_Ht; cf32 *d_Ct; float2 *d_tw;
+    DevBuf<float> d_Ht; DevBuf<cf32> d_Ct; DevBuf<float2> d_tw;
     // sharding (a bank over several GPUs): this rank's channels [C] of all, the forward transform split by blocks (nbl per rank), Xt = one chunk per rank
-    int rank, world, nbl; const DdcComm *comm; cf32 *d_in_local;
+    int rank, world, nbl; const DdcComm *comm; DevBuf<cf32> d_in_local;
     // time-sliced bank (fftpath.hip: the bank deals the BLOCKS of a batch to the ranks, every rank runs this object unsharded on its run): where the next call's
     // blocks sit in the batch (ddc_mfma_set_segment), and per set the samples every rank's run produces [seg_world][C]
     int seg_nbl = 0, seg_first = 0, seg_total = 0, seg_world = 0, spec_seg_first = 0, spec_seg_total = 0; int *seg_cur = nullptr, *seg_next = nullptr;
     // Two sets of everything a call produces before the fold (transposed spectra, chain tables, phasor checkpoints): submit() fills one set on the side
     // stream -- exchange + forward transform + chains -- while collect() folds the other on the context's stream.
-    cf32 *d_Xt[2]; float2 *d_R[2]; int *d_blk_remain[2], *d_blk_off[2], *d_counts[2]; float *d_blk_phase[2];
+    DevBuf<cf32> d_Xt[2]; DevBuf<float2> d_R[2]; DevBuf<int> d_blk_remain[2], d_blk_off[2], d_counts[2]; DevBuf<float> d_blk_phase[2];
     int pending_blocks[2]; int fill, drain;                            // set being filled next / folded next
     bool inline_set[2], chains_on_side[2];
     bool gemm_three = false, gemm_narrow = false;
     bool y_holds[2] = {false, false};                                  // set k's spectra are still pass-1 output in d_Y (the fold runs pass 2 itself)
     // the NEXT call's chain tables, computed one call ahead by riders of the inverse-transform kernel (data independent; valid for process() calls of equal size
     // with no retune in between).  On the side stream beside the fold they cost more than they hid: 0.182 vs 0.167 ms per step.
-    DdcChanState *d_state_spec = nullptr, *last_state = nullptr; bool spec_valid = false, ahead_ok = false; int spec_set = 0, spec_blocks = 0;                                           // the fold kernel of the last collect(): k_ddc_gemm3 (three real products) or k_ddc_gemm
-    hipStream_t side; hipEvent_t ev_ready[2], ev_free[2], ev_fork; bool free_recorded[2];
+    DevBuf<DdcChanState> d_state_spec; DdcChanState *last_state = nullptr; bool spec_valid = false, ahead_ok = false; int spec_set = 0, spec_blocks = 0;                                           // the fold kernel of the last collect(): k_ddc_gemm3 (three real products) or k_ddc_gemm
+    Event ev_ready[2], ev_free[2], ev_fork; bool free_recorded[2];
     // fused forward transform (65536 = 512 x 128): intermediate Y[block][k1][n2], the kept overlap tail of the input stream, W_65536^lo table
-    cf32 *d_Y, *d_tail[2]; float2 *d_twb; int flip, input_size, overlap;
+    DevBuf<cf32> d_Y, d_tail[2]; DevBuf<float2> d_twb; int flip, input_size, overlap;
     // A/B switches, read ONCE when the object is created: a call never looks at the environment
     struct Opt { bool fwd_off, riders_off, spec_off, pass2_own; } opt;      // test hooks (tests/test_configs_gpu.py::test_c4_bank_alternative_paths): each turns one default choice off, so that the
                                                                             // path other conditions select (a sharded bank, a size change, > 4096 channels) is crossed on one GPU
     // HIP-event timing of the fold kernel on the context's stream (bench_fastddc.py's roofline leg)
-    bool profiling = false; size_t ev_used = 0; double prof_ms = 0; long prof_launches = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    bool profiling = false; double prof_ms = 0; long prof_launches = 0; KernelTimer timer;
     // the same for the forward transform's first pass (stage 1: k_ddc_fwd512) and the inverse transforms (stage 2: k_ddc_ifft256d_post / k_ddc_ifft512_post)
     bool profile_stages = false;
-    struct StageProf { size_t used = 0; double ms = 0; long launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pool; } stage[2];
+    struct StageProf { double ms = 0; long launches = 0; KernelTimer timer; } stage[2];
+    bool stages_timed() const { return profiling && profile_stages; }
 };
-
-static int ddc_stage_begin(DdcMfma *m, int s, hipStream_t st, hipEvent_t *e1)
-{
-    *e1 = nullptr;
-    if (!m->profiling || !m->profile_stages) return 0;
-    DdcMfma::StageProf &p = m->stage[s];
-    if (p.used == p.pool.size()) { hipEvent_t a, b; CSDR_HIP(hipEventCreate(&a)); CSDR_HIP(hipEventCreate(&b)); p.pool.emplace_back(a, b); }
-    CSDR_HIP(hipEventRecord(p.pool[p.used].first, st)); *e1 = p.pool[p.used].second; p.used++;
-    return 0;
-}
 
 namespace {
 
@@ -919,7 +910,7 @@ DdcMfma *ddc_mfma_create(csdr_amd_ctx *ctx, int fft, int inv, int pre, int n_cha
 {
     if (getenv("CSDR_AMD_DDC_MFMA_OFF")) return nullptr;
     if (inv != 512 || pre < 8 || (pre & (pre - 1)) || fft != inv * pre || post_dec < 1 || scrap + post_in > inv) return nullptr;
-    DdcMfma *m = new DdcMfma();
+    Owned<DdcMfma, ddc_mfma_destroy> m(new DdcMfma());
     m->ctx = ctx; m->fft = fft; m->inv = inv; m->pre = pre; m->G = pre / 4; m->C = n_channels; m->Cpad = (n_channels + 31) / 32 * 32;
     m->max_blocks = max_blocks; m->nbp = (max_blocks + 31) / 32 * 32; m->scrap = scrap; m->post_in = post_in; m->post_dec = post_dec;
     m->kmax = (post_in - 1) / post_dec + 1; m->rpitch = (m->kmax + ROT_CK - 1) / ROT_CK;      // checkpoints per chain
@@ -933,66 +924,56 @@ DdcMfma *ddc_mfma_create(csdr_amd_ctx *ctx, int fft, int inv, int pre, int n_cha
     }
     m->nbl = m->world > 1 ? (max_blocks + m->world - 1) / m->world : m->nbp;
     const size_t xt_elems = (size_t)m->world * inv * m->nbl * pre;
-    hipError_t e = hipMalloc((void **)&m->d_Ht, sizeof(float) * 2 * (size_t)m->Cpad * fft);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_Ct, sizeof(cf32) * (size_t)inv * m->Cpad * m->nbp);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_tw, sizeof(float2) * 512);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_twb, sizeof(float2) * 128);
+    hipError_t e = dev_alloc(m->d_Ht, sizeof(float) * 2 * (size_t)m->Cpad * fft);
+    if (e == hipSuccess) e = dev_alloc(m->d_Ct, sizeof(cf32) * (size_t)inv * m->Cpad * m->nbp);
+    if (e == hipSuccess) e = dev_alloc(m->d_tw, sizeof(float2) * 512);
+    if (e == hipSuccess) e = dev_alloc(m->d_twb, sizeof(float2) * 128);
     for (int k = 0; k < 2 && e == hipSuccess; k++) {
         const size_t n_tab = (size_t)n_channels * max_blocks;
-        e = hipMalloc((void **)&m->d_Xt[k], sizeof(cf32) * xt_elems);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->d_R[k], sizeof(float2) * n_tab * m->rpitch);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->d_blk_remain[k], sizeof(int) * n_tab);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->d_blk_off[k], sizeof(int) * n_tab);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->d_blk_phase[k], sizeof(float) * n_tab);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->d_counts[k], sizeof(int) * n_channels);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->ev_ready[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->ev_free[k], hipEventDisableTiming);
+        e = dev_alloc(m->d_Xt[k], sizeof(cf32) * xt_elems);
+        if (e == hipSuccess) e = dev_alloc(m->d_R[k], sizeof(float2) * n_tab * m->rpitch);
+        if (e == hipSuccess) e = dev_alloc(m->d_blk_remain[k], sizeof(int) * n_tab);
+        if (e == hipSuccess) e = dev_alloc(m->d_blk_off[k], sizeof(int) * n_tab);
+        if (e == hipSuccess) e = dev_alloc(m->d_blk_phase[k], sizeof(float) * n_tab);
+        if (e == hipSuccess) e = dev_alloc(m->d_counts[k], sizeof(int) * n_channels);
+        if (e == hipSuccess) e = event_create(m->ev_ready[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = event_create(m->ev_free[k], hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_state_spec, sizeof(DdcChanState) * (size_t)n_channels);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_Ht, 0, sizeof(float) * 2 * (size_t)m->Cpad * fft, ctx->stream);      // padded channel rows stay zero
+    if (e == hipSuccess) e = event_create(m->ev_fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = dev_alloc(m->d_state_spec, sizeof(DdcChanState) * (size_t)n_channels);
+    if (e == hipSuccess) e = stream_create(m->side);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_Ht.get(), 0, sizeof(float) * 2 * (size_t)m->Cpad * fft, ctx->stream);      // padded channel rows stay zero
     // the fused forward transform's buffers (allocated here, not in the first call: a call allocates nothing)
     m->input_size = input_size; m->overlap = overlap;
     if (e == hipSuccess && fft == 65536 && pre == 128) {
         const int y_blocks = m->world > 1 ? m->nbl : m->max_blocks;
-        e = hipMalloc((void **)&m->d_Y, sizeof(cf32) * (size_t)y_blocks * fft);
+        e = dev_alloc(m->d_Y, sizeof(cf32) * (size_t)y_blocks * fft);
         for (int t = 0; t < 2 && e == hipSuccess; t++) {
-            e = hipMalloc((void **)&m->d_tail[t], sizeof(cf32) * (size_t)(overlap + 1));
-            if (e == hipSuccess) e = hipMemsetAsync(m->d_tail[t], 0, sizeof(cf32) * (size_t)(overlap + 1), ctx->stream);        // csdr.c:2279: the first window starts with zeros
+            e = dev_alloc(m->d_tail[t], sizeof(cf32) * (size_t)(overlap + 1));
+            if (e == hipSuccess) e = hipMemsetAsync(m->d_tail[t].get(), 0, sizeof(cf32) * (size_t)(overlap + 1), ctx->stream);        // csdr.c:2279: the first window starts with zeros
         }
-        if (e == hipSuccess && m->world > 1) e = hipMalloc((void **)&m->d_in_local, sizeof(cf32) * ((size_t)m->nbl * input_size + overlap));
+        if (e == hipSuccess && m->world > 1) e = dev_alloc(m->d_in_local, sizeof(cf32) * ((size_t)m->nbl * input_size + overlap));
     }
-    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc matrix-core path)", __FILE__, __LINE__); ddc_mfma_destroy(m); return nullptr; }
+    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc matrix-core path)", __FILE__, __LINE__); return nullptr; }
     std::vector<float2> tw(512), twb(128);
     for (int k = 0; k < 512; k++) { const double a = -2.0 * M_PI * k / 512.0; tw[k] = make_float2((float)cos(a), (float)sin(a)); }
     for (int k = 0; k < 128; k++) { const double a = -2.0 * M_PI * k / 65536.0; twb[k] = make_float2((float)cos(a), (float)sin(a)); }
-    if (hipMemcpy(m->d_tw, tw.data(), sizeof(float2) * 512, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->d_twb, twb.data(), sizeof(float2) * 128, hipMemcpyHostToDevice) != hipSuccess) { ddc_mfma_destroy(m); return nullptr; }
-    return m;
+    if (hipMemcpy(m->d_tw.get(), tw.data(), sizeof(float2) * 512, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->d_twb.get(), twb.data(), sizeof(float2) * 128, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return m.release();
 }
 
 void ddc_mfma_destroy(DdcMfma *m)
 {
     if (!m) return;
-    if (m->side) { (void)hipStreamSynchronize(m->side); (void)hipStreamDestroy(m->side); }
-    (void)hipFree(m->d_Ht); (void)hipFree(m->d_Ct); (void)hipFree(m->d_tw); (void)hipFree(m->d_twb);
-    (void)hipFree(m->d_Y); (void)hipFree(m->d_tail[0]); (void)hipFree(m->d_tail[1]); (void)hipFree(m->d_in_local);
-    for (int k = 0; k < 2; k++) {
-        (void)hipFree(m->d_Xt[k]); (void)hipFree(m->d_R[k]); (void)hipFree(m->d_blk_remain[k]); (void)hipFree(m->d_blk_off[k]); (void)hipFree(m->d_blk_phase[k]); (void)hipFree(m->d_counts[k]);
-        if (m->ev_ready[k]) (void)hipEventDestroy(m->ev_ready[k]);
-        if (m->ev_free[k]) (void)hipEventDestroy(m->ev_free[k]);
-    }
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    (void)hipFree(m->d_state_spec);
-    for (auto &pr : m->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+    if (m->side) (void)hipStreamSynchronize(m->side.get());
     delete m;
 }
 
 // everything queued by submit / collect has finished (retunes and destruction)
 int ddc_mfma_quiesce(DdcMfma *m)
 {   // (before a retune: the tables computed ahead belong to the old rate / state)
-    CSDR_HIP(hipStreamSynchronize(m->side)); CSDR_HIP(hipStreamSynchronize(m->ctx->stream));
+    CSDR_HIP(hipStreamSynchronize(m->side.get())); CSDR_HIP(hipStreamSynchronize(m->ctx->stream));
     m->spec_valid = false;
     return 0;
 }
@@ -1000,7 +981,7 @@ int ddc_mfma_quiesce(DdcMfma *m)
 int ddc_mfma_set_taps(DdcMfma *m, hipStream_t st, const cf32 *d_H, int c_first, int c_count)
 {
     if (c_count <= 0) return 0;
-    hipLaunchKernelGGL(k_ddc_ht, dim3(cdiv(m->inv, 256), m->pre, c_count), dim3(256), 0, st, reinterpret_cast<const float2 *>(d_H), m->d_Ht, m->fft, m->inv, m->G, m->Cpad, c_first);
+    hipLaunchKernelGGL(k_ddc_ht, dim3(cdiv(m->inv, 256), m->pre, c_count), dim3(256), 0, st, reinterpret_cast<const float2 *>(d_H), m->d_Ht.get(), m->fft, m->inv, m->G, m->Cpad, c_first);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -1012,7 +993,7 @@ static DdcChainJob mfma_chain_job(DdcMfma *m, int k, int n_blocks, DdcChanState 
 {
     DdcChainJob j;
     j.state = d_state; j.state_out = d_state; j.mode = 1; j.geom = d_geom; j.n_channels = m->C; j.n_blocks = n_blocks; j.post_in = m->post_in; j.post_dec = m->post_dec; j.kmax = m->kmax;
-    j.blk_remain = m->d_blk_remain[k]; j.blk_phase = m->d_blk_phase[k]; j.blk_off = m->d_blk_off[k]; j.counts = m->d_counts[k]; j.R = m->d_R[k];
+    j.blk_remain = m->d_blk_remain[k].get(); j.blk_phase = m->d_blk_phase[k].get(); j.blk_off = m->d_blk_off[k].get(); j.counts = m->d_counts[k].get(); j.R = m->d_R[k].get();
     j.seg_nbl = m->seg_nbl; j.seg_first = m->seg_first; j.seg_total = m->seg_total; j.seg_world = m->seg_world; j.seg_pref = m->seg_cur;
     return j;
 }
@@ -1073,9 +1054,8 @@ static int mfma_forward(DdcMfma *m, hipStream_t st, const void *in, int fmt, con
     const size_t rider_lanes = riders ? (cj.mode == 2 ? (size_t)cj.n_channels * cj.n_blocks : (size_t)cj.n_channels) : 0;      // mode 2: one lane per (block, channel) chain
     // pass 1: 16 columns n2 per workgroup (128-byte runs)
 #define DDC_FWD_ARGS in, reinterpret_cast<const float2 *>(tail), reinterpret_cast<float2 *>(tail_out), \
-                     reinterpret_cast<float2 *>(m->d_Y), m->d_tw, m->d_twb, m->input_size, m->overlap, n_loc, cj
-    hipEvent_t pe1 = nullptr;
-    { const int rc = ddc_stage_begin(m, 0, st, &pe1); if (rc) return rc; }
+                     reinterpret_cast<float2 *>(m->d_Y.get()), m->d_tw.get(), m->d_twb.get(), m->input_size, m->overlap, n_loc, cj
+    if (m->stages_timed()) { if (const int rc = m->stage[0].timer.begin(st)) return rc; }
     {
         const size_t lds = (size_t)(16 * I512<16>::pitch + 512 + 128) * sizeof(float2);
         const dim3 grid(8, n_loc + (riders ? cdiv(rider_lanes, 8 * 256) : 0));
@@ -1086,12 +1066,12 @@ static int mfma_forward(DdcMfma *m, hipStream_t st, const void *in, int fmt, con
     }
 #undef DDC_FWD_ARGS
     CSDR_LAUNCH_CHECK();
-    if (pe1) CSDR_HIP(hipEventRecord(pe1, st));
+    if (m->stages_timed()) { if (const int rc = m->stage[0].timer.end(st)) return rc; }
     const bool rot_rides = !skip_pass2 && riders && cj.mode == 1 && (size_t)cj.n_channels * cj.n_blocks <= 512u * 256u;      // mode 2: pass 1 did the checkpoints
     if (!rot_rides) cj.R = nullptr;
     if (!skip_pass2)
-    hipLaunchKernelGGL(k_ddc_fwd128, dim3(512, cdiv(n_loc, 32) + (rot_rides ? 1 : 0)), dim3(256), 0, st, reinterpret_cast<const float2 *>(m->d_Y), reinterpret_cast<float2 *>(xt),
-                       m->d_tw, m->nbl, n_loc, cj);
+    hipLaunchKernelGGL(k_ddc_fwd128, dim3(512, cdiv(n_loc, 32) + (rot_rides ? 1 : 0)), dim3(256), 0, st, reinterpret_cast<const float2 *>(m->d_Y.get()), reinterpret_cast<float2 *>(xt),
+                       m->d_tw.get(), m->nbl, n_loc, cj);
     CSDR_LAUNCH_CHECK();
     if (riders && cj.mode == 1 && !rot_rides) {
         hipLaunchKernelGGL(k_ddc_rot, dim3(cdiv((size_t)m->C * cj.n_blocks, 64)), dim3(64), 0, st, *riders);
@@ -1139,7 +1119,7 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
     hipStream_t mainst = m->ctx->stream;
     const bool inl = inline_call && m->world == 1 && !m->pending_blocks[k ^ 1];
     const int chains_side = 0;                        // (1 = the chains on the side stream beside the transforms: measured 0.190 vs 0.186 ms per step, round 3; never selected)
-    hipStream_t st = inl ? mainst : m->side;
+    hipStream_t st = inl ? mainst : m->side.get();
     int rc = 0;
     const bool riders_off = m->opt.riders_off, spec_off = m->opt.spec_off;
     const bool fused_fwd = inl && !chains_side && !spectra && ddc_mfma_can_forward(m);
@@ -1154,15 +1134,15 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
     } else if (inl && !chains_side) {
         rc = mfma_chains(m, mainst, k, n_blocks, d_state, d_geom); if (rc) return rc;
     } else {
-        CSDR_HIP(hipEventRecord(m->ev_fork, mainst));                   // the producers of `in` queued so far; the readers of this set's tables (inline: same stream order)
-        CSDR_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
+        CSDR_HIP(hipEventRecord(m->ev_fork.get(), mainst));                   // the producers of `in` queued so far; the readers of this set's tables (inline: same stream order)
+        CSDR_HIP(hipStreamWaitEvent(m->side.get(), m->ev_fork.get(), 0));
         // (the fold that read this set two calls ago was queued on the context's stream before this call: ev_fork orders the side stream behind it)
-        rc = mfma_chains(m, m->side, k, n_blocks, d_state, d_geom); if (rc) return rc;
+        rc = mfma_chains(m, m->side.get(), k, n_blocks, d_state, d_geom); if (rc) return rc;
     }
     if (spectra) {
         if (m->world > 1) return fail_msg(-3, "fastddc: natural-order spectra cannot feed a sharded bank");
         hipLaunchKernelGGL(k_ddc_xt, dim3(cdiv(m->inv, 32), cdiv(m->pre, 32), n_blocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(spectra),
-                           reinterpret_cast<float2 *>(m->d_Xt[k]), m->fft, m->inv, m->pre, m->nbl);
+                           reinterpret_cast<float2 *>(m->d_Xt[k].get()), m->fft, m->inv, m->pre, m->nbl);
         CSDR_LAUNCH_CHECK();
     } else {
         if (!ddc_mfma_can_forward(m)) return fail_msg(-3, "fastddc: the fused forward transform covers fft_size 65536 / pre_decimation 128 only");
@@ -1170,13 +1150,13 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
         if (!m->d_Y) return fail_msg(-3, "fastddc: forward buffers missing");
         if (m->world == 1) {
             DdcChainJob job = mfma_chain_job(m, k, n_blocks, d_state, d_geom);
-            if (spec_hit) { job.mode = 2; job.state_out = m->d_state_spec; }
+            if (spec_hit) { job.mode = 2; job.state_out = m->d_state_spec.get(); }
             const bool fuse2_off = m->opt.pass2_own;                              // CSDR_AMD_DDC_PASS2: k_ddc_fwd128 stays a kernel of its own
             const bool skip2 = inl && !fuse2_off && ddc_folds_with_gemm3(m, n_blocks) && !ddc_fold_is_narrow(m, n_blocks);      // the fold runs pass 2 itself (d_Y is this call's until its collect())
             // ext_tail: the overlap in front of the first window comes from the caller (a time-sliced bank: the stream before this rank's run is another rank's)
-            if (tail_in_front) rc = mfma_forward(m, st, in, fmt, nullptr, nullptr, n_blocks, m->d_Xt[k], ride ? &job : nullptr, skip2);
-            else if (ext_tail) rc = mfma_forward(m, st, in, fmt, ext_tail, nullptr, n_blocks, m->d_Xt[k], ride ? &job : nullptr, skip2);
-            else { rc = mfma_forward(m, st, in, fmt, m->d_tail[m->flip], m->d_tail[m->flip ^ 1], n_blocks, m->d_Xt[k], ride ? &job : nullptr, skip2); m->flip ^= 1; }
+            if (tail_in_front) rc = mfma_forward(m, st, in, fmt, nullptr, nullptr, n_blocks, m->d_Xt[k].get(), ride ? &job : nullptr, skip2);
+            else if (ext_tail) rc = mfma_forward(m, st, in, fmt, ext_tail, nullptr, n_blocks, m->d_Xt[k].get(), ride ? &job : nullptr, skip2);
+            else { rc = mfma_forward(m, st, in, fmt, m->d_tail[m->flip].get(), m->d_tail[m->flip ^ 1].get(), n_blocks, m->d_Xt[k].get(), ride ? &job : nullptr, skip2); m->flip ^= 1; }
             if (rc) return rc;
             m->y_holds[k] = skip2;
         } else {
@@ -1192,19 +1172,19 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
                     // (the raw samples: 8, 4 or 2 bytes each -- the root's egress is what bounds the scaling of a single-ingest bank; counts in 4-byte words)
                     if (g1 > g0) { rc = cm->send(cm, in + ((size_t)g0 * inp - ovl) * es, ((size_t)(g1 - g0) * inp + ovl) * es / 4, g, st); if (rc) return rc; }
                 }
-            } else if (n_loc > 0) { rc = cm->recv(cm, m->d_in_local, ((size_t)n_loc * inp + ovl) * es / 4, 0, st); if (rc) return rc; }
+            } else if (n_loc > 0) { rc = cm->recv(cm, m->d_in_local.get(), ((size_t)n_loc * inp + ovl) * es / 4, 0, st); if (rc) return rc; }
             rc = cm->group_end(cm); if (rc) return rc;
-            cf32 *chunk = m->d_Xt[k] + (size_t)m->rank * m->inv * m->nbl * m->pre;
+            cf32 *chunk = m->d_Xt[k].get() + (size_t)m->rank * m->inv * m->nbl * m->pre;
             if (m->rank == 0) {
-                rc = mfma_forward(m, st, in, fmt, m->d_tail[m->flip], nullptr, n_loc, chunk, nullptr); if (rc) return rc;
+                rc = mfma_forward(m, st, in, fmt, m->d_tail[m->flip].get(), nullptr, n_loc, chunk, nullptr); if (rc) return rc;
                 // the next call's overlap = the newest ovl samples of the stream (input_size >= overlap_length at this geometry), as complexf
-                rc = ddc_mfma_convert_samples(st, in, fmt, (long long)n_blocks * inp - ovl, ovl, m->d_tail[m->flip ^ 1]); if (rc) return rc;
+                rc = ddc_mfma_convert_samples(st, in, fmt, (long long)n_blocks * inp - ovl, ovl, m->d_tail[m->flip ^ 1].get()); if (rc) return rc;
                 m->flip ^= 1;
-            } else { rc = mfma_forward(m, st, reinterpret_cast<const uint8_t *>(m->d_in_local) + (size_t)ovl * es, fmt, nullptr, nullptr, n_loc, chunk, nullptr); if (rc) return rc; }
-            rc = cm->all_gather(cm, m->d_Xt[k], 2 * (size_t)m->inv * m->nbl * m->pre, st); if (rc) return rc;      // in place: every rank's chunk sits at its offset
+            } else { rc = mfma_forward(m, st, reinterpret_cast<const uint8_t *>(m->d_in_local.get()) + (size_t)ovl * es, fmt, nullptr, nullptr, n_loc, chunk, nullptr); if (rc) return rc; }
+            rc = cm->all_gather(cm, m->d_Xt[k].get(), 2 * (size_t)m->inv * m->nbl * m->pre, st); if (rc) return rc;      // in place: every rank's chunk sits at its offset
         }
     }
-    if (!(inl && !chains_side)) CSDR_HIP(hipEventRecord(m->ev_ready[k], m->side));      // inline: the side stream carries only the chains
+    if (!(inl && !chains_side)) CSDR_HIP(hipEventRecord(m->ev_ready[k].get(), m->side.get()));      // inline: the side stream carries only the chains
     m->inline_set[k] = inl; m->chains_on_side[k] = !(inl && !chains_side);
     m->pending_blocks[k] = n_blocks; m->fill ^= 1;
     return 0;
@@ -1213,9 +1193,9 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
 const char *ddc_mfma_kernel_name(const DdcMfma *m) { return m->gemm_three ? (m->gemm_narrow ? "k_ddc_gemm3n" : "k_ddc_gemm3") : "k_ddc_gemm"; }
 int ddc_mfma_set_profiling(DdcMfma *m, int on)
 {
-    m->profiling = on != 0; m->ev_used = 0; m->prof_ms = 0; m->prof_launches = 0;
+    m->profiling = on != 0; m->timer.reset(); m->prof_ms = 0; m->prof_launches = 0;
     m->profile_stages = on == 2;                                         // (2: the kernels around the fold too -- two more event pairs per call, not for a timed region)
-    for (auto &p : m->stage) { p.used = 0; p.ms = 0; p.launches = 0; }
+    for (auto &p : m->stage) { p.timer.reset(); p.ms = 0; p.launches = 0; }
     return 0;
 }
 // stage 1: the forward transform's first pass (k_ddc_fwd512), stage 2: the inverse transforms + scrap + residual shift (k_ddc_ifft256d_post / k_ddc_ifft512_post)
@@ -1223,23 +1203,13 @@ int ddc_mfma_stage_time(DdcMfma *m, int stage, double *total_ms, long *launches)
 {
     if (stage < 1 || stage > 2) return -3;
     DdcMfma::StageProf &p = m->stage[stage - 1];
-    for (size_t k = 0; k < p.used; k++) {
-        CSDR_HIP(hipEventSynchronize(p.pool[k].second));
-        float ms = 0; CSDR_HIP(hipEventElapsedTime(&ms, p.pool[k].first, p.pool[k].second));
-        p.ms += ms; p.launches++;
-    }
-    p.used = 0;
+    if (const int rc = p.timer.resolve(&p.ms, &p.launches)) return rc;
     *total_ms = p.ms; *launches = p.launches;
     return 0;
 }
 int ddc_mfma_kernel_time(DdcMfma *m, double *total_ms, long *launches)
 {
-    for (size_t k = 0; k < m->ev_used; k++) {
-        CSDR_HIP(hipEventSynchronize(m->ev_pool[k].second));
-        float ms = 0; CSDR_HIP(hipEventElapsedTime(&ms, m->ev_pool[k].first, m->ev_pool[k].second));
-        m->prof_ms += ms; m->prof_launches++;
-    }
-    m->ev_used = 0;
+    if (const int rc = m->timer.resolve(&m->prof_ms, &m->prof_launches)) return rc;
     *total_ms = m->prof_ms; *launches = m->prof_launches;
     return 0;
 }
@@ -1251,20 +1221,12 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     const int k = m->drain, n_blocks = m->pending_blocks[k];
     if (!n_blocks) return fail_msg(-3, "fastddc: nothing staged to collect");
     hipStream_t st = m->ctx->stream;
-    if (m->chains_on_side[k]) CSDR_HIP(hipStreamWaitEvent(st, m->ev_ready[k], 0));
+    if (m->chains_on_side[k]) CSDR_HIP(hipStreamWaitEvent(st, m->ev_ready[k].get(), 0));
     const float scale = 1.0f / (float)m->pre;                              // fastddc.c:144-148 (a power of two: exact)
     const int nbt = n_blocks > 32 ? 2 : 1;
     const size_t lds = (size_t)32 * nbt * (m->pre / 2 + 1) * sizeof(float4);
     const dim3 grid(m->inv, cdiv(m->Cpad, 256), cdiv(n_blocks, 32 * nbt));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (m->profiling) {
-        if (m->ev_used == m->ev_pool.size()) {
-            hipEvent_t a, b; CSDR_HIP(hipEventCreate(&a)); CSDR_HIP(hipEventCreate(&b));
-            m->ev_pool.emplace_back(a, b);
-        }
-        e0 = m->ev_pool[m->ev_used].first; e1 = m->ev_pool[m->ev_used].second; m->ev_used++;
-        CSDR_HIP(hipEventRecord(e0, st));
-    }
+    if (m->profiling) { if (const int rc = m->timer.begin(st)) return rc; }
     // persistent form (one workgroup per CU walks several residues, double-buffered spectra) when a residue's spectra fit the register staging
     // and there are at least two residues per workgroup
     const int n_cu = current_device_cu_count();
@@ -1275,23 +1237,23 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     const dim3 grid_use(persist ? (unsigned)slots : grid.x, grid.y, grid.z);
 #define DDC_GEMM_LAUNCH(NBTV, PV) do {                                                                                                               \
         if (lds_use > 64 * 1024) { const int rc = lds_attr_once((const void *)k_ddc_gemm<NBTV, PV>, lds_use); if (rc) return rc; }                    \
-        hipLaunchKernelGGL((k_ddc_gemm<NBTV, PV>), grid_use, dim3(512), lds_use, st, m->d_Ht, reinterpret_cast<const float2 *>(m->d_Xt[k]),           \
-                           reinterpret_cast<float2 *>(m->d_Ct), d_geom, m->inv, m->pre, m->Cpad, m->C, m->nbp, m->nbl, n_blocks, scale); } while (0)
+        hipLaunchKernelGGL((k_ddc_gemm<NBTV, PV>), grid_use, dim3(512), lds_use, st, m->d_Ht.get(), reinterpret_cast<const float2 *>(m->d_Xt[k].get()),           \
+                           reinterpret_cast<float2 *>(m->d_Ct.get()), d_geom, m->inv, m->pre, m->Cpad, m->C, m->nbp, m->nbl, n_blocks, scale); } while (0)
     // three-product form with LDS-DMA staging: pre_decimation 128 (a spectra row = one 1-KiB piece), persistent shape; other geometries keep the four-product kernel k_ddc_gemm
     const bool three = ddc_folds_with_gemm3(m, n_blocks);
     m->gemm_three = three; m->gemm_narrow = false;
     if (three) {
         // the second pass of the forward transform inside the fold: one GPU, process() (pass 1's output Y belongs to this call), submit() skipped k_ddc_fwd128
         const bool fwd = m->y_holds[k];
-        const float2 *src = fwd ? reinterpret_cast<const float2 *>(m->d_Y) : reinterpret_cast<const float2 *>(m->d_Xt[k]);
+        const float2 *src = fwd ? reinterpret_cast<const float2 *>(m->d_Y.get()) : reinterpret_cast<const float2 *>(m->d_Xt[k].get());
 #define DDC_GEMM3_LAUNCH(NBTV, FV) do { const int rc = lds_attr_once((const void *)k_ddc_gemm3<NBTV, FV>, lds_use); if (rc) return rc;                     \
-        hipLaunchKernelGGL((k_ddc_gemm3<NBTV, FV>), grid_use, dim3(512), lds_use, st, m->d_Ht, src, reinterpret_cast<float2 *>(m->d_Ct), d_geom, m->inv, m->Cpad, m->C,  \
-                           m->nbp, m->nbl, n_blocks, scale, m->d_tw); } while (0)
+        hipLaunchKernelGGL((k_ddc_gemm3<NBTV, FV>), grid_use, dim3(512), lds_use, st, m->d_Ht.get(), src, reinterpret_cast<float2 *>(m->d_Ct.get()), d_geom, m->inv, m->Cpad, m->C,  \
+                           m->nbp, m->nbl, n_blocks, scale, m->d_tw.get()); } while (0)
         m->gemm_narrow = !fwd && ddc_fold_is_narrow(m, n_blocks);
         if (m->gemm_narrow) {
             const dim3 gn(m->inv, 1, cdiv(n_blocks, 32));
             const size_t ldsn = (size_t)32 * (m->pre / 2 + 1) * sizeof(float4);
-#define DDC_GEMM3N_LAUNCH(NWV) hipLaunchKernelGGL((k_ddc_gemm3n<NWV>), gn, dim3(64 * NWV), ldsn, st, m->d_Ht, src, reinterpret_cast<float2 *>(m->d_Ct), d_geom, m->inv, m->Cpad, m->C, \
+#define DDC_GEMM3N_LAUNCH(NWV) hipLaunchKernelGGL((k_ddc_gemm3n<NWV>), gn, dim3(64 * NWV), ldsn, st, m->d_Ht.get(), src, reinterpret_cast<float2 *>(m->d_Ct.get()), d_geom, m->inv, m->Cpad, m->C, \
                                                   m->nbp, m->nbl, n_blocks, scale)
             if (m->Cpad <= 32) DDC_GEMM3N_LAUNCH(1); else if (m->Cpad <= 64) DDC_GEMM3N_LAUNCH(2); else DDC_GEMM3N_LAUNCH(4);
 #undef DDC_GEMM3N_LAUNCH
@@ -1304,15 +1266,14 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     else               { if (persist) DDC_GEMM_LAUNCH(1, true); else DDC_GEMM_LAUNCH(1, false); }
 #undef DDC_GEMM_LAUNCH
     CSDR_LAUNCH_CHECK();
-    if (e1) CSDR_HIP(hipEventRecord(e1, st));
+    if (m->profiling) { if (const int rc = m->timer.end(st)) return rc; }
     // inverse transforms.  post_decimation 2 (every power-of-two decimation): half-size transforms of the aliased bins; otherwise the full-size form.  Half 128-byte
     // bin lines per workgroup (8 blocks: more workgroups per CU than whole lines -- the <16> instantiations measured slower in round 2 and are gone)
     const bool full = m->post_dec != 2;
     const int pairs = m->C * cdiv(n_blocks, 16);
     const dim3 g8(cdiv(pairs, 8) * 16);
-    hipEvent_t pe2 = nullptr;
-    { const int rc = ddc_stage_begin(m, 1, st, &pe2); if (rc) return rc; }
-#define DDC_IFFT_ARGS reinterpret_cast<const float2 *>(m->d_Ct), reinterpret_cast<float2 *>(out), out_pitch, m->d_R[k], m->d_tw, m->d_blk_remain[k], m->d_blk_off[k], d_geom, m->Cpad, m->nbp, n_blocks, m->C, m->scrap, m->post_in
+    if (m->stages_timed()) { if (const int rc = m->stage[1].timer.begin(st)) return rc; }
+#define DDC_IFFT_ARGS reinterpret_cast<const float2 *>(m->d_Ct.get()), reinterpret_cast<float2 *>(out), out_pitch, m->d_R[k].get(), m->d_tw.get(), m->d_blk_remain[k].get(), m->d_blk_off[k].get(), d_geom, m->Cpad, m->nbp, n_blocks, m->C, m->scrap, m->post_in
     DdcChainJob ahead; memset(&ahead, 0, sizeof ahead);
     if (full) {
         hipLaunchKernelGGL(k_ddc_ifft512_post<8>, g8, dim3(256), (size_t)(8 * I512<8>::pitch + I512<8>::tw_n) * sizeof(float2), st, DDC_IFFT_ARGS, m->post_dec);
@@ -1320,7 +1281,7 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
         int n_riders = 0;
         if (m->ahead_ok && m->inline_set[k] && m->last_state && m->C <= 16 * 256) {      // the next call's chain tables into the other set, state into the shadow
             ahead = mfma_chain_job(m, k ^ 1, n_blocks, m->last_state, d_geom);
-            ahead.state_out = m->d_state_spec; ahead.seg_pref = m->seg_next;
+            ahead.state_out = m->d_state_spec.get(); ahead.seg_pref = m->seg_next;
             n_riders = 16;
             m->spec_valid = true; m->spec_set = k ^ 1; m->spec_blocks = n_blocks; m->spec_seg_first = m->seg_first; m->spec_seg_total = m->seg_total;
         }
@@ -1333,9 +1294,9 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     }
 #undef DDC_IFFT_ARGS
     CSDR_LAUNCH_CHECK();
-    if (pe2) CSDR_HIP(hipEventRecord(pe2, st));
+    if (m->stages_timed()) { if (const int rc = m->stage[1].timer.end(st)) return rc; }
     if (after_inverse) CSDR_HIP(hipEventRecord(after_inverse, st));     // (the other inverse-transform variants)
-    if (d_counts) *d_counts = m->d_counts[k];
+    if (d_counts) *d_counts = m->d_counts[k].get();
     m->pending_blocks[k] = 0; m->drain ^= 1;
     return n_blocks;
 }

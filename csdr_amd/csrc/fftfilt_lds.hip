@@ -810,9 +810,9 @@ namespace csdr_amd {
 
 struct FftfiltLds {
     int n, taps_len, k1p, n_streams;
-    float2 *d_hperm, *d_tw1, *d_tws, *d_hist[2]; int flip;
+    DevBuf<float2> d_hperm, d_tw1, d_tws, d_hist[2]; int flip;
     const char *last;                               // the window kernel the last call ran (a call's size and parity pick it)
-    float2 *d_hw, *d_twl, *d_tw2; bool wave, team;  // the tables of the wave-per-window kernel (4096-point windows) / of the team kernel (8192, 16384)
+    DevBuf<float2> d_hw, d_twl, d_tw2; bool wave, team;  // the tables of the wave-per-window kernel (4096-point windows) / of the team kernel (8192, 16384)
     int mode;                                       // CSDR_AMD_FFTFILT_LDS_MODE (A/B: 5 = the kernels of rounds 2-5, 6 = the wave kernel at every call size), read at create
 };
 
@@ -828,9 +828,6 @@ int fftfilt_lds_pick(int taps_len)
 
 void fftfilt_lds_destroy(FftfiltLds *p)
 {
-    if (!p) return;
-    (void)hipFree(p->d_hperm); (void)hipFree(p->d_tw1); (void)hipFree(p->d_tws); (void)hipFree(p->d_hist[0]); (void)hipFree(p->d_hist[1]);
-    (void)hipFree(p->d_hw); (void)hipFree(p->d_twl); (void)hipFree(p->d_tw2);
     delete p;
 }
 
@@ -840,53 +837,53 @@ int fftfilt_lds_set_taps(FftfiltLds *p, hipStream_t st, const cf32 *taps, int ta
     if (p->wave) {
         std::vector<float2> hw, twl; fw_host_tables(taps, taps_len, hw, twl);
         CSDR_HIP(hipStreamSynchronize(st));
-        CSDR_HIP(hipMemcpy(p->d_hw, hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_twl, twl.data(), sizeof(float2) * twl.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_hw.get(), hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_twl.get(), twl.data(), sizeof(float2) * twl.size(), hipMemcpyHostToDevice));
     }                                                                   // (and the 256-thread kernel's tables: it takes the calls with an odd sample count)
     if (p->team) {
         std::vector<float2> hw, t1, t2;
         if (p->n == 8192) ft_host_tables<2>(taps, taps_len, hw, t1, t2); else ft_host_tables<4>(taps, taps_len, hw, t1, t2);
         CSDR_HIP(hipStreamSynchronize(st));
-        CSDR_HIP(hipMemcpy(p->d_hw, hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_twl, t1.data(), sizeof(float2) * t1.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_tw2, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_hw.get(), hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_twl.get(), t1.data(), sizeof(float2) * t1.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_tw2.get(), t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
     }
     if (p->n == 4096) ffl_host_tables<4096>(taps, taps_len, hperm, tw1, tws);
     else if (p->n == 8192) ffl_host_tables<8192>(taps, taps_len, hperm, tw1, tws);
     else ffl_host_tables<16384>(taps, taps_len, hperm, tw1, tws);
     CSDR_HIP(hipStreamSynchronize(st));
-    CSDR_HIP(hipMemcpy(p->d_hperm, hperm.data(), sizeof(float2) * hperm.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_tw1, tw1.data(), sizeof(float2) * tw1.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_tws, tws.data(), sizeof(float2) * tws.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(p->d_hperm.get(), hperm.data(), sizeof(float2) * hperm.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(p->d_tw1.get(), tw1.data(), sizeof(float2) * tw1.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(p->d_tws.get(), tws.data(), sizeof(float2) * tws.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
 int fftfilt_lds_reset(FftfiltLds *p, hipStream_t st)
 {
-    CSDR_HIP(hipMemsetAsync(p->d_hist[0], 0, sizeof(float2) * (size_t)p->n_streams * (p->k1p + 16), st));
-    CSDR_HIP(hipMemsetAsync(p->d_hist[1], 0, sizeof(float2) * (size_t)p->n_streams * (p->k1p + 16), st));
+    CSDR_HIP(hipMemsetAsync(p->d_hist[0].get(), 0, sizeof(float2) * (size_t)p->n_streams * (p->k1p + 16), st));
+    CSDR_HIP(hipMemsetAsync(p->d_hist[1].get(), 0, sizeof(float2) * (size_t)p->n_streams * (p->k1p + 16), st));
     p->flip = 0;
     return 0;
 }
 
 FftfiltLds *fftfilt_lds_create(hipStream_t st, int n, const cf32 *taps, int taps_len, int n_streams)
 {
-    FftfiltLds *p = new FftfiltLds();
+    std::unique_ptr<FftfiltLds> p(new FftfiltLds());
     p->n = n; p->taps_len = taps_len; p->k1p = (taps_len - 1 + 15) & ~15; p->n_streams = n_streams; p->flip = 0;
     p->mode = getenv("CSDR_AMD_FFTFILT_LDS_MODE") ? atoi(getenv("CSDR_AMD_FFTFILT_LDS_MODE")) : 0;
-    p->d_hperm = p->d_tw1 = p->d_tws = p->d_hist[0] = p->d_hist[1] = p->d_hw = p->d_twl = p->d_tw2 = nullptr; p->last = nullptr;
+    p->last = nullptr;
     p->wave = n == 4096 && (p->mode == 0 || p->mode == 6);        // 4096-point windows: one wave per window; CSDR_AMD_FFTFILT_LDS_MODE=5 (A/B): the 256-thread kernel of rounds 2-5
     p->team = (n == 8192 || n == 16384) && (p->mode == 0 || p->mode == 6);      // a team of 2 / 4 waves per window; CSDR_AMD_FFTFILT_LDS_MODE=5: the 512-thread kernels of rounds 2-6
-    hipError_t e = hipMalloc((void **)&p->d_hperm, sizeof(float2) * n);
-    if ((p->wave || p->team) && e == hipSuccess) e = hipMalloc((void **)&p->d_hw, sizeof(float2) * n);
-    if ((p->wave || p->team) && e == hipSuccess) e = hipMalloc((void **)&p->d_twl, sizeof(float2) * FW_TWE * (n / 64));
-    if (p->team && e == hipSuccess) e = hipMalloc((void **)&p->d_tw2, sizeof(float2) * FW_TWE * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_tw1, sizeof(float2) * (n / 16));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_tws, sizeof(float2) * (n / 16));
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&p->d_hist[i], sizeof(float2) * (size_t)n_streams * (p->k1p + 16));
-    if (e != hipSuccess) { fail(e, "hipMalloc(fftfilt_lds)", __FILE__, __LINE__); fftfilt_lds_destroy(p); return nullptr; }
-    if (fftfilt_lds_set_taps(p, st, taps, taps_len) || fftfilt_lds_reset(p, st)) { fftfilt_lds_destroy(p); return nullptr; }
-    return p;
+    hipError_t e = dev_alloc(p->d_hperm, sizeof(float2) * n);
+    if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(p->d_hw, sizeof(float2) * n);
+    if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(p->d_twl, sizeof(float2) * FW_TWE * (n / 64));
+    if (p->team && e == hipSuccess) e = dev_alloc(p->d_tw2, sizeof(float2) * FW_TWE * 4);
+    if (e == hipSuccess) e = dev_alloc(p->d_tw1, sizeof(float2) * (n / 16));
+    if (e == hipSuccess) e = dev_alloc(p->d_tws, sizeof(float2) * (n / 16));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = dev_alloc(p->d_hist[i], sizeof(float2) * (size_t)n_streams * (p->k1p + 16));
+    if (e != hipSuccess) { fail(e, "hipMalloc(fftfilt_lds)", __FILE__, __LINE__); return nullptr; }
+    if (fftfilt_lds_set_taps(p.get(), st, taps, taps_len) || fftfilt_lds_reset(p.get(), st)) return nullptr;
+    return p.release();
 }
 
 const char *fftfilt_lds_kernel_name(const FftfiltLds *p) { return p->last ? p->last : p->wave ? "k_fftfilt_wave" : p->team ? (p->n == 8192 ? "k_fftfilt_team<2>" : "k_fftfilt_team<4>") : p->n == 4096 ? "k_fftfilt_lds<4096>" : p->n == 8192 ? "k_fftfilt_lds<8192>" : "k_fftfilt_lds<16384>"; }
@@ -907,8 +904,8 @@ static int ffl_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_p
     if (grid > n_windows) grid = n_windows;
     grid = (grid + 7) & ~7L;
     hipLaunchKernelGGL((k_fftfilt_lds<N, PF, MINWG, HOIST, LPT>), dim3((unsigned)grid), dim3(G::T / LPT), G::LDS_BYTES, st, (const float2 *)in, in_pitch,
-                       (const float2 *)p->d_hist[p->flip], p->k1p, (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hperm,
-                       (const float2 *)p->d_tw1, (const float2 *)p->d_tws);
+                       (const float2 *)p->d_hist[p->flip].get(), p->k1p, (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hperm.get(),
+                       (const float2 *)p->d_tw1.get(), (const float2 *)p->d_tws.get());
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -925,8 +922,8 @@ static int fw_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pi
     const long need = (n_windows + FW_WAVES - 1) / FW_WAVES;
     if (grid > need) grid = need;
     grid = (grid + 7) & ~7L;
-    hipLaunchKernelGGL(k_fftfilt_wave, dim3((unsigned)grid), dim3(64 * FW_WAVES), lds_bytes, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip], p->k1p,
-                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw, (const float2 *)p->d_twl);
+    hipLaunchKernelGGL(k_fftfilt_wave, dim3((unsigned)grid), dim3(64 * FW_WAVES), lds_bytes, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
+                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get());
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -943,8 +940,8 @@ static int ft_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pi
     long grid = (long)current_device_cu_count() * (8 / M);             // eight waves per CU: two per SIMD at 256 registers
     if (grid > n_windows) grid = n_windows;
     grid = (grid + 7) & ~7L;
-    hipLaunchKernelGGL(k_fftfilt_team<M>, dim3((unsigned)grid), dim3(64 * M), G::LDS_BYTES, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip], p->k1p,
-                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw, (const float2 *)p->d_twl, (const float2 *)p->d_tw2);
+    hipLaunchKernelGGL(k_fftfilt_team<M>, dim3((unsigned)grid), dim3(64 * M), G::LDS_BYTES, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
+                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get(), (const float2 *)p->d_tw2.get());
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -969,8 +966,8 @@ int fftfilt_lds_process(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in
     else rc = ffl_launch<16384, false, 1, false, 2>(p, st, in, in_pitch, m_new, out, out_pitch);
     if (rc) return rc;
     if (p->k1p > 0) {
-        hipLaunchKernelGGL(k_fftfilt_hist, dim3(cdiv(p->k1p, 256), p->n_streams), dim3(256), 0, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip],
-                           p->d_hist[p->flip ^ 1], p->k1p, m_new);
+        hipLaunchKernelGGL(k_fftfilt_hist, dim3(cdiv(p->k1p, 256), p->n_streams), dim3(256), 0, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(),
+                           p->d_hist[p->flip ^ 1].get(), p->k1p, m_new);
         CSDR_LAUNCH_CHECK();
         p->flip ^= 1;
     }

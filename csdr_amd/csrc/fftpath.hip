@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void k_scale_add(cf32 *__restrict__ io, size_t
 } // namespace
 
 // cached single-transform plans for the drop-in FFT layer
-static std::map<std::pair<int, long>, hipfftHandle> g_c2c_plans;
+static std::map<std::pair<int, long>, FftPlan> g_c2c_plans;
 static std::mutex g_c2c_mu;      // the map is shared by every context (the drop-in layer has one context per host thread)
 
 namespace csdr_amd {
@@ -269,7 +269,7 @@ void drop_fft_plans(hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(g_c2c_mu);
     for (auto it = g_c2c_plans.begin(); it != g_c2c_plans.end();) {
-        if (it->first.second == (long)(uintptr_t)st) { hipfftDestroy(it->second); it = g_c2c_plans.erase(it); } else ++it;
+        if (it->first.second == (long)(uintptr_t)st) it = g_c2c_plans.erase(it); else ++it;
     }
 }
 }
@@ -285,10 +285,11 @@ int csdr_amd_fft_c2c(csdr_amd_ctx *c, const csdr_complexf *in, csdr_complexf *ou
         if (!g_c2c_plans.count(key)) {
             hipfftHandle h;
             CSDR_FFT(hipfftPlan1d(&h, n, HIPFFT_C2C, 1));
+            FftPlan owned(h);
             CSDR_FFT(hipfftSetStream(h, c->stream));
-            g_c2c_plans[key] = h;
+            g_c2c_plans[key] = std::move(owned);
         }
-        plan = g_c2c_plans[key];
+        plan = g_c2c_plans[key].get();
     }
     CSDR_FFT(hipfftExecC2C(plan, (hipfftComplex *)in, (hipfftComplex *)out, forward ? HIPFFT_FORWARD : HIPFFT_BACKWARD));
     return 0;
@@ -331,21 +332,22 @@ int fft64k_filter_oa(hipStream_t st, const cf32 *in, size_t in_pitch, int inp, i
 struct csdr_amd_fftfilt {
     csdr_amd_ctx *ctx;
     int fft, taps_len, inp, ovl, n_streams, max_blocks;
-    cf32 *d_taps_fft, *d_pad, *d_td, *d_carry[2];
-    cf32 *d_taps_fft_t; float2 *d_tw;      // fft_size 65536: taps spectrum in [k1][k2] order and the twiddle tables of the three-pass transform (fft64k.hip)
+    DevBuf<cf32> d_taps_fft, d_pad, d_td, d_carry[2];
+    DevBuf<cf32> d_taps_fft_t; DevBuf<float2> d_tw;      // fft_size 65536: taps spectrum in [k1][k2] order and the twiddle tables of the three-pass transform (fft64k.hip)
     int flip;
-    hipfftHandle plan_one, plan_batch; int plan_batch_n;
-    csdr_amd::FftfiltLds *lds;             // taps short enough for LDS-sized windows: the one-pass kernel of fftfilt_lds.hip (every other buffer stays unallocated)
+    FftPlan plan_one, plan_batch; int plan_batch_n;
+    Owned<FftfiltLds, fftfilt_lds_destroy> lds;      // taps short enough for LDS-sized windows: the one-pass kernel of fftfilt_lds.hip (every other buffer stays unallocated)
 };
 
 
 static int fftfilt_make_batch_plan(csdr_amd_fftfilt *f, int batch)
 {
     if (f->plan_batch_n == batch) return 0;
-    if (f->plan_batch_n) { hipfftDestroy(f->plan_batch); f->plan_batch_n = 0; }
-    int n[1] = {f->fft};
-    CSDR_FFT(hipfftPlanMany(&f->plan_batch, 1, n, nullptr, 1, f->fft, nullptr, 1, f->fft, HIPFFT_C2C, batch));
-    CSDR_FFT(hipfftSetStream(f->plan_batch, f->ctx->stream));
+    if (f->plan_batch_n) { f->plan_batch.reset(); f->plan_batch_n = 0; }
+    int n[1] = {f->fft}; hipfftHandle h;
+    CSDR_FFT(hipfftPlanMany(&h, 1, n, nullptr, 1, f->fft, nullptr, 1, f->fft, HIPFFT_C2C, batch));
+    f->plan_batch.reset(h);
+    CSDR_FFT(hipfftSetStream(h, f->ctx->stream));
     f->plan_batch_n = batch;
     return 0;
 }
@@ -355,13 +357,13 @@ extern "C" {
 int csdr_amd_fftfilt_set_taps(csdr_amd_fftfilt *f, const csdr_complexf *host_taps, int taps_length)
 {   // csdr.c:1869-1871: zero padded taps -> forward FFT
     if (taps_length != f->taps_len) return fail_msg(-3, "fftfilt: taps_length changed (%d -> %d); create a new filter", f->taps_len, taps_length);
-    if (f->lds) return fftfilt_lds_set_taps(f->lds, f->ctx->stream, host_taps, taps_length);
+    if (f->lds) return fftfilt_lds_set_taps(f->lds.get(), f->ctx->stream, host_taps, taps_length);
     std::vector<cf32> pad((size_t)f->fft, cf32{0.f, 0.f});
     for (int k = 0; k < taps_length; k++) pad[k] = host_taps[k];
     CSDR_HIP(hipStreamSynchronize(f->ctx->stream));
-    CSDR_HIP(hipMemcpy(f->d_taps_fft, pad.data(), sizeof(cf32) * f->fft, hipMemcpyHostToDevice));
-    CSDR_FFT(hipfftExecC2C(f->plan_one, (hipfftComplex *)f->d_taps_fft, (hipfftComplex *)f->d_taps_fft, HIPFFT_FORWARD));
-    if (f->d_taps_fft_t) return fft64k_transpose_taps(f->ctx->stream, f->d_taps_fft, f->d_taps_fft_t);
+    CSDR_HIP(hipMemcpy(f->d_taps_fft.get(), pad.data(), sizeof(cf32) * f->fft, hipMemcpyHostToDevice));
+    CSDR_FFT(hipfftExecC2C(f->plan_one.get(), (hipfftComplex *)f->d_taps_fft.get(), (hipfftComplex *)f->d_taps_fft.get(), HIPFFT_FORWARD));
+    if (f->d_taps_fft_t) return fft64k_transpose_taps(f->ctx->stream, f->d_taps_fft.get(), f->d_taps_fft_t.get());
     return 0;
 }
 
@@ -369,55 +371,51 @@ csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const
 {
     if (fft_size < 4 || (fft_size & (fft_size - 1)) || taps_length < 1 || taps_length > fft_size || n_streams < 1 || max_blocks < 1) {
         fail_msg(-3, "fftfilt: need power-of-two fft_size >= taps_length"); return nullptr; }
-    csdr_amd_fftfilt *f = new csdr_amd_fftfilt();
+    Owned<csdr_amd_fftfilt, csdr_amd_fftfilt_destroy> f(new csdr_amd_fftfilt());
     f->ctx = ctx; f->fft = fft_size; f->taps_len = taps_length; f->inp = fft_size - taps_length + 1; f->ovl = taps_length - 1;
     f->n_streams = n_streams; f->max_blocks = max_blocks; f->flip = 0; f->plan_batch_n = 0;
-    f->lds = nullptr; f->d_taps_fft = f->d_pad = f->d_td = f->d_carry[0] = f->d_carry[1] = f->d_taps_fft_t = nullptr; f->d_tw = nullptr; f->plan_one = 0;
     if (const int win = fftfilt_lds_pick(taps_length)) {
-        f->lds = fftfilt_lds_create(ctx->stream, win, host_taps, taps_length, n_streams);
-        if (!f->lds) { delete f; return nullptr; }
-        return f;
+        f->lds.reset(fftfilt_lds_create(ctx->stream, win, host_taps, taps_length, n_streams));
+        if (!f->lds) return nullptr;
+        return f.release();
     }
     const size_t tot = (size_t)n_streams * max_blocks * fft_size;
-    hipError_t e = hipMalloc((void **)&f->d_taps_fft, sizeof(cf32) * fft_size);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_pad, sizeof(cf32) * tot);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_td, sizeof(cf32) * tot);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_carry[0], sizeof(cf32) * (size_t)n_streams * (f->ovl + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_carry[1], sizeof(cf32) * (size_t)n_streams * (f->ovl + 1));
-    f->d_taps_fft_t = nullptr; f->d_tw = nullptr;
+    hipError_t e = dev_alloc(f->d_taps_fft, sizeof(cf32) * fft_size);
+    if (e == hipSuccess) e = dev_alloc(f->d_pad, sizeof(cf32) * tot);
+    if (e == hipSuccess) e = dev_alloc(f->d_td, sizeof(cf32) * tot);
+    if (e == hipSuccess) e = dev_alloc(f->d_carry[0], sizeof(cf32) * (size_t)n_streams * (f->ovl + 1));
+    if (e == hipSuccess) e = dev_alloc(f->d_carry[1], sizeof(cf32) * (size_t)n_streams * (f->ovl + 1));
     if (fft_size == 65536 && !getenv("CSDR_AMD_FFT64K_OFF")) {          // config 3: the three-pass transform of fft64k.hip instead of hipFFT
-        if (e == hipSuccess) e = hipMalloc((void **)&f->d_taps_fft_t, sizeof(cf32) * fft_size);
-        if (e == hipSuccess) e = hipMalloc((void **)&f->d_tw, sizeof(float2) * 512);
-        if (e == hipSuccess && fft64k_upload_tables(f->d_tw)) e = hipErrorUnknown;
+        if (e == hipSuccess) e = dev_alloc(f->d_taps_fft_t, sizeof(cf32) * fft_size);
+        if (e == hipSuccess) e = dev_alloc(f->d_tw, sizeof(float2) * 512);
+        if (e == hipSuccess && fft64k_upload_tables(f->d_tw.get())) e = hipErrorUnknown;
     }
-    if (e != hipSuccess) { fail(e, "hipMalloc(fftfilt)", __FILE__, __LINE__); delete f; return nullptr; }
-    if (hipfftPlan1d(&f->plan_one, fft_size, HIPFFT_C2C, 1) != HIPFFT_SUCCESS) { fail_msg(-5, "hipfftPlan1d(%d) failed", fft_size); delete f; return nullptr; }
-    hipfftSetStream(f->plan_one, ctx->stream);
-    if (csdr_amd_fftfilt_set_taps(f, host_taps, taps_length) || csdr_amd_fftfilt_reset(f)) { delete f; return nullptr; }
-    return f;
+    if (e != hipSuccess) { fail(e, "hipMalloc(fftfilt)", __FILE__, __LINE__); return nullptr; }
+    hipfftHandle h;
+    if (hipfftPlan1d(&h, fft_size, HIPFFT_C2C, 1) != HIPFFT_SUCCESS) { fail_msg(-5, "hipfftPlan1d(%d) failed", fft_size); return nullptr; }
+    f->plan_one.reset(h);
+    hipfftSetStream(h, ctx->stream);
+    if (csdr_amd_fftfilt_set_taps(f.get(), host_taps, taps_length) || csdr_amd_fftfilt_reset(f.get())) return nullptr;
+    return f.release();
 }
 
 void csdr_amd_fftfilt_destroy(csdr_amd_fftfilt *f)
 {
     if (!f) return;
     (void)hipStreamSynchronize(f->ctx->stream);
-    if (f->lds) { fftfilt_lds_destroy(f->lds); delete f; return; }
-    hipfftDestroy(f->plan_one); if (f->plan_batch_n) hipfftDestroy(f->plan_batch);
-    (void)hipFree(f->d_taps_fft); (void)hipFree(f->d_pad); (void)hipFree(f->d_td); (void)hipFree(f->d_carry[0]); (void)hipFree(f->d_carry[1]);
-    (void)hipFree(f->d_taps_fft_t); (void)hipFree(f->d_tw);
     delete f;
 }
 
 int csdr_amd_fftfilt_input_size(const csdr_amd_fftfilt *f) { return f->inp; }
 /* which path serves this filter: the one-pass kernel's name and its window size, or "" / 0 */
-const char *csdr_amd_fftfilt_kernel_name(const csdr_amd_fftfilt *f) { return f->lds ? fftfilt_lds_kernel_name(f->lds) : ""; }
-int csdr_amd_fftfilt_window(const csdr_amd_fftfilt *f) { return f->lds ? fftfilt_lds_window(f->lds) : 0; }
+const char *csdr_amd_fftfilt_kernel_name(const csdr_amd_fftfilt *f) { return f->lds ? fftfilt_lds_kernel_name(f->lds.get()) : ""; }
+int csdr_amd_fftfilt_window(const csdr_amd_fftfilt *f) { return f->lds ? fftfilt_lds_window(f->lds.get()) : 0; }
 
 int csdr_amd_fftfilt_reset(csdr_amd_fftfilt *f)
 {   // csdr.c:1862: the first block's overlap source is all zeros
-    if (f->lds) return fftfilt_lds_reset(f->lds, f->ctx->stream);
-    CSDR_HIP(hipMemsetAsync(f->d_carry[0], 0, sizeof(cf32) * (size_t)f->n_streams * (f->ovl + 1), f->ctx->stream));
-    CSDR_HIP(hipMemsetAsync(f->d_carry[1], 0, sizeof(cf32) * (size_t)f->n_streams * (f->ovl + 1), f->ctx->stream));
+    if (f->lds) return fftfilt_lds_reset(f->lds.get(), f->ctx->stream);
+    CSDR_HIP(hipMemsetAsync(f->d_carry[0].get(), 0, sizeof(cf32) * (size_t)f->n_streams * (f->ovl + 1), f->ctx->stream));
+    CSDR_HIP(hipMemsetAsync(f->d_carry[1].get(), 0, sizeof(cf32) * (size_t)f->n_streams * (f->ovl + 1), f->ctx->stream));
     f->flip = 0;
     return 0;
 }
@@ -427,31 +425,31 @@ int csdr_amd_fftfilt_process(csdr_amd_fftfilt *f, const csdr_complexf *in, csdr_
     if (n_blocks <= 0) return 0;
     if (n_blocks > f->max_blocks) return fail_msg(-3, "fftfilt: %d blocks exceed max_blocks %d", n_blocks, f->max_blocks);
     hipStream_t st = f->ctx->stream;
-    if (f->lds) return fftfilt_lds_process(f->lds, st, in, in_pitch, (long)n_blocks * f->inp, out, out_pitch);
+    if (f->lds) return fftfilt_lds_process(f->lds.get(), st, in, in_pitch, (long)n_blocks * f->inp, out, out_pitch);
     const int batch = f->n_streams * n_blocks;
     int rc = 0;
     if (f->d_taps_fft_t && f->ovl <= f->inp) {
         // three passes + a pass over the overlap regions only; the inverse pass writes the output itself (d_td only holds the blocks' tails)
-        rc = fft64k_filter_oa(st, in, in_pitch, f->inp, f->ovl, n_blocks, f->n_streams, f->d_pad, f->d_taps_fft_t, f->d_tw, f->d_td, f->d_carry[f->flip], f->d_carry[f->flip ^ 1], out, out_pitch);
+        rc = fft64k_filter_oa(st, in, in_pitch, f->inp, f->ovl, n_blocks, f->n_streams, f->d_pad.get(), f->d_taps_fft_t.get(), f->d_tw.get(), f->d_td.get(), f->d_carry[f->flip].get(), f->d_carry[f->flip ^ 1].get(), out, out_pitch);
         if (rc) return rc;
         if (f->ovl > 0) f->flip ^= 1;
         return 0;
     }
     if (f->d_taps_fft_t) {
-        rc = fft64k_filter(st, in, in_pitch, f->inp, n_blocks, f->n_streams, f->d_pad, f->d_taps_fft_t, f->d_tw, f->d_td); if (rc) return rc;
+        rc = fft64k_filter(st, in, in_pitch, f->inp, n_blocks, f->n_streams, f->d_pad.get(), f->d_taps_fft_t.get(), f->d_tw.get(), f->d_td.get()); if (rc) return rc;
     } else {
     rc = fftfilt_make_batch_plan(f, batch); if (rc) return rc;
-    hipLaunchKernelGGL(k_oa_frame, dim3(cdiv(f->fft, 256), n_blocks, f->n_streams), dim3(256), 0, st, in, in_pitch, f->d_pad, f->fft, f->inp, n_blocks); CSDR_LAUNCH_CHECK();
-    CSDR_FFT(hipfftExecC2C(f->plan_batch, (hipfftComplex *)f->d_pad, (hipfftComplex *)f->d_pad, HIPFFT_FORWARD));
+    hipLaunchKernelGGL(k_oa_frame, dim3(cdiv(f->fft, 256), n_blocks, f->n_streams), dim3(256), 0, st, in, in_pitch, f->d_pad.get(), f->fft, f->inp, n_blocks); CSDR_LAUNCH_CHECK();
+    CSDR_FFT(hipfftExecC2C(f->plan_batch.get(), (hipfftComplex *)f->d_pad.get(), (hipfftComplex *)f->d_pad.get(), HIPFFT_FORWARD));
     const size_t total = (size_t)batch * f->fft;
-    hipLaunchKernelGGL(k_bin_product, dim3(cdiv(total, 256)), dim3(256), 0, st, f->d_pad, f->d_taps_fft, f->fft, total); CSDR_LAUNCH_CHECK();
-    CSDR_FFT(hipfftExecC2C(f->plan_batch, (hipfftComplex *)f->d_pad, (hipfftComplex *)f->d_td, HIPFFT_BACKWARD));
+    hipLaunchKernelGGL(k_bin_product, dim3(cdiv(total, 256)), dim3(256), 0, st, f->d_pad.get(), f->d_taps_fft.get(), f->fft, total); CSDR_LAUNCH_CHECK();
+    CSDR_FFT(hipfftExecC2C(f->plan_batch.get(), (hipfftComplex *)f->d_pad.get(), (hipfftComplex *)f->d_td.get(), HIPFFT_BACKWARD));
     }
     const float inv_n = 1.0f / (float)f->fft;
-    hipLaunchKernelGGL(k_oa_stitch, dim3(cdiv(f->inp, 256), n_blocks, f->n_streams), dim3(256), 0, st, f->d_td, f->d_carry[f->flip], out, out_pitch,
+    hipLaunchKernelGGL(k_oa_stitch, dim3(cdiv(f->inp, 256), n_blocks, f->n_streams), dim3(256), 0, st, f->d_td.get(), f->d_carry[f->flip].get(), out, out_pitch,
                        f->fft, f->inp, f->ovl, n_blocks, inv_n); CSDR_LAUNCH_CHECK();
     if (f->ovl > 0) {
-        hipLaunchKernelGGL(k_oa_carry, dim3(cdiv(f->ovl, 256), f->n_streams), dim3(256), 0, st, f->d_td, f->d_carry[f->flip], f->d_carry[f->flip ^ 1],
+        hipLaunchKernelGGL(k_oa_carry, dim3(cdiv(f->ovl, 256), f->n_streams), dim3(256), 0, st, f->d_td.get(), f->d_carry[f->flip].get(), f->d_carry[f->flip ^ 1].get(),
                            f->fft, f->inp, f->ovl, n_blocks, inv_n); CSDR_LAUNCH_CHECK();
         f->flip ^= 1;
     }
@@ -463,31 +461,29 @@ int csdr_amd_fftfilt_process(csdr_amd_fftfilt *f, const csdr_complexf *in, csdr_
 // ====================================================================================== fastddc forward
 struct csdr_amd_fastddc_fwd {
     csdr_amd_ctx *ctx; csdr_fastddc_t ddc; int max_blocks;
-    cf32 *d_win, *d_tail[2]; int flip;
-    std::map<int, hipfftHandle> plans;
+    DevBuf<cf32> d_win, d_tail[2]; int flip;
+    std::map<int, FftPlan> plans;
 };
 
 extern "C" {
 
 csdr_amd_fastddc_fwd *csdr_amd_fastddc_fwd_create(csdr_amd_ctx *ctx, const csdr_fastddc_t *ddc, int max_blocks)
 {
-    csdr_amd_fastddc_fwd *f = new csdr_amd_fastddc_fwd();
+    Owned<csdr_amd_fastddc_fwd, csdr_amd_fastddc_fwd_destroy> f(new csdr_amd_fastddc_fwd());
     f->ctx = ctx; f->ddc = *ddc; f->max_blocks = max_blocks; f->flip = 0;
-    hipError_t e = hipMalloc((void **)&f->d_win, sizeof(cf32) * (size_t)max_blocks * ddc->fft_size);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_tail[0], sizeof(cf32) * (size_t)(ddc->overlap_length + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_tail[1], sizeof(cf32) * (size_t)(ddc->overlap_length + 1));
-    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc_fwd)", __FILE__, __LINE__); delete f; return nullptr; }
-    (void)hipMemsetAsync(f->d_tail[0], 0, sizeof(cf32) * (size_t)(ddc->overlap_length + 1), ctx->stream);   // csdr.c:2279 null input buffer
-    (void)hipMemsetAsync(f->d_tail[1], 0, sizeof(cf32) * (size_t)(ddc->overlap_length + 1), ctx->stream);
-    return f;
+    hipError_t e = dev_alloc(f->d_win, sizeof(cf32) * (size_t)max_blocks * ddc->fft_size);
+    if (e == hipSuccess) e = dev_alloc(f->d_tail[0], sizeof(cf32) * (size_t)(ddc->overlap_length + 1));
+    if (e == hipSuccess) e = dev_alloc(f->d_tail[1], sizeof(cf32) * (size_t)(ddc->overlap_length + 1));
+    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc_fwd)", __FILE__, __LINE__); return nullptr; }
+    (void)hipMemsetAsync(f->d_tail[0].get(), 0, sizeof(cf32) * (size_t)(ddc->overlap_length + 1), ctx->stream);   // csdr.c:2279 null input buffer
+    (void)hipMemsetAsync(f->d_tail[1].get(), 0, sizeof(cf32) * (size_t)(ddc->overlap_length + 1), ctx->stream);
+    return f.release();
 }
 
 void csdr_amd_fastddc_fwd_destroy(csdr_amd_fastddc_fwd *f)
 {
     if (!f) return;
     (void)hipStreamSynchronize(f->ctx->stream);
-    for (auto &kv : f->plans) hipfftDestroy(kv.second);
-    (void)hipFree(f->d_win); (void)hipFree(f->d_tail[0]); (void)hipFree(f->d_tail[1]);
     delete f;
 }
 
@@ -500,12 +496,13 @@ int csdr_amd_fastddc_fwd_process(csdr_amd_fastddc_fwd *f, const csdr_complexf *i
     if (!f->plans.count(n_blocks)) {
         hipfftHandle h; int n[1] = {fft};
         CSDR_FFT(hipfftPlanMany(&h, 1, n, nullptr, 1, fft, nullptr, 1, fft, HIPFFT_C2C, n_blocks));
+        FftPlan owned(h);
         CSDR_FFT(hipfftSetStream(h, st));
-        f->plans[n_blocks] = h;
+        f->plans[n_blocks] = std::move(owned);
     }
-    hipLaunchKernelGGL(k_os_frame, dim3(cdiv(fft, 256), n_blocks), dim3(256), 0, st, in, f->d_tail[f->flip], f->d_win, fft, inp, ovl); CSDR_LAUNCH_CHECK();
-    CSDR_FFT(hipfftExecC2C(f->plans[n_blocks], (hipfftComplex *)f->d_win, (hipfftComplex *)spectra, HIPFFT_FORWARD));
-    hipLaunchKernelGGL(k_os_tail, dim3(cdiv(ovl, 256)), dim3(256), 0, st, in, f->d_tail[f->flip], f->d_tail[f->flip ^ 1], inp, ovl, n_blocks); CSDR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_os_frame, dim3(cdiv(fft, 256), n_blocks), dim3(256), 0, st, in, f->d_tail[f->flip].get(), f->d_win.get(), fft, inp, ovl); CSDR_LAUNCH_CHECK();
+    CSDR_FFT(hipfftExecC2C(f->plans[n_blocks].get(), (hipfftComplex *)f->d_win.get(), (hipfftComplex *)spectra, HIPFFT_FORWARD));
+    hipLaunchKernelGGL(k_os_tail, dim3(cdiv(ovl, 256)), dim3(256), 0, st, in, f->d_tail[f->flip].get(), f->d_tail[f->flip ^ 1].get(), inp, ovl, n_blocks); CSDR_LAUNCH_CHECK();
     f->flip ^= 1;
     return 0;
 }
@@ -517,11 +514,12 @@ struct csdr_amd_fastddc_inv {
     csdr_amd_ctx *ctx; int n_channels, max_blocks;
     float tbw; int decimation, window;                             // kept for per-channel retunes
     std::vector<csdr_fastddc_t> geom;
-    cf32 *d_H, *d_inv_in, *d_td;
-    DdcMfma *mf;                                                    // matrix-core path (fastddc_mfma.hip) when the geometry is config 4's, else nullptr
-    ChanGeom *d_geom; DdcChanState *d_state;
-    int *d_blk_remain, *d_blk_off, *d_counts; float *d_blk_phase;
-    std::map<int, hipfftHandle> plans;
+    DevBuf<cf32> d_H, d_inv_in, d_td;
+    DevBuf<ChanGeom> d_geom; DevBuf<DdcChanState> d_state;
+    DevBuf<int> d_blk_remain, d_blk_off, d_counts; DevBuf<float> d_blk_phase;
+    Owned<DdcMfma, ddc_mfma_destroy> mf;                            // matrix-core path (fastddc_mfma.hip) when the geometry is config 4's, else nullptr;
+                                                                    // goes before the buffers: its side stream reads d_geom and d_state
+    std::map<int, FftPlan> plans;
     bool fold_old;                                                  // CSDR_AMD_DDC_FOLD_OLD (A/B: the untiled fold of the general path), read at create
 };
 
@@ -538,33 +536,32 @@ static csdr_amd_fastddc_inv *fastddc_inv_create_comm(csdr_amd_ctx *ctx, float tr
                                                      int n_channels, int window, int max_blocks, const DdcComm *comm)
 {
     if (n_channels < 1 || max_blocks < 1) { fail_msg(-3, "fastddc_inv: bad sizes"); return nullptr; }
-    csdr_amd_fastddc_inv *f = new csdr_amd_fastddc_inv();
+    Owned<csdr_amd_fastddc_inv, csdr_amd_fastddc_inv_destroy> f(new csdr_amd_fastddc_inv());
     f->ctx = ctx; f->n_channels = n_channels; f->max_blocks = max_blocks; f->fold_old = getenv("CSDR_AMD_DDC_FOLD_OLD") != nullptr;
     f->tbw = transition_bw; f->decimation = decimation; f->window = window;
     f->geom.resize(n_channels);
     std::vector<ChanGeom> cg(n_channels);
     for (int c = 0; c < n_channels; c++) {
-        if (csdr_amd_fastddc_init(&f->geom[c], transition_bw, decimation, shift_rates[c])) { fail_msg(-3, "fastddc_init failed (fft_size <= 2)"); delete f; return nullptr; }
+        if (csdr_amd_fastddc_init(&f->geom[c], transition_bw, decimation, shift_rates[c])) { fail_msg(-3, "fastddc_init failed (fft_size <= 2)"); return nullptr; }
         cg[c].offsetbin = f->geom[c].offsetbin; cg[c].sindelta = f->geom[c].dsadata.sindelta; cg[c].cosdelta = f->geom[c].dsadata.cosdelta; cg[c].rate2 = f->geom[c].dsadata.rate;
     }
     const csdr_fastddc_t &g = f->geom[0];
     const int fft = g.fft_size, inv = g.fft_inv_size;
-    f->d_inv_in = nullptr; f->d_td = nullptr;
-    f->mf = ddc_mfma_create(ctx, fft, inv, g.pre_decimation, n_channels, max_blocks, g.scrap, g.post_input_size, g.post_decimation, g.input_size, g.overlap_length, comm);
-    hipError_t e = hipMalloc((void **)&f->d_H, sizeof(cf32) * (size_t)n_channels * fft);
+    f->mf.reset(ddc_mfma_create(ctx, fft, inv, g.pre_decimation, n_channels, max_blocks, g.scrap, g.post_input_size, g.post_decimation, g.input_size, g.overlap_length, comm));
+    hipError_t e = dev_alloc(f->d_H, sizeof(cf32) * (size_t)n_channels * fft);
     if (!f->mf) {                                                  // the general path's [channel][block][inv] intermediates
-        if (e == hipSuccess) e = hipMalloc((void **)&f->d_inv_in, sizeof(cf32) * (size_t)n_channels * max_blocks * inv);
-        if (e == hipSuccess) e = hipMalloc((void **)&f->d_td, sizeof(cf32) * (size_t)n_channels * max_blocks * inv);
+        if (e == hipSuccess) e = dev_alloc(f->d_inv_in, sizeof(cf32) * (size_t)n_channels * max_blocks * inv);
+        if (e == hipSuccess) e = dev_alloc(f->d_td, sizeof(cf32) * (size_t)n_channels * max_blocks * inv);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_geom, sizeof(ChanGeom) * n_channels);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_state, sizeof(DdcChanState) * n_channels);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_blk_remain, sizeof(int) * (size_t)n_channels * max_blocks);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_blk_off, sizeof(int) * (size_t)n_channels * max_blocks);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_blk_phase, sizeof(float) * (size_t)n_channels * max_blocks);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->d_counts, sizeof(int) * n_channels);
-    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc_inv)", __FILE__, __LINE__); delete f; return nullptr; }
-    (void)hipMemcpy(f->d_geom, cg.data(), sizeof(ChanGeom) * n_channels, hipMemcpyHostToDevice);
-    (void)hipMemset(f->d_state, 0, sizeof(DdcChanState) * n_channels);                 // csdr.c:2363-2364 bzero(shift_stat)
+    if (e == hipSuccess) e = dev_alloc(f->d_geom, sizeof(ChanGeom) * n_channels);
+    if (e == hipSuccess) e = dev_alloc(f->d_state, sizeof(DdcChanState) * n_channels);
+    if (e == hipSuccess) e = dev_alloc(f->d_blk_remain, sizeof(int) * (size_t)n_channels * max_blocks);
+    if (e == hipSuccess) e = dev_alloc(f->d_blk_off, sizeof(int) * (size_t)n_channels * max_blocks);
+    if (e == hipSuccess) e = dev_alloc(f->d_blk_phase, sizeof(float) * (size_t)n_channels * max_blocks);
+    if (e == hipSuccess) e = dev_alloc(f->d_counts, sizeof(int) * n_channels);
+    if (e != hipSuccess) { fail(e, "hipMalloc(fastddc_inv)", __FILE__, __LINE__); return nullptr; }
+    (void)hipMemcpy(f->d_geom.get(), cg.data(), sizeof(ChanGeom) * n_channels, hipMemcpyHostToDevice);
+    (void)hipMemset(f->d_state.get(), 0, sizeof(DdcChanState) * n_channels);                 // csdr.c:2363-2364 bzero(shift_stat)
     // per channel band-pass taps (csdr.c:2345-2349), zero padded, FFT'd in one batch, then fft_swap_sides (csdr.c:2350-2351)
     {
         std::vector<cf32> taps((size_t)n_channels * fft, cf32{0.f, 0.f});
@@ -574,7 +571,7 @@ static csdr_amd_fastddc_inv *fastddc_inv_create_comm(csdr_amd_ctx *ctx, float tr
             csdr_amd_firdes_bandpass_c(one.data(), g.taps_length, (-shift_rates[c]) - half_bw, (-shift_rates[c]) + half_bw, window);
             for (int k = 0; k < g.taps_length; k++) taps[(size_t)c * fft + k] = one[k];
         }
-        (void)hipMemcpy(f->d_H, taps.data(), sizeof(cf32) * taps.size(), hipMemcpyHostToDevice);
+        (void)hipMemcpy(f->d_H.get(), taps.data(), sizeof(cf32) * taps.size(), hipMemcpyHostToDevice);
         // The batched plan for the taps is kept for the life of the process, one per (fft, channels), used under a lock: creating AND destroying a plan per
         // object made the create of a SECOND object in a process fault now and then inside this block (GPU memory access fault at addresses of a few MiB, before
         // the new object had processed anything; about one create in five behind a bench run -- profiles/r4_notes.md; not seen once the plan survives).
@@ -587,18 +584,18 @@ static csdr_amd_fastddc_inv *fastddc_inv_create_comm(csdr_amd_ctx *ctx, float tr
         const auto key = std::make_tuple(ctx->device, fft, n_channels);
         if (!taps_plans.count(key)) {
             hipfftHandle h; int n[1] = {fft};
-            if (hipfftPlanMany(&h, 1, n, nullptr, 1, fft, nullptr, 1, fft, HIPFFT_C2C, n_channels) != HIPFFT_SUCCESS) { fail_msg(-5, "hipfftPlanMany(taps) failed"); delete f; return nullptr; }
+            if (hipfftPlanMany(&h, 1, n, nullptr, 1, fft, nullptr, 1, fft, HIPFFT_C2C, n_channels) != HIPFFT_SUCCESS) { fail_msg(-5, "hipfftPlanMany(taps) failed"); return nullptr; }
             taps_plans[key] = h;
         }
         hipfftHandle h = taps_plans[key];
         hipfftSetStream(h, ctx->stream);
-        hipfftExecC2C(h, (hipfftComplex *)f->d_H, (hipfftComplex *)f->d_H, HIPFFT_FORWARD);
+        hipfftExecC2C(h, (hipfftComplex *)f->d_H.get(), (hipfftComplex *)f->d_H.get(), HIPFFT_FORWARD);
         const size_t total = (size_t)n_channels * fft;
-        hipLaunchKernelGGL(k_swap_halves, dim3(cdiv(total / 2, 256)), dim3(256), 0, ctx->stream, f->d_H, fft, total);
-        if (f->mf && ddc_mfma_set_taps(f->mf, ctx->stream, f->d_H, 0, n_channels)) { delete f; return nullptr; }
+        hipLaunchKernelGGL(k_swap_halves, dim3(cdiv(total / 2, 256)), dim3(256), 0, ctx->stream, f->d_H.get(), fft, total);
+        if (f->mf && ddc_mfma_set_taps(f->mf.get(), ctx->stream, f->d_H.get(), 0, n_channels)) return nullptr;
         (void)hipStreamSynchronize(ctx->stream);
     }
-    return f;
+    return f.release();
 }
 
 // Retune ONE channel: what `csdr fastddc_inv_cc --fd` does when a new rate arrives (csdr.c:2329-2376: geometry, band-pass taps, their FFT and the
@@ -615,16 +612,16 @@ int csdr_amd_fastddc_inv_set_rate(csdr_amd_fastddc_inv *f, int channel, float sh
     std::vector<cf32> taps((size_t)fft, cf32{0.f, 0.f});
     const float half_bw = 0.5f / (float)f->decimation;
     csdr_amd_firdes_bandpass_c((csdr_complexf *)taps.data(), g.taps_length, (-shift_rate) - half_bw, (-shift_rate) + half_bw, f->window);
-    if (f->mf) { const int qrc = ddc_mfma_quiesce(f->mf); if (qrc) return qrc; }   // staged calls read the tables on a side stream
+    if (f->mf) { const int qrc = ddc_mfma_quiesce(f->mf.get()); if (qrc) return qrc; }   // staged calls read the tables on a side stream
     CSDR_HIP(hipStreamSynchronize(ctx->stream));                     // the previous process() call may still read this channel's row
-    CSDR_HIP(hipMemcpy(f->d_geom + channel, &cg, sizeof(ChanGeom), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemset(f->d_state + channel, 0, sizeof(DdcChanState)));
-    cf32 *row = f->d_H + (size_t)channel * fft;
+    CSDR_HIP(hipMemcpy(f->d_geom.get() + channel, &cg, sizeof(ChanGeom), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemset(f->d_state.get() + channel, 0, sizeof(DdcChanState)));
+    cf32 *row = f->d_H.get() + (size_t)channel * fft;
     CSDR_HIP(hipMemcpy(row, taps.data(), sizeof(cf32) * (size_t)fft, hipMemcpyHostToDevice));
     int rc = csdr_amd_fft_c2c(ctx, (const csdr_complexf *)row, (csdr_complexf *)row, fft, 1); if (rc) return rc;
     hipLaunchKernelGGL(k_swap_halves, dim3(cdiv((size_t)fft / 2, 256)), dim3(256), 0, ctx->stream, row, fft, (size_t)fft);
     CSDR_LAUNCH_CHECK();
-    if (f->mf) { rc = ddc_mfma_set_taps(f->mf, ctx->stream, f->d_H, channel, 1); if (rc) return rc; }
+    if (f->mf) { rc = ddc_mfma_set_taps(f->mf.get(), ctx->stream, f->d_H.get(), channel, 1); if (rc) return rc; }
     CSDR_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -633,24 +630,20 @@ void csdr_amd_fastddc_inv_destroy(csdr_amd_fastddc_inv *f)
 {
     if (!f) return;
     (void)hipStreamSynchronize(f->ctx->stream);
-    for (auto &kv : f->plans) hipfftDestroy(kv.second);
-    ddc_mfma_destroy(f->mf);
-    (void)hipFree(f->d_H); (void)hipFree(f->d_inv_in); (void)hipFree(f->d_td); (void)hipFree(f->d_geom); (void)hipFree(f->d_state);
-    (void)hipFree(f->d_blk_remain); (void)hipFree(f->d_blk_off); (void)hipFree(f->d_blk_phase); (void)hipFree(f->d_counts);
     delete f;
 }
 
-const char *csdr_amd_fastddc_inv_kernel_name(const csdr_amd_fastddc_inv *f) { return f->mf ? ddc_mfma_kernel_name(f->mf) : "k_ddc_fold_ct"; }
-int csdr_amd_fastddc_inv_set_profiling(csdr_amd_fastddc_inv *f, int on) { return f->mf ? ddc_mfma_set_profiling(f->mf, on) : 0; }
+const char *csdr_amd_fastddc_inv_kernel_name(const csdr_amd_fastddc_inv *f) { return f->mf ? ddc_mfma_kernel_name(f->mf.get()) : "k_ddc_fold_ct"; }
+int csdr_amd_fastddc_inv_set_profiling(csdr_amd_fastddc_inv *f, int on) { return f->mf ? ddc_mfma_set_profiling(f->mf.get(), on) : 0; }
 int csdr_amd_fastddc_inv_kernel_time(csdr_amd_fastddc_inv *f, double *total_ms, long *launches)
 {
     *total_ms = 0; *launches = 0;
-    return f->mf ? ddc_mfma_kernel_time(f->mf, total_ms, launches) : 0;
+    return f->mf ? ddc_mfma_kernel_time(f->mf.get(), total_ms, launches) : 0;
 }
 int csdr_amd_fastddc_inv_stage_time(csdr_amd_fastddc_inv *f, int stage, double *total_ms, long *launches)
 {
     *total_ms = 0; *launches = 0;
-    return f->mf ? ddc_mfma_stage_time(f->mf, stage, total_ms, launches) : 0;
+    return f->mf ? ddc_mfma_stage_time(f->mf.get(), stage, total_ms, launches) : 0;
 }
 
 int csdr_amd_fastddc_inv_geometry(const csdr_amd_fastddc_inv *f, int channel, csdr_fastddc_t *ddc)
@@ -674,9 +667,9 @@ int csdr_amd_fastddc_inv_process(csdr_amd_fastddc_inv *f, const csdr_complexf *s
     const int fft = g.fft_size, inv = g.fft_inv_size, pre = g.pre_decimation;
     if ((size_t)csdr_amd_fastddc_inv_max_output(f, n_blocks) > out_pitch) return fail_msg(-3, "fastddc_inv: out_pitch too small");
     if (f->mf) {   // config 4's geometry: fold on the matrix cores, own inverse transforms fused with scrap + residual shift
-        int rc = ddc_mfma_submit(f->mf, nullptr, spectra, n_blocks, f->d_state, f->d_geom, true); if (rc) return rc;
+        int rc = ddc_mfma_submit(f->mf.get(), nullptr, spectra, n_blocks, f->d_state.get(), f->d_geom.get(), true); if (rc) return rc;
         const int *d_cnt = nullptr;
-        rc = ddc_mfma_collect(f->mf, f->d_geom, out, out_pitch, &d_cnt); if (rc < 0) return rc;
+        rc = ddc_mfma_collect(f->mf.get(), f->d_geom.get(), out, out_pitch, &d_cnt); if (rc < 0) return rc;
         if (out_counts) {
             CSDR_HIP(hipMemcpyAsync(out_counts, d_cnt, sizeof(int) * f->n_channels, hipMemcpyDeviceToHost, st));
             CSDR_HIP(hipStreamSynchronize(st));
@@ -687,30 +680,31 @@ int csdr_amd_fastddc_inv_process(csdr_amd_fastddc_inv *f, const csdr_complexf *s
     if (!f->plans.count(batch)) {
         hipfftHandle h; int n[1] = {inv};
         CSDR_FFT(hipfftPlanMany(&h, 1, n, nullptr, 1, inv, nullptr, 1, inv, HIPFFT_C2C, batch));
+        FftPlan owned(h);
         CSDR_FFT(hipfftSetStream(h, st));
-        f->plans[batch] = h;
+        f->plans[batch] = std::move(owned);
     }
     const bool ct_ok = f->n_channels >= 4 && pre >= 2 && (pre & (pre - 1)) == 0 && !f->fold_old;
     // tile choice measured on config 4 (256 channels, 64 blocks per call), GS/s of wideband input: <8,4> 8.6, <8,8> 7.1-7.2, <4,16> 5.0, <6,12> 3.5,
     // <16,4> 3.0, <2,16> 3.0, <16,8> 2.6, <16,2> 1.9, <32,2> 1.0 -- 8 channels share every spectrum value; the 64 accumulators of <8,4> leave room for
     // 4-5 waves per SIMD, which hides the load latency that <8,8> (2 waves per SIMD) exposes
-#define FOLD_CT(CTV, BTV) hipLaunchKernelGGL((k_ddc_fold_ct<CTV, BTV>), dim3(cdiv(inv, 256), cdiv(n_blocks, BTV), cdiv(f->n_channels, CTV)), dim3(256), 0, st, spectra, f->d_H, f->d_inv_in, f->d_geom, fft, inv, pre, n_blocks, f->n_channels)
+#define FOLD_CT(CTV, BTV) hipLaunchKernelGGL((k_ddc_fold_ct<CTV, BTV>), dim3(cdiv(inv, 256), cdiv(n_blocks, BTV), cdiv(f->n_channels, CTV)), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks, f->n_channels)
     if (ct_ok && f->n_channels >= 8) { FOLD_CT(8, 4); }
     else if (ct_ok) { FOLD_CT(4, 4); }
 #undef FOLD_CT
     else if (n_blocks >= 16) {
-        hipLaunchKernelGGL((k_ddc_fold<16>), dim3(cdiv(inv, 256), cdiv(n_blocks, 16), f->n_channels), dim3(256), 0, st, spectra, f->d_H, f->d_inv_in, f->d_geom, fft, inv, pre, n_blocks);
+        hipLaunchKernelGGL((k_ddc_fold<16>), dim3(cdiv(inv, 256), cdiv(n_blocks, 16), f->n_channels), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks);
     } else {
-        hipLaunchKernelGGL((k_ddc_fold<4>), dim3(cdiv(inv, 256), cdiv(n_blocks, 4), f->n_channels), dim3(256), 0, st, spectra, f->d_H, f->d_inv_in, f->d_geom, fft, inv, pre, n_blocks);
+        hipLaunchKernelGGL((k_ddc_fold<4>), dim3(cdiv(inv, 256), cdiv(n_blocks, 4), f->n_channels), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks);
     }
     CSDR_LAUNCH_CHECK();
-    CSDR_FFT(hipfftExecC2C(f->plans[batch], (hipfftComplex *)f->d_inv_in, (hipfftComplex *)f->d_td, HIPFFT_BACKWARD));
-    hipLaunchKernelGGL(k_ddc_chain, dim3(cdiv(f->n_channels, 64)), dim3(64), 0, st, f->d_state, f->d_geom, f->n_channels, n_blocks, g.post_input_size, g.post_decimation,
-                       f->d_blk_remain, f->d_blk_phase, f->d_blk_off, f->d_counts); CSDR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ddc_post, dim3(cdiv((size_t)batch, 64)), dim3(64), 0, st, f->d_td, out, out_pitch, f->d_geom, f->n_channels, n_blocks, inv, g.scrap,
-                       g.post_input_size, g.post_decimation, f->d_blk_remain, f->d_blk_phase, f->d_blk_off); CSDR_LAUNCH_CHECK();
+    CSDR_FFT(hipfftExecC2C(f->plans[batch].get(), (hipfftComplex *)f->d_inv_in.get(), (hipfftComplex *)f->d_td.get(), HIPFFT_BACKWARD));
+    hipLaunchKernelGGL(k_ddc_chain, dim3(cdiv(f->n_channels, 64)), dim3(64), 0, st, f->d_state.get(), f->d_geom.get(), f->n_channels, n_blocks, g.post_input_size, g.post_decimation,
+                       f->d_blk_remain.get(), f->d_blk_phase.get(), f->d_blk_off.get(), f->d_counts.get()); CSDR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ddc_post, dim3(cdiv((size_t)batch, 64)), dim3(64), 0, st, f->d_td.get(), out, out_pitch, f->d_geom.get(), f->n_channels, n_blocks, inv, g.scrap,
+                       g.post_input_size, g.post_decimation, f->d_blk_remain.get(), f->d_blk_phase.get(), f->d_blk_off.get()); CSDR_LAUNCH_CHECK();
     if (out_counts) {
-        CSDR_HIP(hipMemcpyAsync(out_counts, f->d_counts, sizeof(int) * f->n_channels, hipMemcpyDeviceToHost, st));
+        CSDR_HIP(hipMemcpyAsync(out_counts, f->d_counts.get(), sizeof(int) * f->n_channels, hipMemcpyDeviceToHost, st));
         CSDR_HIP(hipStreamSynchronize(st));
     }
     return 0;
@@ -733,17 +727,20 @@ int csdr_amd_fastddc_inv_process(csdr_amd_fastddc_inv *f, const csdr_complexf *s
 //                            decimating_shift_addition_cc's (remain, phase) per channel (fastddc.c:152-164), is data independent: every rank walks the chain
 //                            over the whole batch itself (ddc_chain_body_seg).  The spectrum never leaves the GPU that computed it.
 struct csdr_amd_fastddc_bank {
-    csdr_amd_ctx *ctx; csdr_amd_fastddc_inv *inv; csdr_amd_fastddc_fwd *fwd; cf32 *d_spec; int max_blocks; bool fused;
+    csdr_amd_ctx *ctx; int max_blocks; bool fused;
     csdr_amd_comm *comm; int first_channel, n_channels_total; int staged[2], n_staged;      // general path: block counts of the staged calls
     const int *last_counts = nullptr; int last_count_n = 0;            // device counts of the batch collected last (csdr_amd_fastddc_bank_finish)
     // ---- time-sliced mode
     int shard_mode = CSDR_AMD_SHARD_CHANNELS; const DdcComm *dc = nullptr; int world = 1, rank = 0, nbl = 0, out_count = 0;
     csdr_amd_comm *comm_out = nullptr; const DdcComm *dc_out = nullptr;      // time slices: the output exchange (stream xout) on a communicator of its own (csdr_amd_comm_dup), the input exchange (xin) on `comm`
     size_t pitch_loc = 0;
-    cf32 *d_in_loc[2] = {nullptr, nullptr}, *d_out_loc[2] = {nullptr, nullptr}, *d_recv[2] = {nullptr, nullptr}, *d_tail_root[2] = {nullptr, nullptr};
-    int *d_pref[3] = {nullptr, nullptr, nullptr}; int tail_flip = 0, pref_at = 0;      // run-offset tables: this batch's, the next one's (computed one call ahead), and the one the previous batch's stitch may still read
-    hipStream_t xin = nullptr, xout = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_in_ready[2] = {nullptr, nullptr}, ev_in_free[2] = {nullptr, nullptr}, ev_out_ready[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    Event ev_fork, ev_in_ready[2], ev_in_free[2], ev_out_ready[2], ev_done[2];
+    DevBuf<cf32> d_in_loc[2], d_out_loc[2], d_recv[2], d_tail_root[2];
+    DevBuf<int> d_pref[3]; int tail_flip = 0, pref_at = 0;      // run-offset tables: this batch's, the next one's (computed one call ahead), and the one the previous batch's stitch may still read
+    DevBuf<cf32> d_spec;
+    Owned<csdr_amd_fastddc_inv, csdr_amd_fastddc_inv_destroy> inv;
+    Owned<csdr_amd_fastddc_fwd, csdr_amd_fastddc_fwd_destroy> fwd;
+    Stream xin, xout;                                                  // (synchronised by csdr_amd_fastddc_bank_destroy, then the first to go)
     bool in_free_rec[2] = {false, false}, done_rec[2] = {false, false};
     struct Batch { int n_glob; const uint8_t *in; bool local; int fmt; } batch[2]; int fill = 0, drain = 0, n_batches = 0, last_slot = -1;
     // a retune applies from the next SUBMITTED batch on.  Time slices: a batch's chain tables are computed at its collect, so retunes that arrive while batches are
@@ -780,15 +777,15 @@ __global__ __launch_bounds__(64) void k_bank_counts(const int *__restrict__ pref
 static csdr_amd_fastddc_bank *bank_create(csdr_amd_ctx *ctx, float transition_bw, int decimation, const float *host_shift_rates, int n_channels,
                                           int window, int max_blocks, csdr_amd_comm *comm, int shard_mode)
 {
-    csdr_amd_fastddc_bank *b = new csdr_amd_fastddc_bank();
-    b->ctx = ctx; b->max_blocks = max_blocks; b->fwd = nullptr; b->d_spec = nullptr; b->comm = comm; b->n_staged = 0;
+    Owned<csdr_amd_fastddc_bank, csdr_amd_fastddc_bank_destroy> b(new csdr_amd_fastddc_bank());
+    b->ctx = ctx; b->max_blocks = max_blocks; b->comm = comm; b->n_staged = 0;
     b->first_channel = 0; b->n_channels_total = n_channels;
     int count = n_channels;
     const DdcComm *dc = comm ? csdr_amd_comm_ddc(comm) : nullptr;
     const bool multi = dc && dc->world > 1;
     if (multi) {
         shard_slice(n_channels, dc->world, dc->rank, &b->first_channel, &count);
-        if (count < 1) { fail_msg(-3, "fastddc_bank: fewer channels than ranks"); delete b; return nullptr; }
+        if (count < 1) { fail_msg(-3, "fastddc_bank: fewer channels than ranks"); return nullptr; }
         b->dc = dc; b->world = dc->world; b->rank = dc->rank; b->out_count = count;
     }
     b->shard_mode = multi ? shard_mode : CSDR_AMD_SHARD_CHANNELS;
@@ -796,39 +793,39 @@ static csdr_amd_fastddc_bank *bank_create(csdr_amd_ctx *ctx, float transition_bw
         b->nbl = (max_blocks + b->world - 1) / b->world;
         // two exchanges per batch from two side streams: each on its own communicator (collective -- every rank creates its bank at the same point)
         b->comm_out = csdr_amd_comm_dup(comm);
-        if (!b->comm_out) { delete b; return nullptr; }
+        if (!b->comm_out) return nullptr;
         b->dc_out = csdr_amd_comm_ddc(b->comm_out);
-        b->inv = fastddc_inv_create_comm(ctx, transition_bw, decimation, host_shift_rates, n_channels, window, b->nbl, nullptr);
+        b->inv.reset(fastddc_inv_create_comm(ctx, transition_bw, decimation, host_shift_rates, n_channels, window, b->nbl, nullptr));
     } else
-        b->inv = fastddc_inv_create_comm(ctx, transition_bw, decimation, host_shift_rates + b->first_channel, count, window, max_blocks, multi ? dc : nullptr);
-    if (!b->inv) { csdr_amd_fastddc_bank_destroy(b); return nullptr; }      // (destroy: a BLOCKS-mode bank already holds its second communicator)
-    b->fused = ddc_mfma_can_forward(b->inv->mf);
-    if (multi && !b->fused) { fail_msg(-3, "fastddc_bank: sharding needs the geometry of the matrix-core path (fft_size 65536, fft_inv_size 512)"); csdr_amd_fastddc_bank_destroy(b); return nullptr; }
+        b->inv.reset(fastddc_inv_create_comm(ctx, transition_bw, decimation, host_shift_rates + b->first_channel, count, window, max_blocks, multi ? dc : nullptr));
+    if (!b->inv) return nullptr;      // (destroyed as a bank: a BLOCKS-mode bank already holds its second communicator)
+    b->fused = ddc_mfma_can_forward(b->inv->mf.get());
+    if (multi && !b->fused) { fail_msg(-3, "fastddc_bank: sharding needs the geometry of the matrix-core path (fft_size 65536, fft_inv_size 512)"); return nullptr; }
     const csdr_fastddc_t g = b->inv->geom[0];
-    if (multi && g.input_size < g.overlap_length) { fail_msg(-3, "fastddc_bank: sharding needs input_size >= overlap_length"); csdr_amd_fastddc_bank_destroy(b); return nullptr; }
+    if (multi && g.input_size < g.overlap_length) { fail_msg(-3, "fastddc_bank: sharding needs input_size >= overlap_length"); return nullptr; }
     if (!b->fused) {
-        b->fwd = csdr_amd_fastddc_fwd_create(ctx, &g, max_blocks);
-        if (!b->fwd || hipMalloc((void **)&b->d_spec, sizeof(cf32) * (size_t)max_blocks * g.fft_size) != hipSuccess) {
-            fail_msg(-2, "fastddc_bank: cannot allocate the spectrum buffer"); csdr_amd_fastddc_bank_destroy(b); return nullptr; }
+        b->fwd.reset(csdr_amd_fastddc_fwd_create(ctx, &g, max_blocks));
+        if (!b->fwd || dev_alloc(b->d_spec, sizeof(cf32) * (size_t)max_blocks * g.fft_size) != hipSuccess) {
+            fail_msg(-2, "fastddc_bank: cannot allocate the spectrum buffer"); return nullptr; }
     }
     if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS) {
-        b->pitch_loc = ((size_t)csdr_amd_fastddc_inv_max_output(b->inv, b->nbl) + 8 + 1) / 2 * 2;
+        b->pitch_loc = ((size_t)csdr_amd_fastddc_inv_max_output(b->inv.get(), b->nbl) + 8 + 1) / 2 * 2;
         const size_t in_elems = (size_t)b->nbl * g.input_size + g.overlap_length;
-        hipError_t e = hipStreamCreateWithFlags(&b->xin, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->xout, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming);
+        hipError_t e = stream_create(b->xin);
+        if (e == hipSuccess) e = stream_create(b->xout);
+        if (e == hipSuccess) e = event_create(b->ev_fork, hipEventDisableTiming);
         for (int k = 0; k < 2 && e == hipSuccess; k++) {
-            e = hipMalloc((void **)&b->d_out_loc[k], sizeof(cf32) * (size_t)n_channels * b->pitch_loc);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->d_recv[k], sizeof(cf32) * (size_t)b->world * count * b->pitch_loc);
-            for (int t = k; t < 3 && e == hipSuccess; t += 2) e = hipMalloc((void **)&b->d_pref[t], sizeof(int) * ((size_t)(b->world + 1) * n_channels + count));      // the chain's table + this slice's counts
-            if (e == hipSuccess && b->rank != 0) e = hipMalloc((void **)&b->d_in_loc[k], sizeof(cf32) * in_elems);
-            if (e == hipSuccess && b->rank == 0) { e = hipMalloc((void **)&b->d_tail_root[k], sizeof(cf32) * (size_t)(g.overlap_length + 1));
-                if (e == hipSuccess) e = hipMemsetAsync(b->d_tail_root[k], 0, sizeof(cf32) * (size_t)(g.overlap_length + 1), ctx->stream); }      // csdr.c:2279: the stream starts behind zeros
-            for (hipEvent_t *ev : {&b->ev_in_ready[k], &b->ev_in_free[k], &b->ev_out_ready[k], &b->ev_done[k]}) if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+            e = dev_alloc(b->d_out_loc[k], sizeof(cf32) * (size_t)n_channels * b->pitch_loc);
+            if (e == hipSuccess) e = dev_alloc(b->d_recv[k], sizeof(cf32) * (size_t)b->world * count * b->pitch_loc);
+            for (int t = k; t < 3 && e == hipSuccess; t += 2) e = dev_alloc(b->d_pref[t], sizeof(int) * ((size_t)(b->world + 1) * n_channels + count));      // the chain's table + this slice's counts
+            if (e == hipSuccess && b->rank != 0) e = dev_alloc(b->d_in_loc[k], sizeof(cf32) * in_elems);
+            if (e == hipSuccess && b->rank == 0) { e = dev_alloc(b->d_tail_root[k], sizeof(cf32) * (size_t)(g.overlap_length + 1));
+                if (e == hipSuccess) e = hipMemsetAsync(b->d_tail_root[k].get(), 0, sizeof(cf32) * (size_t)(g.overlap_length + 1), ctx->stream); }      // csdr.c:2279: the stream starts behind zeros
+            for (Event *ev : {&b->ev_in_ready[k], &b->ev_in_free[k], &b->ev_out_ready[k], &b->ev_done[k]}) if (e == hipSuccess) e = event_create(*ev, hipEventDisableTiming);
         }
-        if (e != hipSuccess) { fail(e, "fastddc_bank (time-sliced buffers)", __FILE__, __LINE__); csdr_amd_fastddc_bank_destroy(b); return nullptr; }
+        if (e != hipSuccess) { fail(e, "fastddc_bank (time-sliced buffers)", __FILE__, __LINE__); return nullptr; }
     }
-    return b;
+    return b.release();
 }
 
 // ---- time-sliced mode: submit = the input exchange of a batch (or nothing, when every rank is handed its own run), collect = this rank's pipeline + output exchange
@@ -844,18 +841,18 @@ static int bank_submit_blocks(csdr_amd_fastddc_bank *b, const void *in_v, int n_
     const int b0 = blk_first_of(b, b->rank, n_glob), b1 = blk_first_of(b, b->rank + 1, n_glob), n_loc = b1 - b0;
     if (!local) {     // the wideband stream lives on rank 0 (ddcd's single fastddc_fwd_cc): every rank is sent the samples of its run, with the overlap in front, over its own link
         const DdcComm *cm = b->dc;
-        if (b->rank == 0) { CSDR_HIP(hipEventRecord(b->ev_fork, b->ctx->stream)); CSDR_HIP(hipStreamWaitEvent(b->xin, b->ev_fork, 0)); }      // the producers of `in`
-        else if (b->in_free_rec[slot]) CSDR_HIP(hipStreamWaitEvent(b->xin, b->ev_out_ready[slot], 0));                                   // the transforms that read this slot two batches ago
+        if (b->rank == 0) { CSDR_HIP(hipEventRecord(b->ev_fork.get(), b->ctx->stream)); CSDR_HIP(hipStreamWaitEvent(b->xin.get(), b->ev_fork.get(), 0)); }      // the producers of `in`
+        else if (b->in_free_rec[slot]) CSDR_HIP(hipStreamWaitEvent(b->xin.get(), b->ev_out_ready[slot].get(), 0));                                   // the transforms that read this slot two batches ago
         int rc = cm->group_start(cm); if (rc) return rc;
         if (b->rank == 0) {
             for (int p = 1; p < b->world; p++) {
                 const int p0 = blk_first_of(b, p, n_glob), p1 = blk_first_of(b, p + 1, n_glob);
                 // (raw samples, 8 / 4 / 2 bytes each: integer ingest halves or quarters the root's egress; counts in 4-byte words)
-                if (p1 > p0) { rc = cm->send(cm, in + ((size_t)p0 * inp - ovl) * es, ((size_t)(p1 - p0) * inp + ovl) * es / 4, p, b->xin); if (rc) return rc; }
+                if (p1 > p0) { rc = cm->send(cm, in + ((size_t)p0 * inp - ovl) * es, ((size_t)(p1 - p0) * inp + ovl) * es / 4, p, b->xin.get()); if (rc) return rc; }
             }
-        } else if (n_loc > 0) { rc = cm->recv(cm, b->d_in_loc[slot], ((size_t)n_loc * inp + ovl) * es / 4, 0, b->xin); if (rc) return rc; }
+        } else if (n_loc > 0) { rc = cm->recv(cm, b->d_in_loc[slot].get(), ((size_t)n_loc * inp + ovl) * es / 4, 0, b->xin.get()); if (rc) return rc; }
         rc = cm->group_end(cm); if (rc) return rc;
-        CSDR_HIP(hipEventRecord(b->ev_in_ready[slot], b->xin));
+        CSDR_HIP(hipEventRecord(b->ev_in_ready[slot].get(), b->xin.get()));
     }
     b->batch[slot] = {n_glob, in, local, fmt};
     b->fill ^= 1; b->n_batches++; b->seq_submit++;
@@ -867,63 +864,63 @@ static int bank_collect_blocks(csdr_amd_fastddc_bank *b, csdr_complexf *out, siz
     if (!b->n_batches) return fail_msg(-3, "fastddc_bank: nothing staged to collect");
     for (size_t k = 0; k < b->deferred.size();) {                     // retunes that concern this batch (and were issued while an earlier one was staged)
         if (b->deferred[k].first_batch <= b->seq_collect) {
-            const int rc = csdr_amd_fastddc_inv_set_rate(b->inv, b->deferred[k].channel, b->deferred[k].rate); if (rc) return rc;
+            const int rc = csdr_amd_fastddc_inv_set_rate(b->inv.get(), b->deferred[k].channel, b->deferred[k].rate); if (rc) return rc;
             b->deferred.erase(b->deferred.begin() + (long)k);
         } else k++;
     }
     b->seq_collect++;
-    csdr_amd_fastddc_inv *f = b->inv;
+    csdr_amd_fastddc_inv *f = b->inv.get();
     const csdr_fastddc_t &g = f->geom[0];
     const int inp = g.input_size, ovl = g.overlap_length, slot = b->drain, W = b->world, me = b->rank;
     const csdr_amd_fastddc_bank::Batch bt = b->batch[slot];
     if ((size_t)csdr_amd_fastddc_inv_max_output(f, bt.n_glob) > out_pitch) return fail_msg(-3, "fastddc_bank: out_pitch too small");
     hipStream_t st = b->ctx->stream;
     const int b0 = blk_first_of(b, me, bt.n_glob), b1 = blk_first_of(b, me + 1, bt.n_glob), n_loc = b1 - b0;
-    if (!bt.local && me != 0) CSDR_HIP(hipStreamWaitEvent(st, b->ev_in_ready[slot], 0));
+    if (!bt.local && me != 0) CSDR_HIP(hipStreamWaitEvent(st, b->ev_in_ready[slot].get(), 0));
     // the output exchange two batches ago read d_out_loc / the offsets table of this slot: normally long finished -- then no wait packet goes into the stream
     // (a cross-stream wait costs ~10 us of bubble in front of the next kernel even when the event has fired)
-    if (b->done_rec[slot] && hipEventQuery(b->ev_done[slot]) != hipSuccess) CSDR_HIP(hipStreamWaitEvent(st, b->ev_done[slot], 0));
+    if (b->done_rec[slot] && hipEventQuery(b->ev_done[slot].get()) != hipSuccess) CSDR_HIP(hipStreamWaitEvent(st, b->ev_done[slot].get(), 0));
     // three tables in rotation: the riders of this batch's inverse-transform kernel write the NEXT batch's offsets while the previous batch's stitch may still
     // read its own table; the one written now was last read by the stitch two batches ago (waited for above)
-    int *pref = b->d_pref[b->pref_at], *pref_next = b->d_pref[(b->pref_at + 1) % 3];
+    int *pref = b->d_pref[b->pref_at].get(), *pref_next = b->d_pref[(b->pref_at + 1) % 3].get();
     b->pref_at = (b->pref_at + 1) % 3;
-    int rc = ddc_mfma_set_segment(f->mf, b->nbl, b0, bt.n_glob, W, pref, pref_next); if (rc) return rc;
+    int rc = ddc_mfma_set_segment(f->mf.get(), b->nbl, b0, bt.n_glob, W, pref, pref_next); if (rc) return rc;
     if (n_loc > 0) {
         // the overlap in front of the run: with the run itself (its own format), except on the root of a scattered stream (complexf, carried between batches)
         const size_t es = ddc_in_bytes(bt.fmt);
         const uint8_t *src; const cf32 *tail = nullptr; bool in_front = true;
         if (bt.local) src = bt.in + (size_t)ovl * es;
-        else if (me == 0) { tail = b->d_tail_root[b->tail_flip]; src = bt.in; in_front = false; }
-        else src = reinterpret_cast<const uint8_t *>(b->d_in_loc[slot]) + (size_t)ovl * es;
-        rc = ddc_mfma_submit(f->mf, src, nullptr, n_loc, f->d_state, f->d_geom, true, tail, bt.fmt, in_front); if (rc) return rc;
-        rc = ddc_mfma_collect(f->mf, f->d_geom, b->d_out_loc[slot], b->pitch_loc, nullptr, b->ev_out_ready[slot]); if (rc < 0) return rc;
-    } else { rc = ddc_mfma_skip_batch(f->mf, f->d_state, f->d_geom); if (rc) return rc; }
+        else if (me == 0) { tail = b->d_tail_root[b->tail_flip].get(); src = bt.in; in_front = false; }
+        else src = reinterpret_cast<const uint8_t *>(b->d_in_loc[slot].get()) + (size_t)ovl * es;
+        rc = ddc_mfma_submit(f->mf.get(), src, nullptr, n_loc, f->d_state.get(), f->d_geom.get(), true, tail, bt.fmt, in_front); if (rc) return rc;
+        rc = ddc_mfma_collect(f->mf.get(), f->d_geom.get(), b->d_out_loc[slot].get(), b->pitch_loc, nullptr, b->ev_out_ready[slot].get()); if (rc < 0) return rc;
+    } else { rc = ddc_mfma_skip_batch(f->mf.get(), f->d_state.get(), f->d_geom.get()); if (rc) return rc; }
     const bool out_ready_recorded = n_loc > 0;                           // (by the call's last kernel itself)
     if (!bt.local && me == 0) {      // the next batch's overlap = the newest ovl samples of the stream (input_size >= overlap_length: checked at create)
-        rc = ddc_mfma_convert_samples(st, bt.in, bt.fmt, (long long)bt.n_glob * inp - ovl, ovl, b->d_tail_root[b->tail_flip ^ 1]); if (rc) return rc;
+        rc = ddc_mfma_convert_samples(st, bt.in, bt.fmt, (long long)bt.n_glob * inp - ovl, ovl, b->d_tail_root[b->tail_flip ^ 1].get()); if (rc) return rc;
         b->tail_flip ^= 1;
     }
     b->in_free_rec[slot] = true;
-    if (!out_ready_recorded) CSDR_HIP(hipEventRecord(b->ev_out_ready[slot], st));
+    if (!out_ready_recorded) CSDR_HIP(hipEventRecord(b->ev_out_ready[slot].get(), st));
     // output exchange on its own stream (under the next batch's transforms): every rank sends each peer that peer's channels of its run
     const DdcComm *cm = b->dc_out;
-    CSDR_HIP(hipStreamWaitEvent(b->xout, b->ev_out_ready[slot], 0));
+    CSDR_HIP(hipStreamWaitEvent(b->xout.get(), b->ev_out_ready[slot].get(), 0));
     rc = cm->group_start(cm); if (rc) return rc;
     for (int p = 0; p < W; p++) {
         if (p == me) continue;
         int pf, pc; shard_slice(b->n_channels_total, W, p, &pf, &pc);
         const int p_loc = blk_first_of(b, p + 1, bt.n_glob) - blk_first_of(b, p, bt.n_glob);
-        if (n_loc > 0) { rc = cm->send(cm, b->d_out_loc[slot] + (size_t)pf * b->pitch_loc, 2 * (size_t)pc * b->pitch_loc, p, b->xout); if (rc) return rc; }
-        if (p_loc > 0) { rc = cm->recv(cm, b->d_recv[slot] + (size_t)p * b->out_count * b->pitch_loc, 2 * (size_t)b->out_count * b->pitch_loc, p, b->xout); if (rc) return rc; }
+        if (n_loc > 0) { rc = cm->send(cm, b->d_out_loc[slot].get() + (size_t)pf * b->pitch_loc, 2 * (size_t)pc * b->pitch_loc, p, b->xout.get()); if (rc) return rc; }
+        if (p_loc > 0) { rc = cm->recv(cm, b->d_recv[slot].get() + (size_t)p * b->out_count * b->pitch_loc, 2 * (size_t)b->out_count * b->pitch_loc, p, b->xout.get()); if (rc) return rc; }
     }
     rc = cm->group_end(cm); if (rc) return rc;
     int *d_cnt = pref + (size_t)(W + 1) * b->n_channels_total;
-    hipLaunchKernelGGL(k_bank_stitch, dim3(b->out_count, W, 8), dim3(256), 0, b->xout, reinterpret_cast<const float2 *>(b->d_out_loc[slot]), reinterpret_cast<const float2 *>(b->d_recv[slot]),
+    hipLaunchKernelGGL(k_bank_stitch, dim3(b->out_count, W, 8), dim3(256), 0, b->xout.get(), reinterpret_cast<const float2 *>(b->d_out_loc[slot].get()), reinterpret_cast<const float2 *>(b->d_recv[slot].get()),
                        pref, reinterpret_cast<float2 *>(out), b->pitch_loc, out_pitch, b->n_channels_total, b->first_channel, b->out_count, me);
     CSDR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bank_counts, dim3(cdiv(b->out_count, 64)), dim3(64), 0, b->xout, pref, d_cnt, b->n_channels_total, b->first_channel, b->out_count, W);
+    hipLaunchKernelGGL(k_bank_counts, dim3(cdiv(b->out_count, 64)), dim3(64), 0, b->xout.get(), pref, d_cnt, b->n_channels_total, b->first_channel, b->out_count, W);
     CSDR_LAUNCH_CHECK();
-    CSDR_HIP(hipEventRecord(b->ev_done[slot], b->xout)); b->done_rec[slot] = true;
+    CSDR_HIP(hipEventRecord(b->ev_done[slot].get(), b->xout.get())); b->done_rec[slot] = true;
     b->last_counts = d_cnt; b->last_count_n = b->out_count; b->last_slot = slot;
     b->drain ^= 1; b->n_batches--;
     return 0;
@@ -959,18 +956,11 @@ int csdr_amd_fastddc_bank_default_shard_mode(int world) { return world > 2 ? CSD
 void csdr_amd_fastddc_bank_destroy(csdr_amd_fastddc_bank *b)
 {
     if (!b) return;
-    if (b->xin) { (void)hipStreamSynchronize(b->xin); (void)hipStreamDestroy(b->xin); }
-    if (b->xout) { (void)hipStreamSynchronize(b->xout); (void)hipStreamDestroy(b->xout); }
-    if (b->fwd) csdr_amd_fastddc_fwd_destroy(b->fwd);
-    if (b->inv) csdr_amd_fastddc_inv_destroy(b->inv);
-    (void)hipFree(b->d_spec);
-    for (int k = 0; k < 2; k++) {
-        (void)hipFree(b->d_in_loc[k]); (void)hipFree(b->d_out_loc[k]); (void)hipFree(b->d_recv[k]); (void)hipFree(b->d_tail_root[k]); (void)hipFree(b->d_pref[k]); if (k == 0) (void)hipFree(b->d_pref[2]);
-        for (hipEvent_t ev : {b->ev_in_ready[k], b->ev_in_free[k], b->ev_out_ready[k], b->ev_done[k]}) if (ev) (void)hipEventDestroy(ev);
-    }
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->comm_out) csdr_amd_comm_destroy(b->comm_out);
+    if (b->xin) (void)hipStreamSynchronize(b->xin.get());
+    if (b->xout) (void)hipStreamSynchronize(b->xout.get());
+    csdr_amd_comm *comm_out = b->comm_out;
     delete b;
+    if (comm_out) csdr_amd_comm_destroy(comm_out);                    // after everything that used it
 }
 
 int csdr_amd_fastddc_bank_channel_slice(const csdr_amd_fastddc_bank *b, int *first, int *count)
@@ -980,7 +970,7 @@ int csdr_amd_fastddc_bank_shard_mode(const csdr_amd_fastddc_bank *b) { return b-
 // same channel is applied directly (left in the queue it would be replayed at the next collect on top of the newer rate: ADVICE r4).
 static int bank_flush_deferred(csdr_amd_fastddc_bank *b)
 {
-    for (const auto &d : b->deferred) { const int rc = csdr_amd_fastddc_inv_set_rate(b->inv, d.channel, d.rate); if (rc) return rc; }
+    for (const auto &d : b->deferred) { const int rc = csdr_amd_fastddc_inv_set_rate(b->inv.get(), d.channel, d.rate); if (rc) return rc; }
     b->deferred.clear();
     return 0;
 }
@@ -993,10 +983,10 @@ int csdr_amd_fastddc_bank_set_rate(csdr_amd_fastddc_bank *b, int channel, float 
         if (csdr_amd_fastddc_bank_channel_slice(b, &first, &count) || channel < 0 || channel >= count) return fail_msg(-3, "fastddc_bank: channel %d outside this rank's slice of %d", channel, count);
         if (b->n_batches) { b->deferred.push_back({b->seq_submit, first + channel, shift_rate}); return 0; }      // (staged batches keep the old rate)
         if (const int rc = bank_flush_deferred(b)) return rc;
-        return csdr_amd_fastddc_inv_set_rate(b->inv, first + channel, shift_rate);
+        return csdr_amd_fastddc_inv_set_rate(b->inv.get(), first + channel, shift_rate);
     }
     if (b->seq_submit != b->seq_collect) return fail_msg(-3, "fastddc_bank: a batch is staged (submitted, not collected): its tables are partly fixed already -- collect it before retuning (a time-sliced bank holds such a retune back itself)");
-    return csdr_amd_fastddc_inv_set_rate(b->inv, channel, shift_rate);
+    return csdr_amd_fastddc_inv_set_rate(b->inv.get(), channel, shift_rate);
 }
 int csdr_amd_fastddc_bank_set_rate_global(csdr_amd_fastddc_bank *b, int channel, float shift_rate)
 {   // every rank makes the same call; a rank applies it to what it computes
@@ -1004,16 +994,16 @@ int csdr_amd_fastddc_bank_set_rate_global(csdr_amd_fastddc_bank *b, int channel,
     if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS) {
         if (b->n_batches) { b->deferred.push_back({b->seq_submit, channel, shift_rate}); return 0; }                 // (staged batches keep the old rate)
         if (const int rc = bank_flush_deferred(b)) return rc;
-        return csdr_amd_fastddc_inv_set_rate(b->inv, channel, shift_rate);
+        return csdr_amd_fastddc_inv_set_rate(b->inv.get(), channel, shift_rate);
     }
     if (b->seq_submit != b->seq_collect) return fail_msg(-3, "fastddc_bank: a batch is staged (submitted, not collected): its tables are partly fixed already -- collect it before retuning (a time-sliced bank holds such a retune back itself)");
     if (channel < b->first_channel || channel >= b->first_channel + b->inv->n_channels) return 0;
-    return csdr_amd_fastddc_inv_set_rate(b->inv, channel - b->first_channel, shift_rate);
+    return csdr_amd_fastddc_inv_set_rate(b->inv.get(), channel - b->first_channel, shift_rate);
 }
 int csdr_amd_fastddc_bank_input_size(const csdr_amd_fastddc_bank *b) { return b->inv->geom[0].input_size; }
 int csdr_amd_fastddc_bank_overlap(const csdr_amd_fastddc_bank *b) { return b->inv->geom[0].overlap_length; }
-int csdr_amd_fastddc_bank_max_output(const csdr_amd_fastddc_bank *b, int n_blocks) { return csdr_amd_fastddc_inv_max_output(b->inv, n_blocks); }
-csdr_amd_fastddc_inv *csdr_amd_fastddc_bank_inverse(csdr_amd_fastddc_bank *b) { return b->inv; }
+int csdr_amd_fastddc_bank_max_output(const csdr_amd_fastddc_bank *b, int n_blocks) { return csdr_amd_fastddc_inv_max_output(b->inv.get(), n_blocks); }
+csdr_amd_fastddc_inv *csdr_amd_fastddc_bank_inverse(csdr_amd_fastddc_bank *b) { return b->inv.get(); }
 int csdr_amd_fastddc_bank_local_blocks(const csdr_amd_fastddc_bank *b, int n_blocks, int *first, int *count)
 {
     if (b->shard_mode != CSDR_AMD_SHARD_BLOCKS) { *first = 0; *count = n_blocks; return 0; }
@@ -1027,13 +1017,13 @@ static int bank_submit(csdr_amd_fastddc_bank *b, const void *in, int n_blocks, b
     if (fmt < 0 || fmt > 2) return fail_msg(-3, "fastddc_bank: unknown input format %d", fmt);
     if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS) return bank_submit_blocks(b, in, n_blocks, false, fmt);
     if (b->fused) {
-        const int rc = ddc_mfma_submit(b->inv->mf, in, nullptr, n_blocks, b->inv->d_state, b->inv->d_geom, inline_call, nullptr, fmt, false);
+        const int rc = ddc_mfma_submit(b->inv->mf.get(), in, nullptr, n_blocks, b->inv->d_state.get(), b->inv->d_geom.get(), inline_call, nullptr, fmt, false);
         if (!rc) b->seq_submit++;
         return rc;
     }
     if (fmt != DDC_IN_CF32) return fail_msg(-3, "fastddc_bank: integer input needs the matrix-core geometry (fft 65536 / inverse 512); convert first (csdr_amd_convert_s16_f / _u8_f)");
     if (b->n_staged) return fail_msg(-3, "fastddc_bank: this geometry stages one call at a time");
-    int rc = csdr_amd_fastddc_fwd_process(b->fwd, reinterpret_cast<const csdr_complexf *>(in), b->d_spec, n_blocks); if (rc) return rc;
+    int rc = csdr_amd_fastddc_fwd_process(b->fwd.get(), reinterpret_cast<const csdr_complexf *>(in), b->d_spec.get(), n_blocks); if (rc) return rc;
     b->staged[0] = n_blocks; b->n_staged = 1; b->seq_submit++;
     return 0;
 }
@@ -1056,7 +1046,7 @@ int csdr_amd_fastddc_bank_submit_local_u8(csdr_amd_fastddc_bank *b, const uint8_
 int csdr_amd_fastddc_bank_finish(csdr_amd_fastddc_bank *b, int *out_counts)
 {
     hipStream_t st = b->ctx->stream;
-    if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS && b->last_slot >= 0) CSDR_HIP(hipStreamWaitEvent(st, b->ev_done[b->last_slot], 0));
+    if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS && b->last_slot >= 0) CSDR_HIP(hipStreamWaitEvent(st, b->ev_done[b->last_slot].get(), 0));
     if (out_counts) {
         if (!b->last_counts) return fail_msg(-3, "fastddc_bank: nothing collected yet");
         CSDR_HIP(hipMemcpyAsync(out_counts, b->last_counts, sizeof(int) * (size_t)b->last_count_n, hipMemcpyDeviceToHost, st));
@@ -1067,7 +1057,7 @@ int csdr_amd_fastddc_bank_finish(csdr_amd_fastddc_bank *b, int *out_counts)
 
 int csdr_amd_fastddc_bank_collect(csdr_amd_fastddc_bank *b, csdr_complexf *out, size_t out_pitch, int *out_counts)
 {
-    csdr_amd_fastddc_inv *f = b->inv;
+    csdr_amd_fastddc_inv *f = b->inv.get();
     if (b->shard_mode == CSDR_AMD_SHARD_BLOCKS) {
         const int rc = bank_collect_blocks(b, out, out_pitch); if (rc) return rc;
         return out_counts ? csdr_amd_fastddc_bank_finish(b, out_counts) : 0;
@@ -1075,12 +1065,12 @@ int csdr_amd_fastddc_bank_collect(csdr_amd_fastddc_bank *b, csdr_complexf *out, 
     if (!b->fused) {
         if (!b->n_staged) return fail_msg(-3, "fastddc_bank: nothing staged to collect");
         b->n_staged = 0; b->seq_collect++;
-        return csdr_amd_fastddc_inv_process(f, b->d_spec, b->staged[0], out, out_pitch, out_counts);
+        return csdr_amd_fastddc_inv_process(f, b->d_spec.get(), b->staged[0], out, out_pitch, out_counts);
     }
-    const int pending = ddc_mfma_pending_blocks(f->mf);                   // validated BEFORE anything is queued that writes `out` with this pitch
+    const int pending = ddc_mfma_pending_blocks(f->mf.get());                   // validated BEFORE anything is queued that writes `out` with this pitch
     if (pending > 0 && (size_t)csdr_amd_fastddc_inv_max_output(f, pending) > out_pitch) return fail_msg(-3, "fastddc_bank: out_pitch too small");
     const int *d_cnt = nullptr;
-    const int rc = ddc_mfma_collect(f->mf, f->d_geom, out, out_pitch, &d_cnt); if (rc < 0) return rc;
+    const int rc = ddc_mfma_collect(f->mf.get(), f->d_geom.get(), out, out_pitch, &d_cnt); if (rc < 0) return rc;
     if (b->seq_collect < b->seq_submit) b->seq_collect++;
     b->last_counts = d_cnt; b->last_count_n = f->n_channels;
     return out_counts ? csdr_amd_fastddc_bank_finish(b, out_counts) : 0;
@@ -1089,7 +1079,7 @@ int csdr_amd_fastddc_bank_collect(csdr_amd_fastddc_bank *b, csdr_complexf *out, 
 static int bank_process_fmt(csdr_amd_fastddc_bank *b, const void *in, int fmt, int n_blocks, csdr_complexf *out, size_t out_pitch, int *out_counts)
 {
     if (n_blocks <= 0) return 0;
-    if ((size_t)csdr_amd_fastddc_inv_max_output(b->inv, n_blocks) > out_pitch) return fail_msg(-3, "fastddc_bank: out_pitch too small");
+    if ((size_t)csdr_amd_fastddc_inv_max_output(b->inv.get(), n_blocks) > out_pitch) return fail_msg(-3, "fastddc_bank: out_pitch too small");
     int rc = bank_submit(b, in, n_blocks, true, fmt); if (rc) return rc;
     rc = csdr_amd_fastddc_bank_collect(b, out, out_pitch, out_counts); if (rc) return rc;
     return out_counts ? 0 : csdr_amd_fastddc_bank_finish(b, nullptr);

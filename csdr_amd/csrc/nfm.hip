@@ -200,14 +200,14 @@ struct csdr_amd_nfm {
     csdr_amd_ctx *ctx;
     int n_streams, D, Ld, agc_block, cli_prefix;
     float limit, agc_ref;
-    csdr_amd_ddc *ddc;
-    cf32 *d_y; size_t y_pitch; cf32 *d_last, *d_last2; int lflip;
-    int8_t *d_planes; size_t plane_bytes; size_t dl_pitch; int dl_fill;   // limited demodulator output (three digit planes) waiting for the de-emphasis filter
-    void *d_fir_frags; float fir_scale;             // de-emphasis taps as int8 digit fragments; scale of the recombined product
-    float *d_de; size_t a_pitch;                    // de-emphasised blocks
-    float *d_agc_state;
+    DevBuf<cf32> d_y; size_t y_pitch; DevBuf<cf32> d_last, d_last2; int lflip;
+    DevBuf<int8_t> d_planes; size_t plane_bytes; size_t dl_pitch; int dl_fill;   // limited demodulator output (three digit planes) waiting for the de-emphasis filter
+    DevBuf<> d_fir_frags; float fir_scale;            // de-emphasis taps as int8 digit fragments; scale of the recombined product
+    DevBuf<float> d_de; size_t a_pitch;             // de-emphasised blocks
+    DevBuf<float> d_agc_state;
     size_t max_y;
     bool fuse_off;                                  // CSDR_AMD_NFM_FUSE=0 (A/B: separate demodulator / AGC-peak passes), read when the object is created
+    Owned<csdr_amd_ddc, csdr_amd_ddc_destroy> ddc;  // the receiver front end
 };
 
 extern "C" {
@@ -221,12 +221,11 @@ static csdr_amd_nfm *nfm_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
     if (!Ld) { fail_msg(-3, "nfm_create: no de-emphasis table for sample rate %d (libcsdr.c:1115-1119)", audio_rate); return nullptr; }
     if (Ld + 15 > 64 * NFM_FIR_NK) { fail_msg(-3, "nfm_create: %d de-emphasis taps exceed the matrix-core tile", Ld); return nullptr; }
     if (max_block_samples < 1024) max_block_samples = 1024;
-    csdr_amd_nfm *w = new csdr_amd_nfm();
-    memset(w, 0, sizeof(*w));
+    Owned<csdr_amd_nfm, csdr_amd_nfm_destroy> w(new csdr_amd_nfm());
     w->ctx = ctx; w->n_streams = n_streams; w->D = decimation; w->Ld = Ld; w->agc_block = agc_block; w->limit = limit_max; w->agc_ref = agc_reference;
-    w->ddc = per_stream ? csdr_amd_ddc_create_rates(ctx, n_streams, rates, decimation, host_taps, taps_length, max_block_samples)
-                        : csdr_amd_ddc_create(ctx, n_streams, rates[0], decimation, host_taps, taps_length, max_block_samples);
-    if (!w->ddc) { delete w; return nullptr; }
+    w->ddc.reset(per_stream ? csdr_amd_ddc_create_rates(ctx, n_streams, rates, decimation, host_taps, taps_length, max_block_samples)
+                            : csdr_amd_ddc_create(ctx, n_streams, rates[0], decimation, host_taps, taps_length, max_block_samples));
+    if (!w->ddc) return nullptr;
     { const char *fe = getenv("CSDR_AMD_NFM_FUSE"); w->fuse_off = fe && atoi(fe) == 0; }
     w->max_y = max_block_samples / decimation + 2;
     w->y_pitch = (w->max_y + 15) & ~(size_t)15;
@@ -237,23 +236,23 @@ static csdr_amd_nfm *nfm_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
     w->dl_pitch = (w->max_y + Ld + agc_block + w->cli_prefix + NFM_FIR_ROW + 63) & ~(size_t)63;        // + the last workgroup's staged span beyond the valid samples (zero weights)
     w->a_pitch = (w->max_y + Ld + agc_block + 1024 + 15) & ~(size_t)15;
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    alloc((void **)&w->d_y, sizeof(cf32) * w->y_pitch * n_streams);
-    alloc((void **)&w->d_last, sizeof(cf32) * n_streams);
-    alloc((void **)&w->d_last2, sizeof(cf32) * n_streams);
+    auto alloc = [&](auto &p, size_t bytes) { if (e == hipSuccess) e = dev_alloc(p, bytes); };
+    alloc(w->d_y, sizeof(cf32) * w->y_pitch * n_streams);
+    alloc(w->d_last, sizeof(cf32) * n_streams);
+    alloc(w->d_last2, sizeof(cf32) * n_streams);
     w->plane_bytes = w->dl_pitch * n_streams;
-    alloc((void **)&w->d_planes, 3 * w->plane_bytes);
-    alloc(&w->d_fir_frags, (size_t)NFM_FIR_NK * 3 * 64 * 16);
-    alloc((void **)&w->d_de, sizeof(float) * w->a_pitch * n_streams);
-    alloc((void **)&w->d_agc_state, sizeof(float) * (size_t)n_streams * (2 * agc_block + 4));
+    alloc(w->d_planes, 3 * w->plane_bytes);
+    alloc(w->d_fir_frags, (size_t)NFM_FIR_NK * 3 * 64 * 16);
+    alloc(w->d_de, sizeof(float) * w->a_pitch * n_streams);
+    alloc(w->d_agc_state, sizeof(float) * (size_t)n_streams * (2 * agc_block + 4));
     {
         std::vector<int8_t> fr;
         w->fir_scale = nfm_fir_table(dt, Ld, limit_max, fr);
-        if (e == hipSuccess) e = hipMemcpy(w->d_fir_frags, fr.data(), fr.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(w->d_fir_frags.get(), fr.data(), fr.size(), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) { fail(e, "hipMalloc/hipMemcpy(nfm state)", __FILE__, __LINE__); csdr_amd_nfm_destroy(w); return nullptr; }
-    if (csdr_amd_nfm_reset(w)) { csdr_amd_nfm_destroy(w); return nullptr; }
-    return w;
+    if (e != hipSuccess) { fail(e, "hipMalloc/hipMemcpy(nfm state)", __FILE__, __LINE__); return nullptr; }
+    if (csdr_amd_nfm_reset(w.get())) return nullptr;
+    return w.release();
 }
 
 csdr_amd_nfm *csdr_amd_nfm_create(csdr_amd_ctx *ctx, int n_streams, float shift_rate, int decimation, const float *host_taps, int taps_length,
@@ -269,15 +268,12 @@ csdr_amd_nfm *csdr_amd_nfm_create_rates(csdr_amd_ctx *ctx, int n_streams, const 
     return nfm_create_impl(ctx, n_streams, shift_rates, true, decimation, host_taps, taps_length, audio_rate, agc_block, agc_reference, limit_max, max_block_samples);
 }
 
-int csdr_amd_nfm_set_rate(csdr_amd_nfm *w, int stream, float shift_rate) { return csdr_amd_ddc_set_rate(w->ddc, stream, shift_rate); }
+int csdr_amd_nfm_set_rate(csdr_amd_nfm *w, int stream, float shift_rate) { return csdr_amd_ddc_set_rate(w->ddc.get(), stream, shift_rate); }
 
 void csdr_amd_nfm_destroy(csdr_amd_nfm *w)
 {
     if (!w) return;
     (void)hipStreamSynchronize(w->ctx->stream);
-    if (w->ddc) csdr_amd_ddc_destroy(w->ddc);
-    (void)hipFree(w->d_y); (void)hipFree(w->d_last); (void)hipFree(w->d_last2); (void)hipFree(w->d_planes); (void)hipFree(w->d_fir_frags); (void)hipFree(w->d_de);
-    (void)hipFree(w->d_agc_state);
     delete w;
 }
 
@@ -285,14 +281,14 @@ int csdr_amd_nfm_reset(csdr_amd_nfm *w)
 {
     hipStream_t st = w->ctx->stream;
     w->dl_fill = w->cli_prefix;                                                                                // zeros (the planes are cleared below): see csdr_amd_nfm_create
-    CSDR_HIP(hipMemsetAsync(w->d_planes, 0, 3 * w->plane_bytes, st));                                          // bytes behind the valid samples meet zero weights, but must be initialised
-    CSDR_HIP(hipMemsetAsync(w->d_last, 0, sizeof(cf32) * w->n_streams, st));                                   // the CLI starts fmdemod from (0, 0) (csdr.c:1044)
-    CSDR_HIP(hipMemsetAsync(w->d_last2, 0, sizeof(cf32) * w->n_streams, st)); w->lflip = 0;
-    CSDR_HIP(hipMemsetAsync(w->d_agc_state, 0, sizeof(float) * (size_t)w->n_streams * (2 * w->agc_block + 4), st));   // calloc'ed fastagc state (csdr.c:1393-1394)
-    return csdr_amd_ddc_reset(w->ddc);
+    CSDR_HIP(hipMemsetAsync(w->d_planes.get(), 0, 3 * w->plane_bytes, st));                                          // bytes behind the valid samples meet zero weights, but must be initialised
+    CSDR_HIP(hipMemsetAsync(w->d_last.get(), 0, sizeof(cf32) * w->n_streams, st));                                   // the CLI starts fmdemod from (0, 0) (csdr.c:1044)
+    CSDR_HIP(hipMemsetAsync(w->d_last2.get(), 0, sizeof(cf32) * w->n_streams, st)); w->lflip = 0;
+    CSDR_HIP(hipMemsetAsync(w->d_agc_state.get(), 0, sizeof(float) * (size_t)w->n_streams * (2 * w->agc_block + 4), st));   // calloc'ed fastagc state (csdr.c:1393-1394)
+    return csdr_amd_ddc_reset(w->ddc.get());
 }
 
-csdr_amd_ddc *csdr_amd_nfm_front_end(csdr_amd_nfm *w) { return w->ddc; }
+csdr_amd_ddc *csdr_amd_nfm_front_end(csdr_amd_nfm *w) { return w->ddc.get(); }
 
 long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, size_t block_samples, int16_t *audio_s16, float *audio_f, size_t out_pitch)
 {
@@ -301,22 +297,22 @@ long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, s
     // front end; on its matrix-core path the reducer epilogue demodulates, limits and writes the digit planes itself (the decimated complex stream never goes
     // to HBM: only the samples at workgroup / kernel boundaries do, for k_nfm_demod_boundary).  CSDR_AMD_NFM_FUSE=0: the separate pass over y.
     const bool fuse_off = w->fuse_off;
-    DdcFuse fz; fz.planes = w->d_planes; fz.plane_bytes = w->plane_bytes; fz.dl_pitch = w->dl_pitch; fz.dl_fill = w->dl_fill; fz.max_amp = w->limit; fz.q_per_amp = NFM_XQ / w->limit;
+    DdcFuse fz; fz.planes = w->d_planes.get(); fz.plane_bytes = w->plane_bytes; fz.dl_pitch = w->dl_pitch; fz.dl_fill = w->dl_fill; fz.max_amp = w->limit; fz.q_per_amp = NFM_XQ / w->limit;
     DdcFuseInfo fi; memset(&fi, 0, sizeof fi);
-    const long n_y = ddc_process_fused(w->ddc, in, in_pitch, block_samples, w->d_y, w->y_pitch, fuse_off ? nullptr : &fz, &fi);
+    const long n_y = ddc_process_fused(w->ddc.get(), in, in_pitch, block_samples, w->d_y.get(), w->y_pitch, fuse_off ? nullptr : &fz, &fi);
     if (n_y < 0) return n_y;
     if (n_y == 0) return 0;
     if ((size_t)n_y > w->max_y) return fail_msg(-3, "nfm: front end produced more than the planned %zu samples", w->max_y);
-    cf32 *last_in = w->lflip ? w->d_last2 : w->d_last, *last_out = w->lflip ? w->d_last : w->d_last2;
+    cf32 *last_in = w->lflip ? w->d_last2.get() : w->d_last.get(), *last_out = w->lflip ? w->d_last.get() : w->d_last2.get();
     if (fi.fused) {
         const long nb_out = fi.n_lead + fi.n_seg + fi.n_trail;
-        hipLaunchKernelGGL(k_nfm_demod_boundary, dim3(cdiv(nb_out > 0 ? nb_out : 1, 64), S), dim3(64), 0, st, w->d_y, w->y_pitch, last_in, last_out, (int)n_y, fi, fz);
+        hipLaunchKernelGGL(k_nfm_demod_boundary, dim3(cdiv(nb_out > 0 ? nb_out : 1, 64), S), dim3(64), 0, st, w->d_y.get(), w->y_pitch, last_in, last_out, (int)n_y, fi, fz);
         CSDR_LAUNCH_CHECK();
     } else {
         // fmdemod_quadri_cf | limit_ff, appended behind the filter's unconsumed input
-        hipLaunchKernelGGL(k_nfm_demod_limit, dim3(cdiv(n_y, 256), S), dim3(256), 0, st, w->d_y, w->y_pitch, (int)n_y, last_in, w->d_planes, w->plane_bytes, w->dl_pitch, w->dl_fill, w->limit, NFM_XQ / w->limit);
+        hipLaunchKernelGGL(k_nfm_demod_limit, dim3(cdiv(n_y, 256), S), dim3(256), 0, st, w->d_y.get(), w->y_pitch, (int)n_y, last_in, w->d_planes.get(), w->plane_bytes, w->dl_pitch, w->dl_fill, w->limit, NFM_XQ / w->limit);
         CSDR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_nfm_store_last, dim3(cdiv(S, 64)), dim3(64), 0, st, w->d_y, w->y_pitch, (int)n_y, last_out, S);
+        hipLaunchKernelGGL(k_nfm_store_last, dim3(cdiv(S, 64)), dim3(64), 0, st, w->d_y.get(), w->y_pitch, (int)n_y, last_out, S);
         CSDR_LAUNCH_CHECK();
     }
     w->lflip ^= 1;
@@ -334,11 +330,11 @@ long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, s
             const bool fuse_peaks = w->agc_block == 16 * NFM_FIR_SPAN && !fuse_off;
             float *peaks = fuse_peaks ? fastagc_peaks_buffer(c, S, nb) : nullptr;
             if (fuse_peaks && !peaks) return -2;
-            hipLaunchKernelGGL(k_nfm_deemph_mfma, dim3(gx, n_sb), dim3(256), 0, st, w->d_planes, w->plane_bytes, w->dl_pitch, (const v4i *)w->d_fir_frags, w->fir_scale,
-                               w->d_de, w->a_pitch, n_tiles, S, peaks, nb + 2);
+            hipLaunchKernelGGL(k_nfm_deemph_mfma, dim3(gx, n_sb), dim3(256), 0, st, w->d_planes.get(), w->plane_bytes, w->dl_pitch, (const v4i *)w->d_fir_frags.get(), w->fir_scale,
+                               w->d_de.get(), w->a_pitch, n_tiles, S, peaks, nb + 2);
             CSDR_LAUNCH_CHECK();
             // fastagc_ff | convert_f_s16 in one pass (the float audio is written only when the caller wants the parity tap)
-            int rc = fastagc_ff_s16(c, w->d_de, audio_f, audio_s16, S, nb, w->agc_block, w->a_pitch, out_pitch, out_pitch, w->agc_ref, w->d_agc_state, fuse_peaks);
+            int rc = fastagc_ff_s16(c, w->d_de.get(), audio_f, audio_s16, S, nb, w->agc_block, w->a_pitch, out_pitch, out_pitch, w->agc_ref, w->d_agc_state.get(), fuse_peaks);
             if (rc) return rc;
         }
     }
@@ -346,7 +342,7 @@ long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, s
     const int rem = n_in - ne;
     if (ne > 0 && rem > 0) {
         if (rem > 2048) return fail_msg(-3, "nfm: internal carry of %d samples", rem);
-        hipLaunchKernelGGL(k_nfm_move_front_planes, dim3(S, 3), dim3(256), 0, st, w->d_planes, w->plane_bytes, w->dl_pitch, ne, rem);
+        hipLaunchKernelGGL(k_nfm_move_front_planes, dim3(S, 3), dim3(256), 0, st, w->d_planes.get(), w->plane_bytes, w->dl_pitch, ne, rem);
         CSDR_LAUNCH_CHECK();
     }
     w->dl_fill = rem;

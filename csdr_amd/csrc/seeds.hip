@@ -93,18 +93,18 @@ __global__ void k_seed_set(float *rates, int *corr_row, int *row_stream, int s, 
 struct csdr_amd::SeedTables {
     csdr_amd_ctx *ctx;
     int n; size_t pitch; int cap; size_t per_call;
-    hipStream_t side;
-    float *d_rates; std::vector<float> rates;
-    float *d_ph[2]; float2 *d_c[2]; float2 *d_corr[2];
-    int *d_corr_row, *d_row_stream; std::vector<int> corr_row, row_stream; int corr_rows;      // rows allocated
+    Stream side;
+    DevBuf<float> d_rates; std::vector<float> rates;
+    DevBuf<float> d_ph[2]; DevBuf<float2> d_c[2], d_corr[2];
+    DevBuf<int> d_corr_row, d_row_stream; std::vector<int> corr_row, row_stream; int corr_rows;      // rows allocated
     const float2 *d_dtab; size_t dtab_stride;
     long long first[2]; bool valid[2];
-    hipEvent_t ev_ready[2], ev_free[2]; bool free_pending[2];
+    Event ev_ready[2], ev_free[2]; bool free_pending[2];
     int cur;
     bool fresh, dirty;
     // few streams (the CLI's one): the phase chain runs on the HOST (the same wrap_plan code, host build: ~25 ns per chunk step against ~130 ns for a lane of
     // k_seed_phases, whose one wave leaves 63 lanes idle) into pinned shadows of the two tables, uploaded on the side stream
-    bool host_chain; float *h_ph[2]; bool h_used[2];
+    bool host_chain; HostBuf<float> h_ph[2]; bool h_used[2];
 };
 
 namespace {
@@ -112,11 +112,11 @@ namespace {
 int alloc_corr(SeedTables *t, int rows)
 {
     for (int b = 0; b < 2; b++) {
-        if (t->d_corr[b]) { CSDR_HIP(hipFree(t->d_corr[b])); t->d_corr[b] = nullptr; }
-        if (rows > 0) CSDR_HIP(hipMalloc((void **)&t->d_corr[b], sizeof(float2) * 32 * (size_t)rows * t->cap));
+        t->d_corr[b].reset();
+        if (rows > 0) CSDR_HIP(dev_alloc(t->d_corr[b], sizeof(float2) * 32 * (size_t)rows * t->cap));
     }
-    if (t->d_row_stream) { CSDR_HIP(hipFree(t->d_row_stream)); t->d_row_stream = nullptr; }
-    if (rows > 0) CSDR_HIP(hipMalloc((void **)&t->d_row_stream, sizeof(int) * rows));
+    t->d_row_stream.reset();
+    if (rows > 0) CSDR_HIP(dev_alloc(t->d_row_stream, sizeof(int) * rows));
     t->corr_rows = rows;
     t->row_stream.assign(rows, -1);
     return 0;
@@ -125,11 +125,11 @@ int alloc_corr(SeedTables *t, int rows)
 // queue the generation of table `dst` on the side stream: from table `src` at entry idx (src < 0: stream start), first chunk `first`
 int generate(SeedTables *t, int dst, int src, long idx, long long first)
 {
-    hipStream_t ss = t->side;
-    if (t->free_pending[dst]) { CSDR_HIP(hipStreamWaitEvent(ss, t->ev_free[dst], 0)); t->free_pending[dst] = false; }      // the data kernels that read it have finished
+    hipStream_t ss = t->side.get();
+    if (t->free_pending[dst]) { CSDR_HIP(hipStreamWaitEvent(ss, t->ev_free[dst].get(), 0)); t->free_pending[dst] = false; }      // the data kernels that read it have finished
     if (t->host_chain) {
-        if (t->h_used[dst]) CSDR_HIP(hipEventSynchronize(t->ev_ready[dst]));       // the previous upload out of this shadow has run (long ago)
-        float *h = t->h_ph[dst]; const float *o = src >= 0 ? t->h_ph[src] : nullptr;
+        if (t->h_used[dst]) CSDR_HIP(hipEventSynchronize(t->ev_ready[dst].get()));       // the previous upload out of this shadow has run (long ago)
+        float *h = t->h_ph[dst].get(); const float *o = src >= 0 ? t->h_ph[src].get() : nullptr;
         for (int s = 0; s < t->n; s++) {
             const float inc = (t->rates[s] * 2) * PI_F, step = inc * (float)1024;  // as k_seed_phases
             const float p0 = o ? o[(size_t)idx * t->pitch + s] : 0.f, p1 = o ? o[(size_t)(idx + 1) * t->pitch + s] : 0.f;
@@ -138,23 +138,23 @@ int generate(SeedTables *t, int dst, int src, long idx, long long first)
             float p = p1;
             for (int k = 2; k < t->cap; k++) { p = wrap_plan_apply(w, p + step); h[(size_t)k * t->pitch + s] = p; }
         }
-        CSDR_HIP(hipMemcpyAsync(t->d_ph[dst], h, sizeof(float) * t->pitch * (size_t)t->cap, hipMemcpyHostToDevice, ss));
+        CSDR_HIP(hipMemcpyAsync(t->d_ph[dst].get(), h, sizeof(float) * t->pitch * (size_t)t->cap, hipMemcpyHostToDevice, ss));
         t->h_used[dst] = true;
     }
     // One launch of 64-lane workgroups (a wave per CU on sixteen CUs at 1024 streams), wave priority raised: a wave of this kernel is a chain of dependent operations that
     // occupies its SIMD for the whole table (milliseconds), and a CU that holds one cannot take a workgroup of the per-stream WFM kernel (2 x 256 registers per SIMD).
     // Round 5 measured the alternatives (larger workgroups on fewer CUs, the table in slices, normal priority, the generator switched off as a ceiling: profiles/r5_notes.md);
     // none paid, their switches are gone.
-    if (!t->host_chain) hipLaunchKernelGGL(k_seed_phases<true>, dim3(cdiv(t->n, 64)), dim3(64), 0, ss, t->d_rates, src >= 0 ? t->d_ph[src] : nullptr, idx, t->d_ph[dst], t->pitch, 2, t->cap, t->n);
+    if (!t->host_chain) hipLaunchKernelGGL(k_seed_phases<true>, dim3(cdiv(t->n, 64)), dim3(64), 0, ss, t->d_rates.get(), src >= 0 ? t->d_ph[src].get() : nullptr, idx, t->d_ph[dst].get(), t->pitch, 2, t->cap, t->n);
     CSDR_LAUNCH_CHECK();
     const size_t count = t->pitch * (size_t)t->cap;
-    hipLaunchKernelGGL(k_seed_cossin, dim3(cdiv(count, 256)), dim3(256), 0, ss, t->d_ph[dst], t->d_c[dst], count);
+    hipLaunchKernelGGL(k_seed_cossin, dim3(cdiv(count, 256)), dim3(256), 0, ss, t->d_ph[dst].get(), t->d_c[dst].get(), count);
     CSDR_LAUNCH_CHECK();
     if (t->corr_rows > 0 && t->d_dtab) {
-        hipLaunchKernelGGL(k_seed_corr, dim3(cdiv(t->cap, 64), t->corr_rows), dim3(64), 0, ss, t->d_c[dst], t->pitch, t->cap, t->d_row_stream, t->d_rates, t->d_dtab, t->dtab_stride, t->d_corr[dst]);
+        hipLaunchKernelGGL(k_seed_corr, dim3(cdiv(t->cap, 64), t->corr_rows), dim3(64), 0, ss, t->d_c[dst].get(), t->pitch, t->cap, t->d_row_stream.get(), t->d_rates.get(), t->d_dtab, t->dtab_stride, t->d_corr[dst].get());
         CSDR_LAUNCH_CHECK();
     }
-    CSDR_HIP(hipEventRecord(t->ev_ready[dst], ss));
+    CSDR_HIP(hipEventRecord(t->ev_ready[dst].get(), ss));
     t->first[dst] = first; t->valid[dst] = true;
     return 0;
 }
@@ -165,75 +165,64 @@ namespace csdr_amd {
 
 SeedTables *seeds_create(csdr_amd_ctx *ctx, int n_streams, const float *rates, const float2 *d_dtab, size_t dtab_stride, size_t max_block_samples)
 {
-    SeedTables *t = new SeedTables();
+    Owned<SeedTables, seeds_destroy> t(new SeedTables());
     t->ctx = ctx; t->n = n_streams; t->pitch = ((size_t)n_streams + 63) & ~(size_t)63;
     t->per_call = max_block_samples / 1024 + 8;
     // calls ahead: up to 8, within ~96 MB for the two tables
     size_t k = (size_t)96 << 20; k /= 2 * t->per_call * t->pitch * 12; if (k > 8) k = 8; if (k < 2) k = 2;
     t->cap = (int)(k * t->per_call);
-    t->side = nullptr; t->d_rates = nullptr; t->d_corr_row = nullptr; t->d_row_stream = nullptr; t->corr_rows = 0;
     t->d_dtab = d_dtab; t->dtab_stride = dtab_stride;
-    for (int b = 0; b < 2; b++) { t->d_ph[b] = nullptr; t->d_c[b] = nullptr; t->d_corr[b] = nullptr; t->ev_ready[b] = nullptr; t->ev_free[b] = nullptr; t->valid[b] = false; t->free_pending[b] = false; t->first[b] = 0; }
     t->rates.assign(rates, rates + n_streams); t->corr_row.assign(n_streams, -1);
-    t->cur = 0; t->fresh = true; t->dirty = false;
-    t->h_ph[0] = t->h_ph[1] = nullptr; t->h_used[0] = t->h_used[1] = false;
+    t->fresh = true;
     { const char *eh = getenv("CSDR_AMD_SEED_HOST"); const int max_host = eh ? atoi(eh) : 2; t->host_chain = n_streams <= max_host; }      // (0: always the device chain)
-    hipError_t e = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking);
+    hipError_t e = stream_create(t->side);
     for (int b = 0; b < 2 && e == hipSuccess && t->host_chain; b++) {
-        e = hipHostMalloc((void **)&t->h_ph[b], sizeof(float) * t->pitch * t->cap, hipHostMallocDefault);
-        if (e == hipSuccess) memset(t->h_ph[b], 0, sizeof(float) * t->pitch * t->cap);
+        e = host_alloc(t->h_ph[b], sizeof(float) * t->pitch * t->cap);
+        if (e == hipSuccess) memset(t->h_ph[b].get(), 0, sizeof(float) * t->pitch * t->cap);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_rates, sizeof(float) * t->pitch);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_corr_row, sizeof(int) * t->pitch);
+    if (e == hipSuccess) e = dev_alloc(t->d_rates, sizeof(float) * t->pitch);
+    if (e == hipSuccess) e = dev_alloc(t->d_corr_row, sizeof(int) * t->pitch);
     for (int b = 0; b < 2 && e == hipSuccess; b++) {
-        e = hipMalloc((void **)&t->d_ph[b], sizeof(float) * t->pitch * t->cap);
-        if (e == hipSuccess) e = hipMalloc((void **)&t->d_c[b], sizeof(float2) * t->pitch * t->cap);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev_ready[b], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev_free[b], hipEventDisableTiming);
+        e = dev_alloc(t->d_ph[b], sizeof(float) * t->pitch * t->cap);
+        if (e == hipSuccess) e = dev_alloc(t->d_c[b], sizeof(float2) * t->pitch * t->cap);
+        if (e == hipSuccess) e = event_create(t->ev_ready[b], hipEventDisableTiming);
+        if (e == hipSuccess) e = event_create(t->ev_free[b], hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipMemset(t->d_rates, 0, sizeof(float) * t->pitch);
-    if (e == hipSuccess) e = hipMemset(t->d_corr_row, 0xff, sizeof(int) * t->pitch);
-    for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMemset(t->d_ph[b], 0, sizeof(float) * t->pitch * t->cap);
-    if (e == hipSuccess) e = hipMemcpy(t->d_rates, rates, sizeof(float) * n_streams, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { fail(e, "seeds_create", __FILE__, __LINE__); seeds_destroy(t); return nullptr; }
-    return t;
+    if (e == hipSuccess) e = hipMemset(t->d_rates.get(), 0, sizeof(float) * t->pitch);
+    if (e == hipSuccess) e = hipMemset(t->d_corr_row.get(), 0xff, sizeof(int) * t->pitch);
+    for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMemset(t->d_ph[b].get(), 0, sizeof(float) * t->pitch * t->cap);
+    if (e == hipSuccess) e = hipMemcpy(t->d_rates.get(), rates, sizeof(float) * n_streams, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { fail(e, "seeds_create", __FILE__, __LINE__); return nullptr; }
+    return t.release();
 }
 
 void seeds_destroy(SeedTables *t)
 {
     if (!t) return;
-    if (t->side) (void)hipStreamSynchronize(t->side);
+    if (t->side) (void)hipStreamSynchronize(t->side.get());
     (void)hipStreamSynchronize(t->ctx->stream);
-    for (int b = 0; b < 2; b++) {
-        (void)hipFree(t->d_ph[b]); (void)hipFree(t->d_c[b]); (void)hipFree(t->d_corr[b]);
-        if (t->ev_ready[b]) (void)hipEventDestroy(t->ev_ready[b]);
-        if (t->ev_free[b]) (void)hipEventDestroy(t->ev_free[b]);
-    }
-    (void)hipFree(t->d_rates); (void)hipFree(t->d_corr_row); (void)hipFree(t->d_row_stream);
-    for (int b = 0; b < 2; b++) if (t->h_ph[b]) (void)hipHostFree(t->h_ph[b]);
-    if (t->side) (void)hipStreamDestroy(t->side);
     delete t;
 }
 
 // the drift rows of all streams at once (create / reset time and when the rows run out): everything is synchronised
 int seeds_set_drift(SeedTables *t, const std::vector<char> &drift)
 {
-    CSDR_HIP(hipStreamSynchronize(t->side)); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
+    CSDR_HIP(hipStreamSynchronize(t->side.get())); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
     int rows = 0;
     for (int s = 0; s < t->n; s++) rows += drift[s] ? 1 : 0;
     if (rows > t->corr_rows) { const int rc = alloc_corr(t, rows + 8); if (rc) return rc; }
     t->row_stream.assign(t->corr_rows, -1);
     int r = 0;
     for (int s = 0; s < t->n; s++) { t->corr_row[s] = drift[s] ? r : -1; if (drift[s]) t->row_stream[r++] = s; }
-    CSDR_HIP(hipMemcpy(t->d_corr_row, t->corr_row.data(), sizeof(int) * t->n, hipMemcpyHostToDevice));
-    if (t->corr_rows > 0) CSDR_HIP(hipMemcpy(t->d_row_stream, t->row_stream.data(), sizeof(int) * t->corr_rows, hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(t->d_corr_row.get(), t->corr_row.data(), sizeof(int) * t->n, hipMemcpyHostToDevice));
+    if (t->corr_rows > 0) CSDR_HIP(hipMemcpy(t->d_row_stream.get(), t->row_stream.data(), sizeof(int) * t->corr_rows, hipMemcpyHostToDevice));
     t->dirty = true;
     return 0;
 }
 
 int seeds_reset(SeedTables *t)
 {
-    CSDR_HIP(hipStreamSynchronize(t->side));
+    CSDR_HIP(hipStreamSynchronize(t->side.get()));
     t->valid[0] = t->valid[1] = false; t->fresh = true; t->dirty = false; t->cur = 0;
     return 0;
 }
@@ -252,8 +241,8 @@ int seeds_set_rate(SeedTables *t, int stream, float rate, bool drift)
                 for (int s = 0; s < t->n; s++) dr[s] = t->corr_row[s] >= 0;
                 dr[stream] = 1;
                 t->rates[stream] = rate;
-                CSDR_HIP(hipStreamSynchronize(t->side)); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
-                CSDR_HIP(hipMemcpy(t->d_rates + stream, &rate, sizeof(float), hipMemcpyHostToDevice));
+                CSDR_HIP(hipStreamSynchronize(t->side.get())); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
+                CSDR_HIP(hipMemcpy(t->d_rates.get() + stream, &rate, sizeof(float), hipMemcpyHostToDevice));
                 // the current table's phases must survive: only the correction buffers are reallocated
                 return seeds_set_drift(t, dr);
             }
@@ -263,7 +252,7 @@ int seeds_set_rate(SeedTables *t, int stream, float rate, bool drift)
     if (row >= 0) t->row_stream[row] = stream;
     t->corr_row[stream] = row; t->rates[stream] = rate;
     // in order behind whatever the side stream is still generating (that table is dropped below), in front of the regeneration
-    hipLaunchKernelGGL(k_seed_set, dim3(1), dim3(1), 0, t->side, t->d_rates, t->d_corr_row, t->d_row_stream, stream, rate, row, old_row);
+    hipLaunchKernelGGL(k_seed_set, dim3(1), dim3(1), 0, t->side.get(), t->d_rates.get(), t->d_corr_row.get(), t->d_row_stream.get(), stream, rate, row, old_row);
     CSDR_LAUNCH_CHECK();
     t->dirty = true;
     return 0;
@@ -274,7 +263,7 @@ const float2 *seeds_corr_entry(SeedTables *t, int stream, long long chunk)
     if (stream < 0 || stream >= t->n || t->corr_row[stream] < 0 || !t->d_dtab || t->corr_rows <= 0) return nullptr;
     const int c = t->cur;
     if (t->fresh || !t->valid[c] || chunk < t->first[c] || chunk >= t->first[c] + t->cap) return nullptr;
-    return t->d_corr[c] + ((size_t)t->corr_row[stream] * t->cap + (size_t)(chunk - t->first[c])) * 32;
+    return t->d_corr[c].get() + ((size_t)t->corr_row[stream] * t->cap + (size_t)(chunk - t->first[c])) * 32;
 }
 
 int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, SeedView *v)
@@ -285,14 +274,14 @@ int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, 
     bool switched = false;
     if (t->fresh) {
         t->valid[0] = t->valid[1] = false; t->cur = 0;
-        CSDR_HIP(hipEventRecord(t->ev_free[0], st)); t->free_pending[0] = true;      // (a reset in mid-stream: earlier calls may still be reading)
-        CSDR_HIP(hipEventRecord(t->ev_free[1], st)); t->free_pending[1] = true;
+        CSDR_HIP(hipEventRecord(t->ev_free[0].get(), st)); t->free_pending[0] = true;      // (a reset in mid-stream: earlier calls may still be reading)
+        CSDR_HIP(hipEventRecord(t->ev_free[1].get(), st)); t->free_pending[1] = true;
         int rc = generate(t, 0, -1, 0, first); if (rc) return rc;
         t->fresh = false; t->dirty = false; switched = true;
     } else if (t->dirty || !covers(t->cur)) {
         const int o = t->cur ^ 1;
         if (!t->dirty && covers(o)) {                                 // the prepared table takes over
-            CSDR_HIP(hipEventRecord(t->ev_free[t->cur], st)); t->free_pending[t->cur] = true;
+            CSDR_HIP(hipEventRecord(t->ev_free[t->cur].get(), st)); t->free_pending[t->cur] = true;
             t->cur = o;
         } else {
             // regenerate from the phases some table holds for chunks first, first + 1 (a retune, or a call the prepared table does not fit): the history chunk and
@@ -301,17 +290,17 @@ int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, 
             for (int b : {t->cur, o}) if (src < 0 && t->valid[b] && first >= t->first[b] && first + 1 < t->first[b] + t->cap) src = b;
             if (src < 0) return fail_msg(-3, "seed table: cannot continue at chunk %lld", first);
             const int dst = src ^ 1;
-            CSDR_HIP(hipEventRecord(t->ev_free[dst], st)); t->free_pending[dst] = true;      // whatever was queued so far may still read it
+            CSDR_HIP(hipEventRecord(t->ev_free[dst].get(), st)); t->free_pending[dst] = true;      // whatever was queued so far may still read it
             t->valid[dst] = false;
             int rc = generate(t, dst, src, (long)(first - t->first[src]), first); if (rc) return rc;
-            if (dst != t->cur) { CSDR_HIP(hipEventRecord(t->ev_free[t->cur], st)); t->free_pending[t->cur] = true; }
+            if (dst != t->cur) { CSDR_HIP(hipEventRecord(t->ev_free[t->cur].get(), st)); t->free_pending[t->cur] = true; }
             t->cur = dst;
         }
         t->dirty = false; switched = true;
     }
     const int c = t->cur, o = c ^ 1;
     // (a wait on an event that has fired is not queued at all: each costs ~10 us of bubble on the stream)
-    if (switched && hipEventQuery(t->ev_ready[c]) != hipSuccess) CSDR_HIP(hipStreamWaitEvent(st, t->ev_ready[c], 0));
+    if (switched && hipEventQuery(t->ev_ready[c].get()) != hipSuccess) CSDR_HIP(hipStreamWaitEvent(st, t->ev_ready[c].get(), 0));
     // prepare the table behind this one on the side stream: it starts at the first call that will not fit, assuming calls that advance by n_next_hint chunks
     if (!(t->valid[o] && t->first[o] > t->first[c]) && n_next_hint > 0) {
         long long f = first;
@@ -320,10 +309,10 @@ int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, 
         if (idx >= 0 && idx + 1 < t->cap) { t->valid[o] = false; int rc = generate(t, o, c, idx, f); if (rc) return rc; }
     }
     v->pitch = t->pitch;
-    v->ctab = t->d_c[c] + (size_t)(first - t->first[c]) * t->pitch;
+    v->ctab = t->d_c[c].get() + (size_t)(first - t->first[c]) * t->pitch;
     v->n_entries = (int)(t->first[c] + t->cap - first);
-    v->corr = t->corr_rows > 0 && t->d_dtab ? t->d_corr[c] + (size_t)(first - t->first[c]) * 32 : nullptr;
-    v->corr_row = t->d_corr_row; v->corr_chunks = (size_t)t->cap;
+    v->corr = t->corr_rows > 0 && t->d_dtab ? t->d_corr[c].get() + (size_t)(first - t->first[c]) * 32 : nullptr;
+    v->corr_row = t->d_corr_row.get(); v->corr_chunks = (size_t)t->cap;
     return 0;
 }
 

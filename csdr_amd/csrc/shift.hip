@@ -203,40 +203,33 @@ __global__ __launch_bounds__(64) void k_dsa(const cf32 *__restrict__ in, cf32 *_
 // thread already walks the NEXT call's n samples from this call's end phase into the other of two pinned buffers.  A streaming caller (same rate, same block length, the
 // phase it was handed back) finds its tile phases ready: round 5 had the scan inside every call (1.6 ms per 2 M samples, 17 % of the roofline for 64 streams: VERDICT r5).
 // Anything else -- first call, a retune, another length -- scans in the call as before.  Same operations in the same order either way: the same bits.
-struct ShiftAheadSlot { float *tiles = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool uploading = false;
-                        bool predicted = false; float rate = 0, phase_in = 0, phase_out = 0; size_t n = 0; std::future<void> fut; };
-struct ShiftAhead { ShiftAheadSlot slot[2]; int cur = 0; };
+struct ShiftAheadSlot { HostBuf<float> tiles; size_t cap = 0; Event ev; bool uploading = false;
+                        bool predicted = false; float rate = 0, phase_in = 0, phase_out = 0; size_t n = 0; std::future<void> fut;
+                        ~ShiftAheadSlot() { if (fut.valid()) fut.wait(); if (uploading && ev) (void)hipEventSynchronize(ev.get()); } };
 static float shift_scan_tiles(float *tiles, float p, float inc, size_t n)
 {
     for (size_t k = 0; k < n; k++) { if (k % SHIFT_TILE == 0) tiles[k / SHIFT_TILE] = p; p = h_wrap_0_2pi(p + inc); }        // libcsdr.c:202-204, 260-262
     return p;
 }
-static void shift_ahead_free(void *v)
-{
-    ShiftAhead *a = (ShiftAhead *)v;
-    for (ShiftAheadSlot &s : a->slot) {
-        if (s.fut.valid()) s.fut.wait();
-        if (s.uploading && s.ev) (void)hipEventSynchronize(s.ev);
-        if (s.tiles) (void)hipHostFree(s.tiles);
-        if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    delete a;
-}
 static int shift_slot_reserve(ShiftAheadSlot &s, size_t n_tiles)
 {
     if (s.fut.valid()) s.fut.wait();
-    if (s.uploading) { CSDR_HIP(hipEventSynchronize(s.ev)); s.uploading = false; }
-    if (!s.ev) CSDR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (s.uploading) { CSDR_HIP(hipEventSynchronize(s.ev.get())); s.uploading = false; }
+    if (!s.ev) CSDR_HIP(event_create(s.ev, hipEventDisableTiming));
     if (n_tiles > s.cap) {
-        if (s.tiles) (void)hipHostFree(s.tiles);
-        s.tiles = nullptr; s.cap = 0;
-        CSDR_HIP(hipHostMalloc((void **)&s.tiles, sizeof(float) * (n_tiles + n_tiles / 2 + 64), hipHostMallocDefault));
+        s.cap = 0;
+        CSDR_HIP(host_alloc(s.tiles, sizeof(float) * (n_tiles + n_tiles / 2 + 64)));
         s.cap = n_tiles + n_tiles / 2 + 64;
     }
     return 0;
 }
 
 } // namespace
+
+namespace csdr_amd {
+struct ShiftAhead { ShiftAheadSlot slot[2]; int cur = 0; };
+void ShiftAheadDel::operator()(ShiftAhead *a) const { delete a; }
+}
 
 extern "C" {
 
@@ -284,8 +277,8 @@ int csdr_amd_rotator_generate(csdr_amd_ctx *c, int variant, float rate, float *p
         const size_t n_tiles = (n + SHIFT_TILE - 1) / SHIFT_TILE;
         float *ph = (float *)c->get_scratch(0, sizeof(float) * n_tiles);
         if (!ph) return -2;
-        if (!c->shift_ahead) { c->shift_ahead = new ShiftAhead(); c->shift_ahead_free = shift_ahead_free; }
-        ShiftAhead *sa = (ShiftAhead *)c->shift_ahead;
+        if (!c->shift_ahead) c->shift_ahead.reset(new ShiftAhead());
+        ShiftAhead *sa = c->shift_ahead.get();
         ShiftAheadSlot *use = nullptr;
         {   // the scan a previous call started for exactly this (rate, phase, n)?
             ShiftAheadSlot &pr = sa->slot[sa->cur ^ 1];
@@ -295,18 +288,18 @@ int csdr_amd_rotator_generate(csdr_amd_ctx *c, int variant, float rate, float *p
         if (!use) {                                                       // no: scan now, in the call
             use = &sa->slot[sa->cur];
             rc = shift_slot_reserve(*use, n_tiles); if (rc) return rc;
-            use->phase_out = shift_scan_tiles(use->tiles, p, inc, n);
+            use->phase_out = shift_scan_tiles(use->tiles.get(), p, inc, n);
         }
         use->predicted = false;
-        CSDR_HIP(hipMemcpyAsync(ph, use->tiles, sizeof(float) * n_tiles, hipMemcpyHostToDevice, st));
-        CSDR_HIP(hipEventRecord(use->ev, st)); use->uploading = true;
+        CSDR_HIP(hipMemcpyAsync(ph, use->tiles.get(), sizeof(float) * n_tiles, hipMemcpyHostToDevice, st));
+        CSDR_HIP(hipEventRecord(use->ev.get(), st)); use->uploading = true;
         p = use->phase_out;
         {   // the next call's scan, from this call's end phase, on a helper thread (the other buffer: its last upload has long run)
             ShiftAheadSlot &nx = sa->slot[sa->cur ^ 1];
             rc = shift_slot_reserve(nx, n_tiles); if (rc) return rc;
             nx.rate = rate; nx.n = n; nx.phase_in = p; nx.predicted = true;
             ShiftAheadSlot *np = &nx; const float p_next = p;
-            nx.fut = std::async(std::launch::async, [np, p_next, inc, n]() { np->phase_out = shift_scan_tiles(np->tiles, p_next, inc, n); });
+            nx.fut = std::async(std::launch::async, [np, p_next, inc, n]() { np->phase_out = shift_scan_tiles(np->tiles.get(), p_next, inc, n); });
         }
         if (variant == CSDR_SHIFT_MATH) {
             hipLaunchKernelGGL(k_fill_math, dim3(cdiv(n, 256)), dim3(256), 0, st, rot, ph, inc, n); CSDR_LAUNCH_CHECK();

@@ -373,8 +373,8 @@ struct csdr_amd_waterfall {
     csdr_amd_ctx *c; int fft, every, avg, in_format, out_format, n_streams; float add_db; size_t max_in;
     bool onepass, force_generic; const char *last_kernel;
     long long total, frames_done;                                        // samples per stream seen, frames completed (lockstep)
-    int hist_len, cur, acc_cur; void *d_hist[2]; float *d_w; float2 *d_tw; float *d_acc; WfSeg *d_segs; int segs_cap;   // d_acc: two [stream][N] buffers
-    float2 *d_frames; size_t frames_cap; int16_t *d_q; size_t q_cap; std::map<int, hipfftHandle> plans;
+    int hist_len, cur, acc_cur; DevBuf<> d_hist[2]; DevBuf<float> d_w; DevBuf<float2> d_tw; DevBuf<float> d_acc; DevBuf<WfSeg> d_segs; int segs_cap;   // d_acc: two [stream][N] buffers
+    DevBuf<float2> d_frames; size_t frames_cap; DevBuf<int16_t> d_q; size_t q_cap; std::map<int, FftPlan> plans;
 };
 
 namespace {
@@ -436,37 +436,37 @@ int run_generic(csdr_amd_waterfall *w, const WfArgs &a, long long k0, int n_fram
     const int pb = N >= (1 << 21) ? 1 : (1 << 21) / N;
     const size_t need = ((size_t)group * n_frames + pb - 1) / pb * pb * N * 8;
     if (need > w->frames_cap) {
-        csdr_amd_free(c, w->d_frames); w->frames_cap = need;
-        w->d_frames = (float2 *)csdr_amd_malloc(c, w->frames_cap);
+        w->d_frames.reset(); w->frames_cap = need;
+        w->d_frames.reset((float2 *)csdr_amd_malloc(c, w->frames_cap));
         if (!w->d_frames) { w->frames_cap = 0; return fail_msg(-2, "waterfall: frame buffer allocation failed"); }
     }
     if (w->out_format == CSDR_AMD_WF_OUT_ADPCM) {
         const size_t q = (size_t)group * n_segs * N * 2;
         if (q > w->q_cap) {
-            csdr_amd_free(c, w->d_q); w->q_cap = q; w->d_q = (int16_t *)csdr_amd_malloc(c, q);
+            w->d_q.reset(); w->q_cap = q; w->d_q.reset((int16_t *)csdr_amd_malloc(c, q));
             if (!w->d_q) { w->q_cap = 0; return fail_msg(-2, "waterfall: scratch allocation failed"); }
         }
     }
     if (!w->plans.count(pb)) {
         hipfftHandle h; int n[1] = {N};
         if (hipfftPlanMany(&h, 1, n, nullptr, 1, N, nullptr, 1, N, HIPFFT_C2C, pb) != HIPFFT_SUCCESS) return fail_msg(-5, "waterfall: hipfftPlanMany(%d x %d) failed", N, pb);
+        w->plans[pb].reset(h);
         hipfftSetStream(h, c->stream);
-        w->plans[pb] = h;
     }
     for (int s0 = 0; s0 < w->n_streams; s0 += group) {
         const int g = s0 + group <= w->n_streams ? group : w->n_streams - s0;
         const unsigned gx = cdiv(N, 256) > 16 ? 16 : cdiv(N, 256);
-        if (w->in_format == CSDR_AMD_WF_IN_U8) hipLaunchKernelGGL(k_wf_frame<1>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames, s0);
-        else hipLaunchKernelGGL(k_wf_frame<0>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames, s0);
+        if (w->in_format == CSDR_AMD_WF_IN_U8) hipLaunchKernelGGL(k_wf_frame<1>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
+        else hipLaunchKernelGGL(k_wf_frame<0>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
         CSDR_LAUNCH_CHECK();
         const size_t used = (size_t)g * n_frames, padded = (used + pb - 1) / pb * pb;
-        if (padded > used) CSDR_HIP(hipMemsetAsync(w->d_frames + used * N, 0, (padded - used) * N * 8, c->stream));   // (defined values in the plan's idle slots)
+        if (padded > used) CSDR_HIP(hipMemsetAsync(w->d_frames.get() + used * N, 0, (padded - used) * N * 8, c->stream));   // (defined values in the plan's idle slots)
         for (size_t f = 0; f < used; f += pb) {
-            hipfftComplex *z = (hipfftComplex *)(w->d_frames + f * N);
-            if (hipfftExecC2C(w->plans[pb], z, z, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "waterfall: hipfftExecC2C failed");
+            hipfftComplex *z = (hipfftComplex *)(w->d_frames.get() + f * N);
+            if (hipfftExecC2C(w->plans[pb].get(), z, z, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "waterfall: hipfftExecC2C failed");
         }
-        hipLaunchKernelGGL(k_wf_post<true>, dim3(n_segs, g), dim3(256), 0, c->stream, (const void *)w->d_frames, N, n_frames, w->avg, a.segs, a.acc_in, a.acc_out, a.out, a.out_pitch,
-                           w->out_format, a.add_db, 1, s0, w->out_format == CSDR_AMD_WF_OUT_ADPCM ? w->d_q : nullptr);
+        hipLaunchKernelGGL(k_wf_post<true>, dim3(n_segs, g), dim3(256), 0, c->stream, (const void *)w->d_frames.get(), N, n_frames, w->avg, a.segs, a.acc_in, a.acc_out, a.out, a.out_pitch,
+                           w->out_format, a.add_db, 1, s0, w->out_format == CSDR_AMD_WF_OUT_ADPCM ? w->d_q.get() : nullptr);
         CSDR_LAUNCH_CHECK();
     }
     return 0;
@@ -524,23 +524,22 @@ csdr_amd_waterfall *csdr_amd_waterfall_create(csdr_amd_ctx *c, int fft_size, int
         fail_msg(-3, "waterfall: fft_size must be a power of two >= 2; every_n, avgnumber, n_streams, max_samples_per_call positive; formats CSDR_AMD_WF_*");
         return nullptr;
     }
-    csdr_amd_waterfall *w = new csdr_amd_waterfall();
+    Owned<csdr_amd_waterfall, csdr_amd_waterfall_destroy> w(new csdr_amd_waterfall());
     w->c = c; w->fft = fft_size; w->every = every_n_samples; w->avg = avgnumber; w->in_format = in_format; w->out_format = out_format; w->n_streams = n_streams;
     w->add_db = (float)(add_db - 10.0 * log10((double)avgnumber));                // csdr.c:1678
     w->max_in = max_samples_per_call; w->onepass = onepass_size(fft_size); w->force_generic = false; w->last_kernel = "";
-    w->total = 0; w->frames_done = 0; w->cur = 0; w->hist_len = fft_size; w->segs_cap = 0; w->d_segs = nullptr;
-    w->d_frames = nullptr; w->frames_cap = 0; w->d_q = nullptr; w->q_cap = 0;
+    w->total = 0; w->frames_done = 0; w->cur = 0; w->hist_len = fft_size;
     const size_t hb = (size_t)n_streams * fft_size * elem_bytes(in_format);
-    w->d_hist[0] = csdr_amd_malloc(c, hb + 256); w->d_hist[1] = csdr_amd_malloc(c, hb + 256);
-    w->d_w = (float *)csdr_amd_malloc(c, 4 * (size_t)fft_size);
-    w->d_tw = (float2 *)csdr_amd_malloc(c, 8 * (size_t)fft_size);
-    w->d_acc = (float *)csdr_amd_malloc(c, 2 * 4 * (size_t)n_streams * fft_size);
-    if (!w->d_hist[0] || !w->d_hist[1] || !w->d_w || !w->d_tw || !w->d_acc) { csdr_amd_waterfall_destroy(w); return nullptr; }
+    w->d_hist[0].reset(csdr_amd_malloc(c, hb + 256)); w->d_hist[1].reset(csdr_amd_malloc(c, hb + 256));
+    w->d_w.reset((float *)csdr_amd_malloc(c, 4 * (size_t)fft_size));
+    w->d_tw.reset((float2 *)csdr_amd_malloc(c, 8 * (size_t)fft_size));
+    w->d_acc.reset((float *)csdr_amd_malloc(c, 2 * 4 * (size_t)n_streams * fft_size));
+    if (!w->d_hist[0] || !w->d_hist[1] || !w->d_w || !w->d_tw || !w->d_acc) return nullptr;
     std::vector<float> win(fft_size); csdr_amd_precalculate_window(win.data(), fft_size, window);
     std::vector<float2> tw; twiddle_table(fft_size, tw);
-    if (csdr_amd_h2d(c, w->d_w, win.data(), 4 * (size_t)fft_size) < 0 || csdr_amd_h2d(c, w->d_tw, tw.data(), 8 * (size_t)fft_size) < 0 ||
-        csdr_amd_waterfall_reset(w) < 0) { csdr_amd_waterfall_destroy(w); return nullptr; }
-    return w;
+    if (csdr_amd_h2d(c, w->d_w.get(), win.data(), 4 * (size_t)fft_size) < 0 || csdr_amd_h2d(c, w->d_tw.get(), tw.data(), 8 * (size_t)fft_size) < 0 ||
+        csdr_amd_waterfall_reset(w.get()) < 0) return nullptr;
+    return w.release();
 }
 
 int csdr_amd_waterfall_reset(csdr_amd_waterfall *w)
@@ -548,7 +547,7 @@ int csdr_amd_waterfall_reset(csdr_amd_waterfall *w)
     // (history positions before the stream's start are read as zeros whatever the buffer holds: wf_windowed)
     w->total = 0; w->frames_done = 0; w->cur = 0; w->acc_cur = 0;
     const size_t hb = (size_t)w->n_streams * w->fft * elem_bytes(w->in_format);
-    if (csdr_amd_memset(w->c, w->d_hist[0], 0, hb) < 0) return -5;
+    if (csdr_amd_memset(w->c, w->d_hist[0].get(), 0, hb) < 0) return -5;
     return 0;
 }
 
@@ -558,9 +557,7 @@ int csdr_amd_waterfall_force_generic(csdr_amd_waterfall *w, int on) { if (!w) re
 void csdr_amd_waterfall_destroy(csdr_amd_waterfall *w)
 {
     if (!w) return;
-    for (auto &kv : w->plans) hipfftDestroy(kv.second);
-    csdr_amd_free(w->c, w->d_hist[0]); csdr_amd_free(w->c, w->d_hist[1]); csdr_amd_free(w->c, w->d_w); csdr_amd_free(w->c, w->d_tw); csdr_amd_free(w->c, w->d_acc);
-    csdr_amd_free(w->c, w->d_segs); csdr_amd_free(w->c, w->d_frames); csdr_amd_free(w->c, w->d_q);
+    (void)hipSetDevice(w->c->device);
     delete w;
 }
 
@@ -578,21 +575,21 @@ int csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_i
     const size_t row_bytes = w->out_format == CSDR_AMD_WF_OUT_DB ? 4 * (size_t)w->fft : (size_t)(w->fft + 10) / 2;
     if (rows && out_pitch < (size_t)rows * row_bytes && w->n_streams > 1) return fail_msg(-3, "waterfall: out_pitch %zu below the %d rows of %zu bytes of this call", out_pitch, rows, row_bytes);
     WfArgs a;
-    a.in = in; a.in_pitch = in_pitch; a.hist = w->d_hist[w->cur]; a.hist_new = w->d_hist[w->cur ^ 1]; a.hist_len = w->hist_len;
+    a.in = in; a.in_pitch = in_pitch; a.hist = w->d_hist[w->cur].get(); a.hist_new = w->d_hist[w->cur ^ 1].get(); a.hist_len = w->hist_len;
     a.base = w->total; a.every = w->every; a.off = w->every < w->fft ? w->every - w->fft : 0;
-    a.window = w->d_w; a.table = w->d_tw;
-    a.acc_in = w->d_acc + (size_t)w->acc_cur * w->n_streams * w->fft; a.acc_out = w->d_acc + (size_t)(w->acc_cur ^ 1) * w->n_streams * w->fft; a.out = out; a.out_pitch = out_pitch; a.out_format = w->out_format; a.add_db = w->add_db;
+    a.window = w->d_w.get(); a.table = w->d_tw.get();
+    a.acc_in = w->d_acc.get() + (size_t)w->acc_cur * w->n_streams * w->fft; a.acc_out = w->d_acc.get() + (size_t)(w->acc_cur ^ 1) * w->n_streams * w->fft; a.out = out; a.out_pitch = out_pitch; a.out_format = w->out_format; a.add_db = w->add_db;
     if (!segs.empty()) {
         if ((int)segs.size() > w->segs_cap) {
-            csdr_amd_free(c, w->d_segs); w->segs_cap = (int)segs.size() + 64;
-            w->d_segs = (WfSeg *)csdr_amd_malloc(c, sizeof(WfSeg) * w->segs_cap);
+            w->d_segs.reset(); w->segs_cap = (int)segs.size() + 64;
+            w->d_segs.reset((WfSeg *)csdr_amd_malloc(c, sizeof(WfSeg) * w->segs_cap));
             if (!w->d_segs) { w->segs_cap = 0; return fail_msg(-2, "waterfall: segment table allocation failed"); }
         }
         void *h = c->pinned_acquire(sizeof(WfSeg) * segs.size());
         if (!h) return fail_msg(-2, "waterfall: pinned staging failed");
         memcpy(h, segs.data(), sizeof(WfSeg) * segs.size());
-        if (c->pinned_upload(w->d_segs, sizeof(WfSeg) * segs.size()) < 0) return -5;
-        a.segs = w->d_segs;
+        if (c->pinned_upload(w->d_segs.get(), sizeof(WfSeg) * segs.size()) < 0) return -5;
+        a.segs = w->d_segs.get();
         const bool onepass = w->onepass && !w->force_generic;
         const int rc = onepass ? run_onepass(w, a, (int)segs.size()) : run_generic(w, a, k0, (int)(k1 - k0), (int)segs.size());
         if (rc < 0) return rc;
@@ -602,7 +599,7 @@ int csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_i
     // the history moves on by n_in samples (after every read of the old one: same stream)
     const size_t eb = elem_bytes(w->in_format), hb = (size_t)w->hist_len * eb;
     hipLaunchKernelGGL(k_wf_hist, dim3(cdiv(hb / 2, 256) > 64 ? 64 : cdiv(hb / 2, 256), (unsigned)w->n_streams), dim3(256), 0, c->stream,
-                       (const uint8_t *)in, in_pitch * eb, (const uint8_t *)w->d_hist[w->cur], (uint8_t *)w->d_hist[w->cur ^ 1], hb, n_in * eb);
+                       (const uint8_t *)in, in_pitch * eb, (const uint8_t *)w->d_hist[w->cur].get(), (uint8_t *)w->d_hist[w->cur ^ 1].get(), hb, n_in * eb);
     CSDR_LAUNCH_CHECK();
     w->cur ^= 1;
     w->total += (long long)n_in; w->frames_done = k1;

@@ -200,11 +200,11 @@ struct csdr_amd_wfm {
     int n_streams, D, L, F, audio_rate;
     float shift_rate, tau, alpha;
     size_t max_block;
-    float *d_taps, *d_demod, *d_last[2];
+    DevBuf<float> d_taps, d_demod, d_last[2];
     float phase;                     // shift_addition_cc starting_phase (host float, like the reference's by-value state)
-    cf32 *d_rot;
-    uint8_t *d_hist;                 // VALU front end: 2 * HIST bytes per stream
-    uint8_t *d_head[2]; int hflip;   // matrix-core chain kernel: 1 KiB per stream, second half = the previous block's newest 512 bytes (two buffers: wfm_mfma.hip)
+    DevBuf<cf32> d_rot;
+    DevBuf<uint8_t> d_hist;          // VALU front end: 2 * HIST bytes per stream
+    DevBuf<uint8_t> d_head[2]; int hflip;   // matrix-core chain kernel: 1 KiB per stream, second half = the previous block's newest 512 bytes (two buffers: wfm_mfma.hip)
     size_t demod_pitch;
     long long B, next_j;
     int last_T, flip;
@@ -212,18 +212,19 @@ struct csdr_amd_wfm {
     std::string kernel_name;
     // optional HIP-event timing of the dominant kernel (bench.py roofline leg)
     bool profiling;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used;
+    KernelTimer timer;
     double prof_ms; long prof_launches;
     // matrix-core front end (wfm_mfma.hip)
     bool use_mfma;
-    WfmMfmaDevice mfma;
-    float2 *d_ctab; size_t ctab_cap;
+    WfmMfmaDevice mfma;              // (its tables are owned by seq_frags, seq_cum, dtab)
+    DevBuf<> seq_frags; DevBuf<float> seq_cum; DevBuf<float2> dtab;
+    DevBuf<float2> d_ctab; size_t ctab_cap;
     float2 c_prev;                   // phasor seed of the previous block's last chunk (history windows)
     long long tab_first; bool tab_valid;      // the device table of seeds covers chunks [tab_first, tab_first + ctab_cap)
     // a shift rate per stream (csdr_amd_wfm_create_rates): one table set per stream in mfma.*, chunk seeds from a seed table (seeds.hip)
-    bool ps; std::vector<float> rates, h_taps; csdr_amd::SeedTables *seeds; float *d_scales;
-    float2 *d_dtab_old; int *d_list, *d_lead_n; float *d_lead_d; std::vector<int> retuned;      // streams retuned since the last call: their first samples straddle two rates
+    bool ps; std::vector<float> rates, h_taps; DevBuf<float> d_scales;
+    DevBuf<float2> d_dtab_old; DevBuf<int> d_lead_n; int *d_list; DevBuf<float> d_lead_d; std::vector<int> retuned;      // streams retuned since the last call: their first samples straddle two rates
+    Owned<csdr_amd::SeedTables, seeds_destroy> seeds;                 // (d_list lives inside d_lead_n)
 };
 
 extern "C" {
@@ -236,7 +237,7 @@ static int wfm_upload_stream_tables(csdr_amd_wfm *w, int s, float rate)
     CSDR_HIP(hipMemcpy((uint8_t *)w->mfma.d_seq_frags + (size_t)s * t.seq_frags.size(), t.seq_frags.data(), t.seq_frags.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(w->mfma.d_seq_cum + (size_t)s * t.seq_cum.size(), t.seq_cum.data(), t.seq_cum.size() * sizeof(float), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(w->mfma.d_dtab + (size_t)s * t.dtab.size(), t.dtab.data(), t.dtab.size() * sizeof(float2), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(w->d_scales + s, &t.seq_scale, sizeof(float), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(w->d_scales.get() + s, &t.seq_scale, sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -247,68 +248,68 @@ static csdr_amd_wfm *wfm_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
     if (n_streams <= 0 || decimation <= 0 || taps_length <= 0 || frac_rate <= 1 || !rates) { fail_msg(-3, "wfm: bad parameters"); return nullptr; }
     if (decimation * 1 + taps_length + 8 > HIST) { fail_msg(-3, "wfm: D + taps (%d + %d) exceed the %d-sample history", decimation, taps_length, HIST); return nullptr; }
     if (max_block_samples < 1024) max_block_samples = 1024;
-    csdr_amd_wfm *w = new csdr_amd_wfm();
+    Owned<csdr_amd_wfm, csdr_amd_wfm_destroy> w(new csdr_amd_wfm());
     w->ctx = ctx; w->n_streams = n_streams; w->D = decimation; w->L = taps_length; w->F = frac_rate; w->audio_rate = audio_rate;
     w->shift_rate = shift_rate; w->tau = tau; w->max_block = max_block_samples;
     const float dt = (float)(1.0 / audio_rate); w->alpha = dt / (tau + dt);          // libcsdr.c:1090-1091
     const size_t max_audio = max_block_samples / ((size_t)decimation * frac_rate) + 8;
     w->demod_pitch = (max_audio + 40 + 63) & ~(size_t)63;          // (VALU path's scratch rows; tile padding)
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    w->d_demod = nullptr; w->d_rot = nullptr; w->d_hist = nullptr; w->d_head[0] = w->d_head[1] = nullptr; w->hflip = 0;
-    w->use_mfma = false; w->d_ctab = nullptr; w->ctab_cap = 0; w->mfma.d_seq_frags = nullptr; w->mfma.d_seq_cum = nullptr; w->mfma.d_dtab = nullptr;
-    w->ps = per_stream; w->seeds = nullptr; w->d_scales = nullptr; w->d_dtab_old = nullptr; w->d_list = nullptr; w->d_lead_n = nullptr; w->d_lead_d = nullptr;
+    auto alloc = [&](auto &p, size_t bytes) { if (e == hipSuccess) e = dev_alloc(p, bytes); };
+    w->ps = per_stream;
     {
         const char *force = getenv("CSDR_AMD_WFM_PATH");          // "valu" forces the VALU/LDS front end (A/B comparisons); read once, here
         w->use_mfma = !(force && !strcmp(force, "valu")) && wfm_mfma_supported(decimation, taps_length, frac_rate);
     }
-    if (per_stream && !w->use_mfma) { fail_msg(-3, "wfm_create_rates: a rate per stream needs the matrix-core chain kernel (decimation x audio decimation even, window <= 256 samples)"); delete w; return nullptr; }
-    alloc((void **)&w->d_taps, sizeof(float) * taps_length);
-    alloc((void **)&w->d_last[0], sizeof(float) * n_streams);
-    alloc((void **)&w->d_last[1], sizeof(float) * n_streams);
+    if (per_stream && !w->use_mfma) { fail_msg(-3, "wfm_create_rates: a rate per stream needs the matrix-core chain kernel (decimation x audio decimation even, window <= 256 samples)"); return nullptr; }
+    alloc(w->d_taps, sizeof(float) * taps_length);
+    alloc(w->d_last[0], sizeof(float) * n_streams);
+    alloc(w->d_last[1], sizeof(float) * n_streams);
     if (w->use_mfma) {
-        alloc((void **)&w->d_head[0], wfm_mfma_head_bytes(n_streams));
-        alloc((void **)&w->d_head[1], wfm_mfma_head_bytes(n_streams));
+        alloc(w->d_head[0], wfm_mfma_head_bytes(n_streams));
+        alloc(w->d_head[1], wfm_mfma_head_bytes(n_streams));
     } else {                                                       // the VALU front end's intermediates: demodulated floats, rotator table, history
-        alloc((void **)&w->d_demod, sizeof(float) * w->demod_pitch * n_streams);
-        alloc((void **)&w->d_rot, sizeof(cf32) * (HIST + max_block_samples + 64));
-        alloc((void **)&w->d_hist, (size_t)2 * HIST * n_streams);
+        alloc(w->d_demod, sizeof(float) * w->demod_pitch * n_streams);
+        alloc(w->d_rot, sizeof(cf32) * (HIST + max_block_samples + 64));
+        alloc(w->d_hist, (size_t)2 * HIST * n_streams);
     }
-    if (e != hipSuccess) { fail(e, "hipMalloc(wfm state)", __FILE__, __LINE__); csdr_amd_wfm_destroy(w); return nullptr; }
-    (void)hipMemcpy(w->d_taps, host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { fail(e, "hipMalloc(wfm state)", __FILE__, __LINE__); return nullptr; }
+    (void)hipMemcpy(w->d_taps.get(), host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice);
     w->kernel_name = "k_wfm_front";
     if (w->use_mfma && per_stream) {
         WfmMfmaTable t;
         wfm_mfma_build_table(decimation, taps_length, frac_rate, shift_rate, host_taps, t);      // (sizes and geometry; the tables themselves per stream below)
         w->mfma.tile_stride_bytes = t.tile_stride_bytes; w->mfma.win_off_bytes = t.win_off_bytes; w->mfma.seq_scale = t.seq_scale;
         w->rates.assign(rates, rates + n_streams); w->h_taps.assign(host_taps, host_taps + taps_length);
-        hipError_t e2 = hipMalloc(&w->mfma.d_seq_frags, t.seq_frags.size() * (size_t)n_streams);
-        if (e2 == hipSuccess) e2 = hipMalloc((void **)&w->mfma.d_seq_cum, t.seq_cum.size() * sizeof(float) * (size_t)n_streams);
-        if (e2 == hipSuccess) e2 = hipMalloc((void **)&w->mfma.d_dtab, t.dtab.size() * sizeof(float2) * (size_t)n_streams);
-        if (e2 == hipSuccess) e2 = hipMalloc((void **)&w->d_scales, sizeof(float) * (size_t)n_streams);
-        if (e2 != hipSuccess) { fail(e2, "hipMalloc(wfm per-stream tables)", __FILE__, __LINE__); csdr_amd_wfm_destroy(w); return nullptr; }
-        for (int s = 0; s < n_streams; s++) if (wfm_upload_stream_tables(w, s, rates[s])) { csdr_amd_wfm_destroy(w); return nullptr; }
-        w->seeds = seeds_create(ctx, n_streams, rates, nullptr, 0, max_block_samples);
-        if (!w->seeds) { csdr_amd_wfm_destroy(w); return nullptr; }
+        hipError_t e2 = dev_alloc(w->seq_frags, t.seq_frags.size() * (size_t)n_streams);
+        if (e2 == hipSuccess) e2 = dev_alloc(w->seq_cum, t.seq_cum.size() * sizeof(float) * (size_t)n_streams);
+        if (e2 == hipSuccess) e2 = dev_alloc(w->dtab, t.dtab.size() * sizeof(float2) * (size_t)n_streams);
+        if (e2 == hipSuccess) e2 = dev_alloc(w->d_scales, sizeof(float) * (size_t)n_streams);
+        w->mfma.d_seq_frags = w->seq_frags.get(); w->mfma.d_seq_cum = w->seq_cum.get(); w->mfma.d_dtab = w->dtab.get();
+        if (e2 != hipSuccess) { fail(e2, "hipMalloc(wfm per-stream tables)", __FILE__, __LINE__); return nullptr; }
+        for (int s = 0; s < n_streams; s++) if (wfm_upload_stream_tables(w.get(), s, rates[s])) return nullptr;
+        w->seeds.reset(seeds_create(ctx, n_streams, rates, nullptr, 0, max_block_samples));
+        if (!w->seeds) return nullptr;
         w->kernel_name = "k_wfm_mfma_seq";
     } else if (w->use_mfma) {
         WfmMfmaTable t;
         wfm_mfma_build_table(decimation, taps_length, frac_rate, shift_rate, host_taps, t);
         w->mfma.tile_stride_bytes = t.tile_stride_bytes; w->mfma.win_off_bytes = t.win_off_bytes; w->mfma.seq_scale = t.seq_scale;
         w->ctab_cap = 16 * (max_block_samples / 1024 + 8);                 // 16 calls of the largest block ahead (2.4 M-sample blocks: 300 KB)
-        hipError_t e2 = hipMalloc((void **)&w->d_ctab, w->ctab_cap * sizeof(float2));
-        if (e2 == hipSuccess) e2 = hipMalloc(&w->mfma.d_seq_frags, t.seq_frags.size());
-        if (e2 == hipSuccess) e2 = hipMalloc((void **)&w->mfma.d_seq_cum, t.seq_cum.size() * sizeof(float));
-        if (e2 == hipSuccess) e2 = hipMalloc((void **)&w->mfma.d_dtab, t.dtab.size() * sizeof(float2));
+        hipError_t e2 = dev_alloc(w->d_ctab, w->ctab_cap * sizeof(float2));
+        if (e2 == hipSuccess) e2 = dev_alloc(w->seq_frags, t.seq_frags.size());
+        if (e2 == hipSuccess) e2 = dev_alloc(w->seq_cum, t.seq_cum.size() * sizeof(float));
+        if (e2 == hipSuccess) e2 = dev_alloc(w->dtab, t.dtab.size() * sizeof(float2));
+        w->mfma.d_seq_frags = w->seq_frags.get(); w->mfma.d_seq_cum = w->seq_cum.get(); w->mfma.d_dtab = w->dtab.get();
         if (e2 == hipSuccess) e2 = hipMemcpy(w->mfma.d_seq_frags, t.seq_frags.data(), t.seq_frags.size(), hipMemcpyHostToDevice);
         if (e2 == hipSuccess) e2 = hipMemcpy(w->mfma.d_seq_cum, t.seq_cum.data(), t.seq_cum.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e2 == hipSuccess) e2 = hipMemcpy(w->mfma.d_dtab, t.dtab.data(), t.dtab.size() * sizeof(float2), hipMemcpyHostToDevice);
-        if (e2 != hipSuccess) { fail(e2, "hipMalloc/hipMemcpy(wfm mfma table)", __FILE__, __LINE__); csdr_amd_wfm_destroy(w); return nullptr; }
+        if (e2 != hipSuccess) { fail(e2, "hipMalloc/hipMemcpy(wfm mfma table)", __FILE__, __LINE__); return nullptr; }
         w->kernel_name = "k_wfm_mfma_seq";
     }
-    w->profiling = false; w->ev_used = 0; w->prof_ms = 0; w->prof_launches = 0;
-    if (csdr_amd_wfm_reset(w)) { csdr_amd_wfm_destroy(w); return nullptr; }
-    return w;
+    w->profiling = false; w->prof_ms = 0; w->prof_launches = 0;
+    if (csdr_amd_wfm_reset(w.get())) return nullptr;
+    return w.release();
 }
 
 csdr_amd_wfm *csdr_amd_wfm_create(csdr_amd_ctx *ctx, int n_streams, float shift_rate, int decimation, const float *host_taps,
@@ -332,16 +333,16 @@ int csdr_amd_wfm_set_rate(csdr_amd_wfm *w, int stream, float shift_rate)
     // The audio samples whose windows reach back across the retune instant are recomputed with both tables (k_wfm_lead): a window spans D + L - 1 samples and audio
     // samples lie D F apart, so d_lead_d holds wfm_lead_max(D, L, F) per stream (10 / 79 / 5: 3; ADVICE r5: sized from the shape, no shape is refused).
     CSDR_HIP(hipStreamSynchronize(w->ctx->stream));                   // calls in flight read this stream's tables
-    if (!w->d_dtab_old) CSDR_HIP(hipMalloc((void **)&w->d_dtab_old, sizeof(float2) * 3072 * (size_t)w->n_streams));
+    if (!w->d_dtab_old) CSDR_HIP(dev_alloc(w->d_dtab_old, sizeof(float2) * 3072 * (size_t)w->n_streams));
     bool listed = false;
     for (int v : w->retuned) listed |= v == stream;
     if (!listed) {
-        CSDR_HIP(hipMemcpy(w->d_dtab_old + (size_t)stream * 3072, w->mfma.d_dtab + (size_t)stream * 3072, sizeof(float2) * 3072, hipMemcpyDeviceToDevice));
+        CSDR_HIP(hipMemcpy(w->d_dtab_old.get() + (size_t)stream * 3072, w->mfma.d_dtab + (size_t)stream * 3072, sizeof(float2) * 3072, hipMemcpyDeviceToDevice));
         w->retuned.push_back(stream);
     }
     const int rc = wfm_upload_stream_tables(w, stream, shift_rate); if (rc) return rc;
     w->rates[stream] = shift_rate;
-    return seeds_set_rate(w->seeds, stream, shift_rate, false);
+    return seeds_set_rate(w->seeds.get(), stream, shift_rate, false);
 }
 
 float csdr_amd_wfm_get_rate(const csdr_amd_wfm *w, int stream) { return w->ps ? ((stream >= 0 && stream < w->n_streams) ? w->rates[stream] : 0.f) : w->shift_rate; }
@@ -350,12 +351,6 @@ void csdr_amd_wfm_destroy(csdr_amd_wfm *w)
 {
     if (!w) return;
     (void)hipStreamSynchronize(w->ctx->stream);
-    if (w->seeds) seeds_destroy(w->seeds);
-    (void)hipFree(w->d_scales); (void)hipFree(w->d_dtab_old); (void)hipFree(w->d_lead_n); (void)hipFree(w->d_lead_d);      // (d_list lives inside d_lead_n)
-    (void)hipFree(w->d_taps); (void)hipFree(w->d_demod); (void)hipFree(w->d_last[0]); (void)hipFree(w->d_last[1]);
-    (void)hipFree(w->d_rot); (void)hipFree(w->d_hist); (void)hipFree(w->d_head[0]); (void)hipFree(w->d_head[1]);
-    for (auto &pr : w->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    (void)hipFree(w->mfma.d_seq_frags); (void)hipFree(w->mfma.d_seq_cum); (void)hipFree(w->mfma.d_dtab); (void)hipFree(w->d_ctab);
     delete w;
 }
 
@@ -363,16 +358,16 @@ int csdr_amd_wfm_reset(csdr_amd_wfm *w)
 {
     hipStream_t st = w->ctx->stream;
     w->phase = 0.f;
-    CSDR_HIP(hipMemsetAsync(w->d_last[0], 0, sizeof(float) * w->n_streams, st));
-    CSDR_HIP(hipMemsetAsync(w->d_last[1], 0, sizeof(float) * w->n_streams, st));
-    if (w->d_rot) CSDR_HIP(hipMemsetAsync(w->d_rot, 0, sizeof(cf32) * (HIST + w->max_block + 64), st));
-    if (w->d_hist) CSDR_HIP(hipMemsetAsync(w->d_hist, 0x80, (size_t)2 * HIST * w->n_streams, st));
-    for (int k = 0; k < 2; k++) if (w->d_head[k]) CSDR_HIP(hipMemsetAsync(w->d_head[k], 0x80, wfm_mfma_head_bytes(w->n_streams), st));      // 0x80 = zero samples in front of the stream
+    CSDR_HIP(hipMemsetAsync(w->d_last[0].get(), 0, sizeof(float) * w->n_streams, st));
+    CSDR_HIP(hipMemsetAsync(w->d_last[1].get(), 0, sizeof(float) * w->n_streams, st));
+    if (w->d_rot) CSDR_HIP(hipMemsetAsync(w->d_rot.get(), 0, sizeof(cf32) * (HIST + w->max_block + 64), st));
+    if (w->d_hist) CSDR_HIP(hipMemsetAsync(w->d_hist.get(), 0x80, (size_t)2 * HIST * w->n_streams, st));
+    for (int k = 0; k < 2; k++) if (w->d_head[k]) CSDR_HIP(hipMemsetAsync(w->d_head[k].get(), 0x80, wfm_mfma_head_bytes(w->n_streams), st));      // 0x80 = zero samples in front of the stream
     w->hflip = 0;
     w->B = 0; w->next_j = 0; w->last_T = 0; w->flip = 0; w->ended = false;
     w->c_prev = make_float2(1.f, 0.f); w->tab_valid = false; w->tab_first = 0;
     w->retuned.clear();
-    if (w->seeds) { const int rc = seeds_reset(w->seeds); if (rc) return rc; }
+    if (w->seeds) { const int rc = seeds_reset(w->seeds.get()); if (rc) return rc; }
     return 0;
 }
 
@@ -381,18 +376,14 @@ int csdr_amd_wfm_fallback(const csdr_amd_wfm *w) { return w->use_mfma ? 0 : 1; }
 
 int csdr_amd_wfm_set_profiling(csdr_amd_wfm *w, int on)
 {
-    w->profiling = on != 0; w->ev_used = 0; w->prof_ms = 0; w->prof_launches = 0;
+    w->profiling = on != 0; w->timer.reset(); w->prof_ms = 0; w->prof_launches = 0;
     return 0;
 }
 
 int csdr_amd_wfm_kernel_time(csdr_amd_wfm *w, double *total_ms, long *launches)
 {   // resolves the recorded event pairs (synchronises the stream)
     CSDR_HIP(hipStreamSynchronize(w->ctx->stream));
-    for (size_t k = 0; k < w->ev_used; k++) {
-        float ms = 0; CSDR_HIP(hipEventElapsedTime(&ms, w->ev_pool[k].first, w->ev_pool[k].second));
-        w->prof_ms += ms; w->prof_launches++;
-    }
-    w->ev_used = 0;
+    if (const int rc = w->timer.resolve(&w->prof_ms, &w->prof_launches)) return rc;
     if (total_ms) *total_ms = w->prof_ms;
     if (launches) *launches = w->prof_launches;
     return 0;
@@ -412,7 +403,7 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
     SeedView sv; memset(&sv, 0, sizeof sv);
     if (w->ps) {
         const size_t nch = ((size_t)T + 1023) / 1024;
-        rc = seeds_acquire(w->seeds, w->B / 1024 - 1, nch + 3, (T % 1024) ? 0 : nch, &sv); if (rc) return rc;
+        rc = seeds_acquire(w->seeds.get(), w->B / 1024 - 1, nch + 3, (T % 1024) ? 0 : nch, &sv); if (rc) return rc;
         ctab_call = sv.ctab;
     } else
     if (w->use_mfma) {
@@ -437,10 +428,10 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
                 while (nx < -PI_F) nx += 2 * PI_F;
                 ph = nx;
             }
-            rc = c->pinned_upload(w->d_ctab, sizeof(float2) * w->ctab_cap); if (rc) return rc;
+            rc = c->pinned_upload(w->d_ctab.get(), sizeof(float2) * w->ctab_cap); if (rc) return rc;
             w->tab_first = first; w->tab_valid = true;
         }
-        ctab_call = w->d_ctab + (first - w->tab_first);
+        ctab_call = w->d_ctab.get() + (first - w->tab_first);
         // the stream's phase behind this block (and the seed of its last chunk, for a table rebuilt at the next call)
         float ph = w->phase;
         for (size_t m = 0; m < nch; m++) {
@@ -454,8 +445,8 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
         w->phase = ph;
     } else {
         // 1b. rotator table for this block behind the previous block's tail (history positions keep their own phasors)
-        if (w->last_T) CSDR_HIP(hipMemcpyAsync(w->d_rot, w->d_rot + w->last_T, sizeof(cf32) * HIST, hipMemcpyDeviceToDevice, st));
-        rc = csdr_amd_rotator_generate(c, CSDR_SHIFT_ADDITION, w->shift_rate, &w->phase, w->d_rot + HIST, (size_t)T, 1024, 0);
+        if (w->last_T) CSDR_HIP(hipMemcpyAsync(w->d_rot.get(), w->d_rot.get() + w->last_T, sizeof(cf32) * HIST, hipMemcpyDeviceToDevice, st));
+        rc = csdr_amd_rotator_generate(c, CSDR_SHIFT_ADDITION, w->shift_rate, &w->phase, w->d_rot.get() + HIST, (size_t)T, 1024, 0);
         if (rc) return rc;
     }
     // 2. audio samples that become computable with this block: F*j+10 is the newest FIR output, needs input up to D*(F*j+10)+L-1
@@ -469,21 +460,15 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
     const int n_audio = n_audio_ll > 0 ? (int)n_audio_ll : 0;
     if (n_audio > 0 && (size_t)n_audio > out_pitch) return fail_msg(-3, "wfm: out_pitch %zu smaller than the %d audio samples of this block", out_pitch, n_audio);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (w->profiling && n_audio > 0) {
-        if (w->ev_used == w->ev_pool.size()) {
-            hipEvent_t a, b; CSDR_HIP(hipEventCreate(&a)); CSDR_HIP(hipEventCreate(&b));
-            w->ev_pool.emplace_back(a, b);
-        }
-        e0 = w->ev_pool[w->ev_used].first; e1 = w->ev_pool[w->ev_used].second; w->ev_used++;
-    }
+    if (w->profiling && n_audio > 0) { if (const int trc = w->timer.take(&e0, &e1)) return trc; }
     if (w->use_mfma) {
         // the whole chain, the carried de-emphasis state and the next call's history in ONE launch (wfm_mfma.hip)
         WfmBackArgs back;
-        back.alpha = w->alpha; back.last_in = w->d_last[w->flip]; back.last_out = w->d_last[w->flip ^ 1];
-        back.s16 = audio_s16; back.af = audio_f; back.out_pitch = out_pitch; back.head_in = w->d_head[w->hflip]; back.head_out = w->d_head[w->hflip ^ 1];
+        back.alpha = w->alpha; back.last_in = w->d_last[w->flip].get(); back.last_out = w->d_last[w->flip ^ 1].get();
+        back.s16 = audio_s16; back.af = audio_f; back.out_pitch = out_pitch; back.head_in = w->d_head[w->hflip].get(); back.head_out = w->d_head[w->hflip ^ 1].get();
         WfmPerStream psa; memset(&psa, 0, sizeof psa);
         if (w->ps) {
-            psa.tab_pitch = sv.pitch; psa.tab_len = sv.n_entries; psa.d_scales = w->d_scales;
+            psa.tab_pitch = sv.pitch; psa.tab_len = sv.n_entries; psa.d_scales = w->d_scales.get();
             // retuned streams: the audio samples whose windows start in front of the block (D (F j + 9) < B) straddle two rates
             long n_lead = 0; const int lead_max = wfm_lead_max(w->D, w->L, w->F);
             psa.lead_stride = lead_max;
@@ -496,15 +481,15 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
             }
             if (n_lead > 0) {
                 const int nr = (int)w->retuned.size(), S = w->n_streams;
-                if (!w->d_lead_n) { CSDR_HIP(hipMalloc((void **)&w->d_lead_n, sizeof(int) * 2 * S)); w->d_list = w->d_lead_n + S; CSDR_HIP(hipMalloc((void **)&w->d_lead_d, sizeof(float) * (size_t)lead_max * S)); }
+                if (!w->d_lead_n) { CSDR_HIP(dev_alloc(w->d_lead_n, sizeof(int) * 2 * S)); w->d_list = w->d_lead_n.get() + S; CSDR_HIP(dev_alloc(w->d_lead_d, sizeof(float) * (size_t)lead_max * S)); }
                 int *hl = (int *)c->pinned_acquire(sizeof(int) * (size_t)(S + nr)); if (!hl) return -2;      // [S] samples per stream, then the list: one upload
                 for (int s = 0; s < S; s++) hl[s] = 0;
                 for (int k = 0; k < nr; k++) { hl[w->retuned[k]] = (int)n_lead; hl[S + k] = w->retuned[k]; }
-                rc = c->pinned_upload(w->d_lead_n, sizeof(int) * (size_t)(S + nr)); if (rc) return rc;
-                rc = wfm_mfma_lead(st, in, in_pitch, back.head_in, w->d_taps, sv.ctab, sv.pitch, w->mfma.d_dtab, w->d_dtab_old, w->d_list, nr, w->d_lead_d, lead_max,
+                rc = c->pinned_upload(w->d_lead_n.get(), sizeof(int) * (size_t)(S + nr)); if (rc) return rc;
+                rc = wfm_mfma_lead(st, in, in_pitch, back.head_in, w->d_taps.get(), sv.ctab, sv.pitch, w->mfma.d_dtab, w->d_dtab_old.get(), w->d_list, nr, w->d_lead_d.get(), lead_max,
                                    w->D, w->L, w->F, w->B, w->next_j, (int)n_lead);
                 if (rc) return rc;
-                psa.d_lead_d = w->d_lead_d; psa.d_lead_n = w->d_lead_n;
+                psa.d_lead_d = w->d_lead_d.get(); psa.d_lead_n = w->d_lead_n.get();
             }
         }
         rc = wfm_mfma_launch(st, e0, e1, in, in_pitch, w->mfma, ctab_call, w->n_streams, T, w->B, w->next_j, n_audio, back, w->ps ? &psa : nullptr);
@@ -521,17 +506,17 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
             if (lds > 64 * 1024) { const int arc = lds_attr_once((const void *)k_wfm_front, lds); if (arc) return arc; }
             if (e0) CSDR_HIP(hipEventRecord(e0, st));
             hipLaunchKernelGGL(k_wfm_front, dim3(w->n_streams, cdiv(n_audio, TILE_A)), dim3(256), lds, st,
-                               in, in_pitch, w->d_hist, w->d_rot, w->d_taps, w->d_demod, w->demod_pitch, p);
+                               in, in_pitch, w->d_hist.get(), w->d_rot.get(), w->d_taps.get(), w->d_demod.get(), w->demod_pitch, p);
             CSDR_LAUNCH_CHECK();
             if (e1) CSDR_HIP(hipEventRecord(e1, st));
             hipLaunchKernelGGL(k_wfm_back, dim3(cdiv(n_audio, BK_CHUNK), w->n_streams), dim3(256), 0, st,
-                               w->d_demod, w->demod_pitch, 0, n_audio, w->alpha, w->d_last[w->flip], w->d_last[w->flip ^ 1], audio_s16, audio_f, out_pitch);
+                               w->d_demod.get(), w->demod_pitch, 0, n_audio, w->alpha, w->d_last[w->flip].get(), w->d_last[w->flip ^ 1].get(), audio_s16, audio_f, out_pitch);
             CSDR_LAUNCH_CHECK();
             w->flip ^= 1;
         }
         // 3. history for the next block
         if (T >= HIST) {
-            hipLaunchKernelGGL(k_wfm_save_hist, dim3(w->n_streams), dim3(256), 0, st, in, in_pitch, T, w->d_hist);
+            hipLaunchKernelGGL(k_wfm_save_hist, dim3(w->n_streams), dim3(256), 0, st, in, in_pitch, T, w->d_hist.get());
             CSDR_LAUNCH_CHECK();
         }
     }

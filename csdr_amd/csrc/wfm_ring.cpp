@@ -33,17 +33,18 @@ inline uint32_t ring_tag(long long k) { return (uint32_t)((unsigned long long)k 
 
 struct csdr_amd_wfm_ring {
     csdr_amd_ctx *ctx;
+    Stream rs; Event ev_exit;          // (declared first: they outlive the resident grid's buffers)
     int S, D, L, F, T, N, nch, lines, grid, audio_rate;
     float rate, tau, alpha;
     std::vector<float> taps;
-    WfmMfmaDevice mfma;
-    float *d_taps; float2 *d_dtab_old, *d_lead_seeds; float *d_lead_d, *d_warm, *d_state; int *d_list;
+    WfmMfmaDevice mfma;                // (its tables are owned by seq_frags, seq_cum, dtab)
+    DevBuf<> seq_frags; DevBuf<float> seq_cum; DevBuf<float2> dtab;
+    DevBuf<float> d_taps; DevBuf<float2> d_dtab_old, d_lead_seeds; DevBuf<float> d_lead_d, d_warm, d_state; DevBuf<int> d_list;
     size_t in_pitch, out_pitch;
-    uint8_t *d_in; int16_t *d_out;
-    uint32_t *h_block;                 // host-coherent: [desc: N * lines * 16][ctrl: 16][done: N * 16]
+    DevBuf<uint8_t> d_in; DevBuf<int16_t> d_out;
+    HostBuf<uint32_t> h_block;         // host-coherent: [desc: N * lines * 16][ctrl: 16][done: N * 16]
     uint32_t *h_desc, *h_ctrl, *h_done;
-    unsigned *d_cnt, *d_exiting; unsigned long long *d_tfirst, *d_next, *d_stats; int fence_mode;
-    hipStream_t rs; hipEvent_t ev_exit;
+    DevBuf<unsigned> d_cnt, d_exiting; DevBuf<unsigned long long> d_tfirst, d_next, d_stats; int fence_mode;
     bool launched;
     long long submitted;               // blocks posted so far (the next block's sequence number)
     float phase; float2 hist[4];       // the shifter's phase in front of the next block; seeds of the four chunks before it
@@ -58,7 +59,7 @@ static int ring_stop(csdr_amd_wfm_ring *r)
 {
     if (!r->launched) return 0;
     __atomic_store_n(r->h_ctrl, 1u, __ATOMIC_RELEASE);
-    CSDR_HIP(hipStreamSynchronize(r->rs));
+    CSDR_HIP(hipStreamSynchronize(r->rs.get()));
     __atomic_store_n(r->h_ctrl, 0u, __ATOMIC_RELEASE);
     r->launched = false;
     return 0;
@@ -67,18 +68,18 @@ static int ring_stop(csdr_amd_wfm_ring *r)
 static int ring_ensure_running(csdr_amd_wfm_ring *r)
 {
     if (r->launched) {
-        const hipError_t q = hipEventQuery(r->ev_exit);
+        const hipError_t q = hipEventQuery(r->ev_exit.get());
         if (q == hipErrorNotReady) return 0;
         if (q != hipSuccess) return fail(q, "hipEventQuery(resident grid)", __FILE__, __LINE__);
         r->launched = false;
     }
     WfmResident rv; memset((void *)&rv, 0, sizeof rv);
-    rv.desc = r->h_desc; rv.ctrl = r->h_ctrl; rv.done = r->h_done; rv.cnt = r->d_cnt; rv.t_first = r->d_tfirst; rv.next_item = r->d_next; rv.exiting = r->d_exiting;
-    rv.in_ring = r->d_in; rv.out_ring = r->d_out; rv.in_slot_bytes = (size_t)r->S * r->in_pitch; rv.out_slot_elems = (size_t)r->S * r->out_pitch;
+    rv.desc = r->h_desc; rv.ctrl = r->h_ctrl; rv.done = r->h_done; rv.cnt = r->d_cnt.get(); rv.t_first = r->d_tfirst.get(); rv.next_item = r->d_next.get(); rv.exiting = r->d_exiting.get();
+    rv.in_ring = r->d_in.get(); rv.out_ring = r->d_out.get(); rv.in_slot_bytes = (size_t)r->S * r->in_pitch; rv.out_slot_elems = (size_t)r->S * r->out_pitch;
     rv.n_slots = r->N; rv.desc_lines = r->lines; rv.T = r->T; rv.D = r->D; rv.L = r->L; rv.F = r->F;
-    rv.idle_ticks = r->idle_ticks; rv.life_ticks = r->life_ticks; rv.lead_d = r->d_lead_d; rv.lead_stride = wfm_lead_max(r->D, r->L, r->F); rv.lead_state = r->d_state; rv.stats = r->d_stats; rv.fence_mode = r->fence_mode;
-    CSDR_HIP(hipMemsetAsync(r->d_exiting, 0, sizeof(unsigned), r->rs));
-    const int rc = wfm_mfma_launch_resident(r->rs, r->ev_exit, r->mfma, r->S, r->in_pitch, r->alpha, r->out_pitch, rv, r->grid);
+    rv.idle_ticks = r->idle_ticks; rv.life_ticks = r->life_ticks; rv.lead_d = r->d_lead_d.get(); rv.lead_stride = wfm_lead_max(r->D, r->L, r->F); rv.lead_state = r->d_state.get(); rv.stats = r->d_stats.get(); rv.fence_mode = r->fence_mode;
+    CSDR_HIP(hipMemsetAsync(r->d_exiting.get(), 0, sizeof(unsigned), r->rs.get()));
+    const int rc = wfm_mfma_launch_resident(r->rs.get(), r->ev_exit.get(), r->mfma, r->S, r->in_pitch, r->alpha, r->out_pitch, rv, r->grid);
     if (rc) return rc;
     r->launched = true; r->launches++;
     return 0;
@@ -111,12 +112,11 @@ static int ring_upload_tables(csdr_amd_wfm_ring *r, float rate)
     WfmMfmaTable t;
     wfm_mfma_build_table(r->D, r->L, r->F, rate, r->taps.data(), t);
     r->mfma.tile_stride_bytes = t.tile_stride_bytes; r->mfma.win_off_bytes = t.win_off_bytes; r->mfma.seq_scale = t.seq_scale;
-    if (!r->mfma.d_seq_frags) {
-        CSDR_HIP(hipMalloc(&r->mfma.d_seq_frags, t.seq_frags.size()));
-        CSDR_HIP(hipMalloc((void **)&r->mfma.d_seq_cum, t.seq_cum.size() * sizeof(float)));
-        CSDR_HIP(hipMalloc((void **)&r->mfma.d_dtab, t.dtab.size() * sizeof(float2)));
-        CSDR_HIP(hipMalloc((void **)&r->d_dtab_old, t.dtab.size() * sizeof(float2)));
-    }
+    if (!r->seq_frags) CSDR_HIP(dev_alloc(r->seq_frags, t.seq_frags.size()));
+    if (!r->seq_cum) CSDR_HIP(dev_alloc(r->seq_cum, t.seq_cum.size() * sizeof(float)));
+    if (!r->dtab) CSDR_HIP(dev_alloc(r->dtab, t.dtab.size() * sizeof(float2)));
+    if (!r->d_dtab_old) CSDR_HIP(dev_alloc(r->d_dtab_old, t.dtab.size() * sizeof(float2)));
+    r->mfma.d_seq_frags = r->seq_frags.get(); r->mfma.d_seq_cum = r->seq_cum.get(); r->mfma.d_dtab = r->dtab.get();
     CSDR_HIP(hipMemcpy(r->mfma.d_seq_frags, t.seq_frags.data(), t.seq_frags.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(r->mfma.d_seq_cum, t.seq_cum.data(), t.seq_cum.size() * sizeof(float), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(r->mfma.d_dtab, t.dtab.data(), t.dtab.size() * sizeof(float2), hipMemcpyHostToDevice));
@@ -127,27 +127,21 @@ void csdr_amd_wfm_ring_destroy(csdr_amd_wfm_ring *r)
 {
     if (!r) return;
     (void)hipSetDevice(r->ctx->device);
-    if (r->rs) { (void)ring_stop(r); (void)hipStreamSynchronize(r->rs); }
-    (void)hipFree(r->mfma.d_seq_frags); (void)hipFree(r->mfma.d_seq_cum); (void)hipFree(r->mfma.d_dtab); (void)hipFree(r->d_dtab_old);
-    (void)hipFree(r->d_taps); (void)hipFree(r->d_lead_seeds); (void)hipFree(r->d_lead_d); (void)hipFree(r->d_warm); (void)hipFree(r->d_state); (void)hipFree(r->d_list);
-    (void)hipFree(r->d_in); (void)hipFree(r->d_out); (void)hipFree(r->d_cnt); (void)hipFree(r->d_exiting); (void)hipFree(r->d_tfirst); (void)hipFree(r->d_next); (void)hipFree(r->d_stats);
-    if (r->h_block) (void)hipHostFree(r->h_block);
-    if (r->ev_exit) (void)hipEventDestroy(r->ev_exit);
-    if (r->rs) (void)hipStreamDestroy(r->rs);
+    if (r->rs) { (void)ring_stop(r); (void)hipStreamSynchronize(r->rs.get()); }
     delete r;
 }
 
 int csdr_amd_wfm_ring_reset(csdr_amd_wfm_ring *r)
 {
     int rc = ring_stop(r); if (rc) return rc;
-    CSDR_HIP(hipStreamSynchronize(r->rs));
-    memset(r->h_block, 0, sizeof(uint32_t) * ((size_t)r->N * r->lines * 16 + 16 + (size_t)r->N * 16));
-    CSDR_HIP(hipMemset(r->d_cnt, 0, sizeof(unsigned) * r->N));
-    CSDR_HIP(hipMemset(r->d_tfirst, 0xff, sizeof(unsigned long long) * r->N));
-    CSDR_HIP(hipMemset(r->d_stats, 0, sizeof(unsigned long long) * 4 * r->grid));
+    CSDR_HIP(hipStreamSynchronize(r->rs.get()));
+    memset(r->h_block.get(), 0, sizeof(uint32_t) * ((size_t)r->N * r->lines * 16 + 16 + (size_t)r->N * 16));
+    CSDR_HIP(hipMemset(r->d_cnt.get(), 0, sizeof(unsigned) * r->N));
+    CSDR_HIP(hipMemset(r->d_tfirst.get(), 0xff, sizeof(unsigned long long) * r->N));
+    CSDR_HIP(hipMemset(r->d_stats.get(), 0, sizeof(unsigned long long) * 4 * r->grid));
     std::vector<unsigned long long> ni(r->grid);
     for (int w = 0; w < r->grid; w++) ni[w] = (unsigned long long)w;
-    CSDR_HIP(hipMemcpy(r->d_next, ni.data(), sizeof(unsigned long long) * r->grid, hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(r->d_next.get(), ni.data(), sizeof(unsigned long long) * r->grid, hipMemcpyHostToDevice));
     r->submitted = 0; r->phase = 0.f; r->pending_lead = false;
     for (int i = 0; i < 4; i++) r->hist[i] = make_float2(1.f, 0.f);
     return 0;
@@ -163,8 +157,7 @@ csdr_amd_wfm_ring *csdr_amd_wfm_ring_create(csdr_amd_ctx *ctx, int n_streams, fl
     // the two warm-up steps (12 tiles) and the first window in front of a block must lie inside the previous block
     if ((size_t)(12 * 4 * decimation * frac_rate + 2 * WFM_HIST + 1024) > block_samples) { fail_msg(-3, "wfm ring: block of %zu samples shorter than the warm-up reach", block_samples); return nullptr; }
     (void)hipSetDevice(ctx->device);
-    csdr_amd_wfm_ring *r = new csdr_amd_wfm_ring();
-    memset((void *)&r->mfma, 0, sizeof r->mfma);
+    Owned<csdr_amd_wfm_ring, csdr_amd_wfm_ring_destroy> r(new csdr_amd_wfm_ring());
     r->ctx = ctx; r->S = n_streams; r->D = decimation; r->L = taps_length; r->F = frac_rate; r->T = (int)block_samples; r->N = n_slots; r->audio_rate = audio_rate;
     r->rate = shift_rate; r->tau = tau;
     const float dt = (float)(1.0 / audio_rate); r->alpha = dt / (tau + dt);                  // libcsdr.c:1090-1091
@@ -176,48 +169,47 @@ csdr_amd_wfm_ring *csdr_amd_wfm_ring_create(csdr_amd_ctx *ctx, int n_streams, fl
     long long want = (long long)n_wsb * (n_slots - 2);                                       // items that can be in flight
     r->grid = (int)(want < wfm_resident_max_grid() ? want : wfm_resident_max_grid());
     { const char *g = getenv("CSDR_AMD_RING_GRID"); if (g && atoi(g) > 0 && atoi(g) < r->grid) r->grid = atoi(g); }
-    r->d_taps = nullptr; r->d_dtab_old = nullptr; r->d_lead_seeds = nullptr; r->d_lead_d = nullptr; r->d_warm = nullptr; r->d_state = nullptr; r->d_list = nullptr; r->d_in = nullptr; r->d_out = nullptr;
-    r->h_block = nullptr; r->d_cnt = nullptr; r->d_exiting = nullptr; r->d_tfirst = nullptr; r->d_next = nullptr; r->d_stats = nullptr; r->fence_mode = getenv("CSDR_AMD_RING_FENCE") ? atoi(getenv("CSDR_AMD_RING_FENCE")) : 0; r->rs = nullptr; r->ev_exit = nullptr;
-    r->launched = false; r->launches = 0; r->submitted = 0; r->pending_lead = false;
+    r->fence_mode = getenv("CSDR_AMD_RING_FENCE") ? atoi(getenv("CSDR_AMD_RING_FENCE")) : 0;
     int khz = 100000; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || khz <= 0) khz = 100000;
     r->clock_khz = khz;
     r->idle_ticks = (long long)khz * 200 / 1000;                                             // 200 us
     r->life_ticks = (long long)khz * 250;                                                    // 250 ms
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    alloc((void **)&r->d_taps, sizeof(float) * taps_length);
-    alloc((void **)&r->d_lead_seeds, sizeof(float2) * 8);
-    alloc((void **)&r->d_lead_d, sizeof(float) * (size_t)wfm_lead_max(decimation, taps_length, frac_rate) * n_streams);
-    alloc((void **)&r->d_warm, sizeof(float) * WFM_RES_WARM * n_streams);
-    alloc((void **)&r->d_state, sizeof(float) * n_streams);
-    alloc((void **)&r->d_list, sizeof(int) * n_streams);
-    alloc((void **)&r->d_in, (size_t)n_slots * n_streams * r->in_pitch);
-    alloc((void **)&r->d_out, sizeof(int16_t) * (size_t)n_slots * n_streams * r->out_pitch);
-    alloc((void **)&r->d_cnt, sizeof(unsigned) * n_slots);
-    alloc((void **)&r->d_exiting, sizeof(unsigned));
-    alloc((void **)&r->d_tfirst, sizeof(unsigned long long) * n_slots);
-    alloc((void **)&r->d_next, sizeof(unsigned long long) * r->grid);
-    alloc((void **)&r->d_stats, sizeof(unsigned long long) * 4 * r->grid);
+    auto alloc = [&](auto &p, size_t bytes) { if (e == hipSuccess) e = dev_alloc(p, bytes); };
+    alloc(r->d_taps, sizeof(float) * taps_length);
+    alloc(r->d_lead_seeds, sizeof(float2) * 8);
+    alloc(r->d_lead_d, sizeof(float) * (size_t)wfm_lead_max(decimation, taps_length, frac_rate) * n_streams);
+    alloc(r->d_warm, sizeof(float) * WFM_RES_WARM * n_streams);
+    alloc(r->d_state, sizeof(float) * n_streams);
+    alloc(r->d_list, sizeof(int) * n_streams);
+    alloc(r->d_in, (size_t)n_slots * n_streams * r->in_pitch);
+    alloc(r->d_out, sizeof(int16_t) * (size_t)n_slots * n_streams * r->out_pitch);
+    alloc(r->d_cnt, sizeof(unsigned) * n_slots);
+    alloc(r->d_exiting, sizeof(unsigned));
+    alloc(r->d_tfirst, sizeof(unsigned long long) * n_slots);
+    alloc(r->d_next, sizeof(unsigned long long) * r->grid);
+    alloc(r->d_stats, sizeof(unsigned long long) * 4 * r->grid);
     const size_t hwords = (size_t)n_slots * r->lines * 16 + 16 + (size_t)n_slots * 16;
-    if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_block, sizeof(uint32_t) * hwords, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) e = host_alloc(r->h_block, sizeof(uint32_t) * hwords, hipHostMallocCoherent | hipHostMallocMapped);
     // The grid's stream gets a PRIORITY of its own: HIP multiplexes a process's streams onto a few hardware queues (four by default), and whatever shares a queue with the
     // resident grid waits behind it until it leaves -- a block's input copy then takes idle_us instead of microseconds (seen in the test suite once earlier tests had used up
     // the queues: 35 launches for 40 blocks).  Queues are per priority level, so a high-priority stream never shares one with the default-priority streams of the caller.
     if (e == hipSuccess) {
         int lo = 0, hi = 0;
         const char *pe = getenv("CSDR_AMD_RING_PRIO");                      // (A/B: 0 = a default-priority stream)
-        if (!(pe && atoi(pe) == 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) e = hipStreamCreateWithPriority(&r->rs, hipStreamNonBlocking, hi);
-        else e = hipStreamCreateWithFlags(&r->rs, hipStreamNonBlocking);
+        if (!(pe && atoi(pe) == 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) {
+            hipStream_t rs = nullptr; e = hipStreamCreateWithPriority(&rs, hipStreamNonBlocking, hi); r->rs.reset(rs);
+        } else e = stream_create(r->rs);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_exit, hipEventDisableTiming);
-    if (e != hipSuccess) { fail(e, "wfm ring: allocation", __FILE__, __LINE__); csdr_amd_wfm_ring_destroy(r); return nullptr; }
-    r->h_desc = r->h_block; r->h_ctrl = r->h_desc + (size_t)n_slots * r->lines * 16; r->h_done = r->h_ctrl + 16;
+    if (e == hipSuccess) e = event_create(r->ev_exit, hipEventDisableTiming);
+    if (e != hipSuccess) { fail(e, "wfm ring: allocation", __FILE__, __LINE__); return nullptr; }
+    r->h_desc = r->h_block.get(); r->h_ctrl = r->h_desc + (size_t)n_slots * r->lines * 16; r->h_done = r->h_ctrl + 16;
     std::vector<int> list(n_streams); for (int s = 0; s < n_streams; s++) list[s] = s;
-    if (hipMemcpy(r->d_taps, host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r->d_list, list.data(), sizeof(int) * n_streams, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(r->d_in, 0x80, (size_t)n_slots * n_streams * r->in_pitch) != hipSuccess ||
-        ring_upload_tables(r, shift_rate) || csdr_amd_wfm_ring_reset(r)) { csdr_amd_wfm_ring_destroy(r); return nullptr; }
-    return r;
+    if (hipMemcpy(r->d_taps.get(), host_taps, sizeof(float) * taps_length, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(r->d_list.get(), list.data(), sizeof(int) * n_streams, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(r->d_in.get(), 0x80, (size_t)n_slots * n_streams * r->in_pitch) != hipSuccess ||
+        ring_upload_tables(r.get(), shift_rate) || csdr_amd_wfm_ring_reset(r.get())) return nullptr;
+    return r.release();
 }
 
 int csdr_amd_wfm_ring_slots(const csdr_amd_wfm_ring *r) { return r->N; }
@@ -237,7 +229,7 @@ int csdr_amd_wfm_ring_set_timeouts(csdr_amd_wfm_ring *r, double idle_us, double 
 int csdr_amd_wfm_ring_resident(csdr_amd_wfm_ring *r)
 {
     if (!r->launched) return 0;
-    if (hipEventQuery(r->ev_exit) == hipErrorNotReady) return 1;
+    if (hipEventQuery(r->ev_exit.get()) == hipErrorNotReady) return 1;
     r->launched = false;
     return 0;
 }
@@ -256,13 +248,13 @@ int csdr_amd_wfm_ring_acquire(csdr_amd_wfm_ring *r, long long seq, double timeou
 uint8_t *csdr_amd_wfm_ring_input(csdr_amd_wfm_ring *r, long long seq, size_t *pitch)
 {
     if (pitch) *pitch = r->in_pitch;
-    return r->d_in + (size_t)(seq % r->N) * r->S * r->in_pitch;
+    return r->d_in.get() + (size_t)(seq % r->N) * r->S * r->in_pitch;
 }
 
 const int16_t *csdr_amd_wfm_ring_output(csdr_amd_wfm_ring *r, long long seq, size_t *pitch)
 {
     if (pitch) *pitch = r->out_pitch;
-    return r->d_out + (size_t)(seq % r->N) * r->S * r->out_pitch;
+    return r->d_out.get() + (size_t)(seq % r->N) * r->S * r->out_pitch;
 }
 
 // audio samples of block k (host mirror of the kernel's arithmetic and of csdr_amd_wfm_process)
@@ -313,12 +305,12 @@ long long csdr_amd_wfm_ring_submit(csdr_amd_wfm_ring *r)
         n_lead = (int)nl; retuned = 1;
         {
             rc = ring_stop(r); if (rc) return rc;
-            CSDR_HIP(hipMemcpy(r->d_lead_seeds, seeds.data(), sizeof(float2) * 8, hipMemcpyHostToDevice));          // [0] = chunk first - 4
-            const uint8_t *in = r->d_in + (size_t)slot * r->S * r->in_pitch, *prev = r->d_in + (size_t)((slot + r->N - 1) % r->N) * r->S * r->in_pitch;
-            rc = wfm_mfma_lead_shared(r->rs, in, r->in_pitch, prev, (size_t)2 * r->T, r->d_taps, r->d_lead_seeds, r->mfma.d_dtab, r->d_dtab_old, r->d_list, r->S, r->d_lead_d, wfm_lead_max(r->D, r->L, r->F),
-                                      r->d_warm, r->d_state, r->alpha, r->D, r->L, r->F, k * r->T, j_first, n_lead);
+            CSDR_HIP(hipMemcpy(r->d_lead_seeds.get(), seeds.data(), sizeof(float2) * 8, hipMemcpyHostToDevice));          // [0] = chunk first - 4
+            const uint8_t *in = r->d_in.get() + (size_t)slot * r->S * r->in_pitch, *prev = r->d_in.get() + (size_t)((slot + r->N - 1) % r->N) * r->S * r->in_pitch;
+            rc = wfm_mfma_lead_shared(r->rs.get(), in, r->in_pitch, prev, (size_t)2 * r->T, r->d_taps.get(), r->d_lead_seeds.get(), r->mfma.d_dtab, r->d_dtab_old.get(), r->d_list.get(), r->S, r->d_lead_d.get(), wfm_lead_max(r->D, r->L, r->F),
+                                      r->d_warm.get(), r->d_state.get(), r->alpha, r->D, r->L, r->F, k * r->T, j_first, n_lead);
             if (rc) return rc;
-            CSDR_HIP(hipStreamSynchronize(r->rs));
+            CSDR_HIP(hipStreamSynchronize(r->rs.get()));
         }
         r->pending_lead = false;
     }
@@ -388,7 +380,7 @@ int csdr_amd_wfm_ring_set_rate(csdr_amd_wfm_ring *r, float shift_rate)
     int rc;
     for (long long k = r->submitted - r->N; k < r->submitted; k++) if (k >= 0) { rc = ring_wait_block(r, k, 0); if (rc) return rc; }
     rc = ring_stop(r); if (rc) return rc;
-    if (!r->pending_lead) CSDR_HIP(hipMemcpy(r->d_dtab_old, r->mfma.d_dtab, sizeof(float2) * 3072, hipMemcpyDeviceToDevice));      // (two retunes without a block between them: the samples in front still carry the first rate)
+    if (!r->pending_lead) CSDR_HIP(hipMemcpy(r->d_dtab_old.get(), r->mfma.d_dtab, sizeof(float2) * 3072, hipMemcpyDeviceToDevice));      // (two retunes without a block between them: the samples in front still carry the first rate)
     rc = ring_upload_tables(r, shift_rate); if (rc) return rc;
     r->rate = shift_rate;
     r->pending_lead = r->submitted > 0;
@@ -403,7 +395,7 @@ int csdr_amd_wfm_ring_stats(csdr_amd_wfm_ring *r, double out[4])
 {
     int rc = ring_stop(r); if (rc) return rc;
     std::vector<unsigned long long> st((size_t)4 * r->grid);
-    CSDR_HIP(hipMemcpy(st.data(), r->d_stats, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost));
+    CSDR_HIP(hipMemcpy(st.data(), r->d_stats.get(), sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost));
     unsigned long long sum[4] = {0, 0, 0, 0};
     for (int w = 0; w < r->grid; w++) for (int i = 0; i < 4; i++) sum[i] += st[(size_t)4 * w + i];
     for (int i = 0; i < 3; i++) out[i] = sum[3] ? (double)sum[i] * 1000.0 / r->clock_khz / (double)sum[3] : 0.0;
