@@ -103,6 +103,27 @@ def lib():
     L.csdr_amd_waterfall_kernel_name.restype = C.c_char_p; L.csdr_amd_waterfall_kernel_name.argtypes = [vp]
     L.csdr_amd_waterfall_force_generic.argtypes = [vp, i]
     L.csdr_amd_waterfall_destroy.argtypes = [vp]; L.csdr_amd_waterfall_destroy.restype = None
+    ll = C.c_longlong
+    L.csdr_amd_resampler_create.restype = vp; L.csdr_amd_resampler_create.argtypes = [vp, i, i, vp, i, i]
+    L.csdr_amd_resampler_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
+    L.csdr_amd_resampler_max_out.restype = ll; L.csdr_amd_resampler_max_out.argtypes = [vp, ll]
+    L.csdr_amd_resampler_reset.argtypes = [vp]
+    L.csdr_amd_resampler_set_cli_bufsize.argtypes = [vp, i]
+    L.csdr_amd_resampler_set_last_taps_delay.argtypes = [vp, i]
+    L.csdr_amd_resampler_force_generic.argtypes = [vp, i]
+    L.csdr_amd_resampler_kernel_name.restype = C.c_char_p; L.csdr_amd_resampler_kernel_name.argtypes = [vp]
+    L.csdr_amd_resampler_destroy.argtypes = [vp]; L.csdr_amd_resampler_destroy.restype = None
+    L.csdr_amd_resampler_window.argtypes = [i, i, i, i, i, vp]
+    L.csdr_amd_interp_create.restype = vp; L.csdr_amd_interp_create.argtypes = [vp, i, vp, i, i]
+    L.csdr_amd_interp_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
+    L.csdr_amd_interp_max_out.restype = ll; L.csdr_amd_interp_max_out.argtypes = [vp, ll]
+    L.csdr_amd_interp_reset.argtypes = [vp]
+    L.csdr_amd_interp_set_cli_bufsize.argtypes = [vp, i]
+    L.csdr_amd_interp_force_generic.argtypes = [vp, i]
+    L.csdr_amd_interp_kernel_name.restype = C.c_char_p; L.csdr_amd_interp_kernel_name.argtypes = [vp]
+    L.csdr_amd_interp_destroy.argtypes = [vp]; L.csdr_amd_interp_destroy.restype = None
+    L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
+    L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
     L.csdr_amd_fft_exchange_sides_ff.argtypes = [vp, vp, vp, i, i]
     L.csdr_amd_accumulate_power_cf.argtypes = [vp, vp, vp, sz]
@@ -340,6 +361,128 @@ class Waterfall:
             self.close()
         except Exception:
             pass
+
+
+def rational_resampler_get_lowpass_f(taps_length, interpolation, decimation, window="HAMMING"):
+    """rational_resampler_get_lowpass_f (libcsdr.c:665-673), on the host"""
+    t = np.zeros(taps_length, f32)
+    lib().csdr_amd_rational_resampler_get_lowpass_f(_hp(t), taps_length, interpolation, decimation, WINDOWS[window])
+    return t
+
+
+def fir_interpolate_lowpass_f(taps_length, interpolation, window="HAMMING"):
+    """the taps `csdr fir_interpolate_cc` designs (csdr.c:1212): firdes_lowpass_f(taps_length, 0.5 / interpolation, window), on the host"""
+    t = np.zeros(taps_length, f32)
+    lib().csdr_amd_firdes_lowpass_f(_hp(t), taps_length, C.c_float(np.float32(0.5) / np.float32(interpolation)), WINDOWS[window])
+    return t
+
+
+def resampler_schedule(interpolation, decimation, taps_length, n, last_taps_delay=0):
+    """[n, 3] int32: (startingi, delayi, taps used) of rational_resampler_ff's first n outputs from last_taps_delay (host)"""
+    out = np.zeros((n, 3), np.int32)
+    if lib().csdr_amd_debug_resampler_schedule(interpolation, decimation, taps_length, last_taps_delay, n, _hp(out)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out
+
+
+def resampler_window(interpolation, decimation, taps_length, input_size, last_taps_delay=0):
+    """what one rational_resampler_ff call returns: (input_processed, output_size, last_taps_delay)"""
+    st = np.zeros(3, np.int32)
+    if lib().csdr_amd_resampler_window(interpolation, decimation, taps_length, input_size, last_taps_delay, _hp(st)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return tuple(int(v) for v in st)
+
+
+class _Resampling:
+    """Shared driver of csdr_amd_resampler (real, "resampler") and csdr_amd_interp (complex, "interp"): n_streams streams in lockstep."""
+    _dt, _eb, _pre = f32, 4, "resampler"
+
+    def _fn(self, name):
+        return getattr(self.ctx.L, "csdr_amd_%s_%s" % (self._pre, name))
+
+    def max_out(self, n_in):
+        return int(self._fn("max_out")(self.h, n_in))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch):
+        """device pointers: n_in new samples per stream (in_pitch apart) -> outputs per stream written at d_out (out_pitch elements apart)"""
+        n = C.c_longlong(0)
+        self.ctx.check(self._fn("process")(self.h, d_in, n_in, in_pitch, d_out, out_pitch, C.byref(n)), self._pre + "_process")
+        return n.value
+
+    def process(self, x, calls=None):
+        """x: [n_streams, n] (or [n]) host samples; calls: per-call sample counts (default one call) -> [n_streams, outputs] (or [outputs])"""
+        x = np.ascontiguousarray(x, self._dt)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        calls = [n] if calls is None else list(calls)
+        di = self.ctx.upload(x)
+        opitch = max(self.max_out(max(calls) if calls else 0), 1)
+        do = self.ctx.alloc(self._eb * opitch * s + 256)
+        out, at = [], 0
+        for k in calls:
+            r = self.process_dev(di.at(self._eb * at), k, n, do.ptr, opitch)
+            if r:
+                out.append(self.ctx.download(do, self._dt, opitch * s).reshape(s, opitch)[:, :r].copy())
+            at += k
+        y = np.concatenate(out, axis=1) if out else np.zeros((s, 0), self._dt)
+        return y[0] if squeeze else y
+
+    def reset(self):
+        self.ctx.check(self._fn("reset")(self.h), self._pre + "_reset")
+
+    def set_cli_bufsize(self, the_bufsize):
+        self.ctx.check(self._fn("set_cli_bufsize")(self.h, int(the_bufsize)), self._pre + "_set_cli_bufsize")
+
+    def force_generic(self, on=True):
+        self.ctx.check(self._fn("force_generic")(self.h, int(on)), self._pre + "_force_generic")
+
+    def kernel_name(self):
+        return self._fn("kernel_name")(self.h).decode()
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler(_Resampling):
+    """csdr_amd_resampler: rational_resampler_ff (libcsdr.c:607-640) by interpolation/decimation for n_streams float streams."""
+
+    def __init__(self, ctx, interpolation, decimation, taps, n_streams=1, bufsize=None, last_taps_delay=0):
+        self.ctx, self.I, self.D, self.n_streams = ctx, interpolation, decimation, n_streams
+        self.taps = np.ascontiguousarray(taps, f32)
+        self.h = ctx.L.csdr_amd_resampler_create(ctx.h, interpolation, decimation, _hp(self.taps), self.taps.size, n_streams)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+        if bufsize:
+            self.set_cli_bufsize(bufsize)
+        if last_taps_delay:
+            self.set_last_taps_delay(last_taps_delay)
+
+    def set_last_taps_delay(self, d):
+        self.ctx.check(self.ctx.L.csdr_amd_resampler_set_last_taps_delay(self.h, int(d)), "resampler_set_last_taps_delay")
+
+
+class Interpolator(_Resampling):
+    """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
+    _dt, _eb, _pre = c64, 8, "interp"
+
+    def __init__(self, ctx, interpolation, taps, n_streams=1, bufsize=None):
+        self.ctx, self.I, self.n_streams = ctx, interpolation, n_streams
+        self.taps = np.ascontiguousarray(taps, f32)
+        self.h = ctx.L.csdr_amd_interp_create(ctx.h, interpolation, _hp(self.taps), self.taps.size, n_streams)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+        if bufsize:
+            self.set_cli_bufsize(bufsize)
 
 
 class Context:
@@ -682,6 +825,37 @@ class Context:
         self.sync(); self.L.csdr_amd_fracdec_destroy(d)
         y = self.download(do, f32, s * n).reshape(s, n)[:, :no]
         return y[0].copy() if squeeze else y.copy()
+
+    # ---- FIR resamplers (resampler.hip)
+    def resampler(self, interpolation, decimation, taps=None, n_streams=1, transition_bw=0.05, window="HAMMING", bufsize=None):
+        """A batched rational_resampler_ff object; taps default to rational_resampler_get_lowpass_f(firdes_filter_len(transition_bw), I, D, window)."""
+        if taps is None:
+            taps = rational_resampler_get_lowpass_f(self.firdes_filter_len(transition_bw), interpolation, decimation, window)
+        return Resampler(self, interpolation, decimation, taps, n_streams, bufsize)
+
+    def interpolator(self, interpolation, taps=None, n_streams=1, transition_bw=0.05, window="HAMMING", bufsize=None):
+        """A batched fir_interpolate_cc object; taps default to firdes_lowpass_f(firdes_filter_len(transition_bw), 0.5 / I, window) as csdr.c:1212 designs them."""
+        if taps is None:
+            taps = fir_interpolate_lowpass_f(self.firdes_filter_len(transition_bw), interpolation, window)
+        return Interpolator(self, interpolation, taps, n_streams, bufsize)
+
+    def rational_resampler_ff(self, x, interpolation, decimation, taps=None, transition_bw=0.05, window="HAMMING", bufsize=None, calls=None):
+        """x: [n] or [n_streams, n] float.  Default: the reference function over the whole stream; bufsize=B: the `csdr rational_resampler_ff` stream at that buffer size."""
+        x2 = np.ascontiguousarray(x, f32)
+        r = self.resampler(interpolation, decimation, taps, 1 if x2.ndim == 1 else x2.shape[0], transition_bw, window, bufsize)
+        try:
+            return r.process(x2, calls)
+        finally:
+            r.close()
+
+    def fir_interpolate_cc(self, x, interpolation, taps=None, transition_bw=0.05, window="HAMMING", bufsize=None, calls=None):
+        """x: [n] or [n_streams, n] complex.  Default: the reference function over the whole stream; bufsize=B: the `csdr fir_interpolate_cc` stream (B zeros first)."""
+        x2 = np.ascontiguousarray(x, c64)
+        p = self.interpolator(interpolation, taps, 1 if x2.ndim == 1 else x2.shape[0], transition_bw, window, bufsize)
+        try:
+            return p.process(x2, calls)
+        finally:
+            p.close()
 
     def fft_c2c(self, x, forward=True):
         x = np.ascontiguousarray(x, c64); di = self.upload(x); do = self.alloc(x.nbytes + 64)

@@ -330,6 +330,47 @@ void fractional_decimator_ff(float *in, float *out, int n, fractional_decimator_
     csdr_amd_fracdec_destroy(fd);
 }
 
+// One call of each FIR resampler = a fresh batch object fed the whole block once (resampler.hip).
+rational_resampler_ff_t rational_resampler_ff(float *in, float *out, int n, int interpolation, int decimation, float *taps, int taps_length, int last_taps_delay)
+{
+    rational_resampler_ff_t d;
+    int st[3];
+    MUST(csdr_amd_resampler_window(interpolation, decimation, taps_length, n, last_taps_delay, st));
+    d.input_processed = st[0]; d.output_size = st[1]; d.last_taps_delay = st[2];
+    if (!d.output_size) return d;
+    csdr_amd_resampler *r = csdr_amd_resampler_create(ctx(), interpolation, decimation, taps, taps_length, 1);
+    if (!r) die("rational_resampler_ff", -3);
+    MUST(csdr_amd_resampler_set_cli_bufsize(r, n));                      // one window of n samples: the reference's cap exit included
+    MUST(csdr_amd_resampler_set_last_taps_delay(r, last_taps_delay));
+    float *din = stage_in<float>(4, in, n); float *dout = stage_out<float>(5, (size_t)d.output_size + 2);
+    long long produced = 0;
+    MUST(csdr_amd_resampler_process(r, din, n, n, dout, (size_t)d.output_size + 2, &produced));
+    if (produced != d.output_size) die("rational_resampler_ff", -5);
+    fetch(out, dout, (size_t)produced);
+    csdr_amd_resampler_destroy(r);
+    return d;
+}
+
+void rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, window_t window)
+{
+    csdr_amd_rational_resampler_get_lowpass_f(output, output_size, interpolation, decimation, (int)window);
+}
+
+int fir_interpolate_cc(complexf *in, complexf *out, int n, int interpolation, float *taps, int taps_length)
+{
+    if (n <= 0) return 0;
+    csdr_amd_interp *p = csdr_amd_interp_create(ctx(), interpolation, taps, taps_length, 1);
+    if (!p) die("fir_interpolate_cc", -3);
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n);
+    const size_t cap = (size_t)csdr_amd_interp_max_out(p, n);
+    cf32 *dout = stage_out<cf32>(5, cap);
+    long long produced = 0;
+    MUST(csdr_amd_interp_process(p, din, n, n, dout, cap, &produced));
+    fetch((cf32 *)out, dout, (size_t)produced);
+    csdr_amd_interp_destroy(p);
+    return (int)produced;
+}
+
 // ------------------------------------------------------------------ FFT plan layer (fft_fftw.c:6-45) on hipFFT
 void *csdr_fft_malloc(size_t n) { void *p = nullptr; if (posix_memalign(&p, 64, n ? n : 64)) return nullptr; return p; }
 void csdr_fft_free(void *p) { free(p); }

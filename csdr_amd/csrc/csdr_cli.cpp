@@ -227,6 +227,55 @@ struct FracDec : Stage {   // csdr.c:1465-1525
     }
 };
 
+struct Copy : Stage {   // csdr.c:1427, 1494: `rational_resampler_ff 1 1` and `fractional_decimator_ff 1` copy their input (inside `chain`; alone they become `clone`)
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    { *cons = n; if (n) MUST(csdr_amd_d2d(c, o, i, 4 * n)); return (long)n; }
+};
+
+struct Resample : Stage {   // csdr.c:1409-1460: rational_resampler_ff over the_bufsize windows (the object replays the window loop, cap-exit repeats included)
+    csdr_amd_resampler *r; int I, D;
+    Resample(csdr_amd_ctx *c, int interpolation, int decimation, float tbw, int window, int the_bufsize) : I(interpolation), D(decimation)
+    {
+        const int nt = csdr_amd_firdes_filter_len(tbw);
+        std::vector<float> t(nt);
+        csdr_amd_rational_resampler_get_lowpass_f(t.data(), nt, I, D, window);
+        r = csdr_amd_resampler_create(c, I, D, t.data(), nt, 1); if (!r) die("resampler_create");
+        if (csdr_amd_resampler_set_cli_bufsize(r, the_bufsize) < 0) { badsyntax(csdr_amd_last_error()); exit(255); }
+        min_block = (size_t)the_bufsize;
+    }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_resampler_max_out(r, (long long)n) + 16; }
+    int next_bufsize(int b) override { return (int)((long long)b * I / D); }       // csdr.c:1433
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        long long no = 0;
+        MUST(csdr_amd_resampler_process(r, (const float *)i, (long long)n, n, (float *)o, cap, &no));
+        *cons = n; return (long)no;
+    }
+};
+
+struct Interp : Stage {   // csdr.c:1179-1232: fir_interpolate_cc over the_bufsize windows, the first over a buffer of zeros
+    csdr_amd_interp *p; int I;
+    Interp(csdr_amd_ctx *c, int factor, float tbw, int window, int the_bufsize) : I(factor)
+    {
+        in_elem = 8; out_elem = 8;
+        const int nt = csdr_amd_firdes_filter_len(tbw);
+        fprintf(stderr, "csdr fir_interpolate_cc: taps_length = %d\n", nt);
+        std::vector<float> t(nt);
+        csdr_amd_firdes_lowpass_f(t.data(), nt, 0.5f / (float)factor, window);
+        p = csdr_amd_interp_create(c, factor, t.data(), nt, 1); if (!p) die("interp_create");
+        MUST(csdr_amd_interp_set_cli_bufsize(p, the_bufsize));
+        min_block = (size_t)nt;
+    }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_interp_max_out(p, (long long)n) + 16; }
+    int next_bufsize(int b) override { return b * I; }                            // csdr.c:1207
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        long long no = 0;
+        MUST(csdr_amd_interp_process(p, (const csdr_complexf *)i, (long long)n, n, (csdr_complexf *)o, cap, &no));
+        *cons = n; return (long)no;
+    }
+};
+
 struct Bandpass : Stage {   // csdr.c:1810-1886
     csdr_amd_fftfilt *f; int inp; int n_taps, win;
     const char *ctl_format() override { return "%g %g\n"; }
@@ -1547,6 +1596,7 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
     if (cmd == "fractional_decimator_ff") {
         if (argc <= 2) { badsyntax("need required parameters (rate)"); return nullptr; }
         float rate; sscanf(argv[2], "%g", &rate);
+        if (rate == 1) return new Copy();
         int points = 12; if (argc >= 4) sscanf(argv[3], "%d", &points);
         if (points & 1) { badsyntax("num_poly_points should be even"); return nullptr; }
         if (points < 2) { badsyntax("num_poly_points should be >= 2"); return nullptr; }
@@ -1557,6 +1607,28 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
             csdr_amd_firdes_lowpass_f(taps.data(), nt, 0.5f / (rate - tbw), CSDR_WINDOW_HAMMING);
         }
         return new FracDec(rate, points, taps.empty() ? nullptr : taps.data(), (int)taps.size(), g_dynamic ? the_bufsize : unitround(g_fixed));
+    }
+    if (cmd == "rational_resampler_ff" || cmd == "suboptimal_rational_resampler_ff") {   // csdr.c:1409-1430
+        if (argc <= 3) { badsyntax("need required parameters (interpolation, decimation)"); return nullptr; }
+        int I = 0, D = 0; sscanf(argv[2], "%d", &I); sscanf(argv[3], "%d", &D);
+        if (I < 1 || D < 1) { badsyntax("interpolation and decimation must be integers >= 1"); return nullptr; }
+        if (I == 1 && D == 1) return new Copy();
+        float tbw = 0.05f; if (argc >= 5) sscanf(argv[4], "%g", &tbw);
+        if (!(tbw > 0)) { badsyntax("transition_bw must be positive"); return nullptr; }
+        int window = CSDR_WINDOW_HAMMING; if (argc >= 6) window = window_from(argv[5]); else fprintf(stderr, "csdr %s: window = HAMMING\n", g_cmd);
+        if (cmd[0] == 's') fprintf(stderr, "csdr %s: note: suboptimal rational resampler chosen.\n", g_cmd);
+        return new Resample(c, I, D, tbw, window, g_dynamic ? the_bufsize : unitround(g_fixed));
+    }
+    if (cmd == "fir_interpolate_cc") {   // csdr.c:1179-1201
+        if (argc <= 2) { badsyntax("need required parameter (interpolation factor)"); return nullptr; }
+        int factor = 0; sscanf(argv[2], "%d", &factor);
+        if (factor < 1) { badsyntax("interpolation factor must be an integer >= 1"); return nullptr; }
+        float tbw = 0.05f; if (argc >= 4) sscanf(argv[3], "%g", &tbw);
+        if (!(tbw > 0 && tbw < 1)) { badsyntax("transition_bw must be in (0, 1)"); return nullptr; }
+        int window = CSDR_WINDOW_HAMMING; if (argc >= 5) window = window_from(argv[4]); else fprintf(stderr, "csdr %s: window = HAMMING\n", g_cmd);
+        int big = g_fixed_big;                                       // csdr.c:1198: the big buffer doubles until it holds two filters
+        while (big < 2 * csdr_amd_firdes_filter_len(tbw)) big *= 2;
+        return new Interp(c, factor, tbw, window, g_dynamic ? the_bufsize : unitround(big));
     }
     if (cmd == "bandpass_fir_fft_cc") {
         float lo = 0, hi = 0, tbw = 0;
@@ -1764,7 +1836,7 @@ int main(int argc, char **argv)
     if (argc <= 1 || !strcmp(argv[1], "--help")) {
         fprintf(stderr, "csdr (MI355X back end): convert_u8_f convert_f_u8 convert_s8_f convert_f_s8 convert_f_s16 convert_s16_f convert_f_i16 convert_i16_f "
                         "convert_f_s24 convert_s24_f shift_math_cc shift_addition_cc shift_addition_fc shift_table_cc shift_addfast_cc shift_unroll_cc "
-                        "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff deemphasis_wfm_ff "
+                        "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff rational_resampler_ff suboptimal_rational_resampler_ff fir_interpolate_cc deemphasis_wfm_ff "
                         "deemphasis_nfm_ff limit_ff fastagc_ff bandpass_fir_fft_cc fastddc_fwd_cc fastddc_inv_cc firdes_lowpass_f firdes_bandpass_c "
                         "amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
@@ -1805,6 +1877,9 @@ int main(int argc, char **argv)
         }
         if (octave) { fflush(stdout); getchar(); }                   // keep octave's window open until the user closes the pipe
         return 0;
+    }
+    if ((cmd == "rational_resampler_ff" || cmd == "suboptimal_rational_resampler_ff") && argc > 3) {   // csdr.c:1427: 1/1 copies input to output
+        int I = 0, D = 0; sscanf(argv[2], "%d", &I); sscanf(argv[3], "%d", &D); if (I == 1 && D == 1) return passthrough(true, 0);
     }
     if (cmd == "fractional_decimator_ff" && argc > 2) { float r = 0; sscanf(argv[2], "%g", &r); if (r == 1) return passthrough(true, 0); }   // csdr.c:1494
     // device hand-off from the previous process of the shell pipeline (the streaming commands only): listen before anything slow -- the producer looks for this

@@ -165,6 +165,45 @@ void  csdr_amd_fracdec_set_where(csdr_amd_fracdec *d, float where);   /* fractio
 void  csdr_amd_fracdec_set_cli_bufsize(csdr_amd_fracdec *d, int the_bufsize);
 float csdr_amd_fracdec_get_where(const csdr_amd_fracdec *d);
 
+/* ------------------------------------------------------------------ FIR resamplers (resampler.hip)
+ * rational_resampler_ff libcsdr.c:607-640 (interpolation I, decimation D, taps T long, typically from csdr_amd_rational_resampler_get_lowpass_f) and
+ * fir_interpolate_cc libcsdr.c:579-605, for n_streams streams in lockstep.  The objects keep each stream's recent input on the device, so a stream may be cut into
+ * calls anywhere (also 0- and 1-sample calls) without changing a bit of the output.
+ * Streaming (default): the output equals the reference function applied once to the whole stream seen since the last reset.
+ * set_cli_bufsize(B > 0): the output equals the reference CLI's stream at that buffer size -- `csdr rational_resampler_ff` (csdr.c:1441-1459: B-sample windows,
+ * the state of the last computed output carried when a window hits its output cap, whose output then repeats), `csdr fir_interpolate_cc` (csdr.c:1215-1231:
+ * B zeros in front of the stream).  Setting it resets the object; 0 goes back to streaming.
+ * process: n_in new samples per stream (device, in_pitch elements apart) -> *n_out outputs per stream (out_pitch elements apart; at most *_max_out(n_in)).
+ * kernel_name: what the last call ran ("k_rr_poly" / "k_rr_generic", "k_interp_poly" / "k_interp_generic"); force_generic(1) takes the generic kernel always. */
+typedef struct csdr_amd_resampler csdr_amd_resampler;
+csdr_amd_resampler *csdr_amd_resampler_create(csdr_amd_ctx *ctx, int interpolation, int decimation, const float *host_taps, int taps_length, int n_streams);
+int  csdr_amd_resampler_process(csdr_amd_resampler *r, const float *in, long long n_in, size_t in_pitch, float *out, size_t out_pitch, long long *n_out);
+long long csdr_amd_resampler_max_out(const csdr_amd_resampler *r, long long n_in);
+int  csdr_amd_resampler_reset(csdr_amd_resampler *r);
+int  csdr_amd_resampler_set_cli_bufsize(csdr_amd_resampler *r, int the_bufsize);
+int  csdr_amd_resampler_force_generic(csdr_amd_resampler *r, int on);
+/* the incoming last_taps_delay (0 <= d < I) of the stream's first output (or first CLI window): call after create / reset / set_cli_bufsize */
+int  csdr_amd_resampler_set_last_taps_delay(csdr_amd_resampler *r, int last_taps_delay);
+/* what one rational_resampler_ff call over input_size samples returns, without the samples: state = {input_processed, output_size, last_taps_delay}
+ * (libcsdr.c:616-639, both loop exits; the outputs themselves are those of a set_cli_bufsize(input_size) object fed input_size samples) */
+int  csdr_amd_resampler_window(int interpolation, int decimation, int taps_length, int input_size, int last_taps_delay, int *state);
+const char *csdr_amd_resampler_kernel_name(const csdr_amd_resampler *r);
+void csdr_amd_resampler_destroy(csdr_amd_resampler *r);
+typedef struct csdr_amd_interp csdr_amd_interp;
+csdr_amd_interp *csdr_amd_interp_create(csdr_amd_ctx *ctx, int interpolation, const float *host_taps, int taps_length, int n_streams);
+int  csdr_amd_interp_process(csdr_amd_interp *p, const csdr_complexf *in, long long n_in, size_t in_pitch, csdr_complexf *out, size_t out_pitch, long long *n_out);
+long long csdr_amd_interp_max_out(const csdr_amd_interp *p, long long n_in);
+int  csdr_amd_interp_reset(csdr_amd_interp *p);
+int  csdr_amd_interp_set_cli_bufsize(csdr_amd_interp *p, int the_bufsize);
+int  csdr_amd_interp_force_generic(csdr_amd_interp *p, int on);
+const char *csdr_amd_interp_kernel_name(const csdr_amd_interp *p);
+void csdr_amd_interp_destroy(csdr_amd_interp *p);
+/* rational_resampler_get_lowpass_f libcsdr.c:665-673 (host) */
+void csdr_amd_rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, int window);
+/* Host-side schedule of rational_resampler_ff from an incoming last_taps_delay: out[3k..3k+2] = (startingi, delayi, taps used) of output k, k < n
+ * (libcsdr.c:621-626).  The kernels' tables are built from the same recurrence. */
+int  csdr_amd_debug_resampler_schedule(int interpolation, int decimation, int taps_length, int last_taps_delay, int n, int *out);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

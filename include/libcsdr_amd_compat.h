@@ -77,6 +77,11 @@ typedef struct fractional_decimator_ff_s {                                      
 fractional_decimator_ff_t fractional_decimator_ff_init(float rate, int num_poly_points, float *taps, int taps_length);
 void fractional_decimator_ff(float *input, float *output, int input_size, fractional_decimator_ff_t *d);
 
+int fir_interpolate_cc(complexf *input, complexf *output, int input_size, int interpolation, float *taps, int taps_length);   /* libcsdr.h:105 */
+typedef struct rational_resampler_ff_s { int input_processed; int output_size; int last_taps_delay; } rational_resampler_ff_t;   /* libcsdr.h:132-137 */
+rational_resampler_ff_t rational_resampler_ff(float *input, float *output, int input_size, int interpolation, int decimation, float *taps, int taps_length, int last_taps_delay);
+void rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, window_t window);
+
 typedef struct shift_table_data_s { float *table; int table_size; } shift_table_data_t;     /* libcsdr.h:180-184 */
 void shift_table_deinit(shift_table_data_t table_data);
 shift_table_data_t shift_table_init(int table_size);
