@@ -9,15 +9,22 @@ on 1024 parallel 2.4 MS/s u8 IQ streams per GPU, synthetic i.i.d. uniform u8 (SU
 signal"), inputs resident in HBM before the timed region.  One step = one block of 2344*1024 = 2 400 256 complex
 samples (1.0001 s of signal) of every stream through the whole chain (state carried from step to step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--block T] [--no-cpu-baseline] [--verify | --no-verify] [--no-other-configs] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--block T] [--dump-outputs DIR] [--verify]
+    python bench.py --full [...] [--no-cpu-baseline] [--no-verify | --strict-rows-only] [--no-other-configs]
 
-The line checks itself: four rows of the batch carry a real FM signal (put there BEFORE the timed loop) and are held to +-1 LSB on every sample against the CPU
-oracle after it, and 16 rows of the noise batch spread over all stream blocks go through the statistical gate of tests/verify_configs.py ("verify", default;
---strict-rows-only drops the noise rows; --no-verify skips).  The exit code is non-zero when the headline OR any operating point OR any other config's leg fails its
-verify or crashes ("all_legs_verified").  At N = 1 the line also
-carries the other BASELINE configs as short legs of their own bench scripts ("other_configs": C1 fir_decimate_cc, C3 at 1023 and 4095 taps, C4 fastddc, C5 NFM with a
-rate per channel -- each with its own verify) and short-block operating points of this chain ("operating_points": the reference's 16384-sample block -- one launch per
-block, and through the resident ring csdr_amd_wfm_ring_* --, and 65536 streams x 10 ms), so that every config's number exists on the driver's clock.
+A plain run does only what the headline needs: set-up, spin-up and warm-up, the K timed steps, --dump-outputs if given, the JSON line (value, ms_per_step, and the
+roofline of the chain kernel from the HIP events of the same timed steps).  Four rows of the batch carry a real FM signal in every run (put there BEFORE the timed loop,
+so a plain and a --full run time and dump the same bytes; --no-verify leaves the batch pure noise); --verify checks them in a plain run too.
+
+--full adds everything else, each part after the timed steps:
+  * verify (on unless --no-verify): the four FM rows are held to +-1 LSB on every sample against the CPU oracle, and 16 rows of the noise batch spread over all stream
+    blocks go through the statistical gate of tests/verify_configs.py (--strict-rows-only drops the noise rows).  The exit code is non-zero when the headline OR any
+    operating point OR any other config's leg fails its verify or crashes ("all_legs_verified").
+  * at N = 1 (unless --no-other-configs), the other BASELINE configs as short legs of their own bench scripts ("other_configs": C1 fir_decimate_cc, C3 at 1023 and 4095
+    taps, C4 fastddc, C5 NFM with a rate per channel -- each with its own verify) and short-block operating points of this chain ("operating_points": the reference's
+    16384-sample block -- one launch per block, and through the resident ring csdr_amd_wfm_ring_* --, and 65536 streams x 10 ms), so that every config's number exists
+    on the same clock.
+  * at N = 1 (unless --no-cpu-baseline), the reference CPU path on the host cores ("cpu_baseline").
 
 N > 1: launched by torch.distributed.run, one rank per GPU; streams are independent, so ranks share nothing on
 the data path (replicas of the per-GPU workload, "scaling": "weak"); barrier + max-over-ranks timing over RCCL.
@@ -231,13 +238,16 @@ def main():
                          "launches of the chain kernel run up to 25 %% slower (profiles/r3_notes.md) -- and the metric is a stream's steady-state rate; 0 = off")
     ap.add_argument("--streams", type=int, default=1024)
     ap.add_argument("--block", type=int, default=2344 * 1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--verify", action="store_true", help="kept for old command lines: the full check is the default now")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the check against the oracle, the other BASELINE configs, the short-block operating "
+                                                        "points and the CPU baseline (each can be dropped with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the reference CPU path")
+    ap.add_argument("--verify", action="store_true", help="check the headline's outputs against the oracle in a plain run too (--full checks them by default)")
     ap.add_argument("--strict-rows-only", action="store_true", help="check only the four planted FM rows (+-1 LSB, <= 1e-5), not the 16 noise rows")
-    ap.add_argument("--no-verify", action="store_true", help="skip the default check: after the timed region, reset, one more pass over all streams with the same object / "
-                         "buffers; four planted FM rows held to +-1 LSB and <= 1e-5 on every sample and 16 full audio rows of the noise batch spread over all stream "
-                         "blocks under the statistical gate of tests/verify_configs.py, all against the CPU oracle on the same bytes")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the short legs of the other BASELINE configs and the short-block operating points")
+    ap.add_argument("--no-verify", action="store_true", help="plant no FM rows and skip the check that --full does by default: after the timed region, reset, one more "
+                         "pass over all streams with the same object / buffers; four planted FM rows held to +-1 LSB and <= 1e-5 on every sample and 16 full audio rows "
+                         "of the noise batch spread over all stream blocks under the statistical gate of tests/verify_configs.py, all against the CPU oracle on the "
+                         "same bytes")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, N = 1: skip the short legs of the other BASELINE configs and the short-block operating points")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the s16 audio of the last one as DIR/audio_s16.npy (float32; a seeded sample of "
                                                          "the streams, at most 64 MB)")
     args = ap.parse_args()
@@ -278,10 +288,12 @@ def main():
     g = torch.Generator(device="cuda"); g.manual_seed(42 + rank)
     x = torch.randint(0, 256, (S, pitch), dtype=torch.uint8, device="cuda", generator=g)
     strict_rows = []
-    do_verify = rank == 0 and not args.no_verify
-    if do_verify:
+    plant = rank == 0 and not args.no_verify
+    do_verify = plant and (args.full or args.verify)
+    if plant:
         # rows held to +-1 LSB on every sample: a real FM signal in a few rows spread over the batch, put there BEFORE the timed loop (the kernel's work does not
-        # depend on the data; the rest of the batch stays i.i.d. noise, which only a statistical gate can check: tests/verify_configs.py)
+        # depend on the data; the rest of the batch stays i.i.d. noise, which only a statistical gate can check: tests/verify_configs.py).  Planted whether or
+        # not this run checks them, so that a plain and a --full run time and dump the same bytes.
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from tests_helpers import wfm_signal_u8
         strict_rows = sorted({r for r in (5, S // 3 + 1, (2 * S) // 3 + 2, S - 2) if 0 <= r < S})
@@ -342,7 +354,7 @@ def main():
         achieved_gbs = ALGO_BYTES_PER_SAMPLE * samples_per_step_gpu / (k_avg_ms * 1e-3) / 1e9
         res = {
             "metric": "complex MS/s in->out, WFM demod chain @2.4 MS/s x N streams",
-            "value": round(msps, 1), "unit": "complex MS/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_steps_before_warmup": spin_steps,
+            "value": round(msps, 1), "unit": "complex MS/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full), "spinup_steps_before_warmup": spin_steps,
             "ms_per_step": round(wall / args.steps * 1e3, 4), "cold_ms_per_step_first_%d_steps_after_idle" % cold_k: round(cold_ms, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "configs[1]: full WFM pipe u8 IQ -> s16 audio (convert_u8_f|shift_addition_cc -0.085|fir_decimate_cc 10 0.05 HAMMING|"
@@ -375,13 +387,13 @@ def main():
             res["verify"] = vc.verify_wfm(ctx, w, x, out_s16, S, T, pitch, n_audio_max, taps, rows=[] if args.strict_rows_only else [r for r in vc.pick_rows(S) if r not in strict_rows],
                                           strict_rows=strict_rows, out_f32=out_f32)
             del out_f32
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             L.csdr_amd_wfm_destroy(w); w = None
             del x, out_s16; torch.cuda.empty_cache()
             res["operating_points"] = operating_points(ctx, taps, verify=do_verify)
             res["operating_points"].append(resident_point(ctx, taps, verify=do_verify))
             res["other_configs"] = other_configs()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         # every leg must have verified: a failed or crashed leg turns the run red (the line is still printed first, with the failure inside it)
         bad = []

@@ -22,7 +22,7 @@ for step in "$@"; do
     tests)      timeout 1500 python -m pytest tests -q -x -m gpu 2>&1 | grep -E "passed|failed|rror" | tail -4 ;;
     tests:*)    timeout 1500 python -m pytest tests -q -x -m gpu -k "${step#tests:}" 2>&1 | tail -15 ;;
     smoke)      timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
-    bench)      line bench_n1 bench.py --verify ;;
+    bench)      line bench_n1 bench.py --full ;;
     nfm)        line nfm_n1 bench_nfm.py --verify ;;
     fir)        line fir_n1 bench_fir.py --verify ;;
     fir50)      line fir50_n1 bench_fir.py --decimation 50 --tbw 0.005 --streams 64 --verify ;;

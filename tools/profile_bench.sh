@@ -21,7 +21,7 @@ grep '^{' $out/trace.log | tail -1 > $out/run/bench.json
 (cd $root && python tools/pmc_summary.py $out/run $tag "$kern" "$script $*" && cp profiles/${tag}_pmc_traffic.json gpurun_out/profiles_$tag/)
 ks=$(find $out/trace -name "*kernel_stats.csv" | head -1)
 [ -n "$ks" ] && python tools/tidy_kernel_stats.py $ks $root/gpurun_out/profiles_$tag/${tag}_kernel_stats.csv "$tag: rocprofv3 --kernel-trace --stats -- python $script $* --steps 120 --warmup 5 (durations in ns)"
-vflag="--verify"; [ "$script" = "bench.py" ] && vflag=""          # (bench.py verifies by default)
+vflag="--verify"; [ "$script" = "bench.py" ] && vflag="--full"    # (bench.py verifies and runs its CPU baseline with --full)
 timeout ${LINE_TIMEOUT:-240} python $script "$@" $vflag > $out/n1.log 2> $out/n1.err
 grep '^{' $out/n1.log | tail -1 > $root/gpurun_out/profiles_$tag/${tag}_n1.json
 head -6 $root/gpurun_out/profiles_$tag/${tag}_kernel_stats.csv | cut -c1-200
