@@ -122,6 +122,22 @@ def lib():
     L.csdr_amd_interp_force_generic.argtypes = [vp, i]
     L.csdr_amd_interp_kernel_name.restype = C.c_char_p; L.csdr_amd_interp_kernel_name.argtypes = [vp]
     L.csdr_amd_interp_destroy.argtypes = [vp]; L.csdr_amd_interp_destroy.restype = None
+    L.csdr_amd_psk31_create.restype = vp; L.csdr_amd_psk31_create.argtypes = [vp, vp, i, i, i]
+    L.csdr_amd_psk31_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, vp, vp]
+    L.csdr_amd_psk31_max_out.restype = ll; L.csdr_amd_psk31_max_out.argtypes = [vp, ll]
+    L.csdr_amd_psk31_reset.argtypes = [vp]
+    L.csdr_amd_psk31_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_psk31_get_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_psk31_set_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_psk31_set_lanes.argtypes = [vp, i]
+    L.csdr_amd_psk31_force_generic.argtypes = [vp, i]
+    L.csdr_amd_psk31_lanes.argtypes = [vp]
+    L.csdr_amd_psk31_kernel_name.restype = C.c_char_p; L.csdr_amd_psk31_kernel_name.argtypes = [vp]
+    L.csdr_amd_psk31_destroy.argtypes = [vp]; L.csdr_amd_psk31_destroy.restype = None
+    L.csdr_amd_simple_agc_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, C.c_float, C.c_float, C.c_float, vp]
+    L.csdr_amd_psk31_varicode_decoder_push.restype = C.c_char; L.csdr_amd_psk31_varicode_decoder_push.argtypes = [vp, C.c_ubyte]
+    L.csdr_amd_psk31_varicode_table.restype = None; L.csdr_amd_psk31_varicode_table.argtypes = [vp]
+    L.csdr_amd_debug_psk31_walk.restype = ll; L.csdr_amd_debug_psk31_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
@@ -469,6 +485,161 @@ class Resampler(_Resampling):
 
     def set_last_taps_delay(self, d):
         self.ctx.check(self.ctx.L.csdr_amd_resampler_set_last_taps_delay(self.h, int(d)), "resampler_set_last_taps_delay")
+
+
+class Psk31Params(C.Structure):
+    """csdr_amd_psk31_params"""
+    _fields_ = [("rate", C.c_float), ("reference", C.c_float), ("max_gain", C.c_float), ("algorithm", C.c_int), ("decimation", C.c_int),
+                ("loop_gain", C.c_float), ("max_error", C.c_float), ("use_q", C.c_int)]
+
+
+class Psk31Chan(C.Structure):
+    """csdr_amd_psk31_chan: one channel's state"""
+    _fields_ = [("gain", C.c_float), ("tail_len", C.c_int), ("correction_offset", C.c_int), ("base", C.c_uint), ("last_i", C.c_float),
+                ("last_q", C.c_float), ("varicode_shr", C.c_ulonglong)]
+
+
+PSK31_STAGES = {"agc": 0, "timing": 1, "dbpsk": 2, "varicode": 3}
+TIMING_ALGORITHMS = {"GARDNER": 0, "EARLYLATE": 1}
+
+
+def psk31_params(rate=0.001, reference=0.5, max_gain=65535.0, algorithm="GARDNER", decimation=256, loop_gain=0.5, max_error=2.0, use_q=True):
+    """the chain's parameters; the defaults are OpenWebRX's `simple_agc_cc 0.001 0.5 | timing_recovery_cc GARDNER 256 0.5 2 --add_q`"""
+    alg = TIMING_ALGORITHMS[algorithm] if isinstance(algorithm, str) else int(algorithm)
+    return Psk31Params(rate, reference, max_gain, alg, decimation, loop_gain, max_error, int(bool(use_q)))
+
+
+def _psk31_stage(s):
+    return PSK31_STAGES[s] if isinstance(s, str) else int(s)
+
+
+def _psk31_types(first, last):
+    return (np.uint8 if first == 3 else c64), (c64 if last <= 1 else np.uint8)
+
+
+def psk31_debug_walk(params, first="agc", last="varicode", x=None, cuts=(), state=None, with_extras=False):
+    """CPU run of k_psk31's walk for one channel (csdr_amd_debug_psk31_walk): x cut into calls of `cuts` items and the rest -> outputs
+    (and, with_extras, the timing errors and indexes).  state: a Psk31Chan carried in and out."""
+    f, l = _psk31_stage(first), _psk31_stage(last)
+    ti, to = _psk31_types(f, l)
+    x = np.ascontiguousarray(x, ti)
+    n = x.size
+    cap = n + 16 if (f >= 2 or l == 0) else 2 * n // max(params.decimation, 1) + 3 * len(cuts) + 16
+    out = np.zeros(cap, to)
+    err = np.zeros(cap, f32) if with_extras else None
+    idx = np.zeros(cap, np.uint32) if with_extras else None
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_psk31_walk(C.byref(params), f, l, _hp(x), n, _hp(cu) if cu.size else None, cu.size, _hp(out),
+                                        _hp(err) if with_extras else None, _hp(idx) if with_extras else None, C.byref(state) if state is not None else None)
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return (out[:k], err[:k], idx[:k]) if with_extras else out[:k]
+
+
+def psk31_varicode_table():
+    """[128, 2] int32: (code, length) of each character, as the library holds it"""
+    t = np.zeros(256, np.int32)
+    lib().csdr_amd_psk31_varicode_table(_hp(t))
+    return t.reshape(128, 2)
+
+
+class Psk31:
+    """csdr_amd_psk31: the BPSK31 receive chain (simple_agc_cc | timing_recovery_cc | dbpsk_decoder_c_u8 | psk31_varicode_decoder_u8_u8) for
+    n_channels channels, stages first..last ("agc", "timing", "dbpsk", "varicode"), state kept on the device between calls."""
+
+    def __init__(self, ctx, params=None, n_channels=1, first="agc", last="varicode"):
+        self.ctx, self.n_channels = ctx, n_channels
+        self.params = params if params is not None else psk31_params()
+        self.first, self.last = _psk31_stage(first), _psk31_stage(last)
+        self.in_dtype, self.out_dtype = _psk31_types(self.first, self.last)
+        self.h = ctx.L.csdr_amd_psk31_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def max_out(self, n_in):
+        return int(self.ctx.L.csdr_amd_psk31_max_out(self.h, n_in))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err=None, d_idx=None):
+        """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err, d_idx), "psk31_process")
+
+    def process(self, x, calls=None, with_extras=False):
+        """x: [n_channels, n] (or [n]) host items; calls: per-call item counts (default one call) -> a list of per-channel output arrays
+        (or one array for 1-D x); with_extras (last == "timing"): (symbols, errors, indexes) per channel."""
+        x = np.ascontiguousarray(x, self.in_dtype)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        eb = np.dtype(self.in_dtype).itemsize
+        ob = np.dtype(self.out_dtype).itemsize
+        di = self.ctx.upload(x)
+        opitch = max(self.max_out(max(calls) if calls else 0), 1)
+        do = self.ctx.alloc(ob * opitch * s + 256)
+        dc = self.ctx.alloc(4 * s + 256)
+        de = self.ctx.alloc(4 * opitch * s + 256) if with_extras else None
+        dx = self.ctx.alloc(4 * opitch * s + 256) if with_extras else None
+        outs = [[] for _ in range(s)]
+        errs = [[] for _ in range(s)]
+        idxs = [[] for _ in range(s)]
+        at = 0
+        for k in calls:
+            self.process_dev(di.at(eb * at), k, n, do.ptr, opitch, dc.ptr, de.ptr if de else None, dx.ptr if dx else None)
+            cnt = self.ctx.download(dc, np.int32, s)
+            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
+            if with_extras:
+                e = self.ctx.download(de, f32, opitch * s).reshape(s, opitch)
+                ix = self.ctx.download(dx, np.uint32, opitch * s).reshape(s, opitch)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c]].copy())
+                if with_extras:
+                    errs[c].append(e[c, :cnt[c]].copy()); idxs[c].append(ix[c, :cnt[c]].copy())
+            at += k
+        cat = lambda lst, dt: np.concatenate(lst) if lst else np.zeros(0, dt)
+        res = [cat(o, self.out_dtype) for o in outs]
+        if with_extras:
+            res = [(res[c], cat(errs[c], f32), cat(idxs[c], np.uint32)) for c in range(s)]
+        return res[0] if squeeze else res
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_reset(self.h), "psk31_reset")
+
+    def reset_channel(self, ch):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_reset_channel(self.h, int(ch)), "psk31_reset_channel")
+
+    def get_channel(self, ch):
+        st = Psk31Chan()
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_get_channel(self.h, int(ch), C.byref(st)), "psk31_get_channel")
+        return st
+
+    def set_channel(self, ch, st):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_set_channel(self.h, int(ch), C.byref(st)), "psk31_set_channel")
+
+    def set_lanes(self, lanes):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_set_lanes(self.h, int(lanes)), "psk31_set_lanes")
+
+    def lanes(self):
+        return int(self.ctx.L.csdr_amd_psk31_lanes(self.h))
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31_force_generic(self.h, int(on)), "psk31_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_psk31_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:                   # (after Context.close the object's context is gone: destroy would read it)
+            self.ctx.L.csdr_amd_psk31_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Interpolator(_Resampling):
@@ -832,6 +1003,27 @@ class Context:
         if taps is None:
             taps = rational_resampler_get_lowpass_f(self.firdes_filter_len(transition_bw), interpolation, decimation, window)
         return Resampler(self, interpolation, decimation, taps, n_streams, bufsize)
+
+    # ---- BPSK31 receive chain (psk31.hip)
+    def psk31(self, params=None, n_channels=1, first="agc", last="varicode"):
+        """A batched BPSK31 receive chain object (Psk31); params from psk31_params()"""
+        return Psk31(self, params, n_channels, first, last)
+
+    def simple_agc_cc(self, x, rate, reference=1.0, max_gain=65535.0, gain=None):
+        """simple_agc_cc (libcsdr.c:2201-2217) on [n_streams, n] (or [n]) complex samples; gain: per-stream starting gain (default 1, as the CLI)
+        -> (output, gain after the last sample)"""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        g = np.ascontiguousarray(np.ones(s, f32) if gain is None else np.broadcast_to(np.asarray(gain, f32), (s,)), f32)
+        di = self.upload(x); dg = self.upload(g)
+        do = self.alloc(8 * max(n, 1) * s + 256)
+        self.check(self.L.csdr_amd_simple_agc_cc(self.h, di.ptr, do.ptr, s, n, n, n, rate, reference, max_gain, dg.ptr), "simple_agc_cc")
+        y = self.download(do, c64, n * s).reshape(s, n)
+        g = self.download(dg, f32, s)
+        return (y[0].copy(), float(g[0])) if squeeze else (y.copy(), g.copy())
 
     def interpolator(self, interpolation, taps=None, n_streams=1, transition_bw=0.05, window="HAMMING", bufsize=None):
         """A batched fir_interpolate_cc object; taps default to firdes_lowpass_f(firdes_filter_len(transition_bw), 0.5 / I, window) as csdr.c:1212 designs them."""

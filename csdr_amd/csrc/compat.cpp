@@ -330,6 +330,104 @@ void fractional_decimator_ff(float *in, float *out, int n, fractional_decimator_
     csdr_amd_fracdec_destroy(fd);
 }
 
+// ------------------------------------------------------------------ BPSK31 receive (psk31.hip)
+void simple_agc_cc(complexf *in, complexf *out, int n, float rate, float reference, float max_gain, float *current_gain)
+{   // libcsdr.c:2201-2217
+    if (n <= 0) return;
+    complexf *din = stage_in<complexf>(4, in, n); complexf *dout = stage_out<complexf>(5, n);
+    float *dg = stage_in<float>(6, current_gain, 1);
+    MUST(csdr_amd_simple_agc_cc(ctx(), (const csdr_complexf *)din, (csdr_complexf *)dout, 1, n, n, n, rate, reference, max_gain, dg));
+    fetch(out, dout, n);
+    fetch(current_gain, dg, 1);
+}
+
+timing_recovery_state_t timing_recovery_init(timing_recovery_algorithm_t algorithm, int decimation_rate, int use_q, float loop_gain, float max_error,
+                                             int debug_every_nth, char *debug_writefiles_path)
+{   // libcsdr.c:1955-1970
+    timing_recovery_state_t t;
+    memset(&t, 0, sizeof t);
+    t.algorithm = algorithm; t.decimation_rate = decimation_rate; t.use_q = use_q; t.debug_phase = debug_every_nth; t.debug_every_nth = debug_every_nth;
+    t.debug_writefiles_path = debug_writefiles_path; t.last_correction_offset = 0; t.earlylate_ratio = 0.25f; t.loop_gain = loop_gain; t.max_error = max_error;
+    return t;
+}
+
+// One call = a fresh one-channel timing-only object whose correction_offset is the state's: it consumes up to the reference's input_processed and keeps the rest
+void timing_recovery_cc(complexf *in, complexf *out, int n, float *timing_error, int *sampled_indexes, timing_recovery_state_t *state)
+{   // libcsdr.c:1977-2075
+    if (state->debug_every_nth >= 0) { fprintf(stderr, "libcsdr_amd: timing_recovery_cc: debug_every_nth >= 0 (Octave plots) is not supported\n"); abort(); }
+    csdr_amd_psk31_params pr; memset(&pr, 0, sizeof pr);
+    pr.algorithm = (int)state->algorithm; pr.decimation = state->decimation_rate; pr.loop_gain = state->loop_gain; pr.max_error = state->max_error; pr.use_q = state->use_q;
+    // one object per thread, kept while the parameters stay the same: a client calls this once per buffer
+    struct TrCache { csdr_amd_psk31 *p = nullptr; csdr_amd_psk31_params pr; ~TrCache() { if (p && (long)syscall(SYS_gettid) != (long)getpid()) csdr_amd_psk31_destroy(p); } };
+    static thread_local TrCache cache;
+    if (!cache.p || memcmp(&cache.pr, &pr, sizeof pr)) {
+        if (cache.p) csdr_amd_psk31_destroy(cache.p);
+        cache.p = csdr_amd_psk31_create(ctx(), &pr, 1, CSDR_AMD_PSK31_TIMING, CSDR_AMD_PSK31_TIMING);
+        if (!cache.p) die("timing_recovery_cc", -3);
+        cache.pr = pr;
+    }
+    csdr_amd_psk31 *p = cache.p;
+    csdr_amd_psk31_chan st; memset(&st, 0, sizeof st);
+    st.correction_offset = state->last_correction_offset;
+    MUST(csdr_amd_psk31_set_channel(p, 0, &st));
+    const long long mo = csdr_amd_psk31_max_out(p, n > 0 ? n : 0);
+    complexf *din = stage_in<complexf>(4, in, n > 0 ? n : 0); complexf *dout = stage_out<complexf>(5, (size_t)mo);
+    float *derr = stage_out<float>(6, (size_t)mo); unsigned *didx = stage_out<unsigned>(7, (size_t)mo + 16);
+    int *dcnt = (int *)(didx + mo);
+    MUST(csdr_amd_psk31_process(p, din, n > 0 ? n : 0, n > 0 ? n : 1, dout, (size_t)mo, dcnt, derr, didx));
+    int k = 0; fetch(&k, dcnt, 1);
+    MUST(csdr_amd_psk31_get_channel(p, 0, &st));
+    if (k) {
+        fetch(out, dout, (size_t)k);
+        if (timing_error) fetch(timing_error, derr, (size_t)k);
+        if (sampled_indexes) fetch((unsigned *)sampled_indexes, didx, (size_t)k);
+    }
+    state->input_processed = (int)st.base; state->output_size = k; state->last_correction_offset = st.correction_offset;
+}
+
+timing_recovery_algorithm_t timing_recovery_get_algorithm_from_string(char *input)
+{   // libcsdr.c:2080-2086
+    if (!strcmp(input, "GARDNER")) return TIMING_RECOVERY_ALGORITHM_GARDNER;
+    if (!strcmp(input, "EARLYLATE")) return TIMING_RECOVERY_ALGORITHM_EARLYLATE;
+    return TIMING_RECOVERY_ALGORITHM_DEFAULT;
+}
+
+char *timing_recovery_get_string_from_algorithm(timing_recovery_algorithm_t algorithm)
+{   // libcsdr.c:2090-2096
+    if (algorithm == TIMING_RECOVERY_ALGORITHM_GARDNER) return (char *)"GARDNER";
+    if (algorithm == TIMING_RECOVERY_ALGORITHM_EARLYLATE) return (char *)"EARLYLATE";
+    return (char *)"INVALID";
+}
+
+// the reference's function-level static last_input: one per process, its calls serialised
+static std::mutex g_dbpsk_mu;
+static csdr_amd_psk31_chan g_dbpsk_last;
+void dbpsk_decoder_c_u8(complexf *in, unsigned char *out, int n)
+{   // libcsdr.c:2319-2333
+    if (n <= 0) return;
+    std::lock_guard<std::mutex> lk(g_dbpsk_mu);
+    // one object per thread (on that thread's context), kept between calls; last_input itself is the process-wide g_dbpsk_last
+    struct DbCache { csdr_amd_psk31 *p = nullptr; ~DbCache() { if (p && (long)syscall(SYS_gettid) != (long)getpid()) csdr_amd_psk31_destroy(p); } };
+    static thread_local DbCache cache;
+    if (!cache.p) {
+        csdr_amd_psk31_params pr; memset(&pr, 0, sizeof pr);
+        cache.p = csdr_amd_psk31_create(ctx(), &pr, 1, CSDR_AMD_PSK31_DBPSK, CSDR_AMD_PSK31_DBPSK);
+        if (!cache.p) die("dbpsk_decoder_c_u8", -3);
+    }
+    csdr_amd_psk31 *p = cache.p;
+    csdr_amd_psk31_chan st; memset(&st, 0, sizeof st); st.last_i = g_dbpsk_last.last_i; st.last_q = g_dbpsk_last.last_q;
+    MUST(csdr_amd_psk31_set_channel(p, 0, &st));
+    complexf *din = stage_in<complexf>(4, in, n); unsigned char *dout = stage_out<unsigned char>(5, n); int *dcnt = stage_out<int>(6, 1);
+    MUST(csdr_amd_psk31_process(p, din, n, n, dout, n, dcnt, nullptr, nullptr));
+    fetch(out, dout, n);
+    MUST(csdr_amd_psk31_get_channel(p, 0, &g_dbpsk_last));
+}
+
+char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char symbol)
+{   // libcsdr.c:1536-1549, on the host
+    return csdr_amd_psk31_varicode_decoder_push(status_shr, symbol);
+}
+
 // One call of each FIR resampler = a fresh batch object fed the whole block once (resampler.hip).
 rational_resampler_ff_t rational_resampler_ff(float *in, float *out, int n, int interpolation, int decimation, float *taps, int taps_length, int last_taps_delay)
 {

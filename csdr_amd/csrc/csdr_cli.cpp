@@ -253,6 +253,35 @@ struct Resample : Stage {   // csdr.c:1409-1460: rational_resampler_ff over the_
     }
 };
 
+struct Psk31 : Stage {   // simple_agc_cc csdr.c:2902-2930 | timing_recovery_cc csdr.c:2573-2648 | dbpsk_decoder_c_u8 csdr.c:3256-3268 | psk31_varicode_decoder_u8_u8
+                        // csdr.c:2418-2431: one object for a consecutive run of them (`chain` fuses the run); the state lives on the device
+    csdr_amd_psk31 *p; int first, last, extra, D; int *d_count; float *d_ex; size_t ex_cap;
+    Psk31(csdr_amd_ctx *c, const csdr_amd_psk31_params &pr, int f, int l, int ex) : first(f), last(l), extra(ex), D(pr.decimation), d_ex(nullptr), ex_cap(0)
+    {
+        p = csdr_amd_psk31_create(c, &pr, 1, f, l); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = f == CSDR_AMD_PSK31_VARICODE ? 1 : 8;
+        out_elem = l <= CSDR_AMD_PSK31_TIMING ? (extra ? 4 : 8) : 1;
+        d_count = (int *)csdr_amd_malloc(c, 64); if (!d_count) die("malloc");
+        ctx = c;
+    }
+    ~Psk31() { csdr_amd_psk31_destroy(p); csdr_amd_free(ctx, d_count); if (d_ex) csdr_amd_free(ctx, d_ex); }
+    csdr_amd_ctx *ctx;
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_psk31_max_out(p, (long long)n) + 16; }
+    int next_bufsize(int b) override { return (first <= CSDR_AMD_PSK31_TIMING && last >= CSDR_AMD_PSK31_TIMING) ? b / D : b; }     // csdr.c:2620
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        void *out = o; float *err = nullptr; unsigned *idx = nullptr;
+        if (extra) {                                                   // --output_error / --output_indexes: the symbols go to a scratch buffer
+            if (cap > ex_cap) { if (d_ex) csdr_amd_free(c, d_ex); ex_cap = cap + 64; d_ex = (float *)csdr_amd_malloc(c, 8 * ex_cap); if (!d_ex) die("malloc"); }
+            out = d_ex; if (extra == 1) err = (float *)o; else idx = (unsigned *)o;
+        }
+        MUST(csdr_amd_psk31_process(p, i, (long long)n, n, out, cap, d_count, err, idx));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count, sizeof k));
+        return k;
+    }
+};
+
 struct Interp : Stage {   // csdr.c:1179-1232: fir_interpolate_cc over the_bufsize windows, the first over a buffer of zeros
     csdr_amd_interp *p; int I;
     Interp(csdr_amd_ctx *c, int factor, float tbw, int window, int the_bufsize) : I(factor)
@@ -1541,8 +1570,63 @@ int run_waterfall_bank(csdr_amd_ctx *c, int argc, char **argv)
 
 // Build the operator for one command line.  `block` = the largest input this stage will be handed in one call.
 // ctl: opened when the command line carries --fifo/--fd (single-command mode only).  Returns nullptr after printing why.
+// the BPSK31 commands: stage index, parameters into *pr, *extra = 1 / 2 for --output_error / --output_indexes; -1 (message given) on bad syntax
+int parse_psk31(int argc, char **argv, csdr_amd_psk31_params *pr, int *extra)
+{
+    const std::string cmd = argv[1];
+    if (cmd == "simple_agc_cc") {                                                   // csdr.c:2902-2921
+        if (argc <= 2) { badsyntax("need required parameter (rate)"); return -1; }
+        sscanf(argv[2], "%f", &pr->rate);
+        if (pr->rate <= 0) { badsyntax("rate should be > 0"); return -1; }
+        pr->reference = 1.f; if (argc > 3) sscanf(argv[3], "%f", &pr->reference);
+        if (pr->reference <= 0) { badsyntax("reference should be > 0"); return -1; }
+        pr->max_gain = 65535.f; if (argc > 4) sscanf(argv[4], "%f", &pr->max_gain);
+        if (pr->max_gain <= 0) { badsyntax("max_gain should be > 0"); return -1; }
+        return CSDR_AMD_PSK31_AGC;
+    }
+    if (cmd == "timing_recovery_cc") {                                              // csdr.c:2573-2618
+        if (argc <= 2) { badsyntax("need required parameter (algorithm)"); return -1; }
+        pr->algorithm = !strcmp(argv[2], "EARLYLATE") ? 1 : 0;                      // timing_recovery_get_algorithm_from_string: anything else is GARDNER
+        if (argc <= 3) { badsyntax("need required parameter (decimation factor)"); return -1; }
+        int d = 0; sscanf(argv[3], "%d", &d);
+        if (d <= 4 || (d & 3)) { badsyntax("decimation factor should be a positive integer divisible by 4"); return -1; }
+        pr->decimation = d;
+        pr->loop_gain = 0.5f; if (argc > 4) sscanf(argv[4], "%f", &pr->loop_gain);
+        pr->max_error = 2.f; if (argc > 5) sscanf(argv[5], "%f", &pr->max_error);
+        const int add_q = argc >= 7 && !strcmp(argv[6], "--add_q");
+        pr->use_q = add_q;
+        if (argc >= 7 + add_q && !strncmp(argv[6 + add_q], "--octave", 8)) { badsyntax("--octave / --octave_save (debug plots) are not supported"); return -1; }
+        *extra = 0;
+        if (argc >= 7 + add_q && !strcmp(argv[6 + add_q], "--output_error")) *extra = 1;
+        if (argc >= 7 + add_q && !strcmp(argv[6 + add_q], "--output_indexes")) *extra = 2;
+        return CSDR_AMD_PSK31_TIMING;
+    }
+    if (cmd == "dbpsk_decoder_c_u8") return CSDR_AMD_PSK31_DBPSK;
+    if (cmd == "psk31_varicode_decoder_u8_u8") return CSDR_AMD_PSK31_VARICODE;
+    return -2;
+}
+
 Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control *ctl, int the_bufsize)
 {
+    if (!strcmp(argv[1], "psk31_rx")) {                                             // `chain`'s fused BPSK31 run: argv[2..] are its commands, one per argument
+        csdr_amd_psk31_params pr; memset(&pr, 0, sizeof pr);
+        int first = -1, last = -1, extra = 0;
+        for (int k = 2; k < argc; k++) {
+            std::vector<std::string> t; { std::string w; for (const char *q = argv[k];; q++) { if (!*q || *q == ' ') { if (!w.empty()) t.push_back(w); w.clear(); if (!*q) break; } else w += *q; } }
+            std::vector<char *> av = {argv[0]}; for (auto &w : t) av.push_back(const_cast<char *>(w.c_str()));
+            const int st = parse_psk31((int)av.size(), av.data(), &pr, &extra);
+            if (st < 0) return nullptr;
+            if (first < 0) first = st;
+            last = st;
+        }
+        return new Psk31(c, pr, first, last, last == CSDR_AMD_PSK31_TIMING ? extra : 0);
+    }
+    {
+        csdr_amd_psk31_params pr; memset(&pr, 0, sizeof pr); int extra = 0;
+        const int st = parse_psk31(argc, argv, &pr, &extra);
+        if (st == -1) return nullptr;
+        if (st >= 0) return new Psk31(c, pr, st, st, extra);
+    }
     g_cmd = argv[1];
     const std::string cmd = argv[1];
     const bool has_ctl = ctl && ctl->open_from(argc, argv);
@@ -1811,6 +1895,29 @@ bool is_waterfall_pattern(const std::vector<std::vector<std::string>> &cmds, std
 }
 
 // convert_u8_f | shift_addition_cc r | fir_decimate_cc D [tbw [window]] at the head of a chain -> one ddc_u8_cc command
+// consecutive runs (two or more) of simple_agc_cc -> timing_recovery_cc -> dbpsk_decoder_c_u8 -> psk31_varicode_decoder_u8_u8, in this order, become one
+// `psk31_rx` object that walks them in one launch
+bool fuse_psk31(std::vector<std::vector<std::string>> &cmds)
+{
+    static const char *order[4] = {"simple_agc_cc", "timing_recovery_cc", "dbpsk_decoder_c_u8", "psk31_varicode_decoder_u8_u8"};
+    auto stage_of = [&](const std::vector<std::string> &c) { for (int k = 0; k < 4; k++) if (c.size() > 1 && c[1] == order[k]) return k; return -1; };
+    bool any = false;
+    for (size_t a = 0; a < cmds.size(); a++) {
+        int s = stage_of(cmds[a]);
+        if (s < 0) continue;
+        size_t b = a + 1;
+        while (b < cmds.size() && stage_of(cmds[b]) == s + (int)(b - a)) b++;
+        if (b - a < 2) continue;
+        std::vector<std::string> fused = {"csdr", "psk31_rx"};
+        for (size_t k = a; k < b; k++) { std::string w; for (size_t t = 1; t < cmds[k].size(); t++) w += (t > 1 ? " " : "") + cmds[k][t]; fused.push_back(w); }
+        fprintf(stderr, "csdr chain: %s .. %s recognised -> one fused BPSK31 object (k_psk31)\n", order[s], order[s + (int)(b - a) - 1]);
+        cmds.erase(cmds.begin() + a, cmds.begin() + b);
+        cmds.insert(cmds.begin() + a, fused);
+        any = true;
+    }
+    return any;
+}
+
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
 {
     if (cmds.size() < 3 || cmds[0].size() != 2 || cmds[0][1] != "convert_u8_f") return false;
@@ -1838,6 +1945,7 @@ int main(int argc, char **argv)
                         "convert_f_s24 convert_s24_f shift_math_cc shift_addition_cc shift_addition_fc shift_table_cc shift_addfast_cc shift_unroll_cc "
                         "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff rational_resampler_ff suboptimal_rational_resampler_ff fir_interpolate_cc deemphasis_wfm_ff "
                         "deemphasis_nfm_ff limit_ff fastagc_ff bandpass_fir_fft_cc fastddc_fwd_cc fastddc_inv_cc firdes_lowpass_f firdes_bandpass_c "
+                        "simple_agc_cc timing_recovery_cc (needs |mu| * max_error <= 1) dbpsk_decoder_c_u8 psk31_varicode_decoder_u8_u8 "
                         "amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
                         "waterfall_u8 / waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>, "
@@ -1912,6 +2020,7 @@ int main(int argc, char **argv)
         } else if (fuse_front_end(cmds)) {
             fprintf(stderr, "csdr chain: convert_u8_f | shift_addition_cc | fir_decimate_cc recognised -> fused matrix-core front end\n");
         }
+        fuse_psk31(cmds);
     } else {
         cmds.assign(1, std::vector<std::string>(argv, argv + argc));
     }

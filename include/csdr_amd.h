@@ -204,6 +204,62 @@ void csdr_amd_rational_resampler_get_lowpass_f(float *output, int output_size, i
  * (libcsdr.c:621-626).  The kernels' tables are built from the same recurrence. */
 int  csdr_amd_debug_resampler_schedule(int interpolation, int decimation, int taps_length, int last_taps_delay, int n, int *out);
 
+/* ------------------------------------------------------------------ BPSK31 receive chain (psk31.hip)
+ * simple_agc_cc libcsdr.c:2201-2217 | timing_recovery_cc libcsdr.c:1977-2075 | dbpsk_decoder_c_u8 libcsdr.c:2319-2333 | psk31_varicode_decoder_u8_u8 csdr.c:2418-2431,
+ * for n_channels channels, all with the same parameters.  The object runs the stages first_stage .. last_stage (CSDR_AMD_PSK31_*) in one launch and keeps each
+ * channel's state on the device: the gain (starting at 1, as the CLI), the samples timing recovery has not consumed yet (< 3 D/2 + 1), correction_offset,
+ * the last symbol (starting at 0 + 0i) and the varicode shift register.  The output equals the reference functions applied once to the whole stream since the
+ * last reset, however the stream is cut into calls (0- and 1-sample calls included) and whatever a channel's position in the batch.
+ * params: rate, reference, max_gain > 0 (AGC); algorithm 0 = GARDNER, 1 = EARLYLATE; decimation > 4 and a multiple of 4; |loop_gain| * max_error <= 1
+ * (OpenWebRX: 0.5 * 2); use_q = the CLI's --add_q.
+ * process: n_in new items per channel (complexf, or one byte per bit when first_stage is VARICODE), in_pitch items apart; out: complexf (last_stage AGC or
+ * TIMING) or bytes (DBPSK: one bit per byte; VARICODE: the decoded characters, NUL and "no character" left out), out_pitch items apart, at least
+ * max_out(n_in); counts (device, n_channels ints) receives each channel's output count.  err / idx (device, may be NULL; last_stage TIMING only, out_pitch
+ * apart): the unclamped timing error and the absolute sample index (unsigned, wrapping, as --output_error / --output_indexes) of each symbol.
+ * Asynchronous on the context's stream.  kernel_name: "k_psk31_tiled" (the fused range: first_stage AGC, last_stage TIMING or later, the ring of
+ * 3 D/2 + 66 samples per channel within 63 KiB of LDS) or "k_psk31" (every other case); force_generic(1) takes k_psk31 always.
+ * set_lanes(n): channels per wave (0: automatic; k_psk31_tiled takes at most 16; every choice gives the same bits).
+ * Timing recovery needs |loop_gain| * max_error <= 1, so that a symbol moves on by D/2 .. 3D/2 samples (the reference accepts more; its loop can then
+ * step backwards and read before its buffer).
+ * get_channel / set_channel: one channel's state (synchronous). */
+enum { CSDR_AMD_PSK31_AGC = 0, CSDR_AMD_PSK31_TIMING = 1, CSDR_AMD_PSK31_DBPSK = 2, CSDR_AMD_PSK31_VARICODE = 3 };
+typedef struct csdr_amd_psk31_params {
+    float rate, reference, max_gain;     /* simple_agc_cc */
+    int algorithm, decimation;           /* timing_recovery_cc */
+    float loop_gain, max_error;
+    int use_q;
+} csdr_amd_psk31_params;
+typedef struct csdr_amd_psk31_chan {
+    float gain;                          /* first_stage AGC: the gain in front of the unconsumed tail (AGC alone: after the last sample) */
+    int tail_len, correction_offset;
+    unsigned base;                       /* absolute index of the tail's first sample */
+    float last_i, last_q;                /* dbpsk_decoder_c_u8's last_input */
+    unsigned long long varicode_shr;
+} csdr_amd_psk31_chan;
+typedef struct csdr_amd_psk31 csdr_amd_psk31;
+csdr_amd_psk31 *csdr_amd_psk31_create(csdr_amd_ctx *ctx, const csdr_amd_psk31_params *params, int n_channels, int first_stage, int last_stage);
+int  csdr_amd_psk31_process(csdr_amd_psk31 *p, const void *in, long long n_in, size_t in_pitch, void *out, size_t out_pitch, int *counts, float *err, unsigned *idx);
+long long csdr_amd_psk31_max_out(const csdr_amd_psk31 *p, long long n_in);
+int  csdr_amd_psk31_reset(csdr_amd_psk31 *p);
+int  csdr_amd_psk31_reset_channel(csdr_amd_psk31 *p, int channel);
+int  csdr_amd_psk31_get_channel(csdr_amd_psk31 *p, int channel, csdr_amd_psk31_chan *state);
+int  csdr_amd_psk31_set_channel(csdr_amd_psk31 *p, int channel, const csdr_amd_psk31_chan *state);
+int  csdr_amd_psk31_set_lanes(csdr_amd_psk31 *p, int lanes);
+int  csdr_amd_psk31_force_generic(csdr_amd_psk31 *p, int on);
+int  csdr_amd_psk31_lanes(const csdr_amd_psk31 *p);
+const char *csdr_amd_psk31_kernel_name(const csdr_amd_psk31 *p);
+void csdr_amd_psk31_destroy(csdr_amd_psk31 *p);
+/* simple_agc_cc libcsdr.c:2201-2217 on n_streams streams of n samples; gain_io (device, n_streams floats) carries each stream's gain in and out */
+int  csdr_amd_simple_agc_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                            float rate, float reference, float max_gain, float *gain_io);
+/* psk31_varicode_decoder_push libcsdr.c:1536-1549 (host, one bit per call) and the varicode table: out[2a], out[2a + 1] = code, length of character a < 128 */
+char csdr_amd_psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char symbol);
+void csdr_amd_psk31_varicode_table(int *out);
+/* CPU run of k_psk31's walk (the same step functions) for one channel, the n items cut into calls of cuts[0..n_cuts) items and the rest; outputs concatenated.
+ * state_io: the channel state in and out (NULL: a fresh channel).  Returns the output count. */
+long long csdr_amd_debug_psk31_walk(const csdr_amd_psk31_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
+                                    int n_cuts, void *out, float *err, unsigned *idx, csdr_amd_psk31_chan *state_io);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

@@ -80,6 +80,34 @@ void fractional_decimator_ff(float *input, float *output, int input_size, fracti
 int fir_interpolate_cc(complexf *input, complexf *output, int input_size, int interpolation, float *taps, int taps_length);   /* libcsdr.h:105 */
 typedef struct rational_resampler_ff_s { int input_processed; int output_size; int last_taps_delay; } rational_resampler_ff_t;   /* libcsdr.h:132-137 */
 rational_resampler_ff_t rational_resampler_ff(float *input, float *output, int input_size, int interpolation, int decimation, float *taps, int taps_length, int last_taps_delay);
+/* BPSK31 receive, libcsdr.h:314-336 and libcsdr.c:1536-1549, 1977-2075, 2201-2217, 2319-2333.  debug_every_nth >= 0 (the Octave plots) is not supported:
+ * timing_recovery_cc aborts on it.  dbpsk_decoder_c_u8 keeps ONE process-wide last_input, like the reference's function-level static: concurrent callers
+ * share it (calls are serialised).  psk31_varicode_decoder_push runs on the host (one bit per call).
+ * timing_recovery_cc needs |loop_gain| * max_error <= 1 (a symbol then moves on by D/2 .. 3D/2 samples; beyond that the reference's loop can step
+ * backwards and read before its buffer): outside it the call prints the reason and aborts, like debug_every_nth >= 0. */
+typedef enum timing_recovery_algorithm_e { TIMING_RECOVERY_ALGORITHM_GARDNER, TIMING_RECOVERY_ALGORITHM_EARLYLATE } timing_recovery_algorithm_t;
+#define TIMING_RECOVERY_ALGORITHM_DEFAULT TIMING_RECOVERY_ALGORITHM_GARDNER
+typedef struct timing_recovery_state_s {
+    timing_recovery_algorithm_t algorithm;
+    int decimation_rate;
+    int output_size;
+    int input_processed;
+    int use_q;
+    int debug_phase;
+    int debug_every_nth;
+    char *debug_writefiles_path;
+    int last_correction_offset;
+    float earlylate_ratio;
+    float loop_gain;
+    float max_error;
+} timing_recovery_state_t;
+timing_recovery_state_t timing_recovery_init(timing_recovery_algorithm_t algorithm, int decimation_rate, int use_q, float loop_gain, float max_error, int debug_every_nth, char *debug_writefiles_path);
+void timing_recovery_cc(complexf *input, complexf *output, int input_size, float *timing_error, int *sampled_indexes, timing_recovery_state_t *state);
+timing_recovery_algorithm_t timing_recovery_get_algorithm_from_string(char *input);
+char *timing_recovery_get_string_from_algorithm(timing_recovery_algorithm_t algorithm);
+void simple_agc_cc(complexf *input, complexf *output, int input_size, float rate, float reference, float max_gain, float *current_gain);
+void dbpsk_decoder_c_u8(complexf *input, unsigned char *output, int input_size);
+char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char symbol);
 void rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, window_t window);
 
 typedef struct shift_table_data_s { float *table; int table_size; } shift_table_data_t;     /* libcsdr.h:180-184 */
