@@ -240,6 +240,12 @@ static bool poly_cfg(int D, int ntaps, size_t elem, PolyCfg &c)
     }
     return false;
 }
+// the template instance a launch_poly call selects (csdr_amd_fir_last_instance / csdr_amd_fir_ff_last_instance)
+static const char *poly_instance(const PolyCfg &g)
+{
+    if (g.R == 4) return g.U == 24 ? "k_fir_poly<R4,U24>" : "k_fir_poly<R4,U44>";
+    return g.U == 24 ? "k_fir_poly<R2,U24>" : "k_fir_poly<R2,U44>";
+}
 template <typename T>
 static void launch_poly(csdr_amd_ctx *c, const PolyCfg &g, const T *in, T *out, int n_out, int n_streams, size_t in_pitch, size_t out_pitch,
                         int D, const float *taps, int ntaps)
@@ -473,11 +479,16 @@ static int pick_tile(int D, int ntaps, int floats_per_sample, int n_out)
 }
 
 static thread_local const char *g_fir_last_kernel = "";
+static thread_local const char *g_fir_last_instance = "";
+static thread_local const char *g_fir_ff_last_instance = "";
 
 extern "C" {
 
 /* which kernel the calling thread's last csdr_amd_fir_decimate_cc launched (bench_fir.py's roofline.kernel; "" before the first call) */
 const char *csdr_amd_fir_last_kernel(void) { return g_fir_last_kernel; }
+/* the template instance behind it (k_fir_poly<R2,U24>, k_fir_mfma<2,32>, k_fir_mfma3<12>, k_fir_generic), and the same for csdr_amd_fir_ff */
+const char *csdr_amd_fir_last_instance(void) { return g_fir_last_instance; }
+const char *csdr_amd_fir_ff_last_instance(void) { return g_fir_ff_last_instance; }
 
 int csdr_amd_fir_decimate_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_complexf *out, int n_streams, int input_size,
                              size_t in_pitch, size_t out_pitch, int decimation, const float *taps, int taps_length)
@@ -494,6 +505,7 @@ int csdr_amd_fir_decimate_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_comp
         launch_poly<float2>(c, g, (const float2 *)in, (float2 *)out, n_out, n_streams, in_pitch, out_pitch, decimation, taps, taps_length);
         CSDR_LAUNCH_CHECK();
         g_fir_last_kernel = "k_fir_poly";
+        g_fir_last_instance = poly_instance(g);
         return n_out;
     }
     {   // long filters: banded product on the fp32 matrix cores (NT groups of 16 outputs per workgroup, window <= ~64 KiB)
@@ -507,7 +519,7 @@ int csdr_amd_fir_decimate_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_comp
             const dim3 grid(cdiv(n_tiles, tpw), (unsigned)n_streams);
 #define FIR_MFMA(NTV, NSV) do { if (lds > 64 * 1024) { const int arc = lds_attr_once((const void *)k_fir_mfma<NTV, NSV>, lds); if (arc) return arc; }                 \
             hipLaunchKernelGGL((k_fir_mfma<NTV, NSV>), grid, dim3(256), lds, c->stream, (const float2 *)in, (float2 *)out, n_out, input_size, in_pitch, out_pitch,   \
-                               decimation, taps, taps_length, tpw); } while (0)
+                               decimation, taps, taps_length, tpw); g_fir_last_instance = "k_fir_mfma<" #NTV "," #NSV ">"; } while (0)
 #define FIR_MFMA_NS(NTV) do { if (ns <= 8) FIR_MFMA(NTV, 8); else if (ns <= 16) FIR_MFMA(NTV, 16); else FIR_MFMA(NTV, 32); } while (0)
             const int nblk = (steps + 3) / 4;
             // k_fir_mfma3: the window by LDS-DMA.  Needs: 8 outputs groups, <= 14 blocks per wave, the window + slack inside 64 KiB, 16-byte aligned stream rows
@@ -520,7 +532,7 @@ int csdr_amd_fir_decimate_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_comp
                     // slower, profiles/r5_notes.md; it is no longer instantiated.)
 #define FIR_MFMA3(MB, NWV, DBV, LDSV) do { const int arc = lds_attr_once((const void *)k_fir_mfma3<MB, NWV, DBV>, LDSV); if (arc) return arc;                                                      \
                     hipLaunchKernelGGL((k_fir_mfma3<MB, NWV, DBV>), grid, dim3(64 * NWV), LDSV, c->stream, (const float2 *)in, (float2 *)out, n_out, input_size, in_pitch, out_pitch,        \
-                                       decimation, taps, taps_length, tpw); } while (0)
+                                       decimation, taps, taps_length, tpw); g_fir_last_instance = "k_fir_mfma3<" #MB ">"; } while (0)
                     const int need = (nblk + 7) / 8;                 // the largest wave share: wave w takes blocks [w nblk / 8, (w + 1) nblk / 8)
                     if (need <= 8) FIR_MFMA3(8, 8, false, lds3); else if (need <= 10) FIR_MFMA3(10, 8, false, lds3); else if (need <= 12) FIR_MFMA3(12, 8, false, lds3); else if (need <= 13) FIR_MFMA3(13, 8, false, lds3); else FIR_MFMA3(14, 8, false, lds3);
 #undef FIR_MFMA3
@@ -546,6 +558,7 @@ int csdr_amd_fir_decimate_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_comp
                        in_pitch, out_pitch, decimation, taps, taps_length);
     CSDR_LAUNCH_CHECK();
     g_fir_last_kernel = "k_fir_generic";
+    g_fir_last_instance = "k_fir_generic";
     return n_out;
 }
 
@@ -560,6 +573,7 @@ int csdr_amd_fir_ff(csdr_amd_ctx *c, const float *in, float *out, int n_streams,
     if (!force_generic && poly_cfg(1, taps_length, 4, g)) {
         launch_poly<float>(c, g, in, out, n_out, n_streams, in_pitch, out_pitch, 1, taps, taps_length);
         CSDR_LAUNCH_CHECK();
+        g_fir_ff_last_instance = poly_instance(g);
         return n_out;
     }
     // window for n outputs of the generic kernel is (outs-1)*1 + ntaps, exactly what those outputs read
@@ -568,6 +582,7 @@ int csdr_amd_fir_ff(csdr_amd_ctx *c, const float *in, float *out, int n_streams,
     dim3 grid(cdiv(n_out, to), (unsigned)n_streams);
     hipLaunchKernelGGL((k_fir_generic<false>), grid, dim3(256), win_bytes + 16, c->stream, in, out, n_out, to, in_pitch, out_pitch, 1, taps, taps_length);
     CSDR_LAUNCH_CHECK();
+    g_fir_ff_last_instance = "k_fir_generic";
     return n_out;
 }
 

@@ -123,6 +123,10 @@ void csdr_amd_shift_addition_init(float rate, float *out3);
 /* the kernel the calling thread's last csdr_amd_fir_decimate_cc launched: k_fir_poly (short filters), k_fir_mfma3 / k_fir_mfma (long filters on the fp32 matrix cores),
  * k_fir_generic */
 const char *csdr_amd_fir_last_kernel(void);
+/* the template instance behind it: k_fir_poly<R4,U24> / <R4,U44> / <R2,U24> / <R2,U44>, k_fir_mfma<NT,NS>, k_fir_mfma3<MAXB>, k_fir_generic ("" before the first call) */
+const char *csdr_amd_fir_last_instance(void);
+/* the same for the calling thread's last csdr_amd_fir_ff: a k_fir_poly<R,U> instance or k_fir_generic */
+const char *csdr_amd_fir_ff_last_instance(void);
 int csdr_amd_fir_decimate_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out,
                              int n_streams, int input_size, size_t in_pitch, size_t out_pitch,
                              int decimation, const float *taps, int taps_length);

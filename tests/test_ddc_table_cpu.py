@@ -8,16 +8,31 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fir_reference
+
 f32 = np.float32
 
 
 @pytest.mark.parametrize("D,Lt,rate", [(50, 801, 0.11), (50, 801, -0.4321), (10, 79, -0.085), (20, 321, 0.3)])
 def test_ddc_tile_matches_direct_evaluation(port, D, Lt, rate):
+    worst, scale = _ddc_tile_worst(port.firdes_lowpass_f(Lt, 0.5 / D), D, rate)
+    assert worst < 1e-6 * max(scale, 1.0), worst                 # 23-bit weights, float D^e table and float partial sums
+
+
+@pytest.mark.parametrize("D,Lt,rate", [(50, 801, 0.11), (50, 801, -0.4321), (10, 79, -0.085), (20, 321, 0.3)])
+def test_ddc_tile_asymmetric_taps(D, Lt, rate):
+    """The same with random taps without symmetry, which would show reversed or mirrored tap indices in the weight table."""
+    worst, scale = _ddc_tile_worst(fir_reference.random_taps(Lt, D + Lt), D, rate)
+    assert worst < 1e-6 * max(scale, 1.0), worst
+
+
+def _ddc_tile_worst(taps, D, rate):
+    """(worst |tile output - direct double-precision evaluation|, sum |taps|) over every 16-sample tile position inside a chunk"""
+    Lt = taps.size
     import csdr_amd
     L = csdr_amd.lib()
     fn = L.csdr_amd_debug_ddc_mfma_tile
     fn.argtypes = [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
-    taps = port.firdes_lowpass_f(Lt, 0.5 / D)
     rng = np.random.default_rng(11)
     PI = f32(3.14159265358979323846)
     inc = f32(f32(f32(rate) * f32(2)) * PI)
@@ -40,7 +55,7 @@ def test_ddc_tile_matches_direct_evaluation(port, D, Lt, rate):
             y = np.sum(taps.astype(np.float64) * R * xc[D * o:D * o + Lt])
             got = complex(out[2 * o], out[2 * o + 1])
             worst = max(worst, abs(got - y))
-    assert worst < 1e-6 * max(scale, 1.0), worst                 # 23-bit weights, float D^e table and float partial sums
+    return worst, scale
 
 
 def test_ddc_unsupported_shapes():

@@ -6,18 +6,33 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fir_reference
+
 f32 = np.float32
 
 
 def test_seq_tile_matches_direct_evaluation(port):
     """The sequential kernel's phase-independent weight set: every window position inside a chunk (all chunk-boundary positions at 16-byte
     granularity) against the direct double-precision evaluation."""
+    worst = _seq_tile_worst(port.firdes_lowpass_f(79, 0.05))
+    assert worst < 1e-6, worst
+
+
+def test_seq_tile_asymmetric_taps():
+    """The same with random taps without symmetry, which would show reversed or mirrored tap indices in the weight table.  (/ 64, exact: a
+    unit-scale gain like the lowpass design's, which the absolute bound assumes.)"""
+    worst = _seq_tile_worst(fir_reference.random_taps(79, 79) / f32(64))
+    assert worst < 1e-6, worst
+
+
+def _seq_tile_worst(taps):
+    """worst |tile output - direct double-precision evaluation| of the 79 taps at D = 10, F = 5"""
     import csdr_amd
     L = csdr_amd.lib()
     fn = L.csdr_amd_debug_wfm_seq_tile
     fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     D, Lt, F, rate = 10, 79, 5, -0.085
-    taps = port.firdes_lowpass_f(Lt, 0.05)
+    assert taps.size == Lt
     rng = np.random.default_rng(6)
     PI = f32(3.14159265358979323846)
     inc = f32(f32(rate * 2) * PI)
@@ -41,4 +56,4 @@ def test_seq_tile_matches_direct_evaluation(port):
                 y = np.sum(taps.astype(np.float64) * R * xc[off:off + Lt])
                 got = complex(out[4 * q + 2 * which], out[4 * q + 2 * which + 1])
                 worst = max(worst, abs(got - y))
-    assert worst < 1e-6, worst
+    return worst
