@@ -138,6 +138,24 @@ def lib():
     L.csdr_amd_psk31_varicode_decoder_push.restype = C.c_char; L.csdr_amd_psk31_varicode_decoder_push.argtypes = [vp, C.c_ubyte]
     L.csdr_amd_psk31_varicode_table.restype = None; L.csdr_amd_psk31_varicode_table.argtypes = [vp]
     L.csdr_amd_debug_psk31_walk.restype = ll; L.csdr_amd_debug_psk31_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
+    L.csdr_amd_rtty_create.restype = vp; L.csdr_amd_rtty_create.argtypes = [vp, vp, i, i, i]
+    L.csdr_amd_rtty_process.argtypes = [vp, vp, ll, sz, vp, sz, vp]
+    L.csdr_amd_rtty_max_out.restype = ll; L.csdr_amd_rtty_max_out.argtypes = [vp, ll]
+    L.csdr_amd_rtty_reset.argtypes = [vp]
+    L.csdr_amd_rtty_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_rtty_force_generic.argtypes = [vp, i]
+    L.csdr_amd_rtty_kernel_name.restype = C.c_char_p; L.csdr_amd_rtty_kernel_name.argtypes = [vp]
+    L.csdr_amd_rtty_destroy.argtypes = [vp]; L.csdr_amd_rtty_destroy.restype = None
+    L.csdr_amd_bfsk_demod_cf.argtypes = [vp, vp, vp, i, ll, sz, sz, vp, vp, i, i]
+    L.csdr_amd_bfsk_last_kernel.restype = C.c_char_p; L.csdr_amd_bfsk_last_kernel.argtypes = []
+    L.csdr_amd_binary_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
+    L.csdr_amd_rtty_line_decoder_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, vp, vp]
+    L.csdr_amd_serial_line_decoder_f_u8.argtypes = [vp, vp, vp, i, i, sz, sz, C.c_float, i, C.c_float, C.c_float, vp, vp]
+    L.csdr_amd_rtty_baudot_decoder_lookup.restype = C.c_char; L.csdr_amd_rtty_baudot_decoder_lookup.argtypes = [vp, C.c_ubyte]
+    L.csdr_amd_rtty_baudot_decoder_push.restype = C.c_char; L.csdr_amd_rtty_baudot_decoder_push.argtypes = [vp, C.c_ubyte]
+    L.csdr_amd_firdes_add_peak_c.restype = None; L.csdr_amd_firdes_add_peak_c.argtypes = [vp, i, C.c_float, i, i, i]
+    L.csdr_amd_firdes_peak_c.restype = None; L.csdr_amd_firdes_peak_c.argtypes = [vp, i, C.c_float, i]
+    L.csdr_amd_debug_rtty_walk.restype = ll; L.csdr_amd_debug_rtty_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp]
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
@@ -644,6 +662,147 @@ class Psk31:
             pass
 
 
+class RttyParams(C.Structure):
+    """csdr_amd_rtty_params"""
+    _fields_ = [("spacing", C.c_float), ("filter_length", C.c_int), ("window", C.c_int), ("samples_per_bits", C.c_float), ("databits", C.c_int),
+                ("stopbits", C.c_float), ("bit_sampling_width_ratio", C.c_float), ("cli_bufsize", C.c_int)]
+
+
+class RttyPushState(C.Structure):
+    """csdr_amd_rtty_push_state: rtty_baudot_decoder_push's state (zeros: a fresh decoder)"""
+    _fields_ = [("fig_mode", C.c_int), ("character_received", C.c_int), ("shr", C.c_int), ("bit_cntr", C.c_int), ("state", C.c_int)]
+
+
+RTTY_STAGES = {"bfsk": 0, "serial": 1, "baudot": 2}
+
+
+def rtty_params(spacing=0.02125, filter_length=101, window=1024, samples_per_bits=176.0176, databits=5, stopbits=1.5, bit_sampling_width_ratio=0.4,
+                cli_bufsize=16384):
+    """the chain's parameters; the defaults are 45.45 Bd at 170 Hz shift and 8 kS/s: `bfsk_demod_cf 0.02125 101 | serial_line_decoder_f_u8 176.0176 5 1.5`"""
+    return RttyParams(spacing, filter_length, window, samples_per_bits, databits, stopbits, bit_sampling_width_ratio, cli_bufsize)
+
+
+def _rtty_stage(s):
+    return RTTY_STAGES[s] if isinstance(s, str) else int(s)
+
+
+def _rtty_types(params, first, last):
+    ti = c64 if first == 0 else (f32 if first == 1 else np.uint8)
+    if last == 0:
+        to = f32
+    elif last == 1:
+        to = np.uint8 if params.databits <= 8 else (np.uint16 if params.databits <= 16 else np.uint32)
+    else:
+        to = np.uint8
+    return ti, to
+
+
+def firdes_peak_c(length, rate, window="HAMMING"):
+    """firdes_peak_c (csdr.c:2932-2972 / firdes_add_peak_c libcsdr.c:2219-2257, add 0, normalize 1) -> complex64 taps"""
+    t = np.zeros(length, c64)
+    lib().csdr_amd_firdes_peak_c(_hp(t), int(length), float(rate), WINDOWS[window] if isinstance(window, str) else int(window))
+    return t
+
+
+def rtty_debug_walk(params, first="bfsk", last="baudot", x=None, cuts=()):
+    """CPU run of the object's walk for one channel (csdr_amd_debug_rtty_walk): x cut into calls of `cuts` items and the rest -> outputs"""
+    f, l = _rtty_stage(first), _rtty_stage(last)
+    ti, to = _rtty_types(params, f, l)
+    x = np.ascontiguousarray(x, ti)
+    n = x.size
+    out = np.zeros(n + 16, to)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_rtty_walk(C.byref(params), f, l, _hp(x), n, _hp(cu) if cu.size else None, cu.size, _hp(out))
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out[:k]
+
+
+def rtty_baudot_decoder_push(state, symbol):
+    """rtty_baudot_decoder_push (libcsdr.c:1615-1655) on the host: state (RttyPushState) in and out -> the character or 0"""
+    return lib().csdr_amd_rtty_baudot_decoder_push(C.byref(state), int(symbol) & 255)[0]
+
+
+def rtty_baudot_decoder_lookup(fig_mode, c):
+    """rtty_baudot_decoder_lookup (libcsdr.c:1606-1613) -> (character or 0, new fig_mode)"""
+    f = C.c_ubyte(fig_mode)
+    r = lib().csdr_amd_rtty_baudot_decoder_lookup(C.byref(f), int(c) & 255)[0]
+    return r, f.value
+
+
+class Rtty:
+    """csdr_amd_rtty: the RTTY receive chain (bfsk_demod_cf | serial_line_decoder_f_u8 | rtty_baudot2ascii_u8_u8) for n_channels channels, stages
+    first..last ("bfsk", "serial", "baudot"), state kept on the device between calls."""
+
+    def __init__(self, ctx, params=None, n_channels=1, first="bfsk", last="baudot"):
+        self.ctx, self.n_channels = ctx, n_channels
+        self.params = params if params is not None else rtty_params()
+        self.first, self.last = _rtty_stage(first), _rtty_stage(last)
+        self.in_dtype, self.out_dtype = _rtty_types(self.params, self.first, self.last)
+        self.h = ctx.L.csdr_amd_rtty_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def max_out(self, n_in):
+        return int(self.ctx.L.csdr_amd_rtty_max_out(self.h, n_in))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts):
+        """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
+        self.ctx.check(self.ctx.L.csdr_amd_rtty_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_counts), "rtty_process")
+
+    def process(self, x, calls=None):
+        """x: [n_channels, n] (or [n]) host items; calls: per-call item counts (default one call) -> a list of per-channel output arrays
+        (or one array for 1-D x)"""
+        x = np.ascontiguousarray(x, self.in_dtype)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        eb = np.dtype(self.in_dtype).itemsize
+        ob = np.dtype(self.out_dtype).itemsize
+        di = self.ctx.upload(x)
+        opitch = max(self.max_out(max(calls) if calls else 0), 1)
+        do = self.ctx.alloc(ob * opitch * s + 256)
+        dc = self.ctx.alloc(4 * s + 256)
+        outs = [[] for _ in range(s)]
+        at = 0
+        for k in calls:
+            self.process_dev(di.at(eb * at), k, n, do.ptr, opitch, dc.ptr)
+            cnt = self.ctx.download(dc, np.int32, s)
+            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c]].copy())
+            at += k
+        res = [np.concatenate(o) if o else np.zeros(0, self.out_dtype) for o in outs]
+        return res[0] if squeeze else res
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_rtty_reset(self.h), "rtty_reset")
+
+    def reset_channel(self, ch):
+        self.ctx.check(self.ctx.L.csdr_amd_rtty_reset_channel(self.h, int(ch)), "rtty_reset_channel")
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_rtty_force_generic(self.h, int(on)), "rtty_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_rtty_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.csdr_amd_rtty_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Interpolator(_Resampling):
     """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
     _dt, _eb, _pre = c64, 8, "interp"
@@ -1026,6 +1185,64 @@ class Context:
         y = self.download(do, c64, n * s).reshape(s, n)
         g = self.download(dg, f32, s)
         return (y[0].copy(), float(g[0])) if squeeze else (y.copy(), g.copy())
+
+    # ---- RTTY receive chain (rtty.hip)
+    def rtty(self, params=None, n_channels=1, first="bfsk", last="baudot"):
+        """A batched RTTY receive chain object (Rtty); params from rtty_params()"""
+        return Rtty(self, params, n_channels, first, last)
+
+    def bfsk_demod_cf(self, x, mark, space, force_generic=False):
+        """bfsk_demod_cf (libcsdr.c:2335-2350) with caller taps on [n_streams, n] (or [n]) complex samples -> [n_streams, n - L + 1] float32"""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        mark = np.ascontiguousarray(mark, c64); space = np.ascontiguousarray(space, c64)
+        L = mark.size
+        no = max(n - L + 1, 0)
+        di = self.upload(x); dt = self.upload(np.concatenate([mark, space]))
+        do = self.alloc(4 * max(no, 1) * s + 256)
+        self.check(self.L.csdr_amd_bfsk_demod_cf(self.h, di.ptr, do.ptr, s, n, n, max(no, 1), dt.ptr, dt.at(8 * L), L, int(force_generic)), "bfsk_demod_cf")
+        y = self.download(do, f32, max(no, 1) * s).reshape(s, max(no, 1))[:, :no].copy()
+        self.last_bfsk_kernel = self.L.csdr_amd_bfsk_last_kernel().decode()
+        return y[0] if squeeze else y
+
+    def binary_slicer_f_u8(self, x):
+        """binary_slicer_f_u8 (libcsdr.c:1767-1770) on [n_streams, n] (or [n]) floats"""
+        x = np.ascontiguousarray(x, f32)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        di = self.upload(x); do = self.alloc(max(n, 1) * s + 256)
+        self.check(self.L.csdr_amd_binary_slicer_f_u8(self.h, di.ptr, do.ptr, s, n, n, n), "binary_slicer_f_u8")
+        y = self.download(do, np.uint8, n * s).reshape(s, n)
+        return y[0].copy() if squeeze else y.copy()
+
+    def rtty_line_decoder_u8_u8(self, x, calls=None):
+        """rtty_line_decoder_u8_u8 (csdr.c:2446-2458) on [n_streams, n] (or [n]) bytes, fresh decoders, cut into `calls` -> per-stream text"""
+        x = np.ascontiguousarray(x, np.uint8)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        calls = [n] if calls is None else list(calls)
+        di = self.upload(x)
+        mx = max(max(calls) if calls else 0, 1)
+        do = self.alloc(mx * s + 256); dc = self.alloc(4 * s + 256)
+        dst = self.upload(np.zeros(5 * s, np.int32))
+        outs = [[] for _ in range(s)]
+        at = 0
+        for k in calls:
+            self.check(self.L.csdr_amd_rtty_line_decoder_u8_u8(self.h, di.at(at), do.ptr, s, k, n, mx, dst.ptr, dc.ptr), "rtty_line_decoder_u8_u8")
+            cnt = self.download(dc, np.int32, s)
+            y = self.download(do, np.uint8, mx * s).reshape(s, mx)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c]].copy())
+            at += k
+        res = [np.concatenate(o) for o in outs]
+        return res[0] if squeeze else res
 
     def interpolator(self, interpolation, taps=None, n_streams=1, transition_bw=0.05, window="HAMMING", bufsize=None):
         """A batched fir_interpolate_cc object; taps default to firdes_lowpass_f(firdes_filter_len(transition_bw), 0.5 / I, window) as csdr.c:1212 designs them."""

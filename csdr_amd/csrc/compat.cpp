@@ -428,6 +428,57 @@ char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char s
     return csdr_amd_psk31_varicode_decoder_push(status_shr, symbol);
 }
 
+// ------------------------------------------------------------------ RTTY receive (rtty.hip)
+int bfsk_demod_cf(complexf *in, float *out, int n, complexf *mark_filter, complexf *space_filter, int taps_length)
+{   // libcsdr.c:2335-2350
+    const int no = n - taps_length + 1;
+    if (no <= 0 || taps_length < 1) return no;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); float *dout = stage_out<float>(5, no);
+    cf32 *dt = stage_in<cf32>(6, (const cf32 *)mark_filter, taps_length, taps_length);
+    MUST(hipMemcpyAsync(dt + taps_length, space_filter, sizeof(cf32) * taps_length, hipMemcpyHostToDevice, ctx()->stream) == hipSuccess ? 0 : -1);
+    MUST(csdr_amd_bfsk_demod_cf(ctx(), din, dout, 1, n, n, no, dt, dt + taps_length, taps_length, 0));
+    fetch(out, dout, no);
+    return no;
+}
+
+void firdes_add_peak_c(complexf *output, int length, float rate, window_t window, int add, int normalize)
+{   // libcsdr.c:2219-2257, on the host
+    csdr_amd_firdes_add_peak_c((cf32 *)output, length, rate, (int)window, add, normalize);
+}
+
+void serial_line_decoder_f_u8(serial_line_t *s, float *input, unsigned char *output, int input_size)
+{   // libcsdr.c:1662-1728: one window per call; output elements of 1, 2 or 4 bytes by databits
+    s->output_size = 0; s->input_used = 0;
+    if (input_size <= 0) return;
+    const size_t esz = s->databits <= 8 ? 1 : s->databits <= 16 ? 2 : 4;
+    float *din = stage_in<float>(4, input, input_size); unsigned char *dout = stage_out<unsigned char>(5, esz * input_size);
+    int *dcu = stage_out<int>(6, 2);
+    MUST(csdr_amd_serial_line_decoder_f_u8(ctx(), din, dout, 1, input_size, input_size, input_size, s->samples_per_bits, s->databits, s->stopbits,
+                                           s->bit_sampling_width_ratio, dcu, dcu + 1));
+    int cu[2]; fetch(cu, dcu, 2);
+    if (cu[0]) fetch(output, dout, esz * cu[0]);
+    s->output_size = cu[0]; s->input_used = cu[1];
+}
+
+void binary_slicer_f_u8(float *input, unsigned char *output, int input_size)
+{   // libcsdr.c:1767-1770
+    if (input_size <= 0) return;
+    float *din = stage_in<float>(4, input, input_size); unsigned char *dout = stage_out<unsigned char>(5, input_size);
+    MUST(csdr_amd_binary_slicer_f_u8(ctx(), din, dout, 1, input_size, input_size, input_size));
+    fetch(output, dout, input_size);
+}
+
+char rtty_baudot_decoder_lookup(unsigned char *fig_mode, unsigned char c) { return csdr_amd_rtty_baudot_decoder_lookup(fig_mode, c); }   // libcsdr.c:1606-1613
+
+char rtty_baudot_decoder_push(rtty_baudot_decoder_t *s, unsigned char symbol)
+{   // libcsdr.c:1615-1655, on the host
+    csdr_amd_rtty_push_state p = {s->fig_mode, s->character_received, s->shr, s->bit_cntr, (int)s->state};
+    const char r = csdr_amd_rtty_baudot_decoder_push(&p, symbol);
+    s->fig_mode = (unsigned char)p.fig_mode; s->character_received = (unsigned char)p.character_received; s->shr = (unsigned short)p.shr;
+    s->bit_cntr = (unsigned char)p.bit_cntr; s->state = (rtty_baudot_decoder_state_t)p.state;
+    return r;
+}
+
 // One call of each FIR resampler = a fresh batch object fed the whole block once (resampler.hip).
 rational_resampler_ff_t rational_resampler_ff(float *in, float *out, int n, int interpolation, int decimation, float *taps, int taps_length, int last_taps_delay)
 {

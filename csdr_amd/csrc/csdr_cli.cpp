@@ -282,6 +282,51 @@ struct Psk31 : Stage {   // simple_agc_cc csdr.c:2902-2930 | timing_recovery_cc 
     }
 };
 
+struct Rtty : Stage {   // bfsk_demod_cf csdr.c:3271-3300 | serial_line_decoder_f_u8 csdr.c:2490-2528 | rtty_baudot2ascii_u8_u8 csdr.c:2461-2473: one object for a
+                       // consecutive run of them (`chain` fuses the run); the complex history, the serial decoder's window remainder and the shift live on the device
+    csdr_amd_rtty *p; int first, last, B; int *d_count; csdr_amd_ctx *ctx;
+    Rtty(csdr_amd_ctx *c, const csdr_amd_rtty_params &pr, int f, int l) : first(f), last(l), B(pr.cli_bufsize), ctx(c)
+    {
+        p = csdr_amd_rtty_create(c, &pr, 1, f, l); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = f == CSDR_AMD_RTTY_BFSK ? 8 : f == CSDR_AMD_RTTY_SERIAL ? 4 : 1;
+        out_elem = l == CSDR_AMD_RTTY_BFSK ? 4 : 1;
+        d_count = (int *)csdr_amd_malloc(c, 64); if (!d_count) die("malloc");
+        if (f != l) fprintf(stderr, "csdr rtty_rx: one fused RTTY receive object\n");
+    }
+    ~Rtty() { csdr_amd_rtty_destroy(p); csdr_amd_free(ctx, d_count); }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_rtty_max_out(p, (long long)n) + 16; }
+    int next_bufsize(int b) override { return (first <= CSDR_AMD_RTTY_SERIAL && last >= CSDR_AMD_RTTY_SERIAL) ? B : b; }     // csdr.c:2506: its own (big) buffer
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        MUST(csdr_amd_rtty_process(p, i, (long long)n, n, o, cap, d_count));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count, sizeof k));
+        return k;
+    }
+};
+struct RttyLine : Stage {   // rtty_line_decoder_u8_u8 csdr.c:2446-2458: rtty_baudot_decoder_push per byte, the decoder on the device
+    csdr_amd_rtty_push_state *d_st; int *d_count;
+    RttyLine(csdr_amd_ctx *c)
+    {
+        in_elem = 1; out_elem = 1;
+        d_st = (csdr_amd_rtty_push_state *)csdr_amd_malloc(c, 256); d_count = (int *)(d_st + 4);
+        if (!d_st) die("malloc");
+        MUST(csdr_amd_memset(c, d_st, 0, 256));
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        MUST(csdr_amd_rtty_line_decoder_u8_u8(c, (const uint8_t *)i, (uint8_t *)o, 1, (long long)n, n, n, d_st, d_count));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count, sizeof k));
+        return k;
+    }
+};
+struct BinarySlicer : Stage {   // binary_slicer_f_u8 csdr.c:2475-2487
+    BinarySlicer() { in_elem = 4; out_elem = 1; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    { *cons = n; MUST(csdr_amd_binary_slicer_f_u8(c, (const float *)i, (uint8_t *)o, 1, (long long)n, n, n)); return (long)n; }
+};
+
 struct Interp : Stage {   // csdr.c:1179-1232: fir_interpolate_cc over the_bufsize windows, the first over a buffer of zeros
     csdr_amd_interp *p; int I;
     Interp(csdr_amd_ctx *c, int factor, float tbw, int window, int the_bufsize) : I(factor)
@@ -1606,8 +1651,67 @@ int parse_psk31(int argc, char **argv, csdr_amd_psk31_params *pr, int *extra)
     return -2;
 }
 
+// the RTTY commands: stage index, parameters into *pr; -1 (message given) on bad syntax.  B: the serial decoder's window, as the reference's
+// getbufsize() gives it with bigbufs (csdr.c:332): the fixed big buffer, or the preamble's size in dynamic mode
+int parse_rtty(int argc, char **argv, csdr_amd_rtty_params *pr, int B)
+{
+    const std::string cmd = argv[1];
+    if (cmd == "bfsk_demod_cf") {                                                   // csdr.c:3271-3284
+        if (argc <= 2) { badsyntax("required parameter <frequency_shift> is missing."); return -1; }
+        sscanf(argv[2], "%f", &pr->spacing);
+        if (argc <= 3) { badsyntax("required parameter <filter_length> is missing."); return -1; }
+        sscanf(argv[3], "%d", &pr->filter_length);
+        if (pr->filter_length < 1) { badsyntax("filter_length should be at least 1"); return -1; }
+        return CSDR_AMD_RTTY_BFSK;
+    }
+    if (cmd == "serial_line_decoder_f_u8") {                                        // csdr.c:2490-2507
+        if (argc <= 2) { badsyntax("need required parameter (samples_per_bits)"); return -1; }
+        sscanf(argv[2], "%f", &pr->samples_per_bits);
+        if (pr->samples_per_bits < 1) { badsyntax("samples_per_bits should be at least 1."); return -1; }
+        if (pr->samples_per_bits < 5) fprintf(stderr, "%s: warning: this algorithm does not work well if samples_per_bits is too low. It should be at least 5.\n", argv[1]);
+        pr->databits = 8; if (argc > 3) sscanf(argv[3], "%d", &pr->databits);
+        if (pr->databits > 8 || pr->databits < 1) { badsyntax("databits should be between 1 and 8."); return -1; }
+        pr->stopbits = 1; if (argc > 4) sscanf(argv[4], "%f", &pr->stopbits);
+        if (pr->stopbits < 1) { badsyntax("stopbits should be equal or above 1."); return -1; }
+        pr->bit_sampling_width_ratio = 0.4f;
+        pr->cli_bufsize = B;
+        if ((float)2 + pr->samples_per_bits * ((float)(1 + pr->databits) + pr->stopbits) >= (float)B) {
+            badsyntax("a character does not fit in the buffer: serial_line_decoder_f_u8() would get stuck (raise CSDR_FIXED_BUFSIZE)"); return -1;
+        }
+        return CSDR_AMD_RTTY_SERIAL;
+    }
+    if (cmd == "rtty_baudot2ascii_u8_u8") return CSDR_AMD_RTTY_BAUDOT;
+    return -2;
+}
+
 Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control *ctl, int the_bufsize)
 {
+    {
+        const int B = g_dynamic ? unitround(the_bufsize) : unitround(g_fixed_big);
+        if (!strcmp(argv[1], "rtty_rx")) {                                          // `chain`'s fused RTTY run: argv[2..] are its commands, one per argument
+            csdr_amd_rtty_params pr; memset(&pr, 0, sizeof pr); pr.window = the_bufsize;
+            int first = -1, last = -1;
+            for (int k = 2; k < argc; k++) {
+                std::vector<std::string> t; { std::string w; for (const char *q = argv[k];; q++) { if (!*q || *q == ' ') { if (!w.empty()) t.push_back(w); w.clear(); if (!*q) break; } else w += *q; } }
+                std::vector<char *> av = {argv[0]}; for (auto &w : t) av.push_back(const_cast<char *>(w.c_str()));
+                g_cmd = av[1];
+                const int st = parse_rtty((int)av.size(), av.data(), &pr, B);
+                if (st < 0) return nullptr;
+                if (first < 0) first = st;
+                last = st;
+            }
+            g_cmd = argv[1];
+            return new Rtty(c, pr, first, last);
+        }
+        csdr_amd_rtty_params pr; memset(&pr, 0, sizeof pr); pr.window = the_bufsize;
+        const char *keep = g_cmd; g_cmd = argv[1];
+        const int st = parse_rtty(argc, argv, &pr, B);
+        if (st == -1) return nullptr;
+        if (st >= 0) return new Rtty(c, pr, st, st);
+        g_cmd = keep;
+        if (!strcmp(argv[1], "rtty_line_decoder_u8_u8")) return new RttyLine(c);
+        if (!strcmp(argv[1], "binary_slicer_f_u8")) return new BinarySlicer();
+    }
     if (!strcmp(argv[1], "psk31_rx")) {                                             // `chain`'s fused BPSK31 run: argv[2..] are its commands, one per argument
         csdr_amd_psk31_params pr; memset(&pr, 0, sizeof pr);
         int first = -1, last = -1, extra = 0;
@@ -1918,6 +2022,28 @@ bool fuse_psk31(std::vector<std::vector<std::string>> &cmds)
     return any;
 }
 
+// consecutive runs (two or more) of bfsk_demod_cf -> serial_line_decoder_f_u8 -> rtty_baudot2ascii_u8_u8, in this order, become one `rtty_rx` object
+bool fuse_rtty(std::vector<std::vector<std::string>> &cmds)
+{
+    static const char *order[3] = {"bfsk_demod_cf", "serial_line_decoder_f_u8", "rtty_baudot2ascii_u8_u8"};
+    auto stage_of = [&](const std::vector<std::string> &c) { for (int k = 0; k < 3; k++) if (c.size() > 1 && c[1] == order[k]) return k; return -1; };
+    bool any = false;
+    for (size_t a = 0; a < cmds.size(); a++) {
+        int s = stage_of(cmds[a]);
+        if (s < 0) continue;
+        size_t b = a + 1;
+        while (b < cmds.size() && stage_of(cmds[b]) == s + (int)(b - a)) b++;
+        if (b - a < 2) continue;
+        std::vector<std::string> fused = {"csdr", "rtty_rx"};
+        for (size_t k = a; k < b; k++) { std::string w; for (size_t t = 1; t < cmds[k].size(); t++) w += (t > 1 ? " " : "") + cmds[k][t]; fused.push_back(w); }
+        fprintf(stderr, "csdr chain: %s .. %s recognised -> one fused RTTY object (rtty_rx: k_bfsk_mfma + k_rtty_walk)\n", order[s], order[s + (int)(b - a) - 1]);
+        cmds.erase(cmds.begin() + a, cmds.begin() + b);
+        cmds.insert(cmds.begin() + a, fused);
+        any = true;
+    }
+    return any;
+}
+
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
 {
     if (cmds.size() < 3 || cmds[0].size() != 2 || cmds[0][1] != "convert_u8_f") return false;
@@ -1946,6 +2072,7 @@ int main(int argc, char **argv)
                         "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff rational_resampler_ff suboptimal_rational_resampler_ff fir_interpolate_cc deemphasis_wfm_ff "
                         "deemphasis_nfm_ff limit_ff fastagc_ff bandpass_fir_fft_cc fastddc_fwd_cc fastddc_inv_cc firdes_lowpass_f firdes_bandpass_c "
                         "simple_agc_cc timing_recovery_cc (needs |mu| * max_error <= 1) dbpsk_decoder_c_u8 psk31_varicode_decoder_u8_u8 "
+                        "bfsk_demod_cf serial_line_decoder_f_u8 rtty_baudot2ascii_u8_u8 rtty_line_decoder_u8_u8 binary_slicer_f_u8 firdes_peak_c "
                         "amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
                         "waterfall_u8 / waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>, "
@@ -1961,6 +2088,21 @@ int main(int argc, char **argv)
         return passthrough(false, b);
     }
     if (cmd == "clone" || cmd == "REM" || cmd == "through") return passthrough(true, 0);
+    if (cmd == "firdes_peak_c") {                                     // csdr.c:2932-2972: print the designed taps, "(%g)+(%g)*i " each
+        if (argc <= 3) return badsyntax("need required parameters (rate, length)");
+        float rate = 0; int length = 0;
+        sscanf(argv[2], "%g", &rate);
+        sscanf(argv[3], "%d", &length);
+        if (length % 2 == 0) return badsyntax("number of symmetric FIR filter taps should be odd");
+        if (length < 1) return badsyntax("length should be at least 1");
+        int window = CSDR_WINDOW_HAMMING;
+        if (argc >= 5) window = window_from(argv[4]); else fprintf(stderr, "csdr %s: window = HAMMING\n", g_cmd);
+        if (argc >= 6 && !strcmp(argv[5], "--octave")) return badsyntax("--octave (debug plot) is not supported");
+        std::vector<csdr_complexf> t(length); csdr_amd_firdes_peak_c(t.data(), length, rate, window);
+        for (int i = 0; i < length; i++) printf("(%g)+(%g)*i ", t[i].i, t[i].q);
+        fflush(stdout);
+        return 0;
+    }
     if (cmd == "firdes_lowpass_f" || cmd == "firdes_bandpass_c") {   // csdr.c:1251-1335: print the designed taps ("%g " each), --octave wraps them in a plot script
         const bool bp = cmd == "firdes_bandpass_c";
         const int a0 = bp ? 5 : 4;                                    // argv index of the optional window
@@ -2021,13 +2163,15 @@ int main(int argc, char **argv)
             fprintf(stderr, "csdr chain: convert_u8_f | shift_addition_cc | fir_decimate_cc recognised -> fused matrix-core front end\n");
         }
         fuse_psk31(cmds);
+        fuse_rtty(cmds);
     } else {
         cmds.assign(1, std::vector<std::string>(argv, argv + argc));
     }
     if (g_dynamic) ipc_source_decide(dev ? atoi(dev) : 0);           // (before the preamble is read: a producer of ours connects first, then writes it)
     // (logaveragepower_cf reads no preamble: csdr.c:1663-1695 never calls getbufsize())
     const int in_bufsize = cmds[0].size() > 1 && cmds[0][1] == "logaveragepower_cf" ? unitround(g_dynamic ? 1024 : g_fixed)
-                         : get_bufsize(cmds[0].size() > 1 && (cmds[0][1] == "shift_addition_cc" || cmds[0][1] == "decimating_shift_addition_cc" || cmds[0][1] == "shift_addition_fc"));
+                         : get_bufsize(cmds[0].size() > 1 && (cmds[0][1] == "shift_addition_cc" || cmds[0][1] == "decimating_shift_addition_cc" || cmds[0][1] == "shift_addition_fc" ||
+                                                              cmds[0][1] == "serial_line_decoder_f_u8"));
     int out_bufsize = in_bufsize;
     // every command may have its control channel, also inside `chain` (fusion and retune together): the newest complete line is applied in front of a pass
     std::vector<Control> ctls(cmds.size());

@@ -55,6 +55,33 @@ void csdr_amd_firdes_bandpass_c(csdr_complexf *taps, int length, float lowcut, f
     free(proto);
 }
 
+void csdr_amd_firdes_add_peak_c(csdr_complexf *output, int length, float rate, int window, int add, int normalize)
+{   // libcsdr.c:2219-2257: a windowed tone at -rate, written (add = 0) or added (add = 1) to output, then optionally normalised to unit sum of |h|;
+    // the phase wraps against the double 2*M_PI as the reference compares it
+    const int middle = length / 2;
+    csdr_complexf *taps = (csdr_complexf *)malloc(sizeof(csdr_complexf) * (size_t)(length > 0 ? length : 1));
+    float phase = 0;
+    const float phase_addition = (float)(-rate * M_PI * 2);
+    for (int i = 0; i < length; i++) {
+        taps[i].i = (float)cos((double)phase); taps[i].q = (float)sin((double)phase);
+        const float wm = window_value(window, (float)fabs((double)((float)(middle - i) / middle)));
+        taps[i].i *= wm; taps[i].q *= wm;
+        phase += phase_addition;
+        while (phase > 2 * M_PI) phase = (float)(phase - 2 * M_PI);
+        while (phase < 0) phase = (float)(phase + 2 * M_PI);
+    }
+    if (add) for (int i = 0; i < length; i++) { output[i].i += taps[i].i; output[i].q += taps[i].q; }
+    else for (int i = 0; i < length; i++) output[i] = taps[i];
+    free(taps);
+    if (normalize) {
+        float sum = 0;
+        for (int i = 0; i < length; i++) sum = (float)(sum + sqrt((double)(output[i].i * output[i].i + output[i].q * output[i].q)));
+        for (int i = 0; i < length; i++) { output[i].i /= sum; output[i].q /= sum; }
+    }
+}
+
+void csdr_amd_firdes_peak_c(csdr_complexf *taps, int length, float rate, int window) { csdr_amd_firdes_add_peak_c(taps, length, rate, window, 0, 1); }
+
 void csdr_amd_shift_addition_init(float rate, float *out3)
 {   // libcsdr_gpl.c:81-89
     rate *= 2;

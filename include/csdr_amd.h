@@ -264,6 +264,71 @@ void csdr_amd_psk31_varicode_table(int *out);
 long long csdr_amd_debug_psk31_walk(const csdr_amd_psk31_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
                                     int n_cuts, void *out, float *err, unsigned *idx, csdr_amd_psk31_chan *state_io);
 
+/* ------------------------------------------------------------------ RTTY receive chain (rtty.hip)
+ * bfsk_demod_cf libcsdr.c:2335-2350 (csdr.c:3271-3300) | serial_line_decoder_f_u8 libcsdr.c:1662-1728 (csdr.c:2490-2528) | rtty_baudot2ascii_u8_u8 csdr.c:2461-2473,
+ * for n_channels channels, all with the same parameters.  The object runs the stages first_stage .. last_stage (CSDR_AMD_RTTY_*) and keeps each channel's
+ * state on the device: the last < L complex samples (the CLI keeps L - 1 between its windows, so its stream is the valid correlation over the whole input),
+ * the < B discriminator samples the serial decoder has not consumed, and the letters / figures shift.  The serial decoder works in windows of cli_bufsize
+ * (B) samples exactly as the CLI's bigbufs loop does: its output depends on B.  Only whole windows are decoded (no stale window at the end of a stream).
+ * The output equals the stages applied once to the whole stream since the last reset, however the stream is cut into calls and whatever a channel's
+ * position in the batch.
+ * params: spacing and filter_length (> 0) for BFSK (mark filter at +spacing/2, space at -spacing/2, Hamming); samples_per_bits >= 1, databits 1 .. 8
+ * (1 .. 32 when SERIAL is the last stage: 2- / 4-byte outputs above 8 and 16 bits, as the library function), stopbits >= 1, bit_sampling_width_ratio
+ * 0 .. 1 (the CLI: 0.4), cli_bufsize B with 2 + samples_per_bits * (1 + databits + stopbits) < B (otherwise the reference CLI "gets stuck").
+ * `window` is the bfsk_demod_cf CLI's buffer size; it changes no output.
+ * process: n_in new items per channel (complexf for BFSK, float for SERIAL, bytes for BAUDOT), in_pitch items apart; out: float (last BFSK), the serial
+ * decoder's characters (last SERIAL) or ASCII (last BAUDOT, NULs left out), out_pitch items apart, at least max_out(n_in); counts (device, n_channels
+ * ints) receives each channel's output count.  Asynchronous on the context's stream.
+ * kernel_name: the discriminator's kernel ("k_bfsk_mfma": the fp32 matrix cores, filters up to 256 taps; "k_bfsk_generic": one thread per output),
+ * or, when the range starts behind it, "k_rtty_walk" (the serial decoder, one wave per channel) / "k_rtty_baudot" (Baudot alone).  force_generic(1) takes
+ * k_bfsk_generic always: the same bits. */
+enum { CSDR_AMD_RTTY_BFSK = 0, CSDR_AMD_RTTY_SERIAL = 1, CSDR_AMD_RTTY_BAUDOT = 2 };
+typedef struct csdr_amd_rtty_params {
+    float spacing;
+    int filter_length;
+    int window;                        /* bfsk_demod_cf */
+    float samples_per_bits;
+    int databits;
+    float stopbits;
+    float bit_sampling_width_ratio;    /* serial_line_decoder_f_u8; CLI defaults 8, 1, 0.4 */
+    int cli_bufsize;                   /* B, default 16384 */
+} csdr_amd_rtty_params;
+typedef struct csdr_amd_rtty csdr_amd_rtty;
+csdr_amd_rtty *csdr_amd_rtty_create(csdr_amd_ctx *ctx, const csdr_amd_rtty_params *params, int n_channels, int first_stage, int last_stage);
+int  csdr_amd_rtty_process(csdr_amd_rtty *r, const void *in, long long n_in, size_t in_pitch, void *out, size_t out_pitch, int *counts);
+long long csdr_amd_rtty_max_out(const csdr_amd_rtty *r, long long n_in);
+int  csdr_amd_rtty_reset(csdr_amd_rtty *r);
+int  csdr_amd_rtty_reset_channel(csdr_amd_rtty *r, int channel);
+int  csdr_amd_rtty_force_generic(csdr_amd_rtty *r, int on);
+const char *csdr_amd_rtty_kernel_name(const csdr_amd_rtty *r);
+void csdr_amd_rtty_destroy(csdr_amd_rtty *r);
+/* bfsk_demod_cf with caller taps (device, taps_length complexf each) on n_streams independent streams of n samples: n - taps_length + 1 outputs each
+ * (none below that), stateless.  force_generic: k_bfsk_generic; csdr_amd_bfsk_last_kernel() names the kernel of the last call. */
+int  csdr_amd_bfsk_demod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                            const csdr_complexf *mark_filter, const csdr_complexf *space_filter, int taps_length, int force_generic);
+const char *csdr_amd_bfsk_last_kernel(void);
+/* binary_slicer_f_u8 libcsdr.c:1767-1770: out = in > 0, on n_streams (<= 65535) rows */
+int  csdr_amd_binary_slicer_f_u8(csdr_amd_ctx *ctx, const float *in, uint8_t *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch);
+/* rtty_line_decoder_u8_u8 csdr.c:2446-2458 (rtty_baudot_decoder_push libcsdr.c:1623-1655 per byte, NULs left out) on n_streams streams; state (device,
+ * n_streams entries, zero = the CLI's fresh decoder) carries each stream's decoder; counts (device) receives each stream's output count */
+typedef struct csdr_amd_rtty_push_state { int fig_mode, character_received, shr, bit_cntr, state; } csdr_amd_rtty_push_state;
+int  csdr_amd_rtty_line_decoder_u8_u8(csdr_amd_ctx *ctx, const uint8_t *in, uint8_t *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                                      csdr_amd_rtty_push_state *state, int *counts);
+/* serial_line_decoder_f_u8 libcsdr.c:1662-1728 as the library call: ONE window of n samples per stream (device arrays); out elements are 1, 2 or 4 bytes
+ * (databits <= 8, <= 16, above); counts / used (device) receive output_size / input_used */
+int  csdr_amd_serial_line_decoder_f_u8(csdr_amd_ctx *ctx, const float *in, void *out, int n_streams, int n, size_t in_pitch, size_t out_pitch,
+                                       float samples_per_bits, int databits, float stopbits, float bit_sampling_width_ratio, int *counts, int *used);
+/* rtty_baudot_decoder_lookup / _push libcsdr.c:1606-1655 on the host */
+char csdr_amd_rtty_baudot_decoder_lookup(unsigned char *fig_mode, unsigned char c);
+char csdr_amd_rtty_baudot_decoder_push(csdr_amd_rtty_push_state *s, unsigned char symbol);
+/* firdes_add_peak_c libcsdr.c:2219-2257, and firdes_peak_c (csdr.c:2932-2972: add = 0, normalize = 1) */
+void csdr_amd_firdes_add_peak_c(csdr_complexf *output, int length, float rate, int window, int add, int normalize);
+void csdr_amd_firdes_peak_c(csdr_complexf *taps, int length, float rate, int window);
+/* CPU run of the object's walk (the same step functions) for one channel, the n items cut into calls of cuts[0..n_cuts) items and the rest; outputs
+ * concatenated.  Returns the output count (< 0: refused parameters, the reason in csdr_amd_last_error()). */
+long long csdr_amd_debug_rtty_walk(const csdr_amd_rtty_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
+                                   int n_cuts, void *out);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

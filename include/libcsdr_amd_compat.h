@@ -108,6 +108,33 @@ char *timing_recovery_get_string_from_algorithm(timing_recovery_algorithm_t algo
 void simple_agc_cc(complexf *input, complexf *output, int input_size, float rate, float reference, float max_gain, float *current_gain);
 void dbpsk_decoder_c_u8(complexf *input, unsigned char *output, int input_size);
 char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char symbol);
+/* RTTY receive, libcsdr.h:236-289, 412.  bfsk_demod_cf and serial_line_decoder_f_u8 run on the device (one library call = one window, as the reference);
+ * serial_line_decoder_f_u8 writes unsigned char, short or unsigned outputs for databits <= 8, <= 16, above.  The Baudot functions run on the host. */
+typedef struct rtty_baudot_item_s { unsigned long long code; unsigned char ascii_letter; unsigned char ascii_figure; } rtty_baudot_item_t;
+typedef enum rtty_baudot_decoder_state_e { RTTY_BAUDOT_WAITING_STOP_PULSE = 0, RTTY_BAUDOT_WAITING_START_PULSE, RTTY_BAUDOT_RECEIVING_DATA } rtty_baudot_decoder_state_t;
+typedef struct rtty_baudot_decoder_s {
+    unsigned char fig_mode;
+    unsigned char character_received;
+    unsigned short shr;
+    unsigned char bit_cntr;
+    rtty_baudot_decoder_state_t state;
+} rtty_baudot_decoder_t;
+#define RTTY_FIGURE_MODE_SELECT_CODE 0b11011
+#define RTTY_LETTER_MODE_SELECT_CODE 0b11111
+char rtty_baudot_decoder_lookup(unsigned char *fig_mode, unsigned char c);
+char rtty_baudot_decoder_push(rtty_baudot_decoder_t *s, unsigned char symbol);
+typedef struct serial_line_s {
+    float samples_per_bits;
+    int databits; /* including parity */
+    float stopbits;
+    int output_size;
+    int input_used;
+    float bit_sampling_width_ratio;
+} serial_line_t;
+void serial_line_decoder_f_u8(serial_line_t *s, float *input, unsigned char *output, int input_size);
+void binary_slicer_f_u8(float *input, unsigned char *output, int input_size);
+int bfsk_demod_cf(complexf *input, float *output, int input_size, complexf *mark_filter, complexf *space_filter, int taps_length);
+void firdes_add_peak_c(complexf *output, int length, float rate, window_t window, int add, int normalize);
 void rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, window_t window);
 
 typedef struct shift_table_data_s { float *table; int table_size; } shift_table_data_t;     /* libcsdr.h:180-184 */
