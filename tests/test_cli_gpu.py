@@ -1,4 +1,4 @@
-"""`csdr <function>` front end (csdr_amd/csdr, built from csdr_amd/csrc/csdr_cli.cpp) on the GPU: raw streams in and out through real
+"""`csdr <function>` front end (csdr_amd/csdr, built from csdr_amd/csrc/csdr_cli.cpp and its cli_*.hpp) on the GPU: raw streams in and out through real
 pipes, compared with the oracle's stream models of the reference CLI loops (csdr.c, cited per test) and -- when the compiled reference
 CLI travelled with the snapshot (oracle/_ref/csdr) -- with the reference processes themselves in the README.md:66 pipeline.
 Small CSDR_AMD_BLOCK values force several host iterations so that every carry path (refeed, overlap, phase, AGC history) is crossed."""
@@ -1081,6 +1081,42 @@ def test_cli_stream_bank(port, tmp_path, cmd):
             want, _ = port.nfm_chain(sig[k], -0.05, taps48)
         else:
             want, _ = port.wfm_chain(sig[k], -0.085, 10, port.firdes_lowpass_f(79, 0.05))
+        m = min(got.size, want.size)
+        assert m > 0 and abs(got.size - want.size) <= (1024 if nfm else 2)
+        d = np.abs(got[:m].astype(np.int32) - want[:m].astype(np.int32))
+        assert d.max() <= 1 and (d > 0).mean() < 0.05, "stream %d" % k
+
+
+@pytest.mark.parametrize("cmd", ["wfm_bank_u8_s16", "nfm_bank_u8_s16"])
+def test_cli_stream_bank_ends_with_the_first_input(port, tmp_path, cmd):
+    """The streams are read in lock step and the process ends when ANY input ends (`wfm_bank_u8_s16`), also when that input ends on a block
+    boundary, with nothing left for the next pass: one input of exactly two blocks beside two longer ones gives what the same inputs cut to two blocks give,
+    byte for byte, and that is the oracle's audio of the common prefix."""
+    from tests_helpers import wfm_signal_u8, nfm_signal_u8
+    nfm = cmd.startswith("nfm")
+    B = 65536
+    lengths = [2 * B, 2 * B + 3 * 1024 + 100, 3 * B + 5 * 1024]
+    sig = [(nfm_signal_u8(920 + k, lengths[k], offset=0.05) if nfm else wfm_signal_u8(920 + k, lengths[k])) for k in range(3)]
+    env = dict(os.environ, CSDR_AMD_BANK_BLOCK=str(B))
+    outs = {}
+    for run_name, cut in (("whole", None), ("cut", 2 * B)):
+        args = [cmd, "-0.05" if nfm else "-0.085"]
+        outs[run_name] = []
+        for k in range(3):
+            fi = tmp_path / ("%s_in%d.u8" % (run_name, k)); fo = tmp_path / ("%s_out%d.s16" % (run_name, k))
+            (sig[k] if cut is None else sig[k][:2 * cut]).tofile(fi); outs[run_name].append(fo); args += [str(fi), str(fo)]
+        p = subprocess.run([CLI] + args, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=120)
+        assert p.returncode == 0, p.stderr.decode()
+    taps48 = np.load(os.path.join(ROOT, "tests", "golden", "nfm_deemph_taps.npz"))["sr48000"]
+    for k in range(3):
+        whole = outs["whole"][k].read_bytes()
+        assert whole == outs["cut"][k].read_bytes(), "stream %d" % k
+        got = np.frombuffer(whole, np.int16)
+        prefix = sig[k][:2 * 2 * B]
+        if nfm:
+            want, _ = port.nfm_chain(prefix, -0.05, taps48)
+        else:
+            want, _ = port.wfm_chain(prefix, -0.085, 10, port.firdes_lowpass_f(79, 0.05))
         m = min(got.size, want.size)
         assert m > 0 and abs(got.size - want.size) <= (1024 if nfm else 2)
         d = np.abs(got[:m].astype(np.int32) - want[:m].astype(np.int32))
