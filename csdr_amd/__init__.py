@@ -156,6 +156,22 @@ def lib():
     L.csdr_amd_firdes_add_peak_c.restype = None; L.csdr_amd_firdes_add_peak_c.argtypes = [vp, i, C.c_float, i, i, i]
     L.csdr_amd_firdes_peak_c.restype = None; L.csdr_amd_firdes_peak_c.argtypes = [vp, i, C.c_float, i]
     L.csdr_amd_debug_rtty_walk.restype = ll; L.csdr_amd_debug_rtty_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp]
+    L.csdr_amd_squelch_create.restype = vp; L.csdr_amd_squelch_create.argtypes = [vp, i, i, i, vp, ll]
+    L.csdr_amd_squelch_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, sz, vp, vp]
+    L.csdr_amd_squelch_set_level.argtypes = [vp, i, fl]
+    L.csdr_amd_squelch_get_level.restype = fl; L.csdr_amd_squelch_get_level.argtypes = [vp, i]
+    L.csdr_amd_squelch_block_index.restype = ll; L.csdr_amd_squelch_block_index.argtypes = [vp, i]
+    L.csdr_amd_squelch_max_blocks.argtypes = [vp]
+    L.csdr_amd_squelch_reset.argtypes = [vp]
+    L.csdr_amd_squelch_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_squelch_force_generic.argtypes = [vp, i]
+    L.csdr_amd_squelch_kernel_name.restype = C.c_char_p; L.csdr_amd_squelch_kernel_name.argtypes = [vp]
+    L.csdr_amd_squelch_destroy.argtypes = [vp]; L.csdr_amd_squelch_destroy.restype = None
+    L.csdr_amd_get_power_c.argtypes = [vp, vp, i, i, i, i, sz, vp]
+    L.csdr_amd_get_power_f.argtypes = [vp, vp, i, i, i, i, sz, vp]
+    L.csdr_amd_squelch_report_due.argtypes = [i, ll]
+    L.csdr_amd_squelch_gate_open.argtypes = [fl, fl]
+    L.csdr_amd_debug_squelch_power.restype = fl; L.csdr_amd_debug_squelch_power.argtypes = [vp, i, i, i]
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
@@ -803,6 +819,114 @@ class Rtty:
             pass
 
 
+def squelch_report_due(report_every_nth, block_index):
+    """whether block `block_index` (0-based) of squelch_and_smeter_cc reports its power (csdr.c:2224-2229)"""
+    return bool(lib().csdr_amd_squelch_report_due(int(report_every_nth), int(block_index)))
+
+
+def squelch_gate_open(power, level):
+    """the gate decision of one block (csdr.c:2230)"""
+    return bool(lib().csdr_amd_squelch_gate_open(float(power), float(level)))
+
+
+def squelch_debug_power(x, decimation=1):
+    """the library's power step function on the host (csdr_amd_debug_squelch_power): one block = all of x (complex or real)"""
+    cplx = np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, c64 if cplx else f32)
+    return f32(lib().csdr_amd_debug_squelch_power(_hp(x), x.size, int(decimation), int(cplx)))
+
+
+class Squelch:
+    """csdr_amd_squelch: squelch_and_smeter_cc for n_channels channels in blocks of block_size samples; the samples behind a channel's last whole block
+    stay on the device between calls."""
+
+    def __init__(self, ctx, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
+        self.ctx, self.n_channels, self.B = ctx, n_channels, block_size
+        lv = None if levels is None else np.ascontiguousarray(np.broadcast_to(np.asarray(levels, f32), (n_channels,)))
+        self.h = ctx.L.csdr_amd_squelch_create(ctx.h, n_channels, block_size, use_every_nth, None if lv is None else _hp(lv), max_samples_per_call)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def max_blocks(self):
+        return int(self.ctx.L.csdr_amd_squelch_max_blocks(self.h))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_power=None, power_pitch=0, d_flags=None, counts=None):
+        """device pointers (power / flags may be None); counts: a host int32 array of n_channels, or None -> the largest block count.  Asynchronous."""
+        return self.ctx.check(self.ctx.L.csdr_amd_squelch_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_power, power_pitch, d_flags,
+                                                                  None if counts is None else _hp(counts)), "squelch_process")
+
+    def process(self, x, calls=None, in_pitch=None, out_pitch=None, levels_between=None):
+        """x: [n_channels, n] (or [n]) complex samples; calls: per-call sample counts (default one call); in_pitch / out_pitch: row pitches in samples
+        (default: the row); levels_between: {call index: [(channel, level), ...]} applied in front of that call
+        -> (out, power, flags): per-channel lists of the concatenated blocks, their powers and their open flags (arrays for 1-D x)"""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else [int(k) for k in calls]
+        ip = n if in_pitch is None else int(in_pitch)
+        xin = np.zeros((s, ip), c64)
+        xin[:, :n] = x
+        di = self.ctx.upload(xin)
+        mb = max((max(calls) if calls else 0) // self.B + 1, 1)
+        op = mb * self.B if out_pitch is None else int(out_pitch)
+        do = self.ctx.alloc(8 * op * s + 256)
+        dp = self.ctx.alloc(4 * mb * s + 256)
+        df = self.ctx.alloc(mb * s + 256)
+        cnt = np.zeros(s, np.int32)
+        outs, pws, fls = [[] for _ in range(s)], [[] for _ in range(s)], [[] for _ in range(s)]
+        at = 0
+        for ci, k in enumerate(calls):
+            for ch, lv in (levels_between or {}).get(ci, ()):
+                self.set_level(ch, lv)
+            self.process_dev(di.at(8 * at), k, ip, do.ptr, op, dp.ptr, mb, df.ptr, cnt)
+            y = self.ctx.download(do, c64, op * s).reshape(s, op)
+            pw = self.ctx.download(dp, f32, mb * s).reshape(s, mb)
+            fl = self.ctx.download(df, np.uint8, mb * s).reshape(s, mb)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c] * self.B].copy()); pws[c].append(pw[c, :cnt[c]].copy()); fls[c].append(fl[c, :cnt[c]].copy())
+            at += k
+        cat = lambda v, dt: [np.concatenate(o) if o else np.zeros(0, dt) for o in v]
+        o, p, f = cat(outs, c64), cat(pws, f32), cat(fls, np.uint8)
+        return (o[0], p[0], f[0]) if squeeze else (o, p, f)
+
+    def set_level(self, ch, level):
+        """takes effect from the next block that a later call starts; ch = -1: all channels"""
+        self.ctx.check(self.ctx.L.csdr_amd_squelch_set_level(self.h, int(ch), float(level)), "squelch_set_level")
+
+    def get_level(self, ch):
+        return float(self.ctx.L.csdr_amd_squelch_get_level(self.h, int(ch)))
+
+    def block_index(self, ch=0):
+        return int(self.ctx.L.csdr_amd_squelch_block_index(self.h, int(ch)))
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_squelch_reset(self.h), "squelch_reset")
+
+    def reset_channel(self, ch):
+        self.ctx.check(self.ctx.L.csdr_amd_squelch_reset_channel(self.h, int(ch)), "squelch_reset_channel")
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_squelch_force_generic(self.h, int(on)), "squelch_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_squelch_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.csdr_amd_squelch_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Interpolator(_Resampling):
     """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
     _dt, _eb, _pre = c64, 8, "interp"
@@ -1207,6 +1331,33 @@ class Context:
         y = self.download(do, f32, max(no, 1) * s).reshape(s, max(no, 1))[:, :no].copy()
         self.last_bfsk_kernel = self.L.csdr_amd_bfsk_last_kernel().decode()
         return y[0] if squeeze else y
+
+    # ---- squelch and S-meter (squelch.hip)
+    def squelch(self, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
+        """A batched squelch_and_smeter_cc object (Squelch)"""
+        return Squelch(self, n_channels, block_size, use_every_nth, levels, max_samples_per_call)
+
+    def _get_power(self, x, block_size, decimation, dt, fn):
+        x = np.ascontiguousarray(x, dt)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        B = n if block_size is None else int(block_size)
+        nb = n // B if B > 0 else 0
+        di = self.upload(x); do = self.alloc(4 * max(nb, 1) * s + 256)
+        self.check(fn(self.h, di.ptr, s, nb, B, int(decimation), n, do.ptr), "get_power")
+        y = self.download(do, f32, nb * s).reshape(s, nb)
+        return y[0].copy() if squeeze else y.copy()
+
+    def get_power_c(self, x, block_size=None, decimation=1):
+        """get_power_c (libcsdr.c:1154-1162) of the whole blocks of block_size samples (default: one block = the row) of [n_streams, n] (or [n])
+        complex samples -> [n_streams, n_blocks] float32"""
+        return self._get_power(x, block_size, decimation, c64, self.L.csdr_amd_get_power_c)
+
+    def get_power_f(self, x, block_size=None, decimation=1):
+        """get_power_f (libcsdr.c:1144-1152), as get_power_c on real samples"""
+        return self._get_power(x, block_size, decimation, f32, self.L.csdr_amd_get_power_f)
 
     def binary_slicer_f_u8(self, x):
         """binary_slicer_f_u8 (libcsdr.c:1767-1770) on [n_streams, n] (or [n]) floats"""

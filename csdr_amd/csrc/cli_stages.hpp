@@ -257,6 +257,39 @@ struct BinarySlicer : Stage {   // binary_slicer_f_u8 csdr.c:2475-2487
     { *cons = n; MUST(csdr_amd_binary_slicer_f_u8(c, (const float *)i, (uint8_t *)o, 1, (long long)n, n, n)); return (long)n; }
 };
 
+struct Squelch : Stage {   // squelch_and_smeter_cc csdr.c:2192-2243: blocks of the_bufsize samples counted from the start of the stream, however many a pass moves;
+                          // a new level (control channel, polled in front of every pass) applies from the next block; block k's power goes to the out fifo as "%g\n"
+                          // when k mod (report_every_nth + 2) == report_every_nth + 1, written non-blocking as the reference does
+    Owned<csdr_amd_squelch, csdr_amd_squelch_destroy> p; int B, every, fd_out; size_t max_blocks; CtxBuf<float> d_power; std::vector<float> h_power;
+    Squelch(csdr_amd_ctx *c, int the_bufsize, int use_every_nth, int report_every_nth, float level, int out_fd, size_t block) : B(the_bufsize), every(report_every_nth), fd_out(out_fd)
+    {
+        in_elem = 8; out_elem = 8; granule = (size_t)the_bufsize; flush_partial = false;
+        const size_t most = (block > 4 * granule ? block : 4 * granule) + granule + 64;      // the largest pass run() hands this stage
+        p.reset(csdr_amd_squelch_create(c, 1, the_bufsize, use_every_nth, &level, (long long)most)); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        max_blocks = (size_t)csdr_amd_squelch_max_blocks(p.get());
+        d_power = ctx_alloc<float>(c, 4 * max_blocks + 64, "malloc"); h_power.resize(max_blocks);
+    }
+    const char *ctl_format() override { return "%g\n"; }
+    void retune(csdr_amd_ctx *, float level, float) override { MUST(csdr_amd_squelch_set_level(p.get(), 0, level)); fprintf(stderr, "csdr %s: new squelch level is %g\n", g_cmd, level); }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        const size_t nb = n / B; *cons = nb * B;
+        if (!nb) return 0;
+        const long long k0 = csdr_amd_squelch_block_index(p.get(), 0);
+        MUST(csdr_amd_squelch_process(p.get(), (const csdr_complexf *)i, (long long)(nb * B), n, (csdr_complexf *)o, cap, d_power.get(), max_blocks, nullptr, nullptr));
+        bool any = false;
+        for (size_t k = 0; k < nb && !any; k++) any = csdr_amd_squelch_report_due(every, k0 + (long long)k) != 0;
+        if (any && fd_out >= 0) {
+            MUST(csdr_amd_d2h(c, h_power.data(), d_power.get(), 4 * nb));
+            for (size_t k = 0; k < nb; k++) if (csdr_amd_squelch_report_due(every, k0 + (long long)k)) {
+                char line[101]; const int len = snprintf(line, 100, "%g\n", h_power[k]);
+                (void)!write(fd_out, line, (size_t)len);                 // non-blocking: a full fifo drops the line (csdr.c:2211-2228)
+            }
+        }
+        return (long)(nb * B);
+    }
+};
+
 struct Interp : Stage {   // csdr.c:1179-1232: fir_interpolate_cc over the_bufsize windows, the first over a buffer of zeros
     csdr_amd_interp *p; int I;
     Interp(csdr_amd_ctx *c, int factor, float tbw, int window, int the_bufsize) : I(factor)
@@ -771,6 +804,24 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
     g_cmd = argv[1];
     const std::string cmd = argv[1];
     const bool has_ctl = ctl && ctl->open_from(argc, argv);
+    if (cmd == "squelch_and_smeter_cc") {                                           // csdr.c:2192-2218, its checks in its order
+        float level = 0, unused;
+        if (!has_ctl) { badsyntax("need required parameter (--fifo <fifo>)"); return nullptr; }
+        ctl->wait_first("%g\n", &level, &unused);
+        fprintf(stderr, "csdr %s: initial squelch level is %g\n", g_cmd, level);
+        if (argc <= 5 || strcmp(argv[4], "--outfifo")) { badsyntax("need required parameter (--outfifo <fifo>)"); return nullptr; }
+        const int fd2 = open(argv[5], O_WRONLY);
+        if (fd2 == -1) { badsyntax("error while opening --outfifo"); return nullptr; }
+        fcntl(fd2, F_SETFL, fcntl(fd2, F_GETFL, 0) | O_NONBLOCK);
+        if (argc <= 6) { badsyntax("need required parameter (use_every_nth)"); return nullptr; }
+        int decimation = 0, report_every_nth = 0;
+        sscanf(argv[6], "%d", &decimation);
+        if (decimation <= 0) { badsyntax("use_every_nth <= 0 is invalid"); return nullptr; }
+        if (argc <= 7) { badsyntax("need required parameter (report_every_nth)"); return nullptr; }
+        sscanf(argv[7], "%d", &report_every_nth);
+        if (report_every_nth <= 0) { badsyntax("report_every_nth <= 0 is invalid"); return nullptr; }
+        return new Squelch(c, g_dynamic ? the_bufsize : unitround(g_fixed), decimation, report_every_nth, level, fd2, block);   // without the preamble protocol every reference process has its default buffer
+    }
     if (cmd == "convert_u8_f") return new Convert(0, 1, 4);
     if (cmd == "convert_f_u8") return new Convert(1, 4, 1);
     if (cmd == "convert_s8_f") return new Convert(2, 1, 4);

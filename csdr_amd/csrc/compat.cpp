@@ -468,6 +468,25 @@ void binary_slicer_f_u8(float *input, unsigned char *output, int input_size)
     fetch(output, dout, input_size);
 }
 
+// ------------------------------------------------------------------ squelch and S-meter (squelch.hip)
+float get_power_f(float *input, int input_size, int decimation)
+{   // libcsdr.c:1144-1152
+    if (input_size <= 0 || decimation <= 0) return 0.f;
+    float *din = stage_in<float>(4, input, input_size); float *dout = stage_out<float>(5, 1);
+    MUST(csdr_amd_get_power_f(ctx(), din, 1, 1, input_size, decimation, input_size, dout));
+    float p = 0.f; fetch(&p, dout, 1);
+    return p;
+}
+
+float get_power_c(complexf *input, int input_size, int decimation)
+{   // libcsdr.c:1154-1162
+    if (input_size <= 0 || decimation <= 0) return 0.f;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)input, input_size); float *dout = stage_out<float>(5, 1);
+    MUST(csdr_amd_get_power_c(ctx(), din, 1, 1, input_size, decimation, input_size, dout));
+    float p = 0.f; fetch(&p, dout, 1);
+    return p;
+}
+
 char rtty_baudot_decoder_lookup(unsigned char *fig_mode, unsigned char c) { return csdr_amd_rtty_baudot_decoder_lookup(fig_mode, c); }   // libcsdr.c:1606-1613
 
 char rtty_baudot_decoder_push(rtty_baudot_decoder_t *s, unsigned char symbol)

@@ -329,6 +329,49 @@ void csdr_amd_firdes_peak_c(csdr_complexf *taps, int length, float rate, int win
 long long csdr_amd_debug_rtty_walk(const csdr_amd_rtty_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
                                    int n_cuts, void *out);
 
+/* ------------------------------------------------------------------ squelch and S-meter (squelch.hip)
+ * squelch_and_smeter_cc csdr.c:2192-2243 with get_power_c libcsdr.c:1154-1162, for n_channels channels.  Each channel's stream is cut into blocks of
+ * block_size (B) samples counted from its start (the last reset).  A block's power is P = sum over its samples 0, d, 2d, .. of (i*i + q*q) / B with
+ * d = use_every_nth (the divisor is B, as in the reference); the block is written unchanged if level == 0 or P >= level, else as B complex +0.0 (a NaN power
+ * closes the gate unless the level is 0).  The sum runs in the library's own fixed order (squelch_dev.hpp): the power bits and the decision of a block do
+ * not depend on the kernel that served it, on the channel's position in the batch or on how the calls cut the stream; against the float64 power it lies
+ * within (ceil(B/d) + 8) 2^-24 P, as any float32 order does.
+ * create: levels = n_channels floats, or NULL = 0 = always open; process accepts up to max_samples_per_call samples per channel and call.
+ * process: any n_in per call (in: device, in_pitch samples apart).  The blocks that have become complete are emitted: out (device, out_pitch samples apart)
+ * receives them back to back, power / open_flags (device, both [n_channels][power_pitch], either may be NULL) their power and 1 = passed / 0 = zeroed,
+ * n_blocks_out (HOST, n_channels ints, may be NULL) each channel's count; the fewer than B samples behind a channel's last whole block stay in the object,
+ * so the output lags the input by up to B - 1 samples at a call boundary.  Returns the largest count of any channel (all equal unless reset_channel was
+ * used), or a negative code.  out_pitch >= that count * B; power_pitch >= that count: max_blocks() bounds it.  Asynchronous on the context's stream.
+ * set_level: takes effect from the next block that a later call starts (a block already begun keeps the level it began under, as the reference reads a new
+ * level behind a block's output); channel -1 sets all channels.  block_index: the number of blocks the channel has emitted since its reset = the index of
+ * its next block, for the report schedule below.  reset / reset_channel drop the held samples and the block count and keep the levels.
+ * kernel_name: "k_squelch_wave<4>" / "<16>" (one wave per block, B <= 512 / 2048), "k_squelch_wg<8>" / "<16>" / "<32>" (one workgroup per block, B <= 4096 /
+ * 8192 / 16384), each holding the block in registers between its one read and one write, or "k_squelch_generic" (two passes: larger blocks, odd B or pitch,
+ * unaligned pointers, calls that begin inside a block).  force_generic(1) takes k_squelch_generic always: the same bits. */
+typedef struct csdr_amd_squelch csdr_amd_squelch;
+csdr_amd_squelch *csdr_amd_squelch_create(csdr_amd_ctx *ctx, int n_channels, int block_size, int use_every_nth, const float *levels, long long max_samples_per_call);
+int  csdr_amd_squelch_process(csdr_amd_squelch *s, const csdr_complexf *in, long long n_in, size_t in_pitch, csdr_complexf *out, size_t out_pitch, float *power,
+                              size_t power_pitch, uint8_t *open_flags, int *n_blocks_out);
+int  csdr_amd_squelch_set_level(csdr_amd_squelch *s, int channel, float level);
+float csdr_amd_squelch_get_level(const csdr_amd_squelch *s, int channel);
+long long csdr_amd_squelch_block_index(const csdr_amd_squelch *s, int channel);
+int  csdr_amd_squelch_max_blocks(const csdr_amd_squelch *s);
+int  csdr_amd_squelch_reset(csdr_amd_squelch *s);
+int  csdr_amd_squelch_reset_channel(csdr_amd_squelch *s, int channel);
+int  csdr_amd_squelch_force_generic(csdr_amd_squelch *s, int on);
+const char *csdr_amd_squelch_kernel_name(const csdr_amd_squelch *s);
+void csdr_amd_squelch_destroy(csdr_amd_squelch *s);
+/* get_power_c / get_power_f libcsdr.c:1144-1162 on n_blocks consecutive blocks of block_size samples of each of n_streams rows (device, in_pitch samples apart):
+ * power_out (device) [n_streams][n_blocks], the same order and bits as the object's powers.  Stateless. */
+int  csdr_amd_get_power_c(csdr_amd_ctx *ctx, const csdr_complexf *in, int n_streams, int n_blocks, int block_size, int decimation, size_t in_pitch, float *power_out);
+int  csdr_amd_get_power_f(csdr_amd_ctx *ctx, const float *in, int n_streams, int n_blocks, int block_size, int decimation, size_t in_pitch, float *power_out);
+/* host: whether block block_index (0-based) reports its power, csdr.c:2224-2229 (`if (report_cntr++ > report_every_nth)`: the blocks with
+ * block_index mod (report_every_nth + 2) == report_every_nth + 1); the gate decision csdr.c:2230 */
+int  csdr_amd_squelch_report_due(int report_every_nth, long long block_index);
+int  csdr_amd_squelch_gate_open(float power, float level);
+/* the power step function on the host (the source the kernels run): one block of block_size samples at `in` (host; complex: interleaved i, q) */
+float csdr_amd_debug_squelch_power(const float *in, int block_size, int decimation, int is_complex);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

@@ -154,6 +154,9 @@ int log2n(int x);
 int next_pow2(int x);
 void apply_fir_fft_cc(FFT_PLAN_T *plan, FFT_PLAN_T *plan_inverse, complexf *taps_fft, complexf *last_overlap, int overlap_size);
 void gain_ff(float *input, float *output, int input_size, float gain);
+/* libcsdr.h: the power behind squelch_and_smeter_cc and every S-meter (the sum over samples 0, decimation, .. divided by input_size), on the device */
+float get_power_f(float *input, int input_size, int decimation);
+float get_power_c(complexf *input, int input_size, int decimation);
 
 /* f2 blocks: libcsdr.h:97-99, 110-116, 142-147; libcsdr_gpl.h:37 */
 float fmdemod_atan_cf(complexf *input, float *output, int input_size, float last_phase);
