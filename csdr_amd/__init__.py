@@ -172,6 +172,21 @@ def lib():
     L.csdr_amd_squelch_report_due.argtypes = [i, ll]
     L.csdr_amd_squelch_gate_open.argtypes = [fl, fl]
     L.csdr_amd_debug_squelch_power.restype = fl; L.csdr_amd_debug_squelch_power.argtypes = [vp, i, i, i]
+    L.csdr_amd_costas_params.argtypes = [fl, fl, i, vp]
+    L.csdr_amd_pll_params_p.argtypes = [fl, vp]
+    L.csdr_amd_pll_params_pi.argtypes = [fl, fl, fl, fl, vp]
+    L.csdr_amd_carrier_create.restype = vp; L.csdr_amd_carrier_create.argtypes = [vp, vp, i]
+    L.csdr_amd_carrier_process.argtypes = [vp, vp, ll, sz, vp, vp, vp, vp, sz]
+    L.csdr_amd_carrier_reset.argtypes = [vp]
+    L.csdr_amd_carrier_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_carrier_get_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_carrier_set_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_carrier_set_lanes.argtypes = [vp, i]
+    L.csdr_amd_carrier_lanes.argtypes = [vp]
+    L.csdr_amd_carrier_force_generic.argtypes = [vp, i]
+    L.csdr_amd_carrier_kernel_name.restype = C.c_char_p; L.csdr_amd_carrier_kernel_name.argtypes = [vp]
+    L.csdr_amd_carrier_destroy.argtypes = [vp]; L.csdr_amd_carrier_destroy.restype = None
+    L.csdr_amd_debug_carrier_walk.restype = ll; L.csdr_amd_debug_carrier_walk.argtypes = [vp, vp, ll, vp, i, vp, vp, vp, vp, vp]
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
@@ -927,6 +942,140 @@ class Squelch:
             pass
 
 
+class CarrierParams(C.Structure):
+    """csdr_amd_carrier_params"""
+    _fields_ = [("mode", C.c_int), ("alpha", C.c_float), ("beta", C.c_float), ("dphase_max", C.c_float), ("dphase_max_reset_to_zero", C.c_int)]
+
+
+class CarrierChan(C.Structure):
+    """csdr_amd_carrier_chan: one channel's state (nco_phase / output_phase, dphase, current_freq / iir_temp)"""
+    _fields_ = [("phase", C.c_float), ("dphase", C.c_float), ("freq", C.c_float)]
+
+
+CARRIER_MODES = {"costas": 0, "costas_dd": 1, "pll_p": 2, "pll_pi": 3}
+CARRIER_OUTPUTS = ("out", "error", "dphase", "nco")
+
+
+def costas_params(bandwidth, damping=0.707, decision_directed=False, dphase_max_reset_to_zero=False):
+    """what init_bpsk_costas_loop_cc (libcsdr.c:2094-2106) stores, as csdr_amd_carrier_params"""
+    p = CarrierParams()
+    lib().csdr_amd_costas_params(float(bandwidth), float(damping), int(bool(decision_directed)), C.byref(p))
+    p.dphase_max_reset_to_zero = int(bool(dphase_max_reset_to_zero))
+    return p
+
+
+def pll_params(pll_type, alpha=0.01, bandwidth=0.01, ko=10.0, kd=0.1, damping=0.707):
+    """pll_type 1 / "P": pll_cc_init_p_controller(alpha); 2 / "PI": pll_cc_init_pi_controller(bandwidth, ko, kd, damping) (libcsdr.c:1856-1871)"""
+    p = CarrierParams()
+    if pll_type in (1, "P", "p"):
+        lib().csdr_amd_pll_params_p(float(alpha), C.byref(p))
+    elif pll_type in (2, "PI", "pi"):
+        lib().csdr_amd_pll_params_pi(float(bandwidth), float(ko), float(kd), float(damping), C.byref(p))
+    else:
+        raise ValueError("pll_type is 1 (P) or 2 (PI)")
+    return p
+
+
+def _carrier_dtype(name):
+    return c64 if name in ("out", "nco") else f32
+
+
+def carrier_debug_walk(params, x, outputs=CARRIER_OUTPUTS, cuts=(), state=None):
+    """CPU run of the kernels' step function for one channel (csdr_amd_debug_carrier_walk): x cut into calls of `cuts` samples and the rest
+    -> {name: array} for the names in `outputs`.  state: a CarrierChan carried in and out."""
+    x = np.ascontiguousarray(x, c64)
+    res = {k: np.zeros(x.size, _carrier_dtype(k)) for k in outputs}
+    cu = np.ascontiguousarray(cuts, np.int64)
+    ptr = [_hp(res[k]) if k in res else None for k in CARRIER_OUTPUTS]
+    rc = lib().csdr_amd_debug_carrier_walk(C.byref(params), _hp(x), x.size, _hp(cu) if cu.size else None, cu.size, *ptr,
+                                           C.byref(state) if state is not None else None)
+    if rc < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return res
+
+
+class Carrier:
+    """csdr_amd_carrier: bpsk_costas_loop_cc / pll_cc for n_channels channels with shared loop coefficients; each channel's phase, dphase and freq stay
+    on the device between calls."""
+
+    def __init__(self, ctx, params, n_channels=1):
+        self.ctx, self.n_channels, self.params = ctx, n_channels, params
+        self.h = ctx.L.csdr_amd_carrier_create(ctx.h, C.byref(params), n_channels)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def process_dev(self, d_in, n, in_pitch, d_out=None, d_error=None, d_dphase=None, d_nco=None, out_pitch=0):
+        """device pointers, any output may be None but not all.  Asynchronous."""
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_process(self.h, d_in, n, in_pitch, d_out, d_error, d_dphase, d_nco, out_pitch), "carrier_process")
+
+    def process(self, x, outputs=("out",), calls=None, in_pitch=None, out_pitch=None):
+        """x: [n_channels, n] (or [n]) complex samples; outputs: names out of "out", "error", "dphase", "nco"; calls: per-call sample counts (default one
+        call); in_pitch / out_pitch: row pitches in samples (default: the row) -> {name: [n_channels, n] array} (1-D arrays for 1-D x)"""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        for k in outputs:
+            if k not in CARRIER_OUTPUTS:
+                raise ValueError("unknown output %r" % (k,))
+        calls = [n] if calls is None else [int(k) for k in calls]
+        ip = max(n, 1) if in_pitch is None else int(in_pitch)
+        op = max(max(calls) if calls else 0, 1) if out_pitch is None else int(out_pitch)
+        xin = np.zeros((s, ip), c64)
+        xin[:, :n] = x
+        di = self.ctx.upload(xin)
+        bufs = {k: self.ctx.alloc(np.dtype(_carrier_dtype(k)).itemsize * op * s + 256) for k in outputs}
+        res = {k: np.zeros((s, n), _carrier_dtype(k)) for k in outputs}
+        at = 0
+        for k in calls:
+            self.process_dev(di.at(8 * at), k, ip, *[bufs[nm].ptr if nm in bufs else None for nm in CARRIER_OUTPUTS], op)
+            for nm in outputs:
+                y = self.ctx.download(bufs[nm], _carrier_dtype(nm), op * s).reshape(s, op)
+                res[nm][:, at:at + k] = y[:, :k]
+            at += k
+        return {k: v[0] for k, v in res.items()} if squeeze else res
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_reset(self.h), "carrier_reset")
+
+    def reset_channel(self, ch):
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_reset_channel(self.h, int(ch)), "carrier_reset_channel")
+
+    def get_channel(self, ch):
+        st = CarrierChan()
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_get_channel(self.h, int(ch), C.byref(st)), "carrier_get_channel")
+        return st
+
+    def set_channel(self, ch, st):
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_set_channel(self.h, int(ch), C.byref(st)), "carrier_set_channel")
+
+    def set_lanes(self, lanes):
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_set_lanes(self.h, int(lanes)), "carrier_set_lanes")
+
+    def lanes(self):
+        return int(self.ctx.L.csdr_amd_carrier_lanes(self.h))
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_carrier_force_generic(self.h, int(on)), "carrier_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_carrier_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.csdr_amd_carrier_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Interpolator(_Resampling):
     """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
     _dt, _eb, _pre = c64, 8, "interp"
@@ -1336,6 +1485,11 @@ class Context:
     def squelch(self, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
         """A batched squelch_and_smeter_cc object (Squelch)"""
         return Squelch(self, n_channels, block_size, use_every_nth, levels, max_samples_per_call)
+
+    # ---- carrier recovery (carrier.hip)
+    def carrier(self, params, n_channels=1):
+        """A batched bpsk_costas_loop_cc / pll_cc object (Carrier); params from costas_params() or pll_params()"""
+        return Carrier(self, params, n_channels)
 
     def _get_power(self, x, block_size, decimation, dt, fn):
         x = np.ascontiguousarray(x, dt)

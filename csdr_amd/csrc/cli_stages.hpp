@@ -290,6 +290,37 @@ struct Squelch : Stage {   // squelch_and_smeter_cc csdr.c:2192-2243: blocks of 
     }
 };
 
+struct Carrier : Stage {   // bpsk_costas_loop_cc csdr.c:2834-2899 | pll_cc csdr.c:2532-2571: one sample out per sample in, the loop state on the device; every pass, the
+                          // stream's last partial one included, is processed whole (as the simple_agc_cc stage)
+    enum { OUT = 0, ERROR = 1, DPHASE = 2, NCO = 3, COMBINED = 4 };
+    Owned<csdr_amd_carrier, csdr_amd_carrier_destroy> p; int which; FILE *files[3]; CtxBuf<char> d_side; size_t side_cap = 0; std::vector<char> h_side;
+    Carrier(csdr_amd_ctx *c, const csdr_amd_carrier_params &pr, int w, FILE *f_error = nullptr, FILE *f_dphase = nullptr, FILE *f_nco = nullptr) : which(w)
+    {
+        files[0] = f_error; files[1] = f_dphase; files[2] = f_nco;
+        p.reset(csdr_amd_carrier_create(c, &pr, 1)); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = 8; out_elem = (w == ERROR || w == DPHASE) ? 4 : 8;
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        if (!n) return 0;
+        const csdr_complexf *x = (const csdr_complexf *)i;
+        if (which != COMBINED) {
+            MUST(csdr_amd_carrier_process(p.get(), x, (long long)n, n, which == OUT ? (csdr_complexf *)o : nullptr, which == ERROR ? (float *)o : nullptr,
+                                          which == DPHASE ? (float *)o : nullptr, which == NCO ? (csdr_complexf *)o : nullptr, n));
+            return (long)n;
+        }
+        // --output_combined: the samples to stdout; error, dphase and nco to their files (csdr.c:2887-2893).  One side buffer: nco (8 n bytes), error, dphase (4 n each)
+        if (n > side_cap) { d_side.reset(); side_cap = n + 8192; d_side = ctx_alloc<char>(c, 16 * side_cap, "malloc"); h_side.resize(16 * side_cap); }
+        csdr_complexf *d_nco = (csdr_complexf *)d_side.get(); float *d_err = (float *)(d_nco + n), *d_dph = d_err + n;
+        MUST(csdr_amd_carrier_process(p.get(), x, (long long)n, n, (csdr_complexf *)o, d_err, d_dph, d_nco, n));
+        MUST(csdr_amd_d2h(c, h_side.data(), d_side.get(), 16 * n));
+        fwrite(h_side.data() + 8 * n, 4, n, files[0]); fwrite(h_side.data() + 12 * n, 4, n, files[1]); fwrite(h_side.data(), 8, n, files[2]);
+        for (FILE *f : files) fflush(f);
+        return (long)n;
+    }
+};
+
 struct Interp : Stage {   // csdr.c:1179-1232: fir_interpolate_cc over the_bufsize windows, the first over a buffer of zeros
     csdr_amd_interp *p; int I;
     Interp(csdr_amd_ctx *c, int factor, float tbw, int window, int the_bufsize) : I(factor)
@@ -821,6 +852,45 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         sscanf(argv[7], "%d", &report_every_nth);
         if (report_every_nth <= 0) { badsyntax("report_every_nth <= 0 is invalid"); return nullptr; }
         return new Squelch(c, g_dynamic ? the_bufsize : unitround(g_fixed), decimation, report_every_nth, level, fd2, block);   // without the preamble protocol every reference process has its default buffer
+    }
+    if (cmd == "bpsk_costas_loop_cc") {                                             // csdr.c:2834-2873, its checks in its order
+        float bw = 0, damping = 0;
+        if (argc <= 2) { badsyntax("need required parameter (loop_bandwidth)"); return nullptr; }
+        sscanf(argv[2], "%f", &bw);
+        if (argc <= 3) { badsyntax("need required parameter (damping_factor)"); return nullptr; }
+        sscanf(argv[3], "%f", &damping);
+        // (the reference tests argv[5] for the long spelling and passes a mode its init never stores: here argv[4] alone selects the mode)
+        const int dd = argc > 4 && (!strcmp(argv[4], "--dd") || !strcmp(argv[4], "--decision_directed"));
+        if (dd) fprintf(stderr, "csdr %s: decision directed mode\n", g_cmd);
+        const char *opt = argc > 4 + dd ? argv[4 + dd] : "";
+        const int which = !strcmp(opt, "--output_error") ? Carrier::ERROR : !strcmp(opt, "--output_dphase") ? Carrier::DPHASE : !strcmp(opt, "--output_nco") ? Carrier::NCO
+                        : !strcmp(opt, "--output_combined") ? Carrier::COMBINED : Carrier::OUT;
+        csdr_amd_carrier_params pr; csdr_amd_costas_params(bw, damping, dd, &pr);
+        fprintf(stderr, "csdr %s: alpha = %f, beta = %f\n", g_cmd, pr.alpha, pr.beta);
+        FILE *f[3] = {nullptr, nullptr, nullptr};
+        if (which == Carrier::COMBINED) {
+            if (!(argc > 4 + dd + 3)) { badsyntax("need required parameters after --output_combined: <error_file> <dphase_file> <nco_file>"); return nullptr; }
+            for (int k = 0; k < 3; k++) { f[k] = fopen(argv[4 + dd + 1 + k], "w"); if (!f[k]) { badsyntax("error while opening an --output_combined file"); return nullptr; } }
+        }
+        return new Carrier(c, pr, which, f[0], f[1], f[2]);
+    }
+    if (cmd == "pll_cc") {                                                          // csdr.c:2532-2557: the NCO is the output
+        if (argc <= 2) { badsyntax("need required parameter (pll_type)"); return nullptr; }
+        int type = 0; sscanf(argv[2], "%d", &type);
+        csdr_amd_carrier_params pr;
+        if (type == 1) {
+            float alpha = 0.01f; if (argc > 3) sscanf(argv[3], "%f", &alpha);
+            csdr_amd_pll_params_p(alpha, &pr);
+        } else if (type == 2) {
+            float bandwidth = 0.01f, ko = 10, kd = 0.1f, damping = 0.707f;
+            if (argc > 3) sscanf(argv[3], "%f", &bandwidth);
+            if (argc > 4) sscanf(argv[4], "%f", &damping);
+            if (argc > 5) sscanf(argv[5], "%f", &ko);
+            if (argc > 6) sscanf(argv[6], "%f", &kd);
+            csdr_amd_pll_params_pi(bandwidth, ko, kd, damping, &pr);
+            fprintf(stderr, "csdr %s: bw=%f damping=%f ko=%f kd=%f alpha=%f beta=%f\n", g_cmd, bandwidth, damping, ko, kd, pr.alpha, pr.beta);
+        } else { badsyntax("invalid pll_type. Valid values are:\n\t1: PLL_P_CONTROLLER\n\t2: PLL_PI_CONTROLLER"); return nullptr; }
+        return new Carrier(c, pr, Carrier::NCO);
     }
     if (cmd == "convert_u8_f") return new Convert(0, 1, 4);
     if (cmd == "convert_f_u8") return new Convert(1, 4, 1);

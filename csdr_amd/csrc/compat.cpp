@@ -4,6 +4,7 @@
 // created the process is terminated with the reason (there is no CPU fallback).  Host-side code here is limited
 // to state bookkeeping, setup-time table generation and format plumbing around the copies.
 #include "common.hpp"
+#include "carrier_dev.hpp"
 #include "../../include/libcsdr_amd_compat.h"
 #include <math.h>
 #include <stdio.h>
@@ -485,6 +486,87 @@ float get_power_c(complexf *input, int input_size, int decimation)
     MUST(csdr_amd_get_power_c(ctx(), din, 1, 1, input_size, decimation, input_size, dout));
     float p = 0.f; fetch(&p, dout, 1);
     return p;
+}
+
+// ------------------------------------------------------------------ carrier recovery (carrier.hip)
+// One call = the thread's one-channel object with the caller's coefficients and state: state in, n samples, state out.
+static void run_carrier(const csdr_amd_carrier_params &pr, csdr_amd_carrier_chan *st, complexf *in, int n, complexf *out, float *error, float *dphase, complexf *nco)
+{
+    struct CrCache { csdr_amd_carrier *p = nullptr; csdr_amd_carrier_params pr; ~CrCache() { if (p && (long)syscall(SYS_gettid) != (long)getpid()) csdr_amd_carrier_destroy(p); } };
+    static thread_local CrCache cache;
+    if (!cache.p || memcmp(&cache.pr, &pr, sizeof pr)) {
+        if (cache.p) csdr_amd_carrier_destroy(cache.p);
+        cache.p = csdr_amd_carrier_create(ctx(), &pr, 1);
+        if (!cache.p) die("carrier_create", -3);
+        cache.pr = pr;
+    }
+    MUST(csdr_amd_carrier_set_channel(cache.p, 0, st));
+    complexf *din = stage_in<complexf>(4, in, n);
+    // one scratch slot for the four outputs: out, nco (8 bytes per sample), error, dphase (4 bytes)
+    char *d = stage_out<char>(5, 24 * (size_t)n);
+    complexf *dout = (complexf *)d, *dnco = dout + n; float *derr = (float *)(dnco + n), *ddph = derr + n;
+    MUST(csdr_amd_carrier_process(cache.p, (const csdr_complexf *)din, n, n, out ? (csdr_complexf *)dout : nullptr, error ? derr : nullptr, dphase ? ddph : nullptr,
+                                  nco ? (csdr_complexf *)dnco : nullptr, n));
+    if (out) fetch(out, dout, n);
+    if (error) fetch(error, derr, n);
+    if (dphase) fetch(dphase, ddph, n);
+    if (nco) fetch(nco, dnco, n);
+    MUST(csdr_amd_carrier_get_channel(cache.p, 0, st));
+}
+
+void init_bpsk_costas_loop_cc(bpsk_costas_loop_state_t *s, int, float damping_factor, float bandwidth)
+{   // libcsdr.c:2094-2106 (decision_directed is not stored there either)
+    csdr_amd_carrier_params pr;
+    csdr_amd_costas_params(bandwidth, damping_factor, 0, &pr);
+    s->alpha = pr.alpha; s->beta = pr.beta;
+    s->current_freq = s->dphase = s->nco_phase = 0;
+    s->dphase_max = pr.dphase_max;
+    s->dphase_max_reset_to_zero = 0;
+}
+
+void bpsk_costas_loop_cc(complexf *input, complexf *output, int input_size, float *output_error, float *output_dphase, complexf *output_nco, bpsk_costas_loop_state_t *s)
+{   // libcsdr.c:2108-2142
+    if (input_size <= 0) return;
+    csdr_amd_carrier_params pr; memset(&pr, 0, sizeof pr);
+    pr.mode = s->decision_directed ? CSDR_AMD_CARRIER_COSTAS_DD : CSDR_AMD_CARRIER_COSTAS;
+    pr.alpha = s->alpha; pr.beta = s->beta; pr.dphase_max = s->dphase_max; pr.dphase_max_reset_to_zero = s->dphase_max_reset_to_zero != 0;
+    csdr_amd_carrier_chan st = { s->nco_phase, s->dphase, s->current_freq };
+    run_carrier(pr, &st, input, input_size, output, output_error, output_dphase, output_nco);
+    s->nco_phase = st.phase; s->dphase = st.dphase; s->current_freq = st.freq;
+}
+
+void pll_cc_init_pi_controller(pll_t *p, float bandwidth, float ko, float kd, float damping_factor)
+{   // libcsdr.c:1856-1865
+    csdr_amd_carrier_params pr;
+    csdr_amd_pll_params_pi(bandwidth, ko, kd, damping_factor, &pr);
+    p->alpha = pr.alpha; p->beta = pr.beta;
+    p->iir_temp = p->dphase = p->output_phase = 0;
+}
+
+void pll_cc_init_p_controller(pll_t *p, float alpha)
+{   // libcsdr.c:1867-1871
+    p->alpha = alpha;
+    p->dphase = p->output_phase = 0;
+}
+
+void pll_cc(pll_t *p, complexf *input, float *output_dphase, complexf *output_nco, int input_size)
+{   // libcsdr.c:1874-1915
+    if (input_size <= 0) return;
+    if (p->pll_type != PLL_PI_CONTROLLER && p->pll_type != PLL_P_CONTROLLER) {     // :1878-1884, 1911: the phase moves on, the first NCO sample is written
+        p->output_phase = carrier_wrap_pm_pi(p->output_phase + p->dphase);
+        if (output_nco) carrier_sincos(p->output_phase, &output_nco[0].i, &output_nco[0].q);
+        return;
+    }
+    csdr_amd_carrier_params pr; memset(&pr, 0, sizeof pr);
+    pr.mode = p->pll_type == PLL_PI_CONTROLLER ? CSDR_AMD_CARRIER_PLL_PI : CSDR_AMD_CARRIER_PLL_P;
+    pr.alpha = p->alpha; pr.beta = pr.mode == CSDR_AMD_CARRIER_PLL_PI ? p->beta : 0.f;
+    csdr_amd_carrier_chan st = { p->output_phase, p->dphase, pr.mode == CSDR_AMD_CARRIER_PLL_PI ? p->iir_temp : 0.f };
+    float *dph = output_dphase;
+    std::vector<float> unused;
+    if (!output_dphase && !output_nco) { unused.resize(input_size); dph = unused.data(); }      // the state still has to move
+    run_carrier(pr, &st, input, input_size, nullptr, nullptr, dph, output_nco);
+    p->output_phase = st.phase; p->dphase = st.dphase;
+    if (pr.mode == CSDR_AMD_CARRIER_PLL_PI) p->iir_temp = st.freq;
 }
 
 char rtty_baudot_decoder_lookup(unsigned char *fig_mode, unsigned char c) { return csdr_amd_rtty_baudot_decoder_lookup(fig_mode, c); }   // libcsdr.c:1606-1613

@@ -372,6 +372,45 @@ int  csdr_amd_squelch_gate_open(float power, float level);
 /* the power step function on the host (the source the kernels run): one block of block_size samples at `in` (host; complex: interleaved i, q) */
 float csdr_amd_debug_squelch_power(const float *in, int block_size, int decimation, int is_complex);
 
+/* ------------------------------------------------------------------ carrier recovery (carrier.hip)
+ * bpsk_costas_loop_cc libcsdr.c:2094-2142 and pll_cc libcsdr.c:1856-1915 for n_channels channels: the loop coefficients are shared, each channel has its
+ * own state (phase, dphase, freq), kept on the device between calls.  Every float operation is the reference's, in its order; cos, sin and atan2 are taken
+ * in double from the float argument and rounded (carrier_dev.hpp).  A call over a whole stream and any cut of it into calls, any batch position, any
+ * set_lanes and either kernel give the same bits.
+ * params: mode COSTAS (error = PI out.i out.q) / COSTAS_DD (the decision-directed atan2 error) / PLL_P / PLL_PI; alpha, beta; dphase_max and
+ * dphase_max_reset_to_zero (Costas only).  |alpha|, |beta| <= 64 and 0 <= dphase_max <= 64 keep a sample's phase wraps to a few turns; a wrap ends after
+ * 1024 turns in any case, where the reference is on its way to a hang.  The helpers compute what init_bpsk_costas_loop_cc, pll_cc_init_p_controller and
+ * pll_cc_init_pi_controller store, to the bit.
+ * process: in (device, in_pitch samples apart), n samples per channel; out, error, dphase, nco (device, each out_pitch of its own elements apart) receive n
+ * items per channel; any may be NULL, not all.  Costas: out = in * nco, error, dphase (after the clamp), nco = (cos, sin) of the phase before the step.
+ * PLL: nco = (sin, cos) of the advanced phase and dphase = -dphase, the reference's outputs; out and error must be NULL.  Asynchronous on the context's
+ * stream.  n = 0 is a no-op.
+ * set_lanes: channels per wave, 0 = automatic .. 64.  kernel_name: "k_carrier_tiled" (input and outputs staged through LDS in
+ * coalesced tiles) or "k_carrier" (one lane per channel on global memory: pointers that are not 8-byte aligned, or force_generic(1)). */
+enum { CSDR_AMD_CARRIER_COSTAS = 0, CSDR_AMD_CARRIER_COSTAS_DD = 1, CSDR_AMD_CARRIER_PLL_P = 2, CSDR_AMD_CARRIER_PLL_PI = 3 };
+typedef struct csdr_amd_carrier_params { int mode; float alpha, beta, dphase_max; int dphase_max_reset_to_zero; } csdr_amd_carrier_params;
+typedef struct csdr_amd_carrier_chan { float phase, dphase, freq; } csdr_amd_carrier_chan;   /* nco_phase / output_phase, dphase, current_freq / iir_temp */
+typedef struct csdr_amd_carrier csdr_amd_carrier;
+int  csdr_amd_costas_params(float bandwidth, float damping, int decision_directed, csdr_amd_carrier_params *p);
+int  csdr_amd_pll_params_p(float alpha, csdr_amd_carrier_params *p);
+int  csdr_amd_pll_params_pi(float bandwidth, float ko, float kd, float damping, csdr_amd_carrier_params *p);
+csdr_amd_carrier *csdr_amd_carrier_create(csdr_amd_ctx *ctx, const csdr_amd_carrier_params *params, int n_channels);
+int  csdr_amd_carrier_process(csdr_amd_carrier *p, const csdr_complexf *in, long long n, size_t in_pitch, csdr_complexf *out, float *error, float *dphase,
+                              csdr_complexf *nco, size_t out_pitch);
+int  csdr_amd_carrier_reset(csdr_amd_carrier *p);
+int  csdr_amd_carrier_reset_channel(csdr_amd_carrier *p, int channel);
+int  csdr_amd_carrier_get_channel(csdr_amd_carrier *p, int channel, csdr_amd_carrier_chan *out);
+int  csdr_amd_carrier_set_channel(csdr_amd_carrier *p, int channel, const csdr_amd_carrier_chan *state);   /* finite, each magnitude <= 1024 */
+int  csdr_amd_carrier_set_lanes(csdr_amd_carrier *p, int lanes);
+int  csdr_amd_carrier_lanes(const csdr_amd_carrier *p);
+int  csdr_amd_carrier_force_generic(csdr_amd_carrier *p, int on);
+const char *csdr_amd_carrier_kernel_name(const csdr_amd_carrier *p);
+void csdr_amd_carrier_destroy(csdr_amd_carrier *p);
+/* the kernels' step function on the host for one channel, the stream cut into calls of cuts[0], cuts[1], ... samples and the rest; outputs may be NULL;
+ * state_io (may be NULL: a fresh channel) carries the state in and out.  Returns n or a negative code. */
+long long csdr_amd_debug_carrier_walk(const csdr_amd_carrier_params *params, const csdr_complexf *in, long long n, const long long *cuts, int n_cuts,
+                                      csdr_complexf *out, float *error, float *dphase, csdr_complexf *nco, csdr_amd_carrier_chan *state_io);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

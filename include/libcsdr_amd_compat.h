@@ -158,6 +158,20 @@ void gain_ff(float *input, float *output, int input_size, float gain);
 float get_power_f(float *input, int input_size, int decimation);
 float get_power_c(complexf *input, int input_size, int decimation);
 
+/* carrier recovery, libcsdr.h:292-312, 364-378: the loop runs on the device, its state goes in and comes out through the caller's struct.
+ * init_bpsk_costas_loop_cc does not store decision_directed and pll_cc_init_p_controller leaves iir_temp and pll_type alone, as in the reference;
+ * pll_cc with any other pll_type advances the phase, writes output_nco[0] and returns. */
+typedef enum pll_type_e { PLL_P_CONTROLLER = 1, PLL_PI_CONTROLLER = 2 } pll_type_t;
+typedef struct pll_s { pll_type_t pll_type; float output_phase; float dphase; float frequency; float alpha; float beta; float iir_temp; } pll_t;
+void pll_cc_init_pi_controller(pll_t *p, float bandwidth, float ko, float kd, float damping_factor);
+void pll_cc_init_p_controller(pll_t *p, float alpha);
+void pll_cc(pll_t *p, complexf *input, float *output_dphase, complexf *output_nco, int input_size);
+typedef struct bpsk_costas_loop_state_s {
+    float alpha; float beta; int decision_directed; float current_freq; float dphase; float nco_phase; float dphase_max; int dphase_max_reset_to_zero;
+} bpsk_costas_loop_state_t;
+void bpsk_costas_loop_cc(complexf *input, complexf *output, int input_size, float *output_error, float *output_dphase, complexf *output_nco, bpsk_costas_loop_state_t *s);
+void init_bpsk_costas_loop_cc(bpsk_costas_loop_state_t *s, int decision_directed, float damping_factor, float bandwidth);
+
 /* f2 blocks: libcsdr.h:97-99, 110-116, 142-147; libcsdr_gpl.h:37 */
 float fmdemod_atan_cf(complexf *input, float *output, int input_size, float last_phase);
 void amdemod_cf(complexf *input, float *output, int input_size);
