@@ -187,6 +187,21 @@ def lib():
     L.csdr_amd_carrier_kernel_name.restype = C.c_char_p; L.csdr_amd_carrier_kernel_name.argtypes = [vp]
     L.csdr_amd_carrier_destroy.argtypes = [vp]; L.csdr_amd_carrier_destroy.restype = None
     L.csdr_amd_debug_carrier_walk.restype = ll; L.csdr_amd_debug_carrier_walk.argtypes = [vp, vp, ll, vp, i, vp, vp, vp, vp, vp]
+    L.csdr_amd_fmmod_fc.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
+    L.csdr_amd_dsb_fc.argtypes = [vp, vp, vp, sz, fl]
+    L.csdr_amd_add_dcoffset_cc.argtypes = [vp, vp, vp, sz]
+    L.csdr_amd_fixed_amplitude_cc.argtypes = [vp, vp, vp, sz, fl]
+    L.csdr_amd_convert_f_samplerf.argtypes = [vp, vp, vp, sz, C.c_uint]
+    L.csdr_amd_debug_fmmod_walk.restype = ll; L.csdr_amd_debug_fmmod_walk.argtypes = [vp, ll, vp, i, vp, vp, vp]
+    L.csdr_amd_txbank_create.restype = vp; L.csdr_amd_txbank_create.argtypes = [vp, i, i, fl, fl, i, vp, i, vp, i, sz]
+    L.csdr_amd_txbank_process.argtypes = [vp, vp, sz, ll, vp, sz, C.POINTER(ll)]
+    L.csdr_amd_txbank_set_rate.argtypes = [vp, i, fl]
+    L.csdr_amd_txbank_get_rate.restype = fl; L.csdr_amd_txbank_get_rate.argtypes = [vp, i]
+    L.csdr_amd_txbank_reset.argtypes = [vp]
+    L.csdr_amd_txbank_max_out.restype = ll; L.csdr_amd_txbank_max_out.argtypes = [vp, ll]
+    L.csdr_amd_txbank_force_generic.argtypes = [vp, i]
+    L.csdr_amd_txbank_kernel_name.restype = C.c_char_p; L.csdr_amd_txbank_kernel_name.argtypes = [vp]
+    L.csdr_amd_txbank_destroy.argtypes = [vp]; L.csdr_amd_txbank_destroy.restype = None
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]
@@ -1076,6 +1091,102 @@ class Carrier:
             pass
 
 
+TX_MODES = {"fm": 0, "am": 1, "dsb": 2}
+TX_FORMATS = {"cf32": 0, "u8": 1}
+
+
+def fmmod_debug_walk(x, cuts=(), state=0.0, want_out=False):
+    """CPU run of fmmod_fc's phase step function for one stream (csdr_amd_debug_fmmod_walk): x cut into calls of `cuts` samples and the rest
+    -> (phase after every sample, last_phase[, outputs])"""
+    x = np.ascontiguousarray(x, f32)
+    ph = np.zeros(x.size, f32)
+    out = np.zeros(x.size, c64) if want_out else None
+    cu = np.ascontiguousarray(cuts, np.int64)
+    st = C.c_float(state)
+    rc = lib().csdr_amd_debug_fmmod_walk(_hp(x), x.size, _hp(cu) if cu.size else None, cu.size, _hp(ph), _hp(out) if want_out else None, C.byref(st))
+    if rc < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return (ph, np.float32(st.value), out) if want_out else (ph, np.float32(st.value))
+
+
+class TxBank:
+    """csdr_amd_txbank: convert_s16_f | gain_ff | fmmod_fc or dsb_fc [| add_dcoffset_cc] | fir_interpolate_cc | shift_addition_cc [| convert_f_u8] for
+    n_streams s16 audio streams, each with its own shift rate; FM phase, interpolator history and rotator phase stay on the device between calls."""
+
+    def __init__(self, ctx, n_streams, mode, interpolation, taps, rates, gain=1.0, q_value=0.0, out_format="cf32", max_in_samples=1 << 16):
+        self.ctx, self.n_streams, self.I, self.fmt = ctx, n_streams, interpolation, out_format
+        self.taps = np.ascontiguousarray(taps, f32)
+        rates = np.ascontiguousarray(rates, f32)
+        if rates.size != n_streams:
+            raise ValueError("%d rates for %d streams" % (rates.size, n_streams))
+        self.max_in = int(max_in_samples)
+        self.h = ctx.L.csdr_amd_txbank_create(ctx.h, n_streams, TX_MODES[mode], gain, q_value, interpolation, _hp(self.taps), self.taps.size, _hp(rates),
+                                              TX_FORMATS[out_format], self.max_in)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def process_dev(self, d_in, in_pitch, n_in, d_out, out_pitch):
+        """device pointers, pitches in samples -> outputs per stream.  Asynchronous."""
+        no = C.c_longlong(0)
+        self.ctx.check(self.ctx.L.csdr_amd_txbank_process(self.h, d_in, in_pitch, n_in, d_out, out_pitch, C.byref(no)), "txbank_process")
+        return no.value
+
+    def process(self, x, calls=None, out_pitch=None, out_byte_offset=0):
+        """x: [n_streams, n] (or [n]) int16; calls: per-call sample counts (default one call); out_pitch: the output row pitch in samples (default: a
+        multiple of 8 that holds the largest call); out_byte_offset shifts the output pointer -> [n_streams, n_out] complex64, or [n_streams, n_out, 2] uint8"""
+        x = np.ascontiguousarray(x, np.int16)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_streams:
+            raise ValueError("x has %d rows for %d streams" % (s, self.n_streams))
+        calls = [n] if calls is None else [int(k) for k in calls]
+        esz, dt = (2, np.uint8) if self.fmt == "u8" else (8, f32)
+        op = ((max(self.max_out(max(calls)) if calls else 0, 1) + 7) & ~7) if out_pitch is None else int(out_pitch)
+        di = self.ctx.upload(np.concatenate([x.ravel(), np.zeros(8, np.int16)]))
+        do = self.ctx.alloc(esz * op * s + 256)
+        parts, at = [], 0
+        for k in calls:
+            no = self.process_dev(di.at(2 * at), n, k, do.at(out_byte_offset), op)
+            y = self.ctx.download(do, dt, (esz // dt().itemsize) * op * s, out_byte_offset).reshape(s, op, -1)
+            parts.append(y[:, :no].copy())
+            at += k
+        y = np.concatenate(parts, axis=1) if parts else np.zeros((s, 0, 2), dt)
+        if self.fmt != "u8":
+            y = np.ascontiguousarray(y).view(c64)[:, :, 0]
+        return y[0] if squeeze else y
+
+    def set_rate(self, stream, rate):
+        self.ctx.check(self.ctx.L.csdr_amd_txbank_set_rate(self.h, int(stream), float(rate)), "txbank_set_rate")
+
+    def get_rate(self, stream):
+        return float(self.ctx.L.csdr_amd_txbank_get_rate(self.h, int(stream)))
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_txbank_reset(self.h), "txbank_reset")
+
+    def max_out(self, n_in):
+        return int(self.ctx.L.csdr_amd_txbank_max_out(self.h, int(n_in)))
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_txbank_force_generic(self.h, int(on)), "txbank_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_txbank_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.csdr_amd_txbank_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Interpolator(_Resampling):
     """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
     _dt, _eb, _pre = c64, 8, "interp"
@@ -1253,6 +1364,34 @@ class Context:
     def amdemod_estimator_cf(self, x, alpha=0.0, beta=0.0): return self._cf_to_f(self.L.csdr_amd_amdemod_estimator_cf, x, alpha, beta)
     def realpart_cf(self, x): return self._cf_to_f(self.L.csdr_amd_realpart_cf, x)
     def logpower_cf(self, x, add_db=0.0): return self._cf_to_f(self.L.csdr_amd_logpower_cf, x, add_db)
+
+    # ---- transmit-side modulators (txmod.hip)
+    def fmmod_fc(self, x, phase=None, calls=None, in_pitch=None, out_pitch=None):
+        """x: [n] or [streams, n] float32; phase: last_phase per stream; calls: per-call sample counts -> (complex [streams, n], last_phase [streams])"""
+        x2, squeeze = self._2d(x, f32)
+        s, n = x2.shape
+        ph = np.zeros(s, f32) if phase is None else np.ascontiguousarray(phase, f32).reshape(s).copy()
+        calls = [n] if calls is None else [int(k) for k in calls]
+        ip = max(n, 1) if in_pitch is None else int(in_pitch)
+        op = max(n, 1) if out_pitch is None else int(out_pitch)
+        xin = np.zeros((s, ip), f32); xin[:, :n] = x2
+        di = self.upload(xin); do = self.alloc(8 * s * op + 64); dl = self.upload(ph)
+        at = 0
+        for k in calls:
+            self.check(self.L.csdr_amd_fmmod_fc(self.h, di.at(4 * at), do.at(8 * at), s, k, ip, op, dl.ptr), "fmmod_fc"); at += k
+        y = self.download(do, c64, s * op).reshape(s, op)[:, :n].copy(); lo = self.download(dl, f32, s)
+        return (y[0], lo[0]) if squeeze else (y, lo)
+
+    def _flat(self, fn, x, in_dt, out_dt, out_per_in, *extra):
+        x = np.ascontiguousarray(x, in_dt).ravel()
+        di = self.upload(x); do = self.alloc(np.dtype(out_dt).itemsize * out_per_in * x.size + 64)
+        self.check(fn(self.h, di.ptr, do.ptr, x.size, *extra), fn.__name__)
+        return self.download(do, out_dt, out_per_in * x.size)
+
+    def dsb_fc(self, x, q_value=0.0): return self._flat(self.L.csdr_amd_dsb_fc, x, f32, c64, 1, q_value)
+    def add_dcoffset_cc(self, x): return self._flat(self.L.csdr_amd_add_dcoffset_cc, x, c64, c64, 1)
+    def fixed_amplitude_cc(self, x, amp): return self._flat(self.L.csdr_amd_fixed_amplitude_cc, x, c64, c64, 1, amp)
+    def convert_f_samplerf(self, x, wait): return self._flat(self.L.csdr_amd_convert_f_samplerf, x, f32, np.uint8, 16, int(wait))
 
     def fmdemod_atan_cf(self, x, last_phase=None, calls=1):
         x2, squeeze = self._2d(x, c64)
@@ -1490,6 +1629,10 @@ class Context:
     def carrier(self, params, n_channels=1):
         """A batched bpsk_costas_loop_cc / pll_cc object (Carrier); params from costas_params() or pll_params()"""
         return Carrier(self, params, n_channels)
+
+    def txbank(self, n_streams, mode, interpolation, taps, rates, **kw):
+        """The fused transmit bank (TxBank): mode "fm", "am" or "dsb"; kw: gain, q_value, out_format ("cf32" / "u8"), max_in_samples"""
+        return TxBank(self, n_streams, mode, interpolation, taps, rates, **kw)
 
     def _get_power(self, x, block_size, decimation, dt, fn):
         x = np.ascontiguousarray(x, dt)

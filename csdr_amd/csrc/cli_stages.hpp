@@ -599,6 +599,28 @@ struct FmdemodAtan : Stage {   // csdr.c:962-977
     long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
     { *cons = n; MUST(csdr_amd_fmdemod_atan_cf(c, (const csdr_complexf *)i, (float *)o, 1, n, n, n, d_last)); return (long)n; }
 };
+// ------------------------------------------------------------------ transmit-side modulators (csdr.c:2084-2172)
+struct TxFlat : Stage {        // dsb_fc / add_dcoffset_cc / fixed_amplitude_cc / convert_f_samplerf
+    int op; float p0; unsigned wait;
+    TxFlat(int o, float a, unsigned w) : op(o), p0(a), wait(w) { in_elem = o == 0 || o == 3 ? 4 : 8; out_elem = o == 3 ? 16 : 8; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        switch (op) {
+            case 0: MUST(csdr_amd_dsb_fc(c, (const float *)i, (csdr_complexf *)o, n, p0)); break;
+            case 1: MUST(csdr_amd_add_dcoffset_cc(c, (const csdr_complexf *)i, (csdr_complexf *)o, n)); break;
+            case 2: MUST(csdr_amd_fixed_amplitude_cc(c, (const csdr_complexf *)i, (csdr_complexf *)o, n, p0)); break;
+            default: MUST(csdr_amd_convert_f_samplerf(c, (const float *)i, o, n, wait)); break;
+        }
+        return (long)n;
+    }
+};
+struct Fmmod : Stage {         // csdr.c:2142-2154: last_phase carried from read to read
+    float *d_phase;
+    Fmmod(csdr_amd_ctx *c) { in_elem = 4; out_elem = 8; d_phase = (float *)csdr_amd_malloc(c, 4); MUST(csdr_amd_memset(c, d_phase, 0, 4)); }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    { *cons = n; MUST(csdr_amd_fmmod_fc(c, (const float *)i, (csdr_complexf *)o, 1, n, n, n, d_phase)); return (long)n; }
+};
 struct DcBlock : Stage {       // csdr.c:927-939 (a = 0 selects 0.999)
     float *d_state;
     DcBlock(csdr_amd_ctx *c) { d_state = (float *)csdr_amd_malloc(c, 8); MUST(csdr_amd_memset(c, d_state, 0, 8)); }
@@ -1002,6 +1024,17 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
     if (cmd == "logpower_cf") { float add_db = 0; if (argc >= 3) sscanf(argv[2], "%g", &add_db); return new CfToF(3, add_db); }
     if (cmd == "gain_ff") { if (argc <= 2) { badsyntax("need required parameter (gain)"); return nullptr; } float g; sscanf(argv[2], "%g", &g); return new Gain(g); }
     if (cmd == "fmdemod_atan_cf") return new FmdemodAtan(c);
+    if (cmd == "dsb_fc") { float q = 0; if (argc >= 3) sscanf(argv[2], "%g", &q); return new TxFlat(0, q, 0); }
+    if (cmd == "add_dcoffset_cc") return new TxFlat(1, 0, 0);
+    if (cmd == "fixed_amplitude_cc") {
+        if (argc <= 2) { badsyntax("need required parameter (new_amplitude)"); return nullptr; }
+        float a = 0; sscanf(argv[2], "%g", &a); return new TxFlat(2, a, 0);
+    }
+    if (cmd == "convert_f_samplerf") {
+        if (argc <= 2) { badsyntax("need required parameter (wait_for_this_sample)"); return nullptr; }
+        unsigned w = 0; sscanf(argv[2], "%u", &w); return new TxFlat(3, 0, w);
+    }
+    if (cmd == "fmmod_fc") return new Fmmod(c);
     if (cmd == "dcblock_ff") return new DcBlock(c);
     if (cmd == "fastdcblock_ff") { int b = 1024; if (argc >= 3) sscanf(argv[2], "%d", &b); if (b <= 0) { badsyntax("block size must be positive"); return nullptr; } return new FastDcBlock(c, b); }
     if (cmd == "agc_ff") {   // defaults csdr.c:1343-1361

@@ -815,6 +815,27 @@ void apply_window_c(complexf *in, complexf *out, int size, window_t window)
     free(w);
 }
 
+// ------------------------------------------------------------------ transmit-side modulators (txmod.hip), libcsdr.h:216-218
+float fmmod_fc(float *in, complexf *out, int n, float last_phase)
+{
+    if (n <= 0) return last_phase;
+    float *din = stage_in<float>(4, in, n); cf32 *dout = stage_out<cf32>(5, n); float *dl = stage_in<float>(6, &last_phase, 1);
+    MUST(csdr_amd_fmmod_fc(ctx(), din, (csdr_complexf *)dout, 1, n, n, n, dl));
+    fetch((cf32 *)out, dout, n);
+    float l; fetch(&l, dl, 1); return l;
+}
+void add_dcoffset_cc(complexf *in, complexf *out, int n)
+{
+    if (n <= 0) return;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); cf32 *dout = stage_out<cf32>(5, n);
+    MUST(csdr_amd_add_dcoffset_cc(ctx(), (const csdr_complexf *)din, (csdr_complexf *)dout, n)); fetch((cf32 *)out, dout, n);
+}
+void fixed_amplitude_cc(complexf *in, complexf *out, int n, float amp)
+{
+    if (n <= 0) return;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); cf32 *dout = stage_out<cf32>(5, n);
+    MUST(csdr_amd_fixed_amplitude_cc(ctx(), (const csdr_complexf *)din, (csdr_complexf *)dout, n, amp)); fetch((cf32 *)out, dout, n);
+}
 
 // ------------------------------------------------------------------ f3: IMA ADPCM (ima_adpcm.h:5-11)
 ima_adpcm_state_t encode_ima_adpcm_i16_u8(short *in, unsigned char *out, int n, ima_adpcm_state_t state)

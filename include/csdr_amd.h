@@ -411,6 +411,43 @@ void csdr_amd_carrier_destroy(csdr_amd_carrier *p);
 long long csdr_amd_debug_carrier_walk(const csdr_amd_carrier_params *params, const csdr_complexf *in, long long n, const long long *cuts, int n_cuts,
                                       csdr_complexf *out, float *error, float *dphase, csdr_complexf *nco, csdr_amd_carrier_chan *state_io);
 
+/* ------------------------------------------------------------------ the transmit side: analog modulators and the up-converter bank (txmod.hip)
+ * fmmod_fc libcsdr.c:1180-1192 for n_streams rows.  phase_io: device float[n_streams], last_phase in and out.  Bit-equal phases for every cut into calls. */
+int csdr_amd_fmmod_fc(csdr_amd_ctx *ctx, const float *in, csdr_complexf *out, int n_streams, size_t n, size_t in_pitch, size_t out_pitch, float *phase_io);
+/* dsb_fc csdr.c:2084-2102, add_dcoffset_cc libcsdr.c:1174-1178, fixed_amplitude_cc libcsdr.c:1194-1208: flat arrays */
+int csdr_amd_dsb_fc(csdr_amd_ctx *ctx, const float *in, csdr_complexf *out, size_t n, float q_value);
+int csdr_amd_add_dcoffset_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, size_t n);
+int csdr_amd_fixed_amplitude_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, size_t n, float new_amplitude);
+/* convert_f_samplerf csdr.c:2104-2127: 16 bytes per sample = (double)x, wait_for_this_sample, (unsigned)0 */
+int csdr_amd_convert_f_samplerf(csdr_amd_ctx *ctx, const float *in, void *out, size_t n, unsigned wait_for_this_sample);
+/* the phase step function of fmmod_fc on the host for one stream, the samples cut into calls of cuts[0], cuts[1], ... and the rest; phases (the phase after
+ * every sample) and out may be NULL; state_io (may be NULL: phase 0) carries last_phase in and out.  Returns n or a negative code. */
+long long csdr_amd_debug_fmmod_walk(const float *in, long long n, const long long *cuts, int n_cuts, float *phases, csdr_complexf *out, float *state_io);
+
+/* The fused transmit bank: for n_streams s16 audio streams the stream of
+ *     convert_s16_f | gain_ff gain | <modulator> | fir_interpolate_cc interpolation (taps) | shift_addition_cc rate[s] | [convert_f_u8]
+ * with <modulator> = fmmod_fc (CSDR_TX_FM), dsb_fc q_value | add_dcoffset_cc (CSDR_TX_AM) or dsb_fc q_value (CSDR_TX_DSB).
+ * The object keeps each stream's FM phase, the interpolator's last ceil((taps_length - 1) / interpolation) modulated samples and the rotator's phase on the
+ * device: a stream cut into calls anywhere (0-sample calls included) gives the bits of one call.  The output is fir_interpolate_cc (libcsdr.c:579-605) applied
+ * once to the whole modulated stream since the last reset.  The rotator is shift_addition_cc as the CLI runs it, in 1024-sample chunks (csdr.c:911-918) laid on
+ * the output stream from the first output after a reset or a retune, the float phase carried from chunk to chunk.  set_rate takes effect from the first output
+ * of the next process call: the phase is carried and the chunk grid restarts there.  Rates are -0.5 .. 0.5.
+ * process: in_s16 [n_streams][in_pitch] s16 samples, out [n_streams][out_pitch] complex samples (cf32, or u8 pairs), pitches in samples; *n_out <= max_out(n_in).
+ * k_tx_up needs a 16-byte aligned out and row pitch; anything else takes k_tx_up_generic: the same bits. */
+enum { CSDR_TX_FM = 0, CSDR_TX_AM = 1, CSDR_TX_DSB = 2 };
+enum { CSDR_TX_OUT_CF32 = 0, CSDR_TX_OUT_U8 = 1 };
+typedef struct csdr_amd_txbank csdr_amd_txbank;
+csdr_amd_txbank *csdr_amd_txbank_create(csdr_amd_ctx *ctx, int n_streams, int mode, float gain, float q_value, int interpolation, const float *host_taps,
+                                        int taps_length, const float *shift_rates, int out_format, size_t max_in_samples);
+int  csdr_amd_txbank_process(csdr_amd_txbank *p, const int16_t *in_s16, size_t in_pitch, long long n_in, void *out, size_t out_pitch, long long *n_out);
+int  csdr_amd_txbank_set_rate(csdr_amd_txbank *p, int stream, float rate);
+float csdr_amd_txbank_get_rate(const csdr_amd_txbank *p, int stream);
+int  csdr_amd_txbank_reset(csdr_amd_txbank *p);                        /* phases and history; the rates stay as last set */
+long long csdr_amd_txbank_max_out(const csdr_amd_txbank *p, long long n_in);
+int  csdr_amd_txbank_force_generic(csdr_amd_txbank *p, int on);
+const char *csdr_amd_txbank_kernel_name(const csdr_amd_txbank *p);
+void csdr_amd_txbank_destroy(csdr_amd_txbank *p);
+
 /* ------------------------------------------------------------------ f2: the remaining simple blocks
  * amdemod_cf / amdemod_estimator_cf libcsdr.c:861-901, realpart_cf csdr.c:634-645, logpower_cf libcsdr.c:1296-1303: flat arrays */
 int csdr_amd_amdemod_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float *out, size_t n);

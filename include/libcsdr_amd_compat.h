@@ -172,6 +172,11 @@ typedef struct bpsk_costas_loop_state_s {
 void bpsk_costas_loop_cc(complexf *input, complexf *output, int input_size, float *output_error, float *output_dphase, complexf *output_nco, bpsk_costas_loop_state_t *s);
 void init_bpsk_costas_loop_cc(bpsk_costas_loop_state_t *s, int decision_directed, float damping_factor, float bandwidth);
 
+/* transmit-side modulators, libcsdr.h:216-218: fmmod_fc returns the phase to hand to the next call */
+void add_dcoffset_cc(complexf *input, complexf *output, int input_size);
+float fmmod_fc(float *input, complexf *output, int input_size, float last_phase);
+void fixed_amplitude_cc(complexf *input, complexf *output, int input_size, float amp);
+
 /* f2 blocks: libcsdr.h:97-99, 110-116, 142-147; libcsdr_gpl.h:37 */
 float fmdemod_atan_cf(complexf *input, float *output, int input_size, float last_phase);
 void amdemod_cf(complexf *input, float *output, int input_size);
