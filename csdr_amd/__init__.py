@@ -227,6 +227,7 @@ def lib():
     L.csdr_amd_fir_decimate_cc.argtypes = [vp, vp, vp, i, i, sz, sz, i, vp, i]
     L.csdr_amd_fir_last_kernel.restype = C.c_char_p; L.csdr_amd_fir_last_kernel.argtypes = []
     L.csdr_amd_fir_last_instance.restype = C.c_char_p; L.csdr_amd_fir_last_instance.argtypes = []
+    L.csdr_amd_audio_last_path.restype = C.c_char_p; L.csdr_amd_audio_last_path.argtypes = []
     L.csdr_amd_fir_ff_last_instance.restype = C.c_char_p; L.csdr_amd_fir_ff_last_instance.argtypes = []
     L.csdr_amd_fir_ff.argtypes = [vp, vp, vp, i, i, sz, sz, vp, i]
     L.csdr_amd_fmdemod_quadri_cf.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
@@ -238,6 +239,8 @@ def lib():
     L.csdr_amd_fracdec_destroy.argtypes = [vp]
     L.csdr_amd_fractional_decimator_ff.argtypes = [vp, vp, vp, vp, i, i, sz, sz, C.POINTER(i)]
     L.csdr_amd_fracdec_set_cli_bufsize.restype = None; L.csdr_amd_fracdec_set_cli_bufsize.argtypes = [vp, i]
+    L.csdr_amd_fracdec_set_where.restype = None; L.csdr_amd_fracdec_set_where.argtypes = [vp, fl]
+    L.csdr_amd_fracdec_get_where.restype = fl; L.csdr_amd_fracdec_get_where.argtypes = [vp]
     L.csdr_amd_fftfilt_create.restype = vp; L.csdr_amd_fftfilt_create.argtypes = [vp, i, vp, i, i, i]
     L.csdr_amd_fftfilt_destroy.argtypes = [vp]
     L.csdr_amd_fftfilt_input_size.argtypes = [vp]

@@ -27,11 +27,20 @@ __global__ __launch_bounds__(256) void k_fmdemod(const cf32 *__restrict__ in, fl
         const float dq = x.q - p.q, di = x.i - p.i;
         const float num = x.i * dq - x.q * di;
         const float den = x.i * x.i + x.q * x.q;
-        // the reference scales and divides in double (:1067) and rounds once; a float product with a Newton-refined reciprocal is within 2 ulp of
-        // that (gate: 1e-5 relative RMS) and avoids the ~25-instruction fp64 division sequence that made this kernel arithmetic bound
-        float rd = __builtin_amdgcn_rcpf(den);
-        rd = fmaf(fmaf(-den, rd, 1.0f), rd, rd);
-        dst[k] = (den != 0.f) ? (Kf * num) * rd : 0.f;
+        // the reference scales and divides in double (:1067) and rounds once; a float product with a Newton-refined reciprocal is within a few ulp of
+        // that (tests/audio_model.py derives the gate) and avoids the ~25-instruction fp64 division sequence that made this kernel arithmetic bound.
+        // v_rcp_f32 takes a subnormal den as 0 (-> inf, and the refinement then gives NaN) and flushes 1 / den to 0 above den = 2^126, and Kf * num
+        // loses bits once it is subnormal: outside a window that leaves all three (and the refinement's residual) far inside the normal range the
+        // reference's own expression runs instead.  Signals at |x| ~ 1 never leave the window; the compare is the only cost there.
+        const float an = fabsf(num);
+        float v;
+        if (den >= 0x1p-60f && den <= 0x1p60f && (an >= 0x1p-100f || an == 0.f)) {
+            float rd = __builtin_amdgcn_rcpf(den);
+            rd = fmaf(fmaf(-den, rd, 1.0f), rd, rd);
+            v = (Kf * num) * rd;
+        } else
+            v = (den != 0.f) ? (float)(0.340447550238101026565118445432744920253753662109375 * (double)num / (double)den) : 0.f;
+        dst[k] = v;
     }
 }
 __global__ void k_store_last(const cf32 *__restrict__ in, size_t n, size_t in_pitch, cf32 *__restrict__ last, int n_streams)
@@ -305,6 +314,10 @@ __global__ __launch_bounds__(256) void k_fracdec_plan(const FdWin *__restrict__ 
 
 } // namespace
 
+// the kernel path the calling thread's last deemphasis_wfm_ff / agc_ff / fractional_decimator_ff call took (host side only; f2blocks.hip sets it for agc_ff)
+static thread_local const char *g_audio_last_path = "";
+void csdr_amd::set_audio_last_path(const char *path) { g_audio_last_path = path; }
+
 struct csdr_amd_fracdec {
     float where, rate; int input_processed, num_poly_points, xifirst, xilast, taps_length;
     std::vector<float> denom, taps;
@@ -317,6 +330,8 @@ struct csdr_amd_fracdec {
 };
 
 extern "C" {
+
+const char *csdr_amd_audio_last_path(void) { return g_audio_last_path; }
 
 int csdr_amd_fmdemod_quadri_cf(csdr_amd_ctx *c, const csdr_complexf *in, float *out, int n_streams, size_t n,
                                size_t in_pitch, size_t out_pitch, csdr_complexf *last_io)
@@ -359,6 +374,7 @@ int csdr_amd_deemphasis_wfm_ff(csdr_amd_ctx *c, const float *in, float *out, int
     if (n_streams < 32 && n >= 8 * (size_t)DW_L && b > 0.0 && b < 1.0 && in != out) for (int m : {1, 2, 4, 8}) if (256.0 * m * log2(b) < -40.0) { M = m; break; }
     static const bool serial_env = getenv("CSDR_AMD_DEEMPH_SERIAL") != nullptr;       // (A/B, read once per process)
     if (M && !serial_env) {
+        g_audio_last_path = M == 1 ? "k_deemph_wfm_spec<1>" : M == 2 ? "k_deemph_wfm_spec<2>" : M == 4 ? "k_deemph_wfm_spec<4>" : "k_deemph_wfm_spec<8>";
         const size_t n_chunks = (n + DW_L - 1) / DW_L;
         float *st = (float *)c->get_scratch(0, sizeof(float) * 2 * n_chunks * (size_t)n_streams + 256);
         if (!st) return -2;
@@ -378,6 +394,7 @@ int csdr_amd_deemphasis_wfm_ff(csdr_amd_ctx *c, const float *in, float *out, int
         CSDR_LAUNCH_CHECK();
         return 0;
     }
+    g_audio_last_path = "k_deemph_wfm";
     hipLaunchKernelGGL(k_deemph_wfm, dim3(cdiv(n_streams, 64)), dim3(64), 0, c->stream, in, out, n_streams, n, in_pitch, out_pitch, alpha, last_io);
     CSDR_LAUNCH_CHECK();
     return 0;
@@ -442,7 +459,9 @@ int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const
                                      size_t in_pitch, size_t out_pitch, int *input_processed)
 {
     const int P = d->num_poly_points;
-    if (!(d->plan_valid && d->plan_where == d->where && d->plan_n == input_size && d->plan_bufsize == d->cli_bufsize)) {
+    const bool cached = d->plan_valid && d->plan_where == d->where && d->plan_n == input_size && d->plan_bufsize == d->cli_bufsize;
+    if (cached) g_audio_last_path = "fracdec:cached";
+    else {
         // Replay the reference's float position bookkeeping (libcsdr.c:762-792) on the host: it does not depend
         // on the samples, only on (where, rate, input_size).
         d->lo.clear(); d->frac.clear();
@@ -453,6 +472,7 @@ int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const
         int q = lsb_exp(where) < lsb_exp(d->rate) ? lsb_exp(where) : lsb_exp(d->rate); if (q > 0) q = 0;
         const int win_size = (d->cli_bufsize > 0 && input_size >= d->cli_bufsize) ? d->cli_bufsize : input_size;
         const bool exact = q > -40 && ldexp(1.0, q + 24) > (double)win_size + fabs((double)d->rate) + P + d->taps_length + 4 && where >= 0.f;
+        g_audio_last_path = exact ? "fracdec:exact" : "fracdec:walked";
         std::vector<FdWin> wins;
         int n_out = 0;
         // one call of fractional_decimator_ff over in[base .. base + size), exact rates: K outputs from where, then where <- where_K - processed, in closed form

@@ -359,7 +359,9 @@ int csdr_amd_agc_ff(csdr_amd_ctx *c, const float *in, float *out, int n_streams,
     if (!n || n_streams <= 0) return 0;
     if (block <= 0) return fail_msg(-3, "agc_ff: block must be positive");
     static const bool lane_env = getenv("CSDR_AMD_AGC_LANE") != nullptr;                // (A/B, read once per process)
-    if (n_streams < 64 && n >= 256 && !lane_env)
+    const bool coop = n_streams < 64 && n >= 256 && !lane_env;
+    set_audio_last_path(coop ? "k_agc_coop" : "k_agc");
+    if (coop)
         hipLaunchKernelGGL(k_agc_coop, dim3(n_streams), dim3(64), 0, c->stream, in, out, n, block, in_pitch, out_pitch, reference, attack_rate, decay_rate,
                            max_gain, hang_time, attack_wait_time, gain_filter_alpha, last_gain_io);
     else

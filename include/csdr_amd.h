@@ -143,6 +143,10 @@ int csdr_amd_fmdemod_quadri_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, float
 /* limit_ff / gain_ff libcsdr.c:1130-1142 (flat arrays) */
 int csdr_amd_limit_ff(csdr_amd_ctx *ctx, const float *in, float *out, size_t n, float max_amplitude);
 int csdr_amd_gain_ff(csdr_amd_ctx *ctx, const float *in, float *out, size_t n, float gain);
+/* the kernel path the calling thread's last call of one of these three took ("" before the first): csdr_amd_deemphasis_wfm_ff: k_deemph_wfm, k_deemph_wfm_spec<1> /
+ * <2> / <4> / <8>; csdr_amd_agc_ff: k_agc, k_agc_coop; csdr_amd_fractional_decimator_ff: fracdec:exact (plan on the device), fracdec:walked (host walk),
+ * fracdec:cached (the previous call's plan reused) */
+const char *csdr_amd_audio_last_path(void);
 /* deemphasis_wfm_ff libcsdr.c:1081-1097.  last_io: device float[n_streams]. */
 int csdr_amd_deemphasis_wfm_ff(csdr_amd_ctx *ctx, const float *in, float *out, int n_streams, size_t n,
                                size_t in_pitch, size_t out_pitch, float tau, int sample_rate, float *last_io);
