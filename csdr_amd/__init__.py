@@ -138,6 +138,20 @@ def lib():
     L.csdr_amd_psk31_varicode_decoder_push.restype = C.c_char; L.csdr_amd_psk31_varicode_decoder_push.argtypes = [vp, C.c_ubyte]
     L.csdr_amd_psk31_varicode_table.restype = None; L.csdr_amd_psk31_varicode_table.argtypes = [vp]
     L.csdr_amd_debug_psk31_walk.restype = ll; L.csdr_amd_debug_psk31_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
+    L.csdr_amd_psk31tx_create.restype = vp; L.csdr_amd_psk31tx_create.argtypes = [vp, i, i, i, i, i]
+    L.csdr_amd_psk31tx_process.argtypes = [vp, vp, ll, vp, sz, vp, sz, vp]
+    L.csdr_amd_psk31tx_max_out.restype = ll; L.csdr_amd_psk31tx_max_out.argtypes = [vp, ll]
+    L.csdr_amd_psk31tx_reset.argtypes = [vp]
+    L.csdr_amd_psk31tx_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_psk31tx_get_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_psk31tx_set_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_psk31tx_force_generic.argtypes = [vp, i]
+    L.csdr_amd_psk31tx_kernel_name.restype = C.c_char_p; L.csdr_amd_psk31tx_kernel_name.argtypes = [vp]
+    L.csdr_amd_psk31tx_destroy.argtypes = [vp]; L.csdr_amd_psk31tx_destroy.restype = None
+    L.csdr_amd_psk31tx_tables.argtypes = [i, i, vp, vp]
+    L.csdr_amd_differential_decoder_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, vp]
+    L.csdr_amd_duplicate_samples_ntimes_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i, i]
+    L.csdr_amd_debug_psk31tx_walk.restype = ll; L.csdr_amd_debug_psk31tx_walk.argtypes = [i, i, i, i, vp, ll, vp, i, vp, vp]
     L.csdr_amd_rtty_create.restype = vp; L.csdr_amd_rtty_create.argtypes = [vp, vp, i, i, i]
     L.csdr_amd_rtty_process.argtypes = [vp, vp, ll, sz, vp, sz, vp]
     L.csdr_amd_rtty_max_out.restype = ll; L.csdr_amd_rtty_max_out.argtypes = [vp, ll]
@@ -702,6 +716,136 @@ class Psk31:
     def close(self):
         if self.h and self.ctx.h:                   # (after Context.close the object's context is gone: destroy would read it)
             self.ctx.L.csdr_amd_psk31_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Psk31TxChan(C.Structure):
+    """csdr_amd_psk31tx_chan: one channel's state"""
+    _fields_ = [("diff_state", C.c_ubyte), ("last_i", C.c_float), ("last_q", C.c_float)]
+
+
+PSK31TX_STAGES = {"varicode": 0, "diff": 1, "mod": 2, "shape": 3}
+
+
+def _psk31tx_stage(s):
+    return PSK31TX_STAGES[s] if isinstance(s, str) else int(s)
+
+
+def _psk31tx_types(first, last):
+    return (c64 if first == 3 else np.uint8), (c64 if last >= 2 else np.uint8)
+
+
+def _psk31tx_max_out(first, last, interpolation, n):
+    return n * (12 if first == 0 else 1) * (interpolation if last == 3 else 1)
+
+
+def psk31tx_tables(n_psk=2, interpolation=256):
+    """The host tables of a transmit object (csdr_amd_psk31tx_tables) -> (256 symbols complex64, `interpolation` shaping factors float32)"""
+    sym = np.zeros(256, c64); rate = np.zeros(interpolation, f32)
+    if lib().csdr_amd_psk31tx_tables(n_psk, interpolation, _hp(sym), _hp(rate)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return sym, rate
+
+
+def psk31tx_debug_walk(x, n_psk=2, interpolation=256, first="varicode", last="shape", cuts=(), state=None):
+    """CPU run of k_psk31tx_generic's walk for one channel (csdr_amd_debug_psk31tx_walk): x cut into calls of `cuts` items and the rest -> outputs.
+    state: a Psk31TxChan carried in and out."""
+    f, l = _psk31tx_stage(first), _psk31tx_stage(last)
+    ti, to = _psk31tx_types(f, l)
+    x = np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, ti)
+    out = np.zeros(_psk31tx_max_out(f, l, interpolation, x.size) + 16, to)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_psk31tx_walk(n_psk, interpolation, f, l, _hp(x), x.size, _hp(cu) if cu.size else None, cu.size, _hp(out),
+                                          C.byref(state) if state is not None else None)
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out[:k]
+
+
+class Psk31Tx:
+    """csdr_amd_psk31tx: the BPSK31 transmit chain (psk31_varicode_encoder_u8_u8 | differential_encoder_u8_u8 | psk_modulator_u8_c n_psk |
+    psk31_interpolate_sine_cc interpolation) for n_channels channels, stages first..last ("varicode", "diff", "mod", "shape"), state kept on the
+    device between calls."""
+
+    def __init__(self, ctx, n_channels=1, n_psk=2, interpolation=256, first="varicode", last="shape"):
+        self.ctx, self.n_channels, self.n_psk, self.interpolation = ctx, n_channels, n_psk, interpolation
+        self.first, self.last = _psk31tx_stage(first), _psk31tx_stage(last)
+        self.in_dtype, self.out_dtype = _psk31tx_types(self.first, self.last)
+        self.h = ctx.L.csdr_amd_psk31tx_create(ctx.h, n_channels, n_psk, interpolation, self.first, self.last)
+        if not self.h:
+            raise CsdrAmdError(ctx.err())
+
+    def max_out(self, n_in):
+        return int(self.ctx.L.csdr_amd_psk31tx_max_out(self.h, n_in))
+
+    def process_dev(self, d_in, n_in, d_in_counts, in_pitch, d_out, out_pitch, d_counts):
+        """device pointers; in_counts (n_channels int32, or None) gives each channel's item count, counts receives its output count.  Asynchronous."""
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_process(self.h, d_in, n_in, d_in_counts, in_pitch, d_out, out_pitch, d_counts), "psk31tx_process")
+
+    def process(self, x, in_counts=None, calls=None):
+        """x: [n_channels, n] (or [n]) host items; in_counts: per-channel item counts of the (single) call, each 0..n; calls: per-call item counts
+        (default one call) -> a list of per-channel output arrays (or one array for 1-D x)"""
+        x = np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, self.in_dtype)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        dn = None
+        if in_counts is not None:
+            ic = np.ascontiguousarray(in_counts, np.int32)
+            if ic.shape != (s,) or len(calls) != 1 or ic.min() < 0 or ic.max() > calls[0]:
+                raise CsdrAmdError("psk31tx: in_counts holds one count of 0 .. n_in per channel, for one call")
+            dn = self.ctx.upload(ic)
+        eb = np.dtype(self.in_dtype).itemsize
+        ob = np.dtype(self.out_dtype).itemsize
+        di = self.ctx.upload(x) if n else self.ctx.alloc(256)
+        opitch = max(self.max_out(max(calls) if calls else 0), 1)
+        do = self.ctx.alloc(ob * opitch * s + 256)
+        dc = self.ctx.alloc(4 * s + 256)
+        outs = [[] for _ in range(s)]
+        at = 0
+        for k in calls:
+            self.process_dev(di.at(eb * at), k, dn.ptr if dn else None, max(n, 1), do.ptr, opitch, dc.ptr)
+            cnt = self.ctx.download(dc, np.int32, s)
+            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c]].copy())
+            at += k
+        res = [np.concatenate(o) if o else np.zeros(0, self.out_dtype) for o in outs]
+        return res[0] if squeeze else res
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_reset(self.h), "psk31tx_reset")
+
+    def reset_channel(self, ch):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_reset_channel(self.h, int(ch)), "psk31tx_reset_channel")
+
+    def get_channel(self, ch):
+        st = Psk31TxChan()
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_get_channel(self.h, int(ch), C.byref(st)), "psk31tx_get_channel")
+        return st
+
+    def set_channel(self, ch, st):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_set_channel(self.h, int(ch), C.byref(st)), "psk31tx_set_channel")
+
+    def force_generic(self, on=True):
+        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_force_generic(self.h, int(on)), "psk31tx_force_generic")
+
+    def kernel_name(self):
+        return self.ctx.L.csdr_amd_psk31tx_kernel_name(self.h).decode()
+
+    def close(self):
+        if self.h and self.ctx.h:                   # (after Context.close the object's context is gone: destroy would read it)
+            self.ctx.L.csdr_amd_psk31tx_destroy(self.h)
         self.h = None
 
     def __del__(self):
@@ -1600,6 +1744,43 @@ class Context:
         y = self.download(do, c64, n * s).reshape(s, n)
         g = self.download(dg, f32, s)
         return (y[0].copy(), float(g[0])) if squeeze else (y.copy(), g.copy())
+
+    # ---- BPSK31 transmit chain (psk31tx.hip)
+    def psk31_tx(self, n_channels=1, n_psk=2, interpolation=256, first="varicode", last="shape"):
+        """A batched BPSK31 transmit chain object (Psk31Tx)"""
+        return Psk31Tx(self, n_channels, n_psk, interpolation, first, last)
+
+    def differential_decoder_u8_u8(self, x, state=None):
+        """differential_codec's decode branch (libcsdr.c:1830-1835) on [n_streams, n] (or [n]) bytes; state: per-stream previous byte (default 0, as
+        the CLI) -> (output, the last byte of each stream)"""
+        x = np.ascontiguousarray(x, np.uint8)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        st = np.ascontiguousarray(np.zeros(s, np.uint8) if state is None else np.broadcast_to(np.asarray(state, np.uint8), (s,)), np.uint8)
+        di = self.upload(x) if n else self.alloc(256)
+        ds = self.upload(st)
+        do = self.alloc(max(n, 1) * s + 256)
+        self.check(self.L.csdr_amd_differential_decoder_u8_u8(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(n, 1), ds.ptr), "differential_decoder_u8_u8")
+        y = self.download(do, np.uint8, max(n, 1) * s).reshape(s, max(n, 1))[:, :n]
+        st = self.download(ds, np.uint8, s)
+        return (y[0].copy(), int(st[0])) if squeeze else (y.copy(), st.copy())
+
+    def duplicate_samples_ntimes_u8_u8(self, x, sample_size_bytes, ntimes):
+        """duplicate_samples_ntimes_u8_u8 (libcsdr.c:1784-1791) on [n_streams, n_bytes] (or [n_bytes]) bytes -> every whole sample ntimes"""
+        x = np.ascontiguousarray(x, np.uint8)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        m = n // max(sample_size_bytes, 1) * max(sample_size_bytes, 1) * max(ntimes, 0)
+        di = self.upload(x) if n else self.alloc(256)
+        do = self.alloc(max(m, 1) * s + 256)
+        self.check(self.L.csdr_amd_duplicate_samples_ntimes_u8_u8(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(m, 1), sample_size_bytes, ntimes),
+                   "duplicate_samples_ntimes_u8_u8")
+        y = self.download(do, np.uint8, max(m, 1) * s).reshape(s, max(m, 1))[:, :m]
+        return y[0].copy() if squeeze else y.copy()
 
     # ---- RTTY receive chain (rtty.hip)
     def rtty(self, params=None, n_channels=1, first="bfsk", last="baudot"):

@@ -5,6 +5,7 @@ struct Stage {
     size_t min_block = 0;          // run() uses blocks of at least 4x this many elements (operators with a long history)
     size_t granule = 1;            // process() is only called with n_in a multiple of this (except at EOF when flush_partial)
     bool flush_partial = true;     // at EOF, a final n_in % granule != 0 call is allowed
+    size_t max_block = 0;          // as the first operator of a run: at most this many elements per pass (0: no limit); for operators that expand their input
     virtual ~Stage() {}
     // returns elements written; *consumed = input elements that need not be presented again
     virtual long process(csdr_amd_ctx *c, const void *d_in, size_t n_in, void *d_out, size_t out_cap, size_t *consumed) = 0;
@@ -210,6 +211,55 @@ struct Psk31 : Stage {   // simple_agc_cc csdr.c:2902-2930 | timing_recovery_cc 
         MUST(csdr_amd_psk31_process(p.get(), i, (long long)n, n, out, cap, d_count.get(), err, idx));
         int k = 0; MUST(csdr_amd_d2h(c, &k, d_count.get(), sizeof k));
         return k;
+    }
+};
+
+struct Psk31Tx : Stage {   // psk31_varicode_encoder_u8_u8 csdr.c:2780-2800 | differential_encoder_u8_u8 csdr.c:2816-2832 | psk_modulator_u8_c csdr.c:2684-2702 |
+                          // psk31_interpolate_sine_cc csdr.c:2727-2747: one object for a consecutive run of them (`chain` fuses the run); the differential
+                          // state and the shaper's last symbol live on the device.  The encoder is the library function applied to the whole stream.
+    Owned<csdr_amd_psk31tx, csdr_amd_psk31tx_destroy> p; int first, last, I; CtxBuf<int> d_count;
+    Psk31Tx(csdr_amd_ctx *c, int n_psk, int interpolation, int f, int l) : first(f), last(l), I(interpolation)
+    {
+        p.reset(csdr_amd_psk31tx_create(c, 1, n_psk, interpolation, f, l)); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = f == CSDR_AMD_PSK31TX_SHAPE ? 8 : 1;
+        out_elem = l >= CSDR_AMD_PSK31TX_MOD ? 8 : 1;
+        d_count = ctx_alloc<int>(c, 64, "malloc");
+        const size_t per_item = (size_t)csdr_amd_psk31tx_max_out(p.get(), 1) * out_elem;       // a pass writes at most 64 MiB
+        max_block = std::max<size_t>(1024, ((size_t)64 << 20) / per_item / 1024 * 1024);
+        if (f != l) fprintf(stderr, "csdr psk31_tx: one fused BPSK31 transmit object\n");
+    }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_psk31tx_max_out(p.get(), (long long)n) + 16; }
+    int next_bufsize(int b) override
+    {   // csdr.c:2783 (x 8), :2734 (x interpolation); the two between keep it
+        if (first == CSDR_AMD_PSK31TX_VARICODE) b *= 8;
+        if (last == CSDR_AMD_PSK31TX_SHAPE) b *= I;
+        return b;
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        MUST(csdr_amd_psk31tx_process(p.get(), i, (long long)n, nullptr, n, o, cap, d_count.get()));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count.get(), sizeof k));
+        return k;
+    }
+};
+struct DiffDecoder : Stage {   // differential_decoder_u8_u8 csdr.c:2816-2832: the previous byte on the device, 0 at the start
+    CtxBuf<unsigned char> d_state;
+    DiffDecoder(csdr_amd_ctx *c) { in_elem = 1; out_elem = 1; d_state = ctx_alloc<unsigned char>(c, 64, "malloc"); MUST(csdr_amd_memset(c, d_state.get(), 0, 64)); }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    { *cons = n; MUST(csdr_amd_differential_decoder_u8_u8(c, (const unsigned char *)i, (unsigned char *)o, 1, (long long)n, n, n, d_state.get())); return (long)n; }
+};
+struct DuplicateSamples : Stage {   // duplicate_samples_ntimes_u8_u8 csdr.c:2704-2725
+    int ss, nt;
+    DuplicateSamples(int sample_size, int ntimes) : ss(sample_size), nt(ntimes)
+    { in_elem = 1; out_elem = 1; granule = (size_t)sample_size; flush_partial = false; max_block = std::max<size_t>(1024, ((size_t)64 << 20) / ntimes / 1024 * 1024); }
+    size_t out_capacity(size_t n) override { return n * (size_t)nt + 16; }
+    int next_bufsize(int b) override { return b * nt; }              // csdr.c:2714
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        const size_t m = n / ss * ss; *cons = m;
+        if (m) MUST(csdr_amd_duplicate_samples_ntimes_u8_u8(c, (const unsigned char *)i, (unsigned char *)o, 1, (long long)m, m, cap, ss, nt));
+        return (long)(m * nt);
     }
 };
 
@@ -776,6 +826,29 @@ int parse_psk31(int argc, char **argv, csdr_amd_psk31_params *pr, int *extra)
     return -2;
 }
 
+// the BPSK31 transmit commands: stage index, n_psk / interpolation into their arguments; -1 (message given) on bad syntax, -2: not one of them
+int parse_psk31tx(int argc, char **argv, int *n_psk, int *interpolation)
+{
+    const std::string cmd = argv[1];
+    if (cmd == "psk31_varicode_encoder_u8_u8") return CSDR_AMD_PSK31TX_VARICODE;
+    if (cmd == "differential_encoder_u8_u8") return CSDR_AMD_PSK31TX_DIFF;
+    if (cmd == "psk_modulator_u8_c") {                                              // csdr.c:2684-2689
+        if (argc <= 2) { badsyntax("need required parameter (n_psk)"); return -1; }
+        int v = 0; sscanf(argv[2], "%d", &v);
+        if (v <= 0 || v > 256) { badsyntax("n_psk should be between 1 and 256"); return -1; }
+        *n_psk = v;
+        return CSDR_AMD_PSK31TX_MOD;
+    }
+    if (cmd == "psk31_interpolate_sine_cc") {                                       // csdr.c:2727-2732
+        if (argc <= 2) { badsyntax("need required parameter (interpolation)"); return -1; }
+        int v = 0; sscanf(argv[2], "%d", &v);
+        if (v <= 0) { badsyntax("interpolation should be >0"); return -1; }
+        *interpolation = v;
+        return CSDR_AMD_PSK31TX_SHAPE;
+    }
+    return -2;
+}
+
 // the RTTY commands: stage index, parameters into *pr; -1 (message given) on bad syntax.  B: the serial decoder's window, as the reference's
 // getbufsize() gives it with bigbufs (csdr.c:332): the fixed big buffer, or the preamble's size in dynamic mode
 int parse_rtty(int argc, char **argv, csdr_amd_rtty_params *pr, int B)
@@ -853,6 +926,38 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         const int st = parse_psk31(argc, argv, &pr, &extra);
         if (st == -1) return nullptr;
         if (st >= 0) return new Psk31(c, pr, st, st, extra);
+    }
+    if (!strcmp(argv[1], "psk31_tx")) {                                             // `chain`'s fused BPSK31 transmit run: argv[2..] are its commands, one per argument
+        int n_psk = 2, interpolation = 1, first = -1, last = -1;
+        for (int k = 2; k < argc; k++) {
+            std::vector<std::string> words = split_chain(argv[k])[0]; std::vector<char *> av = argv_of(words);
+            g_cmd = av[1];
+            const int st = parse_psk31tx((int)av.size(), av.data(), &n_psk, &interpolation);
+            if (st < 0) return nullptr;
+            if (first < 0) first = st;
+            last = st;
+        }
+        g_cmd = argv[1];
+        return new Psk31Tx(c, n_psk, interpolation, first, last);
+    }
+    {
+        int n_psk = 2, interpolation = 1;
+        const char *keep = g_cmd; g_cmd = argv[1];
+        const int st = parse_psk31tx(argc, argv, &n_psk, &interpolation);
+        if (st == -1) return nullptr;
+        if (st >= 0) return new Psk31Tx(c, n_psk, interpolation, st, st);
+        if (!strcmp(argv[1], "differential_decoder_u8_u8")) return new DiffDecoder(c);
+        if (!strcmp(argv[1], "duplicate_samples_ntimes_u8_u8")) {                   // csdr.c:2704-2712
+            int sample_size_bytes = 0, ntimes = 0;
+            if (argc <= 2) { badsyntax("need required parameter (sample_size_bytes)"); return nullptr; }
+            sscanf(argv[2], "%d", &sample_size_bytes);
+            if (sample_size_bytes <= 0) { badsyntax("sample_size_bytes should be >0"); return nullptr; }
+            if (argc <= 3) { badsyntax("need required parameter (ntimes)"); return nullptr; }
+            sscanf(argv[3], "%d", &ntimes);
+            if (ntimes <= 0) { badsyntax("ntimes should be >0"); return nullptr; }
+            return new DuplicateSamples(sample_size_bytes, ntimes);
+        }
+        g_cmd = keep;
     }
     g_cmd = argv[1];
     const std::string cmd = argv[1];

@@ -429,6 +429,95 @@ char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char s
     return csdr_amd_psk31_varicode_decoder_push(status_shr, symbol);
 }
 
+// ------------------------------------------------------------------ BPSK31 transmit (psk31tx.hip)
+// one one-channel, one-stage object per thread and stage, kept while n_psk and the interpolation stay the same
+static csdr_amd_psk31tx *tx_object(int stage, int n_psk, int interpolation, const char *who)
+{
+    struct TxCache { csdr_amd_psk31tx *p = nullptr; int n_psk = 0, I = 0; ~TxCache() { if (p && (long)syscall(SYS_gettid) != (long)getpid()) csdr_amd_psk31tx_destroy(p); } };
+    static thread_local TxCache cache[4];
+    TxCache &k = cache[stage];
+    if (!k.p || k.n_psk != n_psk || k.I != interpolation) {
+        if (k.p) csdr_amd_psk31tx_destroy(k.p);
+        k.p = csdr_amd_psk31tx_create(ctx(), 1, n_psk, interpolation, stage, stage);
+        if (!k.p) die(who, -3);
+        k.n_psk = n_psk; k.I = interpolation;
+    }
+    return k.p;
+}
+
+void psk31_varicode_encoder_u8_u8(unsigned char *in, unsigned char *out, int n, int output_max_size, int *input_processed, int *output_size)
+{   // libcsdr.c:1551-1575: how many characters fit is counted here from the code lengths, the bits come from the device
+    int table[256];
+    csdr_amd_psk31_varicode_table(table);
+    int take = 0; long long room = output_max_size, bits = 0;
+    for (; take < n; take++) {
+        if (in[take] >= 128) continue;
+        const int len = table[2 * in[take] + 1] + 2;
+        if (room < len) break;
+        room -= len; bits += len;
+    }
+    *input_processed = take; *output_size = (int)bits;
+    if (!bits) return;
+    csdr_amd_psk31tx *p = tx_object(CSDR_AMD_PSK31TX_VARICODE, 2, 1, "psk31_varicode_encoder_u8_u8");
+    const size_t mo = (size_t)csdr_amd_psk31tx_max_out(p, take);
+    unsigned char *din = stage_in<unsigned char>(4, in, take); unsigned char *dout = stage_out<unsigned char>(5, mo); int *dcnt = stage_out<int>(6, 1);
+    MUST(csdr_amd_psk31tx_process(p, din, take, nullptr, take, dout, mo, dcnt));
+    fetch(out, dout, (size_t)bits);
+}
+
+unsigned char differential_codec(unsigned char *in, unsigned char *out, int n, int encode, unsigned char state)
+{   // libcsdr.c:1828-1843
+    if (n <= 0) return state;
+    unsigned char *din = stage_in<unsigned char>(4, in, n); unsigned char *dout = stage_out<unsigned char>(5, n);
+    if (!encode) {
+        unsigned char *dst = stage_in<unsigned char>(6, &state, 1);
+        MUST(csdr_amd_differential_decoder_u8_u8(ctx(), din, dout, 1, n, n, n, dst));
+        fetch(out, dout, n);
+        fetch(&state, dst, 1);
+        return state;
+    }
+    csdr_amd_psk31tx *p = tx_object(CSDR_AMD_PSK31TX_DIFF, 2, 1, "differential_codec");
+    csdr_amd_psk31tx_chan st; memset(&st, 0, sizeof st); st.diff_state = state;
+    MUST(csdr_amd_psk31tx_set_channel(p, 0, &st));
+    int *dcnt = stage_out<int>(6, 1);
+    MUST(csdr_amd_psk31tx_process(p, din, n, nullptr, n, dout, n, dcnt));
+    fetch(out, dout, n);
+    MUST(csdr_amd_psk31tx_get_channel(p, 0, &st));
+    return st.diff_state;
+}
+
+void psk_modulator_u8_c(unsigned char *in, complexf *out, int n, int n_psk)
+{   // libcsdr.c:1772-1782
+    if (n <= 0) return;
+    csdr_amd_psk31tx *p = tx_object(CSDR_AMD_PSK31TX_MOD, n_psk, 1, "psk_modulator_u8_c");
+    unsigned char *din = stage_in<unsigned char>(4, in, n); complexf *dout = stage_out<complexf>(5, n); int *dcnt = stage_out<int>(6, 1);
+    MUST(csdr_amd_psk31tx_process(p, din, n, nullptr, n, dout, n, dcnt));
+    fetch(out, dout, n);
+}
+
+void duplicate_samples_ntimes_u8_u8(unsigned char *in, unsigned char *out, int input_size_bytes, int sample_size_bytes, int ntimes)
+{   // libcsdr.c:1784-1791
+    if (input_size_bytes <= 0 || sample_size_bytes <= 0 || ntimes <= 0) return;
+    const size_t n = (size_t)input_size_bytes, m = n / sample_size_bytes * sample_size_bytes * ntimes;
+    if (!m) return;
+    unsigned char *din = stage_in<unsigned char>(4, in, n); unsigned char *dout = stage_out<unsigned char>(5, m);
+    MUST(csdr_amd_duplicate_samples_ntimes_u8_u8(ctx(), din, dout, 1, (long long)n, n, m, sample_size_bytes, ntimes));
+    fetch(out, dout, m);
+}
+
+complexf psk31_interpolate_sine_cc(complexf *in, complexf *out, int n, int interpolation, complexf last_input)
+{   // libcsdr.c:1793-1808
+    if (n <= 0) return last_input;
+    csdr_amd_psk31tx *p = tx_object(CSDR_AMD_PSK31TX_SHAPE, 2, interpolation, "psk31_interpolate_sine_cc");
+    csdr_amd_psk31tx_chan st; memset(&st, 0, sizeof st); st.last_i = last_input.i; st.last_q = last_input.q;
+    MUST(csdr_amd_psk31tx_set_channel(p, 0, &st));
+    const size_t mo = (size_t)csdr_amd_psk31tx_max_out(p, n);
+    complexf *din = stage_in<complexf>(4, in, n); complexf *dout = stage_out<complexf>(5, mo); int *dcnt = stage_out<int>(6, 1);
+    MUST(csdr_amd_psk31tx_process(p, din, n, nullptr, n, dout, mo, dcnt));
+    fetch(out, dout, mo);
+    return in[n - 1];
+}
+
 // ------------------------------------------------------------------ RTTY receive (rtty.hip)
 int bfsk_demod_cf(complexf *in, float *out, int n, complexf *mark_filter, complexf *space_filter, int taps_length)
 {   // libcsdr.c:2335-2350

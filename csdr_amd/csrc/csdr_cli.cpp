@@ -38,6 +38,7 @@
 #include <sys/stat.h>
 #include <sys/un.h>
 #include <time.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include <atomic>
@@ -132,9 +133,10 @@ bool fuse_run(std::vector<std::vector<std::string>> &cmds, const char *const *na
     return any;
 }
 // simple_agc_cc -> timing_recovery_cc -> dbpsk_decoder_c_u8 -> psk31_varicode_decoder_u8_u8 -> `psk31_rx`;  bfsk_demod_cf -> serial_line_decoder_f_u8 ->
-// rtty_baudot2ascii_u8_u8 -> `rtty_rx`
+// rtty_baudot2ascii_u8_u8 -> `rtty_rx`;  psk31_varicode_encoder_u8_u8 -> differential_encoder_u8_u8 -> psk_modulator_u8_c -> psk31_interpolate_sine_cc -> `psk31_tx`
 const char *const PSK31_RUN[4] = {"simple_agc_cc", "timing_recovery_cc", "dbpsk_decoder_c_u8", "psk31_varicode_decoder_u8_u8"};
 const char *const RTTY_RUN[3] = {"bfsk_demod_cf", "serial_line_decoder_f_u8", "rtty_baudot2ascii_u8_u8"};
+const char *const PSK31TX_RUN[4] = {"psk31_varicode_encoder_u8_u8", "differential_encoder_u8_u8", "psk_modulator_u8_c", "psk31_interpolate_sine_cc"};
 
 // convert_u8_f | shift_addition_cc r | fir_decimate_cc D [tbw [window]] at the head of a chain -> one ddc_u8_cc command
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
@@ -165,6 +167,8 @@ int main(int argc, char **argv)
                         "decimating_shift_addition_cc fir_decimate_cc fmdemod_quadri_cf fmdemod_quadri_novect_cf fractional_decimator_ff rational_resampler_ff suboptimal_rational_resampler_ff fir_interpolate_cc deemphasis_wfm_ff "
                         "deemphasis_nfm_ff limit_ff fastagc_ff bandpass_fir_fft_cc fastddc_fwd_cc fastddc_inv_cc firdes_lowpass_f firdes_bandpass_c "
                         "simple_agc_cc timing_recovery_cc (needs |mu| * max_error <= 1) dbpsk_decoder_c_u8 psk31_varicode_decoder_u8_u8 "
+                        "psk31_varicode_encoder_u8_u8 differential_encoder_u8_u8 differential_decoder_u8_u8 psk_modulator_u8_c (<n_psk>) psk31_interpolate_sine_cc (<interpolation>) "
+                        "duplicate_samples_ntimes_u8_u8 (<sample_size_bytes> <ntimes>) "
                         "bfsk_demod_cf serial_line_decoder_f_u8 rtty_baudot2ascii_u8_u8 rtty_line_decoder_u8_u8 binary_slicer_f_u8 firdes_peak_c "
                         "squelch_and_smeter_cc (--fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>) bpsk_costas_loop_cc (<loop_bandwidth> <damping_factor> [--dd | --decision_directed] [--output_error | --output_dphase | --output_nco | --output_combined <error_file> <dphase_file> <nco_file>]) pll_cc (1 [alpha] | 2 [bandwidth [damping_factor [ko [kd]]]]) amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf dsb_fc ([q_value]) fmmod_fc add_dcoffset_cc fixed_amplitude_cc (<new_amplitude>) convert_f_samplerf (<wait_for_this_sample>) fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
@@ -254,6 +258,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "csdr chain: convert_u8_f | shift_addition_cc | fir_decimate_cc recognised -> fused matrix-core front end\n");
         }
         fuse_run(cmds, PSK31_RUN, 4, "psk31_rx", "csdr chain: %s .. %s recognised -> one fused BPSK31 object (k_psk31)\n");
+        fuse_run(cmds, PSK31TX_RUN, 4, "psk31_tx", "csdr chain: %s .. %s recognised -> one fused BPSK31 transmit object (psk31_tx)\n");
         fuse_run(cmds, RTTY_RUN, 3, "rtty_rx", "csdr chain: %s .. %s recognised -> one fused RTTY object (rtty_rx: k_bfsk_mfma + k_rtty_walk)\n");
     } else {
         cmds.assign(1, std::vector<std::string>(argv, argv + argc));
@@ -280,6 +285,7 @@ int main(int argc, char **argv)
         if (cap_is_bytes) cap = cap / s->in_elem;
         if (cap < 4 * s->min_block) cap = 4 * s->min_block;
         if (cap < 2 * s->granule) cap = 2 * s->granule;
+        if (k == 0 && s->max_block && cap > s->max_block) cap = std::max(s->max_block - s->max_block % s->granule, 2 * s->granule);
         if (k == 0) { cap -= cap % s->granule; block = cap; }
         stages.push_back(s); caps.push_back(cap + (k ? 64 : 0));
         out_bufsize = s->next_bufsize(out_bufsize);

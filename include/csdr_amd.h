@@ -268,6 +268,53 @@ void csdr_amd_psk31_varicode_table(int *out);
 long long csdr_amd_debug_psk31_walk(const csdr_amd_psk31_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
                                     int n_cuts, void *out, float *err, unsigned *idx, csdr_amd_psk31_chan *state_io);
 
+/* ------------------------------------------------------------------ BPSK31 transmit chain (psk31tx.hip)
+ * psk31_varicode_encoder_u8_u8 libcsdr.c:1551-1575 | differential_encoder_u8_u8 libcsdr.c:1836-1841 | psk_modulator_u8_c libcsdr.c:1772-1782 |
+ * psk31_interpolate_sine_cc libcsdr.c:1793-1808, for n_channels channels with the same n_psk (1..256) and interpolation (>= 1).  The object runs the stages
+ * first_stage .. last_stage (CSDR_AMD_PSK31TX_*) and keeps each channel's state on the device: the differential state (0 after a reset, csdr.c:2823) and the
+ * shaper's last symbol (0 + 0i after a reset, csdr.c:2736-2738).  The output equals the reference functions applied once to each channel's whole stream since
+ * its last reset, however the stream is cut into calls (0- and 1-item calls included) and wherever the channel sits in the batch.
+ * process: n_in items per channel, in_pitch items apart: bytes (characters for VARICODE, bits for DIFF, symbol indexes for MOD) or complexf (SHAPE).
+ * in_counts (device, n_channels ints, may be NULL = n_in for every channel): each channel's item count of this call, 0 .. n_in (a value outside is clamped
+ * on the device; a caller that holds the counts on the host checks them there).  out: bytes (last_stage VARICODE or DIFF) or complexf (MOD or SHAPE),
+ * out_pitch items apart, at least max_out(n_in) = n_in (x 12 from VARICODE: a character is at most 12 bits) (x interpolation to SHAPE), at most 2^31 - 1:
+ * a smaller out_pitch is an error, so input is never left unconsumed.  counts (device, n_channels ints) receives each channel's output count; nothing is
+ * written at or beyond it.  Bytes 128..255 have no varicode and produce nothing.  Asynchronous on the context's stream.
+ * kernel_name: "k_psk31tx_plan+k_psk31tx_shape" (the range VARICODE .. SHAPE with interpolation <= 7904, the tables' bound in 63 KiB of LDS) or
+ * "k_psk31tx_generic" (every other case); force_generic(1) takes k_psk31tx_generic always.  Both give the same bits.
+ * get_channel / set_channel: one channel's state (synchronous).  diff_state is any byte, as differential_codec takes it (a byte above 1 is output until
+ * the first toggle makes it 0), except for the range VARICODE .. SHAPE, which takes 0 or 1. */
+enum { CSDR_AMD_PSK31TX_VARICODE = 0, CSDR_AMD_PSK31TX_DIFF = 1, CSDR_AMD_PSK31TX_MOD = 2, CSDR_AMD_PSK31TX_SHAPE = 3 };
+typedef struct csdr_amd_psk31tx_chan {
+    unsigned char diff_state;            /* DIFF */
+    float last_i, last_q;                /* SHAPE: the last symbol */
+} csdr_amd_psk31tx_chan;
+typedef struct csdr_amd_psk31tx csdr_amd_psk31tx;
+csdr_amd_psk31tx *csdr_amd_psk31tx_create(csdr_amd_ctx *ctx, int n_channels, int n_psk, int interpolation, int first_stage, int last_stage);
+int  csdr_amd_psk31tx_process(csdr_amd_psk31tx *p, const void *in, long long n_in, const int *in_counts, size_t in_pitch, void *out, size_t out_pitch, int *counts);
+long long csdr_amd_psk31tx_max_out(const csdr_amd_psk31tx *p, long long n_in);
+int  csdr_amd_psk31tx_reset(csdr_amd_psk31tx *p);
+int  csdr_amd_psk31tx_reset_channel(csdr_amd_psk31tx *p, int channel);
+int  csdr_amd_psk31tx_get_channel(csdr_amd_psk31tx *p, int channel, csdr_amd_psk31tx_chan *state);
+int  csdr_amd_psk31tx_set_channel(csdr_amd_psk31tx *p, int channel, const csdr_amd_psk31tx_chan *state);
+int  csdr_amd_psk31tx_force_generic(csdr_amd_psk31tx *p, int on);
+const char *csdr_amd_psk31tx_kernel_name(const csdr_amd_psk31tx *p);
+void csdr_amd_psk31tx_destroy(csdr_amd_psk31tx *p);
+/* The tables an object with these parameters is created with (host): sym = the 256 symbols of psk_modulator_u8_c, (cos, sin) of float(2 pi / n_psk) * v by
+ * libm in double, rounded to float; rate = the `interpolation` factors of psk31_interpolate_sine_cc.  Either may be NULL. */
+int  csdr_amd_psk31tx_tables(int n_psk, int interpolation, csdr_complexf *sym, float *rate);
+/* differential_codec's decode branch (libcsdr.c:1830-1835) on n_streams streams of n bytes: out = (in == the previous in); state_io (device, n_streams bytes)
+ * carries each stream's previous byte in and out.  out must not be in. */
+int  csdr_amd_differential_decoder_u8_u8(csdr_amd_ctx *ctx, const unsigned char *in, unsigned char *out, int n_streams, long long n, size_t in_pitch,
+                                         size_t out_pitch, unsigned char *state_io);
+/* duplicate_samples_ntimes_u8_u8 (libcsdr.c:1784-1791) on n_streams streams: every whole sample of sample_size_bytes within n_bytes, written ntimes */
+int  csdr_amd_duplicate_samples_ntimes_u8_u8(csdr_amd_ctx *ctx, const unsigned char *in, unsigned char *out, int n_streams, long long n_bytes, size_t in_pitch,
+                                             size_t out_pitch, int sample_size_bytes, int ntimes);
+/* CPU run of k_psk31tx_generic's walk (the same step functions) for one channel, the n items cut into calls of cuts[0..n_cuts) items and the rest; outputs
+ * concatenated.  state_io: the channel state in and out (NULL: a fresh channel).  Returns the output count. */
+long long csdr_amd_debug_psk31tx_walk(int n_psk, int interpolation, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
+                                      int n_cuts, void *out, csdr_amd_psk31tx_chan *state_io);
+
 /* ------------------------------------------------------------------ RTTY receive chain (rtty.hip)
  * bfsk_demod_cf libcsdr.c:2335-2350 (csdr.c:3271-3300) | serial_line_decoder_f_u8 libcsdr.c:1662-1728 (csdr.c:2490-2528) | rtty_baudot2ascii_u8_u8 csdr.c:2461-2473,
  * for n_channels channels, all with the same parameters.  The object runs the stages first_stage .. last_stage (CSDR_AMD_RTTY_*) and keeps each channel's

@@ -108,6 +108,15 @@ char *timing_recovery_get_string_from_algorithm(timing_recovery_algorithm_t algo
 void simple_agc_cc(complexf *input, complexf *output, int input_size, float rate, float reference, float max_gain, float *current_gain);
 void dbpsk_decoder_c_u8(complexf *input, unsigned char *output, int input_size);
 char psk31_varicode_decoder_push(unsigned long long *status_shr, unsigned char symbol);
+/* BPSK31 transmit, libcsdr.h:343-347 and libcsdr.c:1551-1575, 1772-1808, 1828-1843, on the device (one library call = one block).
+ * psk31_varicode_encoder_u8_u8 keeps the output_max_size contract: it stops in front of the first character whose code and two separators do not fit and
+ * reports input_processed and output_size.  duplicate_samples_ntimes_u8_u8 writes the whole samples of input_size_bytes (the reference reads past its
+ * input for a partial one).  psk31_interpolate_sine_cc returns the last input by value, to be passed to the next call. */
+void psk_modulator_u8_c(unsigned char *input, complexf *output, int input_size, int n_psk);
+void duplicate_samples_ntimes_u8_u8(unsigned char *input, unsigned char *output, int input_size_bytes, int sample_size_bytes, int ntimes);
+complexf psk31_interpolate_sine_cc(complexf *input, complexf *output, int input_size, int interpolation, complexf last_input);
+void psk31_varicode_encoder_u8_u8(unsigned char *input, unsigned char *output, int input_size, int output_max_size, int *input_processed, int *output_size);
+unsigned char differential_codec(unsigned char *input, unsigned char *output, int input_size, int encode, unsigned char state);
 /* RTTY receive, libcsdr.h:236-289, 412.  bfsk_demod_cf and serial_line_decoder_f_u8 run on the device (one library call = one window, as the reference);
  * serial_line_decoder_f_u8 writes unsigned char, short or unsigned outputs for databits <= 8, <= 16, above.  The Baudot functions run on the host. */
 typedef struct rtty_baudot_item_s { unsigned long long code; unsigned char ascii_letter; unsigned char ascii_figure; } rtty_baudot_item_t;
