@@ -396,16 +396,121 @@ class DevBuf:
         return C.c_void_p(self.ptr + int(byte_offset))
 
 
-class Waterfall:
+class _Handle:
+    """A C object of the library: `h` is what csdr_amd_<pre>_create returned, the other entry points are csdr_amd_<pre>_<name>(h, ...).
+    ctx is the Context the object was created on, or None for an object whose create takes no context.  Usable as `with`: closed on every path."""
+    h = None                                             # (a constructor that raised in front of _Handle.__init__ leaves nothing to close)
+
+    def __init__(self, ctx, pre, h):
+        self.ctx, self._pre, self._L = ctx, pre, ctx.L if ctx is not None else lib()
+        if not h:
+            raise CsdrAmdError(ctx.err() if ctx is not None else self._L.csdr_amd_last_error().decode())
+        self.h = h
+
+    def _fn(self, name):
+        return getattr(self._L, "csdr_amd_%s_%s" % (self._pre, name))
+
+    def _call(self, name, *args):
+        return self.ctx.check(self._fn(name)(self.h, *args), "%s_%s" % (self._pre, name))
+
+    def reset(self):
+        self._call("reset")
+
+    def force_generic(self, on=True):
+        self._call("force_generic", int(on))
+
+    def kernel_name(self):
+        return self._fn("kernel_name")(self.h).decode()
+
+    def close(self):
+        """Destroys the object once.  After Context.close the object's context is gone and destroy would read it: the handle is dropped and the
+        object goes with the process."""
+        h, self.h = self.h, None
+        if h and (self.ctx is None or self.ctx.h):
+            self._fn("destroy")(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# The members below exist for some objects only; a class lists the mixins of the entry points its C object has.
+class _MaxOut:
+    """csdr_amd_<pre>_max_out: the most outputs per stream that a call of n_in inputs can write"""
+
+    def max_out(self, n_in):
+        return int(self._fn("max_out")(self.h, int(n_in)))
+
+
+class _PerChannel:
+    """csdr_amd_<pre>_reset_channel: one channel back to its start state, the others untouched"""
+
+    def reset_channel(self, ch):
+        self._call("reset_channel", int(ch))
+
+
+class _ChannelState(_PerChannel):
+    """csdr_amd_<pre>_get_channel / _set_channel: one channel's state as the class's `_chan` structure"""
+
+    def get_channel(self, ch):
+        st = self._chan()
+        self._call("get_channel", int(ch), C.byref(st))
+        return st
+
+    def set_channel(self, ch, st):
+        self._call("set_channel", int(ch), C.byref(st))
+
+
+class _Lanes:
+    """csdr_amd_<pre>_set_lanes / _lanes: channels per wave of the tiled kernel (0: the library chooses)"""
+
+    def set_lanes(self, lanes):
+        self._call("set_lanes", int(lanes))
+
+    def lanes(self):
+        return int(self._fn("lanes")(self.h))
+
+
+def _counted_calls(obj, x, calls, extras=(), **inputs):
+    """The call loop of the objects whose process_dev reports one output count per channel: x [n_channels, n] host items, cut into calls of `calls` items
+    -> per channel, the tuple of its concatenated outputs: the "d_out" row (obj.out_dtype) and one row per (process_dev keyword, dtype) in `extras`.
+    inputs: further process_dev keywords, passed on as they are."""
+    ctx, (s, n) = obj.ctx, x.shape
+    rows = [("d_out", obj.out_dtype)] + list(extras)
+    di = ctx.upload(x) if n else ctx.alloc(256)
+    opitch = max(obj.max_out(max(calls) if calls else 0), 1)
+    bufs = [ctx.alloc(np.dtype(dt).itemsize * opitch * s + 256) for _, dt in rows]
+    dc = ctx.alloc(4 * s + 256)
+    parts = [[[] for _ in rows] for _ in range(s)]
+    at = 0
+    for k in calls:
+        obj.process_dev(d_in=di.at(x.itemsize * at), n_in=k, in_pitch=max(n, 1), out_pitch=opitch, d_counts=dc.ptr,
+                        **{nm: b.ptr for (nm, _), b in zip(rows, bufs)}, **inputs)
+        cnt = ctx.download(dc, np.int32, s)
+        for j, ((_, dt), b) in enumerate(zip(rows, bufs)):
+            y = ctx.download(b, dt, opitch * s).reshape(s, opitch)
+            for c in range(s):
+                parts[c][j].append(y[c, :cnt[c]].copy())
+        at += k
+    return [tuple(np.concatenate(p) if p else np.zeros(0, dt) for p, (_, dt) in zip(parts[c], rows)) for c in range(s)]
+
+
+class Waterfall(_Handle):
     """csdr_amd_waterfall: n_streams streams in lockstep -> rows of fft_size float dB values (out_format "db") or (fft_size+10)/2 ADPCM bytes ("adpcm")."""
 
     def __init__(self, ctx, fft_size, every_n, avgnumber, add_db, window, in_format, out_format, n_streams, max_samples_per_call):
-        self.ctx, self.fft, self.every, self.avg, self.n_streams, self.max_in = ctx, fft_size, every_n, avgnumber, n_streams, int(max_samples_per_call)
+        self.fft, self.every, self.avg, self.n_streams, self.max_in = fft_size, every_n, avgnumber, n_streams, int(max_samples_per_call)
         self.in_format, self.out_format = in_format, out_format
-        self.h = ctx.L.csdr_amd_waterfall_create(ctx.h, fft_size, every_n, WINDOWS[window], avgnumber, add_db, 1 if in_format == "u8" else 0,
-                                                 1 if out_format == "adpcm" else 0, n_streams, self.max_in)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        _Handle.__init__(self, ctx, "waterfall", ctx.L.csdr_amd_waterfall_create(ctx.h, fft_size, every_n, WINDOWS[window], avgnumber, add_db,
+                                                                                  1 if in_format == "u8" else 0, 1 if out_format == "adpcm" else 0, n_streams, self.max_in))
         self.row_bytes = 4 * fft_size if out_format == "db" else (fft_size + 10) // 2
 
     def max_rows(self, n_in):
@@ -414,7 +519,7 @@ class Waterfall:
     def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch):
         """device pointers: n_in new samples per stream (in_pitch samples apart) -> rows per stream written at d_out (out_pitch bytes apart)"""
         rows = C.c_int(0)
-        self.ctx.check(self.ctx.L.csdr_amd_waterfall_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, C.byref(rows)), "waterfall_process")
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, C.byref(rows))
         return rows.value
 
     def process(self, x, calls=None):
@@ -440,26 +545,6 @@ class Waterfall:
         dt = f32 if self.out_format == "db" else np.uint8
         per = self.fft if self.out_format == "db" else self.row_bytes
         return np.stack([np.concatenate(o).view(dt).reshape(-1, per) if o else np.zeros((0, per), dt) for o in out])
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_waterfall_kernel_name(self.h).decode()
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_waterfall_force_generic(self.h, int(on)), "waterfall_force_generic")
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_waterfall_reset(self.h), "waterfall_reset")
-
-    def close(self):
-        if self.h:
-            self.ctx.L.csdr_amd_waterfall_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def rational_resampler_get_lowpass_f(taps_length, interpolation, decimation, window="HAMMING"):
@@ -492,20 +577,14 @@ def resampler_window(interpolation, decimation, taps_length, input_size, last_ta
     return tuple(int(v) for v in st)
 
 
-class _Resampling:
+class _Resampling(_Handle, _MaxOut):
     """Shared driver of csdr_amd_resampler (real, "resampler") and csdr_amd_interp (complex, "interp"): n_streams streams in lockstep."""
-    _dt, _eb, _pre = f32, 4, "resampler"
-
-    def _fn(self, name):
-        return getattr(self.ctx.L, "csdr_amd_%s_%s" % (self._pre, name))
-
-    def max_out(self, n_in):
-        return int(self._fn("max_out")(self.h, n_in))
+    _dt, _eb = f32, 4
 
     def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch):
         """device pointers: n_in new samples per stream (in_pitch apart) -> outputs per stream written at d_out (out_pitch elements apart)"""
         n = C.c_longlong(0)
-        self.ctx.check(self._fn("process")(self.h, d_in, n_in, in_pitch, d_out, out_pitch, C.byref(n)), self._pre + "_process")
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, C.byref(n))
         return n.value
 
     def process(self, x, calls=None):
@@ -528,46 +607,24 @@ class _Resampling:
         y = np.concatenate(out, axis=1) if out else np.zeros((s, 0), self._dt)
         return y[0] if squeeze else y
 
-    def reset(self):
-        self.ctx.check(self._fn("reset")(self.h), self._pre + "_reset")
-
     def set_cli_bufsize(self, the_bufsize):
-        self.ctx.check(self._fn("set_cli_bufsize")(self.h, int(the_bufsize)), self._pre + "_set_cli_bufsize")
-
-    def force_generic(self, on=True):
-        self.ctx.check(self._fn("force_generic")(self.h, int(on)), self._pre + "_force_generic")
-
-    def kernel_name(self):
-        return self._fn("kernel_name")(self.h).decode()
-
-    def close(self):
-        if self.h:
-            self._fn("destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("set_cli_bufsize", int(the_bufsize))
 
 
 class Resampler(_Resampling):
     """csdr_amd_resampler: rational_resampler_ff (libcsdr.c:607-640) by interpolation/decimation for n_streams float streams."""
 
     def __init__(self, ctx, interpolation, decimation, taps, n_streams=1, bufsize=None, last_taps_delay=0):
-        self.ctx, self.I, self.D, self.n_streams = ctx, interpolation, decimation, n_streams
+        self.I, self.D, self.n_streams = interpolation, decimation, n_streams
         self.taps = np.ascontiguousarray(taps, f32)
-        self.h = ctx.L.csdr_amd_resampler_create(ctx.h, interpolation, decimation, _hp(self.taps), self.taps.size, n_streams)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        _Handle.__init__(self, ctx, "resampler", ctx.L.csdr_amd_resampler_create(ctx.h, interpolation, decimation, _hp(self.taps), self.taps.size, n_streams))
         if bufsize:
             self.set_cli_bufsize(bufsize)
         if last_taps_delay:
             self.set_last_taps_delay(last_taps_delay)
 
     def set_last_taps_delay(self, d):
-        self.ctx.check(self.ctx.L.csdr_amd_resampler_set_last_taps_delay(self.h, int(d)), "resampler_set_last_taps_delay")
+        self._call("set_last_taps_delay", int(d))
 
 
 class Psk31Params(C.Structure):
@@ -626,25 +683,21 @@ def psk31_varicode_table():
     return t.reshape(128, 2)
 
 
-class Psk31:
+class Psk31(_Handle, _MaxOut, _ChannelState, _Lanes):
     """csdr_amd_psk31: the BPSK31 receive chain (simple_agc_cc | timing_recovery_cc | dbpsk_decoder_c_u8 | psk31_varicode_decoder_u8_u8) for
     n_channels channels, stages first..last ("agc", "timing", "dbpsk", "varicode"), state kept on the device between calls."""
+    _chan = Psk31Chan
 
     def __init__(self, ctx, params=None, n_channels=1, first="agc", last="varicode"):
-        self.ctx, self.n_channels = ctx, n_channels
+        self.n_channels = n_channels
         self.params = params if params is not None else psk31_params()
         self.first, self.last = _psk31_stage(first), _psk31_stage(last)
         self.in_dtype, self.out_dtype = _psk31_types(self.first, self.last)
-        self.h = ctx.L.csdr_amd_psk31_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
-
-    def max_out(self, n_in):
-        return int(self.ctx.L.csdr_amd_psk31_max_out(self.h, n_in))
+        _Handle.__init__(self, ctx, "psk31", ctx.L.csdr_amd_psk31_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last))
 
     def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err=None, d_idx=None):
         """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err, d_idx), "psk31_process")
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err, d_idx)
 
     def process(self, x, calls=None, with_extras=False):
         """x: [n_channels, n] (or [n]) host items; calls: per-call item counts (default one call) -> a list of per-channel output arrays
@@ -657,72 +710,11 @@ class Psk31:
         if s != self.n_channels:
             raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
         calls = [n] if calls is None else list(calls)
-        eb = np.dtype(self.in_dtype).itemsize
-        ob = np.dtype(self.out_dtype).itemsize
-        di = self.ctx.upload(x)
-        opitch = max(self.max_out(max(calls) if calls else 0), 1)
-        do = self.ctx.alloc(ob * opitch * s + 256)
-        dc = self.ctx.alloc(4 * s + 256)
-        de = self.ctx.alloc(4 * opitch * s + 256) if with_extras else None
-        dx = self.ctx.alloc(4 * opitch * s + 256) if with_extras else None
-        outs = [[] for _ in range(s)]
-        errs = [[] for _ in range(s)]
-        idxs = [[] for _ in range(s)]
-        at = 0
-        for k in calls:
-            self.process_dev(di.at(eb * at), k, n, do.ptr, opitch, dc.ptr, de.ptr if de else None, dx.ptr if dx else None)
-            cnt = self.ctx.download(dc, np.int32, s)
-            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
-            if with_extras:
-                e = self.ctx.download(de, f32, opitch * s).reshape(s, opitch)
-                ix = self.ctx.download(dx, np.uint32, opitch * s).reshape(s, opitch)
-            for c in range(s):
-                outs[c].append(y[c, :cnt[c]].copy())
-                if with_extras:
-                    errs[c].append(e[c, :cnt[c]].copy()); idxs[c].append(ix[c, :cnt[c]].copy())
-            at += k
-        cat = lambda lst, dt: np.concatenate(lst) if lst else np.zeros(0, dt)
-        res = [cat(o, self.out_dtype) for o in outs]
         if with_extras:
-            res = [(res[c], cat(errs[c], f32), cat(idxs[c], np.uint32)) for c in range(s)]
+            res = _counted_calls(self, x, calls, (("d_err", f32), ("d_idx", np.uint32)))
+        else:
+            res = [r[0] for r in _counted_calls(self, x, calls)]
         return res[0] if squeeze else res
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_reset(self.h), "psk31_reset")
-
-    def reset_channel(self, ch):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_reset_channel(self.h, int(ch)), "psk31_reset_channel")
-
-    def get_channel(self, ch):
-        st = Psk31Chan()
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_get_channel(self.h, int(ch), C.byref(st)), "psk31_get_channel")
-        return st
-
-    def set_channel(self, ch, st):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_set_channel(self.h, int(ch), C.byref(st)), "psk31_set_channel")
-
-    def set_lanes(self, lanes):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_set_lanes(self.h, int(lanes)), "psk31_set_lanes")
-
-    def lanes(self):
-        return int(self.ctx.L.csdr_amd_psk31_lanes(self.h))
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31_force_generic(self.h, int(on)), "psk31_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_psk31_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:                   # (after Context.close the object's context is gone: destroy would read it)
-            self.ctx.L.csdr_amd_psk31_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Psk31TxChan(C.Structure):
@@ -768,25 +760,21 @@ def psk31tx_debug_walk(x, n_psk=2, interpolation=256, first="varicode", last="sh
     return out[:k]
 
 
-class Psk31Tx:
+class Psk31Tx(_Handle, _MaxOut, _ChannelState):
     """csdr_amd_psk31tx: the BPSK31 transmit chain (psk31_varicode_encoder_u8_u8 | differential_encoder_u8_u8 | psk_modulator_u8_c n_psk |
     psk31_interpolate_sine_cc interpolation) for n_channels channels, stages first..last ("varicode", "diff", "mod", "shape"), state kept on the
     device between calls."""
+    _chan = Psk31TxChan
 
     def __init__(self, ctx, n_channels=1, n_psk=2, interpolation=256, first="varicode", last="shape"):
-        self.ctx, self.n_channels, self.n_psk, self.interpolation = ctx, n_channels, n_psk, interpolation
+        self.n_channels, self.n_psk, self.interpolation = n_channels, n_psk, interpolation
         self.first, self.last = _psk31tx_stage(first), _psk31tx_stage(last)
         self.in_dtype, self.out_dtype = _psk31tx_types(self.first, self.last)
-        self.h = ctx.L.csdr_amd_psk31tx_create(ctx.h, n_channels, n_psk, interpolation, self.first, self.last)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
-
-    def max_out(self, n_in):
-        return int(self.ctx.L.csdr_amd_psk31tx_max_out(self.h, n_in))
+        _Handle.__init__(self, ctx, "psk31tx", ctx.L.csdr_amd_psk31tx_create(ctx.h, n_channels, n_psk, interpolation, self.first, self.last))
 
     def process_dev(self, d_in, n_in, d_in_counts, in_pitch, d_out, out_pitch, d_counts):
         """device pointers; in_counts (n_channels int32, or None) gives each channel's item count, counts receives its output count.  Asynchronous."""
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_process(self.h, d_in, n_in, d_in_counts, in_pitch, d_out, out_pitch, d_counts), "psk31tx_process")
+        self._call("process", d_in, n_in, d_in_counts, in_pitch, d_out, out_pitch, d_counts)
 
     def process(self, x, in_counts=None, calls=None):
         """x: [n_channels, n] (or [n]) host items; in_counts: per-channel item counts of the (single) call, each 0..n; calls: per-call item counts
@@ -805,54 +793,8 @@ class Psk31Tx:
             if ic.shape != (s,) or len(calls) != 1 or ic.min() < 0 or ic.max() > calls[0]:
                 raise CsdrAmdError("psk31tx: in_counts holds one count of 0 .. n_in per channel, for one call")
             dn = self.ctx.upload(ic)
-        eb = np.dtype(self.in_dtype).itemsize
-        ob = np.dtype(self.out_dtype).itemsize
-        di = self.ctx.upload(x) if n else self.ctx.alloc(256)
-        opitch = max(self.max_out(max(calls) if calls else 0), 1)
-        do = self.ctx.alloc(ob * opitch * s + 256)
-        dc = self.ctx.alloc(4 * s + 256)
-        outs = [[] for _ in range(s)]
-        at = 0
-        for k in calls:
-            self.process_dev(di.at(eb * at), k, dn.ptr if dn else None, max(n, 1), do.ptr, opitch, dc.ptr)
-            cnt = self.ctx.download(dc, np.int32, s)
-            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
-            for c in range(s):
-                outs[c].append(y[c, :cnt[c]].copy())
-            at += k
-        res = [np.concatenate(o) if o else np.zeros(0, self.out_dtype) for o in outs]
+        res = [r[0] for r in _counted_calls(self, x, calls, d_in_counts=dn.ptr if dn else None)]
         return res[0] if squeeze else res
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_reset(self.h), "psk31tx_reset")
-
-    def reset_channel(self, ch):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_reset_channel(self.h, int(ch)), "psk31tx_reset_channel")
-
-    def get_channel(self, ch):
-        st = Psk31TxChan()
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_get_channel(self.h, int(ch), C.byref(st)), "psk31tx_get_channel")
-        return st
-
-    def set_channel(self, ch, st):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_set_channel(self.h, int(ch), C.byref(st)), "psk31tx_set_channel")
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_psk31tx_force_generic(self.h, int(on)), "psk31tx_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_psk31tx_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:                   # (after Context.close the object's context is gone: destroy would read it)
-            self.ctx.L.csdr_amd_psk31tx_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class RttyParams(C.Structure):
@@ -923,25 +865,20 @@ def rtty_baudot_decoder_lookup(fig_mode, c):
     return r, f.value
 
 
-class Rtty:
+class Rtty(_Handle, _MaxOut, _PerChannel):
     """csdr_amd_rtty: the RTTY receive chain (bfsk_demod_cf | serial_line_decoder_f_u8 | rtty_baudot2ascii_u8_u8) for n_channels channels, stages
     first..last ("bfsk", "serial", "baudot"), state kept on the device between calls."""
 
     def __init__(self, ctx, params=None, n_channels=1, first="bfsk", last="baudot"):
-        self.ctx, self.n_channels = ctx, n_channels
+        self.n_channels = n_channels
         self.params = params if params is not None else rtty_params()
         self.first, self.last = _rtty_stage(first), _rtty_stage(last)
         self.in_dtype, self.out_dtype = _rtty_types(self.params, self.first, self.last)
-        self.h = ctx.L.csdr_amd_rtty_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
-
-    def max_out(self, n_in):
-        return int(self.ctx.L.csdr_amd_rtty_max_out(self.h, n_in))
+        _Handle.__init__(self, ctx, "rtty", ctx.L.csdr_amd_rtty_create(ctx.h, C.byref(self.params), n_channels, self.first, self.last))
 
     def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts):
         """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
-        self.ctx.check(self.ctx.L.csdr_amd_rtty_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_counts), "rtty_process")
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, d_counts)
 
     def process(self, x, calls=None):
         """x: [n_channels, n] (or [n]) host items; calls: per-call item counts (default one call) -> a list of per-channel output arrays
@@ -954,46 +891,8 @@ class Rtty:
         if s != self.n_channels:
             raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
         calls = [n] if calls is None else list(calls)
-        eb = np.dtype(self.in_dtype).itemsize
-        ob = np.dtype(self.out_dtype).itemsize
-        di = self.ctx.upload(x)
-        opitch = max(self.max_out(max(calls) if calls else 0), 1)
-        do = self.ctx.alloc(ob * opitch * s + 256)
-        dc = self.ctx.alloc(4 * s + 256)
-        outs = [[] for _ in range(s)]
-        at = 0
-        for k in calls:
-            self.process_dev(di.at(eb * at), k, n, do.ptr, opitch, dc.ptr)
-            cnt = self.ctx.download(dc, np.int32, s)
-            y = self.ctx.download(do, self.out_dtype, opitch * s).reshape(s, opitch)
-            for c in range(s):
-                outs[c].append(y[c, :cnt[c]].copy())
-            at += k
-        res = [np.concatenate(o) if o else np.zeros(0, self.out_dtype) for o in outs]
+        res = [r[0] for r in _counted_calls(self, x, calls)]
         return res[0] if squeeze else res
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_rtty_reset(self.h), "rtty_reset")
-
-    def reset_channel(self, ch):
-        self.ctx.check(self.ctx.L.csdr_amd_rtty_reset_channel(self.h, int(ch)), "rtty_reset_channel")
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_rtty_force_generic(self.h, int(on)), "rtty_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_rtty_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.L.csdr_amd_rtty_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def squelch_report_due(report_every_nth, block_index):
@@ -1013,24 +912,22 @@ def squelch_debug_power(x, decimation=1):
     return f32(lib().csdr_amd_debug_squelch_power(_hp(x), x.size, int(decimation), int(cplx)))
 
 
-class Squelch:
+class Squelch(_Handle, _PerChannel):
     """csdr_amd_squelch: squelch_and_smeter_cc for n_channels channels in blocks of block_size samples; the samples behind a channel's last whole block
     stay on the device between calls."""
 
     def __init__(self, ctx, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
-        self.ctx, self.n_channels, self.B = ctx, n_channels, block_size
+        self.n_channels, self.B = n_channels, block_size
         lv = None if levels is None else np.ascontiguousarray(np.broadcast_to(np.asarray(levels, f32), (n_channels,)))
-        self.h = ctx.L.csdr_amd_squelch_create(ctx.h, n_channels, block_size, use_every_nth, None if lv is None else _hp(lv), max_samples_per_call)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        _Handle.__init__(self, ctx, "squelch", ctx.L.csdr_amd_squelch_create(ctx.h, n_channels, block_size, use_every_nth, None if lv is None else _hp(lv),
+                                                                              max_samples_per_call))
 
     def max_blocks(self):
-        return int(self.ctx.L.csdr_amd_squelch_max_blocks(self.h))
+        return int(self._fn("max_blocks")(self.h))
 
     def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_power=None, power_pitch=0, d_flags=None, counts=None):
         """device pointers (power / flags may be None); counts: a host int32 array of n_channels, or None -> the largest block count.  Asynchronous."""
-        return self.ctx.check(self.ctx.L.csdr_amd_squelch_process(self.h, d_in, n_in, in_pitch, d_out, out_pitch, d_power, power_pitch, d_flags,
-                                                                  None if counts is None else _hp(counts)), "squelch_process")
+        return self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, d_power, power_pitch, d_flags, None if counts is None else _hp(counts))
 
     def process(self, x, calls=None, in_pitch=None, out_pitch=None, levels_between=None):
         """x: [n_channels, n] (or [n]) complex samples; calls: per-call sample counts (default one call); in_pitch / out_pitch: row pitches in samples
@@ -1072,36 +969,13 @@ class Squelch:
 
     def set_level(self, ch, level):
         """takes effect from the next block that a later call starts; ch = -1: all channels"""
-        self.ctx.check(self.ctx.L.csdr_amd_squelch_set_level(self.h, int(ch), float(level)), "squelch_set_level")
+        self._call("set_level", int(ch), float(level))
 
     def get_level(self, ch):
-        return float(self.ctx.L.csdr_amd_squelch_get_level(self.h, int(ch)))
+        return float(self._fn("get_level")(self.h, int(ch)))
 
     def block_index(self, ch=0):
-        return int(self.ctx.L.csdr_amd_squelch_block_index(self.h, int(ch)))
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_squelch_reset(self.h), "squelch_reset")
-
-    def reset_channel(self, ch):
-        self.ctx.check(self.ctx.L.csdr_amd_squelch_reset_channel(self.h, int(ch)), "squelch_reset_channel")
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_squelch_force_generic(self.h, int(on)), "squelch_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_squelch_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.L.csdr_amd_squelch_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return int(self._fn("block_index")(self.h, int(ch)))
 
 
 class CarrierParams(C.Structure):
@@ -1156,19 +1030,19 @@ def carrier_debug_walk(params, x, outputs=CARRIER_OUTPUTS, cuts=(), state=None):
     return res
 
 
-class Carrier:
+class Carrier(_Handle, _ChannelState, _Lanes):
     """csdr_amd_carrier: bpsk_costas_loop_cc / pll_cc for n_channels channels with shared loop coefficients; each channel's phase, dphase and freq stay
     on the device between calls."""
 
+    _chan = CarrierChan
+
     def __init__(self, ctx, params, n_channels=1):
-        self.ctx, self.n_channels, self.params = ctx, n_channels, params
-        self.h = ctx.L.csdr_amd_carrier_create(ctx.h, C.byref(params), n_channels)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        self.n_channels, self.params = n_channels, params
+        _Handle.__init__(self, ctx, "carrier", ctx.L.csdr_amd_carrier_create(ctx.h, C.byref(params), n_channels))
 
     def process_dev(self, d_in, n, in_pitch, d_out=None, d_error=None, d_dphase=None, d_nco=None, out_pitch=0):
         """device pointers, any output may be None but not all.  Asynchronous."""
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_process(self.h, d_in, n, in_pitch, d_out, d_error, d_dphase, d_nco, out_pitch), "carrier_process")
+        self._call("process", d_in, n, in_pitch, d_out, d_error, d_dphase, d_nco, out_pitch)
 
     def process(self, x, outputs=("out",), calls=None, in_pitch=None, out_pitch=None):
         """x: [n_channels, n] (or [n]) complex samples; outputs: names out of "out", "error", "dphase", "nco"; calls: per-call sample counts (default one
@@ -1200,43 +1074,6 @@ class Carrier:
             at += k
         return {k: v[0] for k, v in res.items()} if squeeze else res
 
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_reset(self.h), "carrier_reset")
-
-    def reset_channel(self, ch):
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_reset_channel(self.h, int(ch)), "carrier_reset_channel")
-
-    def get_channel(self, ch):
-        st = CarrierChan()
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_get_channel(self.h, int(ch), C.byref(st)), "carrier_get_channel")
-        return st
-
-    def set_channel(self, ch, st):
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_set_channel(self.h, int(ch), C.byref(st)), "carrier_set_channel")
-
-    def set_lanes(self, lanes):
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_set_lanes(self.h, int(lanes)), "carrier_set_lanes")
-
-    def lanes(self):
-        return int(self.ctx.L.csdr_amd_carrier_lanes(self.h))
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_carrier_force_generic(self.h, int(on)), "carrier_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_carrier_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.L.csdr_amd_carrier_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 TX_MODES = {"fm": 0, "am": 1, "dsb": 2}
 TX_FORMATS = {"cf32": 0, "u8": 1}
@@ -1256,26 +1093,24 @@ def fmmod_debug_walk(x, cuts=(), state=0.0, want_out=False):
     return (ph, np.float32(st.value), out) if want_out else (ph, np.float32(st.value))
 
 
-class TxBank:
+class TxBank(_Handle, _MaxOut):
     """csdr_amd_txbank: convert_s16_f | gain_ff | fmmod_fc or dsb_fc [| add_dcoffset_cc] | fir_interpolate_cc | shift_addition_cc [| convert_f_u8] for
     n_streams s16 audio streams, each with its own shift rate; FM phase, interpolator history and rotator phase stay on the device between calls."""
 
     def __init__(self, ctx, n_streams, mode, interpolation, taps, rates, gain=1.0, q_value=0.0, out_format="cf32", max_in_samples=1 << 16):
-        self.ctx, self.n_streams, self.I, self.fmt = ctx, n_streams, interpolation, out_format
+        self.n_streams, self.I, self.fmt = n_streams, interpolation, out_format
         self.taps = np.ascontiguousarray(taps, f32)
         rates = np.ascontiguousarray(rates, f32)
         if rates.size != n_streams:
             raise ValueError("%d rates for %d streams" % (rates.size, n_streams))
         self.max_in = int(max_in_samples)
-        self.h = ctx.L.csdr_amd_txbank_create(ctx.h, n_streams, TX_MODES[mode], gain, q_value, interpolation, _hp(self.taps), self.taps.size, _hp(rates),
-                                              TX_FORMATS[out_format], self.max_in)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        _Handle.__init__(self, ctx, "txbank", ctx.L.csdr_amd_txbank_create(ctx.h, n_streams, TX_MODES[mode], gain, q_value, interpolation, _hp(self.taps),
+                                                                            self.taps.size, _hp(rates), TX_FORMATS[out_format], self.max_in))
 
     def process_dev(self, d_in, in_pitch, n_in, d_out, out_pitch):
         """device pointers, pitches in samples -> outputs per stream.  Asynchronous."""
         no = C.c_longlong(0)
-        self.ctx.check(self.ctx.L.csdr_amd_txbank_process(self.h, d_in, in_pitch, n_in, d_out, out_pitch, C.byref(no)), "txbank_process")
+        self._call("process", d_in, in_pitch, n_in, d_out, out_pitch, C.byref(no))
         return no.value
 
     def process(self, x, calls=None, out_pitch=None, out_byte_offset=0):
@@ -1305,45 +1140,20 @@ class TxBank:
         return y[0] if squeeze else y
 
     def set_rate(self, stream, rate):
-        self.ctx.check(self.ctx.L.csdr_amd_txbank_set_rate(self.h, int(stream), float(rate)), "txbank_set_rate")
+        self._call("set_rate", int(stream), float(rate))
 
     def get_rate(self, stream):
-        return float(self.ctx.L.csdr_amd_txbank_get_rate(self.h, int(stream)))
-
-    def reset(self):
-        self.ctx.check(self.ctx.L.csdr_amd_txbank_reset(self.h), "txbank_reset")
-
-    def max_out(self, n_in):
-        return int(self.ctx.L.csdr_amd_txbank_max_out(self.h, int(n_in)))
-
-    def force_generic(self, on=True):
-        self.ctx.check(self.ctx.L.csdr_amd_txbank_force_generic(self.h, int(on)), "txbank_force_generic")
-
-    def kernel_name(self):
-        return self.ctx.L.csdr_amd_txbank_kernel_name(self.h).decode()
-
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.L.csdr_amd_txbank_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return float(self._fn("get_rate")(self.h, int(stream)))
 
 
 class Interpolator(_Resampling):
     """csdr_amd_interp: fir_interpolate_cc (libcsdr.c:579-605) by `interpolation` for n_streams complex streams."""
-    _dt, _eb, _pre = c64, 8, "interp"
+    _dt, _eb = c64, 8
 
     def __init__(self, ctx, interpolation, taps, n_streams=1, bufsize=None):
-        self.ctx, self.I, self.n_streams = ctx, interpolation, n_streams
+        self.I, self.n_streams = interpolation, n_streams
         self.taps = np.ascontiguousarray(taps, f32)
-        self.h = ctx.L.csdr_amd_interp_create(ctx.h, interpolation, _hp(self.taps), self.taps.size, n_streams)
-        if not self.h:
-            raise CsdrAmdError(ctx.err())
+        _Handle.__init__(self, ctx, "interp", ctx.L.csdr_amd_interp_create(ctx.h, interpolation, _hp(self.taps), self.taps.size, n_streams))
         if bufsize:
             self.set_cli_bufsize(bufsize)
 
@@ -1593,24 +1403,19 @@ class Context:
     def fft_cc(self, x, fft_size, every_n, window="HAMMING", calls=1):
         x = np.ascontiguousarray(x, c64).ravel()
         frames_max = x.size // every_n + 1
-        f = self.L.csdr_amd_fftcc_create(self.h, fft_size, every_n, WINDOWS[window], frames_max)
-        if not f:
-            raise CsdrAmdError(self.err())
-        di = self.upload(x); do = self.alloc(8 * fft_size * frames_max + 64)
-        per = (x.size + calls - 1) // calls; at = 0; total = 0; left = 0
-        while at < x.size or left:
-            take = min(per, x.size - at) + left
-            start = at - left
-            cons = C.c_size_t(0)
-            nf = self.L.csdr_amd_fftcc_process(f, di.at(8 * start), take, do.at(8 * fft_size * total), C.byref(cons))
-            self.check(nf, "fft_cc")
-            total += nf
-            at = start + take; left = take - cons.value
-            if at >= x.size and (nf == 0 or left < every_n):
-                break
-        y = self.download(do, c64, fft_size * total)
-        self.L.csdr_amd_fftcc_destroy(f)
-        return y
+        with _Handle(self, "fftcc", self.L.csdr_amd_fftcc_create(self.h, fft_size, every_n, WINDOWS[window], frames_max)) as f:
+            di = self.upload(x); do = self.alloc(8 * fft_size * frames_max + 64)
+            per = (x.size + calls - 1) // calls; at = 0; total = 0; left = 0
+            while at < x.size or left:
+                take = min(per, x.size - at) + left
+                start = at - left
+                cons = C.c_size_t(0)
+                nf = self.check(f._fn("process")(f.h, di.at(8 * start), take, do.at(8 * fft_size * total), C.byref(cons)), "fft_cc")
+                total += nf
+                at = start + take; left = take - cons.value
+                if at >= x.size and (nf == 0 or left < every_n):
+                    break
+            return self.download(do, c64, fft_size * total)
 
 
     # ---- the waterfall (waterfall.hip)
@@ -1706,14 +1511,12 @@ class Context:
         x2, squeeze = self._2d(x, f32)
         s, n = x2.shape
         tp = None if taps is None else np.ascontiguousarray(taps, f32)
-        d = self.L.csdr_amd_fracdec_create(rate, num_poly_points, None if tp is None else _hp(tp), 0 if tp is None else tp.size)
-        if not d:
-            raise CsdrAmdError(self.err())
-        if bufsize:                                   # the CLI's window loop (csdr.c:1511-1524) instead of one call over the whole array
-            self.L.csdr_amd_fracdec_set_cli_bufsize(d, bufsize)
-        di = self.upload(x2); do = self.alloc(4 * s * n + 64); proc = C.c_int(0)
-        no = self.check(self.L.csdr_amd_fractional_decimator_ff(self.h, d, di.ptr, do.ptr, s, n, n, n, C.byref(proc)), "fracdec")
-        self.sync(); self.L.csdr_amd_fracdec_destroy(d)
+        with _Handle(None, "fracdec", self.L.csdr_amd_fracdec_create(rate, num_poly_points, None if tp is None else _hp(tp), 0 if tp is None else tp.size)) as d:
+            if bufsize:                               # the CLI's window loop (csdr.c:1511-1524) instead of one call over the whole array
+                d._fn("set_cli_bufsize")(d.h, bufsize)
+            di = self.upload(x2); do = self.alloc(4 * s * n + 64); proc = C.c_int(0)
+            no = self.check(self.L.csdr_amd_fractional_decimator_ff(self.h, d.h, di.ptr, do.ptr, s, n, n, n, C.byref(proc)), "fracdec")
+            self.sync()                               # (the kernels read the object's tables: they finish in front of its destroy)
         y = self.download(do, f32, s * n).reshape(s, n)[:, :no]
         return y[0].copy() if squeeze else y.copy()
 
@@ -1909,17 +1712,14 @@ class Context:
         s, n = x2.shape
         inp = fft_size - taps.size + 1; nb = n // inp
         per = nb if not blocks_per_call else blocks_per_call
-        f = self.L.csdr_amd_fftfilt_create(self.h, fft_size, _hp(taps), taps.size, s, max(per, 1))
-        if not f:
-            raise CsdrAmdError(self.err())
-        di = self.upload(x2); do = self.alloc(x2.nbytes + 64)
-        b = 0
-        while b < nb:
-            k = min(per, nb - b)
-            self.check(self.L.csdr_amd_fftfilt_process(f, di.at(8 * b * inp), do.at(8 * b * inp), k, n, n), "fftfilt")
-            b += k
-        y = self.download(do, c64, s * n).reshape(s, n)[:, :nb * inp]
-        self.L.csdr_amd_fftfilt_destroy(f)
+        with _Handle(self, "fftfilt", self.L.csdr_amd_fftfilt_create(self.h, fft_size, _hp(taps), taps.size, s, max(per, 1))) as f:
+            di = self.upload(x2); do = self.alloc(x2.nbytes + 64)
+            b = 0
+            while b < nb:
+                k = min(per, nb - b)
+                self.check(f._fn("process")(f.h, di.at(8 * b * inp), do.at(8 * b * inp), k, n, n), "fftfilt")
+                b += k
+            y = self.download(do, c64, s * n).reshape(s, n)[:, :nb * inp]
         return y[0].copy() if squeeze else y.copy()
 
     def fastddc_init(self, tbw, decimation, shift_rate):
@@ -1928,42 +1728,35 @@ class Context:
     def fastddc_fwd_cc(self, x, ddc, blocks_per_call=None):
         x = np.ascontiguousarray(x, c64); nb = x.size // ddc.input_size
         per = nb if not blocks_per_call else blocks_per_call
-        f = self.L.csdr_amd_fastddc_fwd_create(self.h, C.byref(ddc), max(per, 1))
-        if not f:
-            raise CsdrAmdError(self.err())
-        di = self.upload(x); do = self.alloc(8 * nb * ddc.fft_size + 64)
-        b = 0
-        while b < nb:
-            k = min(per, nb - b)
-            self.check(self.L.csdr_amd_fastddc_fwd_process(f, di.at(8 * b * ddc.input_size), do.at(8 * b * ddc.fft_size), k), "fastddc_fwd")
-            b += k
-        y = self.download(do, c64, nb * ddc.fft_size).reshape(nb, ddc.fft_size)
-        self.L.csdr_amd_fastddc_fwd_destroy(f)
-        return y
+        with _Handle(self, "fastddc_fwd", self.L.csdr_amd_fastddc_fwd_create(self.h, C.byref(ddc), max(per, 1))) as f:
+            di = self.upload(x); do = self.alloc(8 * nb * ddc.fft_size + 64)
+            b = 0
+            while b < nb:
+                k = min(per, nb - b)
+                self.check(f._fn("process")(f.h, di.at(8 * b * ddc.input_size), do.at(8 * b * ddc.fft_size), k), "fastddc_fwd")
+                b += k
+            return self.download(do, c64, nb * ddc.fft_size).reshape(nb, ddc.fft_size)
 
     def fastddc_inv_cc(self, spectra, tbw, decimation, shift_rates, window="HAMMING", blocks_per_call=None):
         """spectra [n_blocks, fft] -> list of per-channel outputs."""
         spectra = np.ascontiguousarray(spectra, c64); nb = spectra.shape[0]
         rates = np.ascontiguousarray(shift_rates, f32); nc = rates.size
         per = nb if not blocks_per_call else blocks_per_call
-        f = self.L.csdr_amd_fastddc_inv_create(self.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], max(per, 1))
-        if not f:
-            raise CsdrAmdError(self.err())
-        fft = spectra.shape[1]
-        di = self.upload(spectra)
-        outs = [[] for _ in range(nc)]
-        b = 0
-        while b < nb:
-            k = min(per, nb - b)
-            pitch = self.L.csdr_amd_fastddc_inv_max_output(f, k) + 8
-            do = self.alloc(8 * nc * pitch)
-            counts = np.zeros(nc, np.int32)
-            self.check(self.L.csdr_amd_fastddc_inv_process(f, di.at(8 * b * fft), k, do.ptr, pitch, _hp(counts)), "fastddc_inv")
-            y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
-            for c in range(nc):
-                outs[c].append(y[c, :counts[c]].copy())
-            b += k
-        self.L.csdr_amd_fastddc_inv_destroy(f)
+        with _Handle(self, "fastddc_inv", self.L.csdr_amd_fastddc_inv_create(self.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], max(per, 1))) as f:
+            fft = spectra.shape[1]
+            di = self.upload(spectra)
+            outs = [[] for _ in range(nc)]
+            b = 0
+            while b < nb:
+                k = min(per, nb - b)
+                pitch = f._fn("max_output")(f.h, k) + 8
+                do = self.alloc(8 * nc * pitch)
+                counts = np.zeros(nc, np.int32)
+                self.check(f._fn("process")(f.h, di.at(8 * b * fft), k, do.ptr, pitch, _hp(counts)), "fastddc_inv")
+                y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
+                for c in range(nc):
+                    outs[c].append(y[c, :counts[c]].copy())
+                b += k
         return [np.concatenate(o) for o in outs]
 
     def fastddc_bank(self, x, tbw, decimation, shift_rates, window="HAMMING", blocks_per_call=None, retune=None, schedule=None, retunes=None):
@@ -1978,28 +1771,25 @@ class Context:
         per = nb if not blocks_per_call else blocks_per_call
         if schedule:
             per = max(schedule)
-        bk = self.L.csdr_amd_fastddc_bank_create(self.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], max(per, 1))
-        if not bk:
-            raise CsdrAmdError(self.err())
-        di = self.upload(x)
-        outs = [[] for _ in range(nc)]
-        b = 0; call = 0
-        while b < nb:
-            k = min(per, nb - b) if not schedule else min(schedule[call % len(schedule)], nb - b)
-            if retune and retune[0] == call:
-                self.check(self.L.csdr_amd_fastddc_bank_set_rate(bk, retune[1], retune[2]), "bank_set_rate")
-            for ch, rt in (retunes or {}).get(call, []):
-                self.check(self.L.csdr_amd_fastddc_bank_set_rate(bk, ch, rt), "bank_set_rate")
-            pitch = self.L.csdr_amd_fastddc_bank_max_output(bk, k) + 8
-            do = self.alloc(8 * nc * pitch)
-            counts = np.zeros(nc, np.int32)
-            self.check(process(bk, di.at(es * b * ddc.input_size), k, do.ptr, pitch, _hp(counts)), "fastddc_bank")
-            y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
-            for c in range(nc):
-                outs[c].append(y[c, :counts[c]].copy())
-            b += k; call += 1
-        self.last_ddc_kernel = self.L.csdr_amd_fastddc_inv_kernel_name(self.L.csdr_amd_fastddc_bank_inverse(bk)).decode()
-        self.L.csdr_amd_fastddc_bank_destroy(bk)
+        with _Handle(self, "fastddc_bank", self.L.csdr_amd_fastddc_bank_create(self.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], max(per, 1))) as bk:
+            di = self.upload(x)
+            outs = [[] for _ in range(nc)]
+            b = 0; call = 0
+            while b < nb:
+                k = min(per, nb - b) if not schedule else min(schedule[call % len(schedule)], nb - b)
+                if retune and retune[0] == call:
+                    self.check(bk._fn("set_rate")(bk.h, retune[1], retune[2]), "bank_set_rate")
+                for ch, rt in (retunes or {}).get(call, []):
+                    self.check(bk._fn("set_rate")(bk.h, ch, rt), "bank_set_rate")
+                pitch = bk._fn("max_output")(bk.h, k) + 8
+                do = self.alloc(8 * nc * pitch)
+                counts = np.zeros(nc, np.int32)
+                self.check(process(bk.h, di.at(es * b * ddc.input_size), k, do.ptr, pitch, _hp(counts)), "fastddc_bank")
+                y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
+                for c in range(nc):
+                    outs[c].append(y[c, :counts[c]].copy())
+                b += k; call += 1
+            self.last_ddc_kernel = self.L.csdr_amd_fastddc_inv_kernel_name(bk._fn("inverse")(bk.h)).decode()
         return [np.concatenate(o) for o in outs]
 
     # (the multi-rank form of the bank on ONE GPU: sharded_bank_loopback below, module level -- one Context per rank thread)
@@ -2024,31 +1814,29 @@ class Context:
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == s
             w = self.L.csdr_amd_wfm_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, max(block, 1024))
-        if not w:
-            raise CsdrAmdError(self.err())
-        di = self.upload(xx)
-        apitch = (n // (decimation * frac_rate) + 64 + 63) // 64 * 64
-        ds = self.alloc(2 * s * apitch); df = self.alloc(4 * s * apitch) if want_float else None
-        pos = 0; na = 0; call = 0; parts_s = []; parts_f = []
-        while pos < n:
-            for st, r in (retunes or {}).get(call, []):
-                self.check(self.L.csdr_amd_wfm_set_rate(w, st, r), "wfm_set_rate")
-            k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+        with _Handle(self, "wfm", w) as w:
+            di = self.upload(xx)
+            apitch = (n // (decimation * frac_rate) + 64 + 63) // 64 * 64
+            ds = self.alloc(2 * s * apitch); df = self.alloc(4 * s * apitch) if want_float else None
+            pos = 0; na = 0; call = 0; parts_s = []; parts_f = []
+            while pos < n:
+                for st, r in (retunes or {}).get(call, []):
+                    w._call("set_rate", st, r)
+                k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+                if out_per_call:
+                    got = w._call("process", di.at(2 * pos), pitch, k, ds.ptr, df.ptr if want_float else None, apitch)
+                    parts_s.append(self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :got].copy())
+                    if want_float: parts_f.append(self.download(df, f32, s * apitch).reshape(s, apitch)[:, :got].copy())
+                else:
+                    got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na) if want_float else None, apitch)
+                pos += k; na += got
             if out_per_call:
-                got = self.check(self.L.csdr_amd_wfm_process(w, di.at(2 * pos), pitch, k, ds.ptr, df.ptr if want_float else None, apitch), "wfm_process")
-                parts_s.append(self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :got].copy())
-                if want_float: parts_f.append(self.download(df, f32, s * apitch).reshape(s, apitch)[:, :got].copy())
+                s16 = np.concatenate(parts_s, axis=1) if parts_s else np.zeros((s, 0), np.int16)
+                af = np.concatenate(parts_f, axis=1) if parts_f else np.zeros((s, 0), f32)
             else:
-                got = self.check(self.L.csdr_amd_wfm_process(w, di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na) if want_float else None, apitch), "wfm_process")
-            pos += k; na += got
-        if out_per_call:
-            s16 = np.concatenate(parts_s, axis=1) if parts_s else np.zeros((s, 0), np.int16)
-            af = np.concatenate(parts_f, axis=1) if parts_f else np.zeros((s, 0), f32)
-        else:
-            s16 = self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :na]
-            af = self.download(df, f32, s * apitch).reshape(s, apitch)[:, :na] if want_float else np.zeros((s, 0), f32)
-        self.last_wfm_kernel = self.L.csdr_amd_wfm_kernel_name(w).decode()
-        self.L.csdr_amd_wfm_destroy(w)
+                s16 = self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :na]
+                af = self.download(df, f32, s * apitch).reshape(s, apitch)[:, :na] if want_float else np.zeros((s, 0), f32)
+            self.last_wfm_kernel = w.kernel_name()
         return (s16[0].copy(), af[0].copy()) if squeeze else (s16.copy(), af.copy())
 
     def ddc_u8(self, iq_u8, shift_rate, decimation, taps, block=None, pitch_pad=0, retunes=None):
@@ -2068,22 +1856,20 @@ class Context:
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == s
             d = self.L.csdr_amd_ddc_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, max(block, 1024))
-        if not d:
-            raise CsdrAmdError(self.err())
-        di = self.upload(xx)
-        opitch = n // decimation + 64
-        do = self.alloc(8 * s * opitch)
-        pos = 0; no = 0; self.ddc_kernels = set(); call = 0
-        while pos < n:
-            for st, r in (retunes or {}).get(call, []):
-                self.check(self.L.csdr_amd_ddc_set_rate(d, st, r), "ddc_set_rate")
-            k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
-            got = self.check(self.L.csdr_amd_ddc_process(d, di.at(2 * pos), pitch, k, do.at(8 * no), opitch), "ddc_process")
-            self.ddc_kernels.add(self.L.csdr_amd_ddc_kernel_name(d).decode())
-            pos += k; no += got
-        y = self.download(do, c64, s * opitch).reshape(s, opitch)[:, :no]
-        self.last_ddc_kernel = self.L.csdr_amd_ddc_kernel_name(d).decode()
-        self.L.csdr_amd_ddc_destroy(d)
+        with _Handle(self, "ddc", d) as d:
+            di = self.upload(xx)
+            opitch = n // decimation + 64
+            do = self.alloc(8 * s * opitch)
+            pos = 0; no = 0; self.ddc_kernels = set(); call = 0
+            while pos < n:
+                for st, r in (retunes or {}).get(call, []):
+                    d._call("set_rate", st, r)
+                k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+                got = d._call("process", di.at(2 * pos), pitch, k, do.at(8 * no), opitch)
+                self.ddc_kernels.add(d.kernel_name())
+                pos += k; no += got
+            y = self.download(do, c64, s * opitch).reshape(s, opitch)[:, :no]
+            self.last_ddc_kernel = d.kernel_name()
         return y[0].copy() if squeeze else y.copy()
 
     def wfm_ring_chain(self, iq_u8, shift_rate, decimation, taps, block=16384, n_slots=8, frac_rate=5, tau=50e-6, audio_rate=48000, retunes=None, in_flight=None,
@@ -2098,10 +1884,9 @@ class Context:
         assert n % block == 0
         nb = n // block
         taps = np.ascontiguousarray(taps, f32)
-        r = self.L.csdr_amd_wfm_ring_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, block, n_slots)
-        if not r:
-            raise CsdrAmdError(self.err())
-        try:
+        with _Handle(self, "wfm_ring", self.L.csdr_amd_wfm_ring_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, block,
+                                                                       n_slots)) as ring:
+            r = ring.h
             if idle_us is not None or life_ms is not None:
                 self.check(self.L.csdr_amd_wfm_ring_set_timeouts(r, 200.0 if idle_us is None else idle_us, 250.0 if life_ms is None else life_ms), "ring_set_timeouts")
             depth = (n_slots - 2) if in_flight is None else in_flight
@@ -2132,8 +1917,6 @@ class Context:
             while len(outs) < nb:
                 collect(len(outs))
             self.last_ring = {"launches": self.L.csdr_amd_wfm_ring_launches(r), "grid": self.L.csdr_amd_wfm_ring_grid(r)}
-        finally:
-            self.L.csdr_amd_wfm_ring_destroy(r)
         y = np.concatenate(outs, axis=1)
         return y[0].copy() if squeeze else y
 
@@ -2154,22 +1937,20 @@ class Context:
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == S
             w = self.L.csdr_amd_nfm_create_rates(self.h, S, _hp(rates), decimation, _hp(taps), taps.size, audio_rate, agc_block, 1.0, 1.0, max(block, 1024))
-        if not w:
-            raise CsdrAmdError(self.err())
-        di = self.upload(xx)
-        apitch = n // decimation + 1024 + 64
-        ds = self.alloc(2 * S * apitch); df = self.alloc(4 * S * apitch)
-        pos = 0; na = 0; call = 0
-        while pos < n:
-            for st, r in (retunes or {}).get(call, []):
-                self.check(self.L.csdr_amd_nfm_set_rate(w, st, r), "nfm_set_rate")
-            k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
-            got = self.check(self.L.csdr_amd_nfm_process(w, di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na), apitch), "nfm_process")
-            pos += k; na += got
-        pcm = self.download(ds, np.int16, S * apitch).reshape(S, apitch)[:, :na]
-        af = self.download(df, f32, S * apitch).reshape(S, apitch)[:, :na]
-        self.last_ddc_kernel = self.L.csdr_amd_ddc_kernel_name(self.L.csdr_amd_nfm_front_end(w)).decode()
-        self.L.csdr_amd_nfm_destroy(w)
+        with _Handle(self, "nfm", w) as w:
+            di = self.upload(xx)
+            apitch = n // decimation + 1024 + 64
+            ds = self.alloc(2 * S * apitch); df = self.alloc(4 * S * apitch)
+            pos = 0; na = 0; call = 0
+            while pos < n:
+                for st, r in (retunes or {}).get(call, []):
+                    w._call("set_rate", st, r)
+                k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+                got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na), apitch)
+                pos += k; na += got
+            pcm = self.download(ds, np.int16, S * apitch).reshape(S, apitch)[:, :na]
+            af = self.download(df, f32, S * apitch).reshape(S, apitch)[:, :na]
+            self.last_ddc_kernel = self.L.csdr_amd_ddc_kernel_name(w._fn("front_end")(w.h)).decode()
         return (pcm[0].copy(), af[0].copy()) if squeeze else (pcm.copy(), af.copy())
 
     def nfm_chain_unfused(self, iq_u8, shift_rate, decimation=50, tbw=0.005, audio_rate=48000, agc_block=1024):
@@ -2242,9 +2023,6 @@ def sharded_bank_loopback(world, x, tbw, decimation, shift_rates, schedule, mode
     spc = 1 if es == 8 else 2                            # array elements per complex sample
     rates = np.ascontiguousarray(shift_rates, f32); nc = rates.size
     retunes = retunes or {}
-    grp = L.csdr_amd_loopback_create(world)
-    if not grp:
-        raise CsdrAmdError(L.csdr_amd_last_error().decode())
     outs = [None] * nc
     errors = []
 
@@ -2252,76 +2030,71 @@ def sharded_bank_loopback(world, x, tbw, decimation, shift_rates, schedule, mode
         ctx = None
         try:
             ctx = Context(device)
-            comm = L.csdr_amd_comm_create_loopback(ctx.h, grp, rank)
-            if not comm:
-                raise CsdrAmdError(ctx.err())
-            per = max(schedule)
-            bank = L.csdr_amd_fastddc_bank_create_sharded_by(ctx.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], per, comm, SHARD[mode])
-            if not bank:
-                raise CsdrAmdError(ctx.err())
-            first = C.c_int(); count = C.c_int()
-            L.csdr_amd_fastddc_bank_channel_slice(bank, C.byref(first), C.byref(count))
-            first, count = first.value, count.value
-            inp = L.csdr_amd_fastddc_bank_input_size(bank); ovl = L.csdr_amd_fastddc_bank_overlap(bank)
-            starts = np.concatenate([[0], np.cumsum(schedule)])
-            di = ctx.upload(x) if (rank == 0 and not local_input) else None
-            mine = [[] for _ in range(count)]
-            held = {}
+            with _Handle(ctx, "comm", L.csdr_amd_comm_create_loopback(ctx.h, grp.h, rank)) as comm, \
+                 _Handle(ctx, "fastddc_bank", L.csdr_amd_fastddc_bank_create_sharded_by(ctx.h, tbw, decimation, _hp(rates), nc, WINDOWS[window], max(schedule),
+                                                                                        comm.h, SHARD[mode])) as bank:      # (left bank first, then comm)
+                first = C.c_int(); count = C.c_int()
+                L.csdr_amd_fastddc_bank_channel_slice(bank.h, C.byref(first), C.byref(count))
+                first, count = first.value, count.value
+                inp = L.csdr_amd_fastddc_bank_input_size(bank.h); ovl = L.csdr_amd_fastddc_bank_overlap(bank.h)
+                starts = np.concatenate([[0], np.cumsum(schedule)])
+                di = ctx.upload(x) if (rank == 0 and not local_input) else None
+                mine = [[] for _ in range(count)]
+                held = {}
 
-            def submit(k):
-                nb = schedule[k]
-                if local_input:
-                    f0 = C.c_int(); n0 = C.c_int()
-                    L.csdr_amd_fastddc_bank_local_blocks(bank, nb, C.byref(f0), C.byref(n0))
-                    a = (starts[k] + f0.value) * inp
-                    run = np.zeros((ovl + n0.value * inp) * spc, x.dtype)          # (zeros in front of the stream: exact for complexf and s16)
-                    lo = max(0, a - ovl)
-                    run[(ovl - (a - lo)) * spc:] = x[lo * spc:(a + n0.value * inp) * spc]
-                    held[k] = ctx.upload(run)
-                    ctx.check(getattr(L, "csdr_amd_fastddc_bank_submit_local" + sfx)(bank, held[k].ptr, nb), "bank_submit_local")
-                else:
-                    ctx.check(getattr(L, "csdr_amd_fastddc_bank_submit" + sfx)(bank, di.at(es * starts[k] * inp) if di is not None else None, nb), "bank_submit")
+                def submit(k):
+                    nb = schedule[k]
+                    if local_input:
+                        f0 = C.c_int(); n0 = C.c_int()
+                        L.csdr_amd_fastddc_bank_local_blocks(bank.h, nb, C.byref(f0), C.byref(n0))
+                        a = (starts[k] + f0.value) * inp
+                        run = np.zeros((ovl + n0.value * inp) * spc, x.dtype)          # (zeros in front of the stream: exact for complexf and s16)
+                        lo = max(0, a - ovl)
+                        run[(ovl - (a - lo)) * spc:] = x[lo * spc:(a + n0.value * inp) * spc]
+                        held[k] = ctx.upload(run)
+                        ctx.check(getattr(L, "csdr_amd_fastddc_bank_submit_local" + sfx)(bank.h, held[k].ptr, nb), "bank_submit_local")
+                    else:
+                        ctx.check(getattr(L, "csdr_amd_fastddc_bank_submit" + sfx)(bank.h, di.at(es * starts[k] * inp) if di is not None else None, nb), "bank_submit")
 
-            submitted = -1
-            for k in range(len(schedule)):
-                if not (retune_while_staged and k > 0):
-                    for ch, rt in retunes.get(k, []):
-                        ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank, ch, rt), "bank_set_rate_global")
-                if submitted < k:
-                    submit(k); submitted = k
-                if retune_while_staged:                               # batch k is staged, not collected: the next batch's retunes arrive now
-                    for ch, rt in retunes.get(k + 1, []):
-                        ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank, ch, rt + 0.0517 if superseded_retune else rt), "bank_set_rate_global")
-                if pipelined and k + 1 < len(schedule) and (retune_while_staged or (k + 1) not in retunes):
-                    submit(k + 1); submitted = k + 1
-                pitch = L.csdr_amd_fastddc_bank_max_output(bank, schedule[k]) + 8
-                do = ctx.alloc(8 * count * pitch)
-                ctx.check(L.csdr_amd_fastddc_bank_collect(bank, do.ptr, pitch, None), "bank_collect")
-                counts = np.zeros(count, np.int32)
-                ctx.check(L.csdr_amd_fastddc_bank_finish(bank, _hp(counts)), "bank_finish")
-                if superseded_retune:                                 # nothing is staged now: the real rate, applied at once
-                    for ch, rt in retunes.get(k + 1, []):
-                        ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank, ch, rt), "bank_set_rate_global")
-                y = ctx.download(do, c64, count * pitch).reshape(count, pitch)
+                submitted = -1
+                for k in range(len(schedule)):
+                    if not (retune_while_staged and k > 0):
+                        for ch, rt in retunes.get(k, []):
+                            ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank.h, ch, rt), "bank_set_rate_global")
+                    if submitted < k:
+                        submit(k); submitted = k
+                    if retune_while_staged:                               # batch k is staged, not collected: the next batch's retunes arrive now
+                        for ch, rt in retunes.get(k + 1, []):
+                            ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank.h, ch, rt + 0.0517 if superseded_retune else rt), "bank_set_rate_global")
+                    if pipelined and k + 1 < len(schedule) and (retune_while_staged or (k + 1) not in retunes):
+                        submit(k + 1); submitted = k + 1
+                    pitch = L.csdr_amd_fastddc_bank_max_output(bank.h, schedule[k]) + 8
+                    do = ctx.alloc(8 * count * pitch)
+                    ctx.check(L.csdr_amd_fastddc_bank_collect(bank.h, do.ptr, pitch, None), "bank_collect")
+                    counts = np.zeros(count, np.int32)
+                    ctx.check(L.csdr_amd_fastddc_bank_finish(bank.h, _hp(counts)), "bank_finish")
+                    if superseded_retune:                                 # nothing is staged now: the real rate, applied at once
+                        for ch, rt in retunes.get(k + 1, []):
+                            ctx.check(L.csdr_amd_fastddc_bank_set_rate_global(bank.h, ch, rt), "bank_set_rate_global")
+                    y = ctx.download(do, c64, count * pitch).reshape(count, pitch)
+                    for c in range(count):
+                        mine[c].append(y[c, :counts[c]].copy())
+                    held.pop(k, None)
                 for c in range(count):
-                    mine[c].append(y[c, :counts[c]].copy())
-                held.pop(k, None)
-            for c in range(count):
-                outs[first + c] = np.concatenate(mine[c])
-            L.csdr_amd_fastddc_bank_destroy(bank); L.csdr_amd_comm_destroy(comm)
+                    outs[first + c] = np.concatenate(mine[c])
         except BaseException as e:      # a dead rank must not leave the others waiting at a rendezvous
             errors.append((rank, e))
-            L.csdr_amd_loopback_abort(grp)
+            L.csdr_amd_loopback_abort(grp.h)
         finally:
             if ctx is not None:
                 ctx.close()
 
-    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    L.csdr_amd_loopback_destroy(grp)
+    with _Handle(None, "loopback", L.csdr_amd_loopback_create(world)) as grp:
+        threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
     if errors:
         raise CsdrAmdError("rank %d: %r" % errors[0])
     return outs

@@ -225,13 +225,7 @@ int csdr_amd_carrier_lanes(const csdr_amd_carrier *p)
 int csdr_amd_carrier_force_generic(csdr_amd_carrier *p, int on) { if (!p) return fail_msg(-3, "carrier: null object"); p->force_generic = on != 0; return 0; }
 const char *csdr_amd_carrier_kernel_name(const csdr_amd_carrier *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_carrier_destroy(csdr_amd_carrier *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_carrier_destroy(csdr_amd_carrier *p) { destroy_on_stream(p); }
 
 int csdr_amd_carrier_process(csdr_amd_carrier *p, const csdr_complexf *in, long long n, size_t in_pitch, csdr_complexf *out, float *error, float *dphase,
                              csdr_complexf *nco, size_t out_pitch)

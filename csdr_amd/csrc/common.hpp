@@ -124,6 +124,18 @@ struct csdr_amd_ctx {
     std::unique_ptr<csdr_amd::ShiftAhead, csdr_amd::ShiftAheadDel> shift_ahead;
 };
 
+namespace csdr_amd {
+// the teardown of an object (its context: member `c`) whose work all runs on the context's stream: wait for it on the context's device, then let the
+// members free what they own
+template <class T> void destroy_on_stream(T *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(p->c->device);
+    (void)hipStreamSynchronize(p->c->stream);
+    delete p;
+}
+} // namespace csdr_amd
+
 // ---- LDS-DMA row-step shared by the ring kernels (wfm_mfma.hip, ddc_mfma.hip).  Device code only.
 #ifdef __HIPCC__
 namespace csdr_amd {

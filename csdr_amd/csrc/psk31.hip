@@ -14,7 +14,6 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 using namespace csdr_amd;
@@ -215,18 +214,6 @@ __global__ __launch_bounds__(64) void k_simple_agc(Psk31Cfg c, const float2 *__r
     gain_io[s] = psk31_agc_run(c, gain_io[s], in + (size_t)s * in_pitch, out + (size_t)s * out_pitch, n);
 }
 
-// compute units of a device, asked once per device and process
-int device_cus(int device)
-{
-    static std::mutex mu;
-    static std::vector<int> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    if (device < 0) return 256;
-    if ((int)cache.size() <= device) cache.resize(device + 1, 0);
-    if (!cache[device]) { hipDeviceProp_t pr; cache[device] = hipGetDeviceProperties(&pr, device) == hipSuccess ? pr.multiProcessorCount : 256; }
-    return cache[device];
-}
-
 // channels per wave when the caller leaves it open.  k_psk31_tiled: about two waves per SIMD (4096 channels on 256 CUs: 2); k_psk31: one wave per CU.
 // profiles/psk31_lanes.txt holds the runs behind both choices.
 int default_lanes(int cus, int n_ch, bool tiled)
@@ -256,7 +243,7 @@ csdr_amd_psk31 *csdr_amd_psk31_create(csdr_amd_ctx *c, const csdr_amd_psk31_para
     p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->last_kernel = "";
     const bool timing = first_stage <= PSK31_TIMING && last_stage >= PSK31_TIMING;
     p->tail_cap = timing ? 3 * cfg.hb + 1 : 1;
-    p->lanes = 0; p->cus = device_cus(c->device); p->force_generic = false;
+    p->lanes = 0; p->cus = current_device_cu_count(); p->force_generic = false;
     p->ring = first_stage == PSK31_AGC && last_stage >= PSK31_TIMING ? tiled_ring(cfg.hb) : 0;     // 0: the stage range runs on k_psk31
     if (dev_alloc(p->d_st, sizeof(Psk31Chan) * n_channels) != hipSuccess || dev_alloc(p->d_tail, sizeof(float2) * (size_t)p->tail_cap * n_channels) != hipSuccess ||
         dev_alloc(p->d_dec, 1024) != hipSuccess) { fail_msg(-2, "psk31: out of device memory"); return nullptr; }
@@ -346,13 +333,7 @@ int csdr_amd_psk31_lanes(const csdr_amd_psk31 *p)
 }
 const char *csdr_amd_psk31_kernel_name(const csdr_amd_psk31 *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_psk31_destroy(csdr_amd_psk31 *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_psk31_destroy(csdr_amd_psk31 *p) { destroy_on_stream(p); }
 
 // simple_agc_cc libcsdr.c:2201-2217 over n_streams streams: the object's AGC-only form with the gain in and out through gain_io (device, n_streams floats)
 int csdr_amd_simple_agc_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_complexf *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,

@@ -347,13 +347,7 @@ int csdr_amd_psk31tx_process(csdr_amd_psk31tx *p, const void *in, long long n_in
 int csdr_amd_psk31tx_force_generic(csdr_amd_psk31tx *p, int on) { if (!p) return fail_msg(-3, "psk31tx: null object"); p->force_generic = on != 0; return 0; }
 const char *csdr_amd_psk31tx_kernel_name(const csdr_amd_psk31tx *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_psk31tx_destroy(csdr_amd_psk31tx *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_psk31tx_destroy(csdr_amd_psk31tx *p) { destroy_on_stream(p); }
 
 // the host's tables of an object with these parameters: sym (256 complexf) and rate (interpolation floats); either may be NULL
 int csdr_amd_psk31tx_tables(int n_psk, int interpolation, csdr_complexf *sym, float *rate)

@@ -371,13 +371,7 @@ int csdr_amd_resampler_window(int I, int D, int T, int input_size, int last_taps
 int csdr_amd_resampler_force_generic(csdr_amd_resampler *r, int on) { if (!r) return -3; r->force_generic = on != 0; return 0; }
 const char *csdr_amd_resampler_kernel_name(const csdr_amd_resampler *r) { return r ? r->last_kernel : ""; }
 
-void csdr_amd_resampler_destroy(csdr_amd_resampler *r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->c->device);
-    (void)hipStreamSynchronize(r->c->stream);
-    delete r;
-}
+void csdr_amd_resampler_destroy(csdr_amd_resampler *r) { destroy_on_stream(r); }
 
 long long csdr_amd_resampler_max_out(const csdr_amd_resampler *r, long long n_in)
 {
@@ -484,13 +478,7 @@ int csdr_amd_interp_set_cli_bufsize(csdr_amd_interp *p, int the_bufsize)
 int csdr_amd_interp_force_generic(csdr_amd_interp *p, int on) { if (!p) return -3; p->force_generic = on != 0; return 0; }
 const char *csdr_amd_interp_kernel_name(const csdr_amd_interp *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_interp_destroy(csdr_amd_interp *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_interp_destroy(csdr_amd_interp *p) { destroy_on_stream(p); }
 
 long long csdr_amd_interp_max_out(const csdr_amd_interp *p, long long n_in)
 {

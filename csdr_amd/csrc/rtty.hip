@@ -346,7 +346,7 @@ csdr_amd_rtty *csdr_amd_rtty_create(csdr_amd_ctx *c, const csdr_amd_rtty_params 
     if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "rtty: hipSetDevice"); return nullptr; }
     Owned<csdr_amd_rtty, csdr_amd_rtty_destroy> p(new csdr_amd_rtty());
     p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->force_generic = false; p->last_kernel = ""; p->mid_cap = 0;
-    { hipDeviceProp_t pr; p->cus = hipGetDeviceProperties(&pr, c->device) == hipSuccess ? pr.multiProcessorCount : 256; }
+    p->cus = current_device_cu_count();
     const bool bfsk = first_stage == RTTY_BFSK, serial = first_stage <= RTTY_SERIAL && last_stage >= RTTY_SERIAL;
     p->hist_cap = bfsk ? std::max(1, cfg.L - 1) : 1;
     if (dev_alloc(p->d_st, sizeof(RttyChan) * n_channels) != hipSuccess ||
@@ -434,13 +434,7 @@ int csdr_amd_rtty_process(csdr_amd_rtty *p, const void *in, long long n_in, size
 int csdr_amd_rtty_force_generic(csdr_amd_rtty *p, int on) { if (!p) return fail_msg(-3, "rtty: null object"); p->force_generic = on != 0; return 0; }
 const char *csdr_amd_rtty_kernel_name(const csdr_amd_rtty *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_rtty_destroy(csdr_amd_rtty *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_rtty_destroy(csdr_amd_rtty *p) { destroy_on_stream(p); }
 
 // bfsk_demod_cf libcsdr.c:2335-2350 with caller taps (device) on n_streams independent streams: n - L + 1 outputs each
 int csdr_amd_bfsk_demod_cf(csdr_amd_ctx *c, const csdr_complexf *in, float *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,

@@ -255,13 +255,7 @@ int csdr_amd_squelch_max_blocks(const csdr_amd_squelch *p) { return p ? (int)((p
 int csdr_amd_squelch_force_generic(csdr_amd_squelch *p, int on) { if (!p) return fail_msg(-3, "squelch: null object"); p->force_generic = on != 0; return 0; }
 const char *csdr_amd_squelch_kernel_name(const csdr_amd_squelch *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_squelch_destroy(csdr_amd_squelch *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_squelch_destroy(csdr_amd_squelch *p) { destroy_on_stream(p); }
 
 int csdr_amd_squelch_process(csdr_amd_squelch *p, const csdr_complexf *in, long long n_in, size_t in_pitch, csdr_complexf *out, size_t out_pitch, float *power,
                              size_t power_pitch, uint8_t *open_flags, int *n_blocks_out)

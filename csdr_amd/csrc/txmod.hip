@@ -523,13 +523,7 @@ long long csdr_amd_txbank_max_out(const csdr_amd_txbank *p, long long n_in) { re
 int csdr_amd_txbank_force_generic(csdr_amd_txbank *p, int on) { if (!p) return fail_msg(-3, "txbank: null object"); p->force_generic = on != 0; return 0; }
 const char *csdr_amd_txbank_kernel_name(const csdr_amd_txbank *p) { return p ? p->last_kernel : ""; }
 
-void csdr_amd_txbank_destroy(csdr_amd_txbank *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;
-}
+void csdr_amd_txbank_destroy(csdr_amd_txbank *p) { destroy_on_stream(p); }
 
 int csdr_amd_txbank_process(csdr_amd_txbank *p, const int16_t *in_s16, size_t in_pitch, long long n_in, void *out, size_t out_pitch, long long *n_out)
 {

@@ -239,3 +239,77 @@ def test_fftcc_cycles(ctx):
         L.csdr_amd_fftcc_destroy(f)
         return alive
     assert _cycles(ctx, one) >= 1 << 30
+
+
+# ---- the stateful wrapper objects, each at the smallest shape of its own test file: created with `with`, two calls, gone at the end of the block
+def _object_cycles(ctx, make, x):
+    def one(c):
+        with make(c) as o:
+            o.process(x); o.process(x)
+            alive = _free()
+        assert o.h is None
+        return alive
+    _cycles(ctx, one)
+
+
+def _noise(shape, dtype, seed):
+    rng = np.random.default_rng(seed)
+    if dtype == np.complex64:
+        return (0.3 * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))).astype(np.complex64)
+    return (0.3 * rng.standard_normal(shape)).astype(dtype)
+
+
+def test_resampler_cycles(ctx):
+    taps = csdr_amd.rational_resampler_get_lowpass_f(80, 3, 2)
+    _object_cycles(ctx, lambda c: csdr_amd.Resampler(c, 3, 2, taps, 2), _noise((2, 1024), np.float32, 1))
+
+
+def test_interpolator_cycles(ctx):
+    taps = csdr_amd.fir_interpolate_lowpass_f(81, 4)
+    _object_cycles(ctx, lambda c: csdr_amd.Interpolator(c, 4, taps, 2), _noise((2, 1024), np.complex64, 2))
+
+
+def test_psk31_cycles(ctx):
+    _object_cycles(ctx, lambda c: csdr_amd.Psk31(c, csdr_amd.psk31_params(), 2), _noise((2, 4096), np.complex64, 3))
+
+
+def test_psk31tx_cycles(ctx):
+    x = np.frombuffer((b"CQ CQ DE TEST PSE K " * 4)[:64], np.uint8).reshape(2, 32)
+    _object_cycles(ctx, lambda c: csdr_amd.Psk31Tx(c, 2, 2, 256), x)
+
+
+def test_rtty_cycles(ctx):
+    _object_cycles(ctx, lambda c: csdr_amd.Rtty(c, csdr_amd.rtty_params(cli_bufsize=4096), 2), _noise((2, 4096), np.complex64, 4))
+
+
+def test_squelch_cycles(ctx):
+    _object_cycles(ctx, lambda c: csdr_amd.Squelch(c, 2, 1024, 1, [0.01, 0.01], 4096), _noise((2, 2048), np.complex64, 5))
+
+
+def test_carrier_cycles(ctx):
+    _object_cycles(ctx, lambda c: csdr_amd.Carrier(c, csdr_amd.costas_params(0.05, 0.707, True), 2), _noise((2, 1024), np.complex64, 6))
+
+
+def test_txbank_cycles(ctx):
+    taps = ctx.firdes_lowpass_f(79, 0.5 / 8)
+    x = (8000 * _noise((2, 1024), np.float32, 7)).astype(np.int16)
+    _object_cycles(ctx, lambda c: csdr_amd.TxBank(c, 2, "fm", 8, taps, [0.1, -0.2], max_in_samples=1024), x)
+
+
+# ---- a Context method whose call fails half way: the C object it made is destroyed on that path too
+@pytest.mark.parametrize("chain", ["wfm_chain", "ddc_u8"])
+def test_failed_retune_leaves_no_object_behind(ctx, chain):
+    """A retune of stream 99 out of 4: csdr_amd_wfm_set_rate / csdr_amd_ddc_set_rate return -3 (an error return on the host, no kernel runs)."""
+    S, T = 4, 16384
+    iq = np.full((S, 2 * T), 0x80, np.uint8)
+    rates = np.linspace(-0.1, 0.1, S).astype(np.float32)
+    if chain == "wfm_chain":
+        args = (10, np.asarray(ctx.firdes_lowpass_f(79, 0.05), np.float32))
+    else:
+        args = (50, np.asarray(ctx.firdes_lowpass_f(801, 0.01), np.float32))
+
+    def one(c):
+        with pytest.raises(csdr_amd.CsdrAmdError, match="set_rate"):
+            getattr(c, chain)(iq, rates, *args, block=T, retunes={0: [(99, 0.1)]})
+        return _free()
+    _cycles(ctx, one)
