@@ -310,6 +310,7 @@ def lib():
     L.csdr_amd_comm_create_null.restype = vp; L.csdr_amd_comm_create_null.argtypes = [vp, i, i]
     L.csdr_amd_comm_create_ipc.restype = vp; L.csdr_amd_comm_create_ipc.argtypes = [vp, C.c_char_p, i, i]
     L.csdr_amd_fastddc_inv_kernel_name.restype = C.c_char_p; L.csdr_amd_fastddc_inv_kernel_name.argtypes = [vp]
+    L.csdr_amd_fastddc_inv_kernels.restype = C.c_char_p; L.csdr_amd_fastddc_inv_kernels.argtypes = [vp]
     L.csdr_amd_fastddc_inv_set_profiling.argtypes = [vp, i]
     L.csdr_amd_fastddc_inv_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     L.csdr_amd_fastddc_inv_stage_time.argtypes = [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_long)]
@@ -1166,6 +1167,7 @@ class Context:
         self.h = self.L.csdr_amd_ctx_create(device, hip_stream)
         if not self.h:
             raise CsdrAmdError("csdr_amd_ctx_create failed: " + self.L.csdr_amd_last_error().decode())
+        self.last_ddc_kernels = ""; self.ddc_kernels_seen = set()      # fastddc_inv_cc / fastddc_bank: _note_ddc_call
 
     def err(self):
         return self.L.csdr_amd_last_error().decode()
@@ -1737,8 +1739,16 @@ class Context:
                 b += k
             return self.download(do, c64, nb * ddc.fft_size).reshape(nb, ddc.fft_size)
 
+    def _note_ddc_call(self, inv, counts):
+        """what a fastddc call ran and wrote: `last_ddc_kernels` (csdr_amd_fastddc_inv_kernels of the call), `ddc_kernels_seen` (the set over all calls of this
+        context), and per call of the current fastddc_inv_cc / fastddc_bank run `ddc_call_kernels` / `ddc_call_counts` (samples written per channel)."""
+        self.last_ddc_kernels = self.L.csdr_amd_fastddc_inv_kernels(inv).decode()
+        self.ddc_kernels_seen.add(self.last_ddc_kernels)
+        self.ddc_call_kernels.append(self.last_ddc_kernels); self.ddc_call_counts.append(counts.copy())
+
     def fastddc_inv_cc(self, spectra, tbw, decimation, shift_rates, window="HAMMING", blocks_per_call=None):
         """spectra [n_blocks, fft] -> list of per-channel outputs."""
+        self.ddc_call_kernels = []; self.ddc_call_counts = []
         spectra = np.ascontiguousarray(spectra, c64); nb = spectra.shape[0]
         rates = np.ascontiguousarray(shift_rates, f32); nc = rates.size
         per = nb if not blocks_per_call else blocks_per_call
@@ -1753,6 +1763,7 @@ class Context:
                 do = self.alloc(8 * nc * pitch)
                 counts = np.zeros(nc, np.int32)
                 self.check(f._fn("process")(f.h, di.at(8 * b * fft), k, do.ptr, pitch, _hp(counts)), "fastddc_inv")
+                self._note_ddc_call(f.h, counts)
                 y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
                 for c in range(nc):
                     outs[c].append(y[c, :counts[c]].copy())
@@ -1764,6 +1775,7 @@ class Context:
         retune = (call_index, channel, rate): applied before that call.  schedule = explicit list of blocks per call (instead of blocks_per_call);
         retunes = {call_index: [(channel, rate), ...]}.  x: complex64, or interleaved IQ as int16 / uint8 (csdr_amd_fastddc_bank_process_s16 / _u8)."""
         x, sfx, es = _bank_input(x)
+        self.ddc_call_kernels = []; self.ddc_call_counts = []
         rates = np.ascontiguousarray(shift_rates, f32); nc = rates.size
         ddc, _ = self.fastddc_init(tbw, decimation, 0.0)
         nb = (x.size if es == 8 else x.size // 2) // ddc.input_size
@@ -1785,6 +1797,7 @@ class Context:
                 do = self.alloc(8 * nc * pitch)
                 counts = np.zeros(nc, np.int32)
                 self.check(process(bk.h, di.at(es * b * ddc.input_size), k, do.ptr, pitch, _hp(counts)), "fastddc_bank")
+                self._note_ddc_call(bk._fn("inverse")(bk.h), counts)
                 y = self.download(do, c64, nc * pitch).reshape(nc, pitch)
                 for c in range(nc):
                     outs[c].append(y[c, :counts[c]].copy())

@@ -48,5 +48,8 @@ int ddc_mfma_set_profiling(DdcMfma *m, int on);
 int ddc_mfma_kernel_time(DdcMfma *m, double *total_ms, long *launches);
 int ddc_mfma_stage_time(DdcMfma *m, int stage, double *total_ms, long *launches);
 const char *ddc_mfma_kernel_name(const DdcMfma *m);       // the fold kernel the last collect() launched
+// every kernel instance of the last collect()ed call, template arguments included: [k_ddc_xt | k_ddc_fwd512<16,F>[+k_ddc_fwd128]] + fold + inverse transforms
+// ("" before the first call; valid until the next collect())
+const char *ddc_mfma_kernels(const DdcMfma *m);
 
 } // namespace csdr_amd

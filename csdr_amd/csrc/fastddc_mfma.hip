@@ -31,6 +31,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 
 namespace csdr_amd {
@@ -53,6 +54,8 @@ struct DdcMfma {
     int pending_blocks[2]; int fill, drain;                            // set being filled next / folded next
     bool inline_set[2], chains_on_side[2];
     bool gemm_three = false, gemm_narrow = false;
+    // csdr_amd_fastddc_inv_kernels: set k's transform in front of the fold (submit: literals); all kernels of the last collect()ed call
+    const char *front[2] = {"", ""}, *front2[2] = {"", ""}; std::string kernels;
     bool y_holds[2] = {false, false};                                  // set k's spectra are still pass-1 output in d_Y (the fold runs pass 2 itself)
     // the NEXT call's chain tables, computed one call ahead by riders of the inverse-transform kernel (data independent; valid for process() calls of equal size
     // with no retune in between).  On the side stream beside the fold they cost more than they hid: 0.182 vs 0.167 ms per step.
@@ -905,11 +908,18 @@ __global__ __launch_bounds__(256) void k_ddc_ifft256d_post(const float2 *__restr
 } // namespace
 
 // ====================================================================================== host side
+// LDS of one spectra buffer of the fold: 32 nbt block rows of pre complex values (+ 16 bytes of pitch padding); a workgroup can have 160 KiB
+static constexpr size_t DDC_LDS_MAX = 160 * 1024;
+static size_t ddc_fold_lds(int pre, int nbt) { return (size_t)32 * nbt * (pre / 2 + 1) * sizeof(float4); }
+// 32-block accumulator tiles per workgroup: two for calls of more than 32 blocks -- where two tiles of spectra fit (pre_decimation <= 256), else one tile per 32 blocks
+static int ddc_fold_tiles(int pre, int n_blocks) { return n_blocks > 32 && ddc_fold_lds(pre, 2) <= DDC_LDS_MAX ? 2 : 1; }
+
 DdcMfma *ddc_mfma_create(csdr_amd_ctx *ctx, int fft, int inv, int pre, int n_channels, int max_blocks, int scrap, int post_in, int post_dec, int input_size, int overlap,
                          const DdcComm *comm)
 {
     if (getenv("CSDR_AMD_DDC_MFMA_OFF")) return nullptr;
     if (inv != 512 || pre < 8 || (pre & (pre - 1)) || fft != inv * pre || post_dec < 1 || scrap + post_in > inv) return nullptr;
+    if (ddc_fold_lds(pre, 1) > DDC_LDS_MAX) return nullptr;              // pre_decimation >= 1024: not even one 32-block tile of spectra fits a workgroup's LDS -- the general path serves it
     Owned<DdcMfma, ddc_mfma_destroy> m(new DdcMfma());
     m->ctx = ctx; m->fft = fft; m->inv = inv; m->pre = pre; m->G = pre / 4; m->C = n_channels; m->Cpad = (n_channels + 31) / 32 * 32;
     m->max_blocks = max_blocks; m->nbp = (max_blocks + 31) / 32 * 32; m->scrap = scrap; m->post_in = post_in; m->post_dec = post_dec;
@@ -1083,11 +1093,11 @@ static int mfma_forward(DdcMfma *m, hipStream_t st, const void *in, int fmt, con
 // will collect() fold n_blocks blocks with k_ddc_gemm3 (persistent shape, pre_decimation 128)?  submit() needs to know: only that kernel can run pass 2 itself
 static bool ddc_folds_with_gemm3(const DdcMfma *m, int n_blocks)
 {
-    const int nbt = n_blocks > 32 ? 2 : 1;
-    const size_t lds = (size_t)32 * nbt * (m->pre / 2 + 1) * sizeof(float4);
+    const int nbt = ddc_fold_tiles(m->pre, n_blocks);
+    const size_t lds = ddc_fold_lds(m->pre, nbt);
     const int per_res = (int)(cdiv(m->Cpad, 256) * cdiv(n_blocks, 32 * nbt));
     int slots = current_device_cu_count() / per_res; if (slots < 1) slots = 1; if (slots > m->inv) slots = m->inv;
-    bool persist = m->pre <= 128 && 2 * lds <= 160 * 1024 - 512 && slots * 2 <= m->inv;
+    bool persist = m->pre <= 128 && 2 * lds <= DDC_LDS_MAX - 512 && slots * 2 <= m->inv;
     return persist && m->pre == 128;
 }
 
@@ -1130,6 +1140,8 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
     const bool ride = fused_fwd && !riders_off;                        // chain work done by extra workgroups of the forward passes (hit: only the commit + the checkpoints)
     m->last_state = d_state; m->ahead_ok = fused_fwd && !spec_off && !riders_off;
     m->y_holds[k] = false;
+    m->front[k] = spectra ? "k_ddc_xt+" : fmt == 1 ? "k_ddc_fwd512<16,1>+" : fmt == 2 ? "k_ddc_fwd512<16,2>+" : "k_ddc_fwd512<16,0>+";
+    m->front2[k] = spectra ? "" : "k_ddc_fwd128+";                     // (pass 2 as a kernel of its own, unless the fold runs it: below)
     if (ride) {
     } else if (inl && !chains_side) {
         rc = mfma_chains(m, mainst, k, n_blocks, d_state, d_geom); if (rc) return rc;
@@ -1159,6 +1171,7 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
             else { rc = mfma_forward(m, st, in, fmt, m->d_tail[m->flip].get(), m->d_tail[m->flip ^ 1].get(), n_blocks, m->d_Xt[k].get(), ride ? &job : nullptr, skip2); m->flip ^= 1; }
             if (rc) return rc;
             m->y_holds[k] = skip2;
+            if (skip2) m->front2[k] = "";
         } else {
             // rank g transforms blocks [g nbl, (g + 1) nbl): the root sends it the samples of its windows, stream[g nbl inp - ovl, min((g + 1) nbl, n) inp),
             // over its own link (seven transfers in flight from the root), then the chunks are all-gathered over the full mesh
@@ -1191,6 +1204,8 @@ int ddc_mfma_submit(DdcMfma *m, const void *in_v, const cf32 *spectra, int n_blo
 }
 
 const char *ddc_mfma_kernel_name(const DdcMfma *m) { return m->gemm_three ? (m->gemm_narrow ? "k_ddc_gemm3n" : "k_ddc_gemm3") : "k_ddc_gemm"; }
+const char *ddc_mfma_kernels(const DdcMfma *m) { return m->kernels.c_str(); }
+static void mfma_note_kernels(DdcMfma *m, int k, const char *fold, const char *inverse) { m->kernels.clear(); m->kernels.append(m->front[k]).append(m->front2[k]).append(fold).append("+").append(inverse); }
 int ddc_mfma_set_profiling(DdcMfma *m, int on)
 {
     m->profiling = on != 0; m->timer.reset(); m->prof_ms = 0; m->prof_launches = 0;
@@ -1223,8 +1238,8 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     hipStream_t st = m->ctx->stream;
     if (m->chains_on_side[k]) CSDR_HIP(hipStreamWaitEvent(st, m->ev_ready[k].get(), 0));
     const float scale = 1.0f / (float)m->pre;                              // fastddc.c:144-148 (a power of two: exact)
-    const int nbt = n_blocks > 32 ? 2 : 1;
-    const size_t lds = (size_t)32 * nbt * (m->pre / 2 + 1) * sizeof(float4);
+    const int nbt = ddc_fold_tiles(m->pre, n_blocks);
+    const size_t lds = ddc_fold_lds(m->pre, nbt);
     const dim3 grid(m->inv, cdiv(m->Cpad, 256), cdiv(n_blocks, 32 * nbt));
     if (m->profiling) { if (const int rc = m->timer.begin(st)) return rc; }
     // persistent form (one workgroup per CU walks several residues, double-buffered spectra) when a residue's spectra fit the register staging
@@ -1232,7 +1247,7 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     const int n_cu = current_device_cu_count();
     const int per_res = (int)(grid.y * grid.z);
     int slots = n_cu / per_res; if (slots < 1) slots = 1; if (slots > m->inv) slots = m->inv;
-    bool persist = m->pre <= 128 && 2 * lds <= 160 * 1024 - 512 && slots * 2 <= m->inv;
+    bool persist = m->pre <= 128 && 2 * lds <= DDC_LDS_MAX - 512 && slots * 2 <= m->inv;
     const size_t lds_use = persist ? 2 * lds : lds;
     const dim3 grid_use(persist ? (unsigned)slots : grid.x, grid.y, grid.z);
 #define DDC_GEMM_LAUNCH(NBTV, PV) do {                                                                                                               \
@@ -1242,6 +1257,7 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
     // three-product form with LDS-DMA staging: pre_decimation 128 (a spectra row = one 1-KiB piece), persistent shape; other geometries keep the four-product kernel k_ddc_gemm
     const bool three = ddc_folds_with_gemm3(m, n_blocks);
     m->gemm_three = three; m->gemm_narrow = false;
+    const char *fold = "";
     if (three) {
         // the second pass of the forward transform inside the fold: one GPU, process() (pass 1's output Y belongs to this call), submit() skipped k_ddc_fwd128
         const bool fwd = m->y_holds[k];
@@ -1256,15 +1272,19 @@ int ddc_mfma_collect(DdcMfma *m, const ChanGeom *d_geom, cf32 *out, size_t out_p
 #define DDC_GEMM3N_LAUNCH(NWV) hipLaunchKernelGGL((k_ddc_gemm3n<NWV>), gn, dim3(64 * NWV), ldsn, st, m->d_Ht.get(), src, reinterpret_cast<float2 *>(m->d_Ct.get()), d_geom, m->inv, m->Cpad, m->C, \
                                                   m->nbp, m->nbl, n_blocks, scale)
             if (m->Cpad <= 32) DDC_GEMM3N_LAUNCH(1); else if (m->Cpad <= 64) DDC_GEMM3N_LAUNCH(2); else DDC_GEMM3N_LAUNCH(4);
+            fold = m->Cpad <= 32 ? "k_ddc_gemm3n<1>" : m->Cpad <= 64 ? "k_ddc_gemm3n<2>" : "k_ddc_gemm3n<4>";
 #undef DDC_GEMM3N_LAUNCH
         }
         else if (nbt == 2) { if (fwd) DDC_GEMM3_LAUNCH(2, true); else DDC_GEMM3_LAUNCH(2, false); }
         else          { if (fwd) DDC_GEMM3_LAUNCH(1, true); else DDC_GEMM3_LAUNCH(1, false); }
 #undef DDC_GEMM3_LAUNCH
+        if (!m->gemm_narrow) fold = nbt == 2 ? (fwd ? "k_ddc_gemm3<2,true>" : "k_ddc_gemm3<2,false>") : (fwd ? "k_ddc_gemm3<1,true>" : "k_ddc_gemm3<1,false>");
     }
     else if (nbt == 2) { if (persist) DDC_GEMM_LAUNCH(2, true); else DDC_GEMM_LAUNCH(2, false); }
     else               { if (persist) DDC_GEMM_LAUNCH(1, true); else DDC_GEMM_LAUNCH(1, false); }
 #undef DDC_GEMM_LAUNCH
+    if (!three) fold = nbt == 2 ? (persist ? "k_ddc_gemm<2,true>" : "k_ddc_gemm<2,false>") : (persist ? "k_ddc_gemm<1,true>" : "k_ddc_gemm<1,false>");
+    mfma_note_kernels(m, k, fold, m->post_dec != 2 ? "k_ddc_ifft512_post<8>" : "k_ddc_ifft256d_post<8>");
     CSDR_LAUNCH_CHECK();
     if (m->profiling) { if (const int rc = m->timer.end(st)) return rc; }
     // inverse transforms.  post_decimation 2 (every power-of-two decimation): half-size transforms of the aliased bins; otherwise the full-size form.  Half 128-byte
@@ -1322,6 +1342,16 @@ extern "C" int csdr_amd_debug_ddc_chain(int mode, float rate2, int post_in, int 
         for (int b = 0; b < n_blocks; b++) { phases_out[b] = s.phase; total += ddc_chain_step(s, rate2, post_in, post_dec, sh); }
     }
     *remain_io = s.remain; *phase_io = s.phase; *count_out = total;
+    return 0;
+}
+
+// Test hook (tests/test_abi_cpu.py): the fold's tiling for a call of n_blocks blocks at pre_decimation `pre`, as ddc_mfma_create / ddc_mfma_collect decide it: -1 when the
+// matrix-core path declines the geometry (not even one 32-block tile of spectra fits a workgroup's LDS), else 0 with the tiles per workgroup and the bytes of one spectra buffer
+extern "C" int csdr_amd_debug_ddc_fold_plan(int pre, int n_blocks, int *tiles, long *lds_bytes)
+{
+    using namespace csdr_amd;
+    if (ddc_fold_lds(pre, 1) > DDC_LDS_MAX) return -1;
+    *tiles = ddc_fold_tiles(pre, n_blocks); *lds_bytes = (long)ddc_fold_lds(pre, *tiles);
     return 0;
 }
 

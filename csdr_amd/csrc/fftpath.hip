@@ -521,6 +521,7 @@ struct csdr_amd_fastddc_inv {
                                                                     // goes before the buffers: its side stream reads d_geom and d_state
     std::map<int, FftPlan> plans;
     bool fold_old;                                                  // CSDR_AMD_DDC_FOLD_OLD (A/B: the untiled fold of the general path), read at create
+    const char *kernels = "";                                       // general path: the kernel instances of the last process() call
 };
 
 extern "C" {
@@ -634,6 +635,7 @@ void csdr_amd_fastddc_inv_destroy(csdr_amd_fastddc_inv *f)
 }
 
 const char *csdr_amd_fastddc_inv_kernel_name(const csdr_amd_fastddc_inv *f) { return f->mf ? ddc_mfma_kernel_name(f->mf.get()) : "k_ddc_fold_ct"; }
+const char *csdr_amd_fastddc_inv_kernels(const csdr_amd_fastddc_inv *f) { return f->mf ? ddc_mfma_kernels(f->mf.get()) : f->kernels; }
 int csdr_amd_fastddc_inv_set_profiling(csdr_amd_fastddc_inv *f, int on) { return f->mf ? ddc_mfma_set_profiling(f->mf.get(), on) : 0; }
 int csdr_amd_fastddc_inv_kernel_time(csdr_amd_fastddc_inv *f, double *total_ms, long *launches)
 {
@@ -689,12 +691,14 @@ int csdr_amd_fastddc_inv_process(csdr_amd_fastddc_inv *f, const csdr_complexf *s
     // <16,4> 3.0, <2,16> 3.0, <16,8> 2.6, <16,2> 1.9, <32,2> 1.0 -- 8 channels share every spectrum value; the 64 accumulators of <8,4> leave room for
     // 4-5 waves per SIMD, which hides the load latency that <8,8> (2 waves per SIMD) exposes
 #define FOLD_CT(CTV, BTV) hipLaunchKernelGGL((k_ddc_fold_ct<CTV, BTV>), dim3(cdiv(inv, 256), cdiv(n_blocks, BTV), cdiv(f->n_channels, CTV)), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks, f->n_channels)
-    if (ct_ok && f->n_channels >= 8) { FOLD_CT(8, 4); }
-    else if (ct_ok) { FOLD_CT(4, 4); }
+    if (ct_ok && f->n_channels >= 8) { FOLD_CT(8, 4); f->kernels = "k_ddc_fold_ct<8,4>+hipfft+k_ddc_post"; }
+    else if (ct_ok) { FOLD_CT(4, 4); f->kernels = "k_ddc_fold_ct<4,4>+hipfft+k_ddc_post"; }
 #undef FOLD_CT
     else if (n_blocks >= 16) {
+        f->kernels = "k_ddc_fold<16>+hipfft+k_ddc_post";
         hipLaunchKernelGGL((k_ddc_fold<16>), dim3(cdiv(inv, 256), cdiv(n_blocks, 16), f->n_channels), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks);
     } else {
+        f->kernels = "k_ddc_fold<4>+hipfft+k_ddc_post";
         hipLaunchKernelGGL((k_ddc_fold<4>), dim3(cdiv(inv, 256), cdiv(n_blocks, 4), f->n_channels), dim3(256), 0, st, spectra, f->d_H.get(), f->d_inv_in.get(), f->d_geom.get(), fft, inv, pre, n_blocks);
     }
     CSDR_LAUNCH_CHECK();

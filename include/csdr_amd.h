@@ -626,6 +626,11 @@ int  csdr_amd_fastddc_inv_process(csdr_amd_fastddc_inv *f, const csdr_complexf *
 /* name of the dominant kernel ("k_ddc_gemm": the alias fold as an fp32 matrix-core product, taken at fft_inv_size 512 = BASELINE config 4;
  * "k_ddc_fold_ct": the general kernel) and HIP-event timing of it on the context's stream (bench_fastddc.py's roofline leg) */
 const char *csdr_amd_fastddc_inv_kernel_name(const csdr_amd_fastddc_inv *f);
+/* every kernel instance of the object's last call, template arguments included and joined by '+': the transform in front of the fold where the object runs one
+ * ("k_ddc_xt" for natural-order spectra, "k_ddc_fwd512<16,F>[+k_ddc_fwd128]" for a bank's fused forward transform), the fold, the inverse transforms -- e.g.
+ * "k_ddc_xt+k_ddc_gemm<2,true>+k_ddc_ifft512_post<8>", "k_ddc_fwd512<16,0>+k_ddc_gemm3<1,true>+k_ddc_ifft256d_post<8>", "k_ddc_fold<16>+hipfft+k_ddc_post".
+ * "" before the first call; the pointer is valid until the object's next call.  csdr_amd_fastddc_inv_kernel_name keeps its coarse names. */
+const char *csdr_amd_fastddc_inv_kernels(const csdr_amd_fastddc_inv *f);
 int  csdr_amd_fastddc_inv_set_profiling(csdr_amd_fastddc_inv *f, int on);
 int  csdr_amd_fastddc_inv_kernel_time(csdr_amd_fastddc_inv *f, double *total_ms, long *launches);
 /* the same for the kernels around it (csdr_amd_fastddc_inv_set_profiling(f, 2): two more event pairs per call): stage 1 = the forward transform's first pass (k_ddc_fwd512), stage 2 = the inverse transforms with scrap and residual
@@ -905,6 +910,9 @@ void csdr_amd_debug_dft8(const float *in16, float *out16, int inverse);
 /* Test hook: the channelizer's residual-shift bookkeeping (decimating_shift_addition_cc's (remain, phase) per block, libcsdr_gpl.c:153-158) over n_blocks blocks on the
  * CPU; mode 0 = the general step, mode 1 = the constant-step fast path of the kernels (-1 when it does not apply).  phases_out[b] = phase in front of block b. */
 int  csdr_amd_debug_ddc_chain(int mode, float rate2, int post_in, int post_dec, int n_blocks, int *remain_io, float *phase_io, float *phases_out, int *count_out);
+/* Test hook: how the channelizer's matrix-core fold tiles a call of n_blocks blocks at `pre_decimation` (32-block accumulator tiles per workgroup, bytes of LDS of one
+ * spectra buffer); -1 when the path declines the geometry because not even one tile fits a workgroup's 160 KiB (the general kernels serve it). */
+int  csdr_amd_debug_ddc_fold_plan(int pre_decimation, int n_blocks, int *tiles, long *lds_bytes);
 /* Test hook: one tile (16 outputs from 256 limited samples) of the NFM chain's matrix-core de-emphasis FIR on the CPU: digit planes,
  * Toeplitz digit table and accumulator classes as k_nfm_deemph_mfma combines them. */
 int csdr_amd_debug_nfm_deemph_tile(int audio_rate, float max_amp, const float *x, float *out16);

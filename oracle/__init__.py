@@ -411,8 +411,9 @@ class Port:
         self.L.orc_fft_swap_sides(_p(tf), ddc.fft_size)
         return tf
 
-    def fastddc_inv_cc(self, spectra, ddc, taps_fft, status=None):
-        """status = (decimation_remain, starting_phase) to continue a stream; with a status the call returns (samples, status after the last block)."""
+    def fastddc_inv_cc(self, spectra, ddc, taps_fft, status=None, per_block=False):
+        """status = (decimation_remain, starting_phase) to continue a stream; with a status the call returns (samples, status after the last block).
+        per_block: the samples as a list of one array per block instead of one stream."""
         spectra = np.ascontiguousarray(spectra, c64); taps_fft = _cf(taps_fft)
         st = _DsaStatus(0, 0.0, 0) if status is None else _DsaStatus(int(status[0]), float(status[1]), 0)
         outs = []
@@ -420,7 +421,7 @@ class Port:
         for b in range(spectra.shape[0]):
             st = self.L.orc_fastddc_inv_cc(_p(spectra[b]), _p(ob), C.byref(ddc), _p(taps_fft), st)
             outs.append(ob[:st.output_size].copy())
-        y = np.concatenate(outs) if outs else np.zeros(0, c64)
+        y = outs if per_block else np.concatenate(outs) if outs else np.zeros(0, c64)
         return y if status is None else (y, (st.decimation_remain, st.starting_phase))
 
     # ---- chains
@@ -798,7 +799,7 @@ class Ref:
         self.L.fft_swap_sides(_p(tf), ddc.fft_size)
         return tf
 
-    def fastddc_inv_cc(self, spectra, ddc, taps_fft):
+    def fastddc_inv_cc(self, spectra, ddc, taps_fft, per_block=False):
         spectra = np.ascontiguousarray(spectra, c64); taps_fft = _cf(taps_fft)
         M = ddc.fft_inv_size
         a_in = np.zeros(M, c64); a_out = np.zeros(M, c64)
@@ -810,7 +811,7 @@ class Ref:
             st = self.L.fastddc_inv_cc(_p(spec), _p(ob), C.byref(ddc), pinv, _p(taps_fft), st)
             outs.append(ob[:st.output_size].copy())
         self.L.fft_destroy(pinv)
-        return np.concatenate(outs) if outs else np.zeros(0, c64)
+        return outs if per_block else np.concatenate(outs) if outs else np.zeros(0, c64)
 
     # ---- chain, stage by stage with the CLI's block sizes
     def wfm_chain(self, iq_u8, shift_rate, decimation, taps, frac_rate=5, tau=50e-6, audio_rate=48000):

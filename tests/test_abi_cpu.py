@@ -264,6 +264,24 @@ def test_ddc_chain_fast_path_is_bit_identical(libpath, port):
     assert fn(0, 0.01, 449, 2, 10, C.byref(rem), C.byref(ph), phases.ctypes.data, C.byref(cnt)) == 0 and cnt.value in (2245, 2246)
 
 
+def test_ddc_fold_never_asks_for_more_lds_than_a_workgroup_has(libpath):
+    """The matrix-core fold of the fastddc inverse stages 32 blocks x pre_decimation spectrum values per accumulator tile in LDS (fastddc_mfma.hip: ddc_mfma_create /
+    ddc_mfma_collect).  Two tiles at pre_decimation 512 (263 168 bytes) and one at 1024 (262 656) exceed the 160 KiB a workgroup can have: the call must fall back to
+    one tile per 32 blocks, or the path must decline the geometry -- never a launch that asks for more."""
+    L = C.CDLL(libpath)
+    fn = L.csdr_amd_debug_ddc_fold_plan
+    fn.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    for pre in (8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096):
+        for nb in (1, 3, 32, 33, 34, 40, 64, 65, 1000):
+            tiles = C.c_int(-1); lds = C.c_long(-1)
+            rc = fn(pre, nb, C.byref(tiles), C.byref(lds))
+            if pre >= 1024:
+                assert rc == -1, (pre, nb)
+                continue
+            assert rc == 0 and lds.value == 32 * tiles.value * (pre // 2 + 1) * 16 and lds.value <= 160 * 1024, (pre, nb, tiles.value, lds.value)
+            assert tiles.value == (2 if nb > 32 and pre <= 256 else 1), (pre, nb, tiles.value)
+
+
 def test_phase_chain_plan_is_the_reference_loop(libpath, port):
     """seeds.hpp: the phase bookkeeping of `csdr shift_addition_cc` (libcsdr_gpl.c:48-51: ph += rate*PI*1024; while (ph > PI) ph -= 2 PI; while (ph < -PI) ph += 2 PI,
     every step rounded to float) without the loops' iterations -- the per-stream chain objects replay it for every 1024-chunk of every stream, one lane per stream.

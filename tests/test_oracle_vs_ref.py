@@ -233,8 +233,9 @@ def test_bandpass_fir_fft(port, ref, ntaps, fft_size):
 
 
 def test_fastddc_geometry(port, ref):
-    for D in [2, 3, 4, 6, 8, 10, 16, 24, 50, 64, 100, 128, 256]:
-        for tbw in [0.05, 0.005, 0.001]:
+    # (D = 5 .. 2048 and tbw = 0.01 .. 0.000125: the geometry classes of tests/test_fastddc_geometries_gpu.py -- pre_decimation 1 .. 1024, post_decimation 2, 3, 5, 25)
+    for D in [2, 3, 4, 6, 8, 10, 16, 24, 50, 64, 100, 128, 256, 5, 32, 40, 48, 384, 512, 640, 768, 1024, 2048]:
+        for tbw in [0.05, 0.005, 0.001, 0.01, 0.0025, 0.002, 0.0005, 0.00025, 0.000125]:
             for s in [0.0, -0.1, 0.4, 0.123456, -0.5 + 0.5 / 256, 0.25]:
                 da, ea = port.fastddc_init(tbw, D, s); db, eb = ref.fastddc_init(tbw, D, s)
                 A, B = da.as_dict(), db.as_dict()
@@ -255,11 +256,24 @@ def test_fastddc_geometry(port, ref):
 
 @pytest.mark.parametrize("D,tbw,shift", [(16, 0.05, -0.1), (256, 0.005, 0.3 + 0.5 / 256), (6, 0.05, 0.2),
                                          # BASELINE config 4's exact geometry (fft 65536 / inverse 512), channels 0, 127, 255 of -0.5 + (c + 0.5) / 256
-                                         (256, 0.001, -0.5 + 0.5 / 256), (256, 0.001, -0.5 + 127.5 / 256), (256, 0.001, -0.5 + 255.5 / 256)])
+                                         (256, 0.001, -0.5 + 0.5 / 256), (256, 0.001, -0.5 + 127.5 / 256), (256, 0.001, -0.5 + 255.5 / 256),
+                                         # one per geometry class of tests/test_fastddc_geometries_gpu.py (its cases a .. k: fft / pre_decimation / post_decimation),
+                                         # shifts at both band edges, at 0, on and off the 1 / fft grid, either sign
+                                         (16, 0.01, 0.1234),                                                    # a  4096 / 8 / 2
+                                         (24, 0.01, -0.4999), (40, 0.01, 0.4999),                               # b  4096 / 8 / 3, 5
+                                         (32, 0.005, -0.3711), (64, 0.0025, 0.0), (128, 0.002, 0.25),           # c  8192 / 16, 16384 / 32, 32768 / 64; post 2
+                                         (48, 0.005, 0.0517),                                                   # d  8192 / 16 / 3
+                                         (512, 0.0005, -0.2222), (768, 0.0005, 0.3711),                         # e  131072 / 256 / 2, 3
+                                         (384, 0.001, -0.5 + 100.5 / 256),                                      # f  65536 / 128 / 3
+                                         (640, 0.001, 0.125),                                                   # g  65536 / 128 / 5
+                                         (1024, 0.00025, -0.1234),                                              # h  262144 / 512 / 2
+                                         (2048, 0.000125, 0.3333),                                              # i  524288 / 1024 / 2
+                                         (5, 0.05, -0.41), (2, 0.05, 0.2),                                      # j  1024 / 1 / 5, 2
+                                         (50, 0.05, 0.33)])                                                     # k  1024 / 2 / 25
 def test_fastddc_stream(port, ref, D, tbw, shift):
     rng = np.random.default_rng(4)
     da, _ = port.fastddc_init(tbw, D, shift); db, _ = ref.fastddc_init(tbw, D, shift)
-    x = crand(rng, da.input_size * (12 if da.fft_size < 65536 else 5))
+    x = crand(rng, da.input_size * (12 if da.fft_size < 65536 else 5 if da.fft_size == 65536 else 3))
     sa = port.fastddc_fwd_cc(x, da); sb = ref.fastddc_fwd_cc(x, db)
     assert relrms(sa, sb) < 1e-6
     ta = port.fastddc_taps_fft(da, shift, D); tb = ref.fastddc_taps_fft(db, shift, D)
@@ -267,6 +281,12 @@ def test_fastddc_stream(port, ref, D, tbw, shift):
     ya = port.fastddc_inv_cc(sa, da, ta); yb = ref.fastddc_inv_cc(sb, db, tb)
     assert ya.size == yb.size and ya.size > 0
     assert relrms(ya, yb) < 1e-5
+    # ... and block by block (the GPU tests of the geometry classes hold every call of every channel to the float gate: a whole-stream ratio hides one bad block)
+    ba = port.fastddc_inv_cc(sa, da, ta, per_block=True); bb = ref.fastddc_inv_cc(sb, db, tb, per_block=True)
+    assert [a.size for a in ba] == [b.size for b in bb]
+    worst = max(relrms(a, b) for a, b in zip(ba, bb))
+    print("fastddc oracle vs reference D %d tbw %g shift %g: stream %.3g, worst block %.3g" % (D, tbw, shift, relrms(ya, yb), worst))
+    assert worst < 1e-5
 
 
 # ---------------------------------------------------------------- the WFM chain

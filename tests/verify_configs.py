@@ -189,17 +189,26 @@ def c4_rates(n_channels=256):
     return (-0.5 + (np.arange(n_channels) + 0.5) / n_channels).astype(f32)
 
 
-def fastddc_oracle_channels(x, tbw, decimation, rates, channels):
-    """Oracle outputs of the listed channels for the wideband input x (whole blocks only): (spectra, {channel: samples})."""
+def fastddc_oracle_channels(x, tbw, decimation, rates, channels, calls=None):
+    """Oracle outputs of the listed channels for the wideband input x (whole blocks only): (spectra, {channel: samples}).
+    calls = blocks per call (a list that covers the blocks of x): {channel: [samples of call 0, samples of call 1, ...]} instead -- the same stream, cut where
+    the calls of the path under test end (the oracle's state runs through: a call boundary is nothing to it)."""
     import oracle
     port = oracle.port()
     pd, err = port.fastddc_init(tbw, decimation, 0.0)
     assert err == 0
     spec = port.fastddc_fwd_cc(x, pd)
+    assert calls is None or sum(calls) == spec.shape[0]
     outs = {}
     for c in channels:
         pdc, _ = port.fastddc_init(tbw, decimation, float(rates[c]))
-        outs[c] = port.fastddc_inv_cc(spec, pdc, port.fastddc_taps_fft(pdc, float(rates[c]), decimation))
+        taps = port.fastddc_taps_fft(pdc, float(rates[c]), decimation)
+        if calls is None:
+            outs[c] = port.fastddc_inv_cc(spec, pdc, taps)
+            continue
+        blocks = port.fastddc_inv_cc(spec, pdc, taps, per_block=True)
+        ends = np.cumsum(calls)
+        outs[c] = [np.concatenate(blocks[e - n:e]) for n, e in zip(calls, ends)]
     return spec, outs
 
 
