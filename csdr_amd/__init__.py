@@ -201,6 +201,25 @@ def lib():
     L.csdr_amd_carrier_kernel_name.restype = C.c_char_p; L.csdr_amd_carrier_kernel_name.argtypes = [vp]
     L.csdr_amd_carrier_destroy.argtypes = [vp]; L.csdr_amd_carrier_destroy.restype = None
     L.csdr_amd_debug_carrier_walk.restype = ll; L.csdr_amd_debug_carrier_walk.argtypes = [vp, vp, ll, vp, i, vp, vp, vp, vp, vp]
+    L.csdr_amd_amssb_params_default.argtypes = [vp, i]
+    L.csdr_amd_amssb_create_cf32.restype = vp; L.csdr_amd_amssb_create_cf32.argtypes = [vp, vp, i, vp, i, i, sz]
+    L.csdr_amd_amssb_create.restype = vp; L.csdr_amd_amssb_create.argtypes = [vp, vp, i, fl, i, vp, i, vp, i, i, sz]
+    L.csdr_amd_amssb_create_rates.restype = vp; L.csdr_amd_amssb_create_rates.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, i, sz]
+    L.csdr_amd_amssb_process.restype = ll; L.csdr_amd_amssb_process.argtypes = [vp, vp, sz, ll, vp, vp, sz]
+    L.csdr_amd_amssb_max_out.restype = ll; L.csdr_amd_amssb_max_out.argtypes = [vp, ll]
+    L.csdr_amd_amssb_set_rate.argtypes = [vp, i, fl]
+    L.csdr_amd_amssb_get_rate.restype = fl; L.csdr_amd_amssb_get_rate.argtypes = [vp, i]
+    L.csdr_amd_amssb_front_end.restype = vp; L.csdr_amd_amssb_front_end.argtypes = [vp]
+    L.csdr_amd_amssb_reset.argtypes = [vp]
+    L.csdr_amd_amssb_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_amssb_get_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_amssb_set_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_amssb_set_lanes.argtypes = [vp, i]
+    L.csdr_amd_amssb_lanes.argtypes = [vp]
+    L.csdr_amd_amssb_force_generic.argtypes = [vp, i]
+    L.csdr_amd_amssb_kernel_name.restype = C.c_char_p; L.csdr_amd_amssb_kernel_name.argtypes = [vp]
+    L.csdr_amd_amssb_destroy.argtypes = [vp]; L.csdr_amd_amssb_destroy.restype = None
+    L.csdr_amd_debug_amssb_walk.restype = ll; L.csdr_amd_debug_amssb_walk.argtypes = [vp, vp, i, vp, vp, vp]
     L.csdr_amd_fmmod_fc.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_dsb_fc.argtypes = [vp, vp, vp, sz, fl]
     L.csdr_amd_add_dcoffset_cc.argtypes = [vp, vp, vp, sz]
@@ -1076,6 +1095,122 @@ class Carrier(_Handle, _ChannelState, _Lanes):
         return {k: v[0] for k, v in res.items()} if squeeze else res
 
 
+AMSSB_MODES = {"am": 0, "ssb": 1}
+
+
+class AmSsbParams(C.Structure):
+    """csdr_amd_amssb_params"""
+    _fields_ = [("mode", C.c_int), ("block", C.c_int), ("reference", C.c_float), ("attack_rate", C.c_float), ("decay_rate", C.c_float), ("max_gain", C.c_float),
+                ("hang_time", C.c_short), ("attack_wait_time", C.c_short), ("gain_filter_alpha", C.c_float), ("limit_max", C.c_float)]
+
+
+class AmSsbChan(C.Structure):
+    """csdr_amd_amssb_chan: one channel's state (fastdcblock_ff's last_dc_level, agc_ff's last_gain)"""
+    _fields_ = [("last_dc", C.c_float), ("last_gain", C.c_float)]
+
+
+def amssb_params(mode, block=1024, agc=None, limit_max=None):
+    """csdr_amd_amssb_params_default for mode "am" / "ssb", then block, agc = (hang_time, reference, attack_rate, decay_rate, max_gain, attack_wait,
+    filter_alpha) in `csdr agc_ff`'s argument order, and limit_max where given"""
+    p = AmSsbParams()
+    if lib().csdr_amd_amssb_params_default(C.byref(p), AMSSB_MODES[mode] if isinstance(mode, str) else int(mode)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    p.block = int(block)
+    if agc is not None:
+        p.hang_time, p.reference, p.attack_rate, p.decay_rate, p.max_gain, p.attack_wait_time, p.gain_filter_alpha = agc
+    if limit_max is not None:
+        p.limit_max = limit_max
+    return p
+
+
+def amssb_debug_walk(params, x, state=None):
+    """CPU run of the kernels' functions for one channel (csdr_amd_debug_amssb_walk): the whole blocks of x -> (s16, pre_agc).  state: an AmSsbChan
+    carried in and out."""
+    x = np.ascontiguousarray(x, c64)
+    nb = x.size // params.block
+    s16 = np.zeros(nb * params.block, np.int16); pre = np.zeros(nb * params.block, f32)
+    rc = lib().csdr_amd_debug_amssb_walk(C.byref(params), _hp(x), nb, C.byref(state) if state is not None else None, _hp(s16), _hp(pre))
+    if rc < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return s16, pre
+
+
+class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
+    """csdr_amd_amssb: the AM / SSB receive chain's demodulator and audio tail for n_channels channels; input "cf32" (decimated complex baseband) or "u8"
+    (wideband u8 IQ through an owned front end: shift_rate one float or one per channel, decimation, ddc_taps); taps / fft_size: SSB's band-pass filter."""
+    _chan = AmSsbChan
+
+    def __init__(self, ctx, params, n_channels=1, in_format="cf32", taps=None, fft_size=0, max_samples_per_call=1 << 20, shift_rate=0.0, decimation=50,
+                 ddc_taps=None):
+        self.n_channels, self.params, self.in_format = n_channels, params, in_format
+        self.taps = np.ascontiguousarray(taps, c64) if taps is not None else np.zeros(0, c64)
+        tp, tn = (_hp(self.taps), self.taps.size) if self.taps.size else (None, 0)
+        if in_format == "cf32":
+            h = ctx.L.csdr_amd_amssb_create_cf32(ctx.h, C.byref(params), n_channels, tp, tn, fft_size, max_samples_per_call)
+        else:
+            self.ddc_taps = np.ascontiguousarray(ddc_taps, f32)
+            if np.ndim(shift_rate) == 0:
+                h = ctx.L.csdr_amd_amssb_create(ctx.h, C.byref(params), n_channels, shift_rate, decimation, _hp(self.ddc_taps), self.ddc_taps.size, tp, tn,
+                                                fft_size, max_samples_per_call)
+            else:
+                rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == n_channels
+                h = ctx.L.csdr_amd_amssb_create_rates(ctx.h, C.byref(params), n_channels, _hp(rates), decimation, _hp(self.ddc_taps), self.ddc_taps.size, tp,
+                                                      tn, fft_size, max_samples_per_call)
+        _Handle.__init__(self, ctx, "amssb", h)
+
+    def set_rate(self, ch, rate):
+        self._call("set_rate", int(ch), rate)
+
+    def get_rate(self, ch):
+        return float(self._fn("get_rate")(self.h, int(ch)))
+
+    def front_end_kernel(self):
+        return self._L.csdr_amd_ddc_kernel_name(self._fn("front_end")(self.h)).decode()
+
+    def process_dev(self, d_in, in_pitch, n_in, d_s16, d_pre, out_pitch):
+        """device pointers (d_pre may be None) -> the audio samples written per channel.  Asynchronous."""
+        return self._call("process", d_in, in_pitch, n_in, d_s16, d_pre, out_pitch)
+
+    def process(self, x, calls=None, with_pre=True, in_pitch=None, out_pitch=None, in_offset=0, retunes=None):
+        """x: [n_channels, n] complex samples (or [n_channels, 2n] u8 IQ bytes); calls: per-call sample counts (default one call); in_pitch: row pitch in
+        samples (bytes for u8); out_pitch in samples; in_offset: bytes by which the input's base is moved off its allocation; retunes: {call index:
+        [(channel, rate), ...]} -> (s16 [n_channels, na], pre_agc [n_channels, na] or None, the counts of the calls)"""
+        u8 = self.in_format == "u8"
+        x = np.ascontiguousarray(x, np.uint8 if u8 else c64)
+        if x.ndim == 1:
+            x = x[None]
+        s, w = x.shape
+        n = w // 2 if u8 else w
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else [int(k) for k in calls]
+        ip = (((w + 127) // 128 * 128) if u8 else max(n, 1)) if in_pitch is None else int(in_pitch)
+        xin = np.full((s, ip), 0x80, np.uint8) if u8 else np.zeros((s, ip), c64)
+        xin[:, :w] = x
+        raw = np.zeros(xin.nbytes + in_offset + 16, np.uint8)
+        raw[in_offset:in_offset + xin.nbytes] = xin.view(np.uint8).ravel()
+        di = self.ctx.upload(raw)
+        op = max(self.max_out(max(calls) if calls else 0), 1) if out_pitch is None else int(out_pitch)
+        ds = self.ctx.alloc(2 * op * s + 256); dp = self.ctx.alloc(4 * op * s + 256) if with_pre else None
+        outs, pres, counts = [], [], []
+        at = 0
+        for ci, k in enumerate(calls):
+            self.ctx.check(self.ctx.L.csdr_amd_memset(self.ctx.h, ds.ptr, 0x55, 2 * op * s + 256), "memset")      # (what a call leaves alone is checked below)
+            for ch, r in (retunes or {}).get(ci, []):
+                self.set_rate(ch, r)
+            got = self.process_dev(di.at(in_offset + (2 if u8 else 8) * at), ip, k, ds.ptr, dp.ptr if with_pre else None, op)
+            counts.append(got)
+            y = self.ctx.download(ds, np.int16, op * s).reshape(s, op)
+            if np.any(y[:, got:] != 0x5555):
+                raise CsdrAmdError("amssb: wrote beyond the %d samples it reported" % got)
+            outs.append(y[:, :got].copy())
+            if with_pre:
+                pres.append(self.ctx.download(dp, f32, op * s).reshape(s, op)[:, :got].copy())
+            at += k
+        cat = lambda parts, dt: np.concatenate(parts, axis=1) if parts else np.zeros((s, 0), dt)
+        return cat(outs, np.int16), (cat(pres, f32) if with_pre else None), counts
+
+
 TX_MODES = {"fm": 0, "am": 1, "dsb": 2}
 TX_FORMATS = {"cf32": 0, "u8": 1}
 
@@ -1613,6 +1748,17 @@ class Context:
     def squelch(self, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
         """A batched squelch_and_smeter_cc object (Squelch)"""
         return Squelch(self, n_channels, block_size, use_every_nth, levels, max_samples_per_call)
+
+    # ---- the AM and SSB receive chains (amssb.hip)
+    def am_bank(self, n_channels=1, block=1024, agc=None, limit_max=None, **kw):
+        """csdr_amd_amssb in AM mode (README.md:95's amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16); kw: AmSsb's in_format, max_samples_per_call
+        and, for "u8", shift_rate, decimation, ddc_taps"""
+        return AmSsb(self, amssb_params("am", block, agc, limit_max), n_channels, **kw)
+
+    def ssb_bank(self, n_channels=1, block=1024, taps=None, fft_size=0, agc=None, limit_max=None, **kw):
+        """csdr_amd_amssb in SSB mode (README.md:110's bandpass_fir_fft_cc | realpart_cf | agc_ff | limit_ff | convert_f_s16); taps: firdes_bandpass_c's, or
+        None for no filter"""
+        return AmSsb(self, amssb_params("ssb", block, agc, limit_max), n_channels, taps=taps, fft_size=fft_size, **kw)
 
     # ---- carrier recovery (carrier.hip)
     def carrier(self, params, n_channels=1):

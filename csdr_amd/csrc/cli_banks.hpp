@@ -130,6 +130,9 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
 // The device batch API wants the opposite shape: N streams side by side in ONE call.  These commands are that producer:
 //   csdr wfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_1> <out_1> ...]      N u8 IQ streams -> N s16 audio streams through ONE fused WFM chain object
 //   csdr nfm_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_1> <out_1> ...]      the same through the NFM chain object (README.md:87 defaults)
+//   csdr am_bank_u8_s16  <shift_rate> <in_0> <out_0> [<in_1> <out_1> ...]      the same through the AM chain object (README.md:95 defaults: decimation 50, tbw 0.005)
+//   csdr ssb_bank_u8_s16 [--lsb] <shift_rate> <in_0> <out_0> [...]             the same through the SSB chain object (README.md:110 defaults: passband 0 0.1 0.05;
+//                                                                              --lsb: -0.1 0)
 // in_k / out_k: a path (file or fifo) or fd:<n>.  Every pass reads one block of CSDR_AMD_BANK_BLOCK samples (default 262144, a multiple of 1024) from
 // EVERY input (the streams advance in lockstep, like the clients of one nmux), uploads them as the rows of one batch, runs the chain once and writes
 // each row's audio to its output.  The pass in which the first stream ends is the last one (lockstep streams end together).
@@ -173,8 +176,12 @@ int run_lockstep(csdr_amd_ctx *c, char **specs, int S, size_t T, size_t in_pitch
     return 0;
 }
 
-int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, bool nfm)
+enum { BANK_WFM, BANK_NFM, BANK_AM, BANK_SSB };
+int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
 {
+    const bool nfm = kind == BANK_NFM, amssb = kind == BANK_AM || kind == BANK_SSB;
+    bool lsb = false;
+    if (kind == BANK_SSB && argc > 2 && !strcmp(argv[2], "--lsb")) { lsb = true; argv += 1; argc -= 1; }
     Fds ctl_fd(1, -1);
     if (argc > 3 && !strcmp(argv[2], "--ctl")) {
         ctl_fd[0] = open_spec(argv[3], O_RDONLY | O_NONBLOCK);
@@ -193,19 +200,32 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, bool nfm)
     if (per_stream && rates.size() == 1) rates.assign(S, rates[0]);
     const float shift = rates[0];
     const size_t T = bank_block() / 1024 * 1024;
-    const int D = nfm ? 50 : 10; const float tbw = nfm ? 0.005f : 0.05f;
+    const int D = kind == BANK_WFM ? 10 : 50; const float tbw = kind == BANK_WFM ? 0.05f : 0.005f;
     const int nt = csdr_amd_firdes_filter_len(tbw);
     std::vector<float> taps(nt); csdr_amd_firdes_lowpass_f(taps.data(), nt, 0.5f / (float)D, CSDR_WINDOW_HAMMING);
-    Owned<csdr_amd_wfm, csdr_amd_wfm_destroy> w; Owned<csdr_amd_nfm, csdr_amd_nfm_destroy> n;
-    if (nfm && per_stream) n.reset(csdr_amd_nfm_create_rates(c, S, rates.data(), D, taps.data(), nt, 48000, 1024, 1.0f, 1.0f, T));
+    Owned<csdr_amd_wfm, csdr_amd_wfm_destroy> w; Owned<csdr_amd_nfm, csdr_amd_nfm_destroy> n; Owned<csdr_amd_amssb, csdr_amd_amssb_destroy> a;
+    if (amssb) {
+        csdr_amd_amssb_params ap;
+        MUST(csdr_amd_amssb_params_default(&ap, kind == BANK_AM ? CSDR_AMD_AMSSB_AM : CSDR_AMD_AMSSB_SSB));
+        std::vector<csdr_complexf> bp; int fft = 0;
+        if (kind == BANK_SSB) {                                       // bandpass_fir_fft_cc 0 0.1 0.05 (the transform's size as csdr.c:1834-1836 chooses it)
+            const int bl = csdr_amd_firdes_filter_len(0.05f);
+            bp.resize(bl); csdr_amd_firdes_bandpass_c(bp.data(), bl, lsb ? -0.1f : 0.f, lsb ? 0.f : 0.1f, CSDR_WINDOW_HAMMING);
+            fft = csdr_amd_next_pow2(bl); if (fft - bl < 200) fft *= 2;
+        }
+        a.reset(per_stream ? csdr_amd_amssb_create_rates(c, &ap, S, rates.data(), D, taps.data(), nt, bp.data(), (int)bp.size(), fft, T)
+                           : csdr_amd_amssb_create(c, &ap, S, shift, D, taps.data(), nt, bp.data(), (int)bp.size(), fft, T));
+    }
+    else if (nfm && per_stream) n.reset(csdr_amd_nfm_create_rates(c, S, rates.data(), D, taps.data(), nt, 48000, 1024, 1.0f, 1.0f, T));
     else if (nfm) n.reset(csdr_amd_nfm_create(c, S, shift, D, taps.data(), nt, 48000, 1024, 1.0f, 1.0f, T));
     else if (per_stream) w.reset(csdr_amd_wfm_create_rates(c, S, rates.data(), D, taps.data(), nt, 5, 50e-6f, 48000, T));
     else w.reset(csdr_amd_wfm_create(c, S, shift, D, taps.data(), nt, 5, 50e-6f, 48000, T));
-    if (!w && !n) die("bank create");
+    if (!w && !n && !a) die("bank create");
     const size_t in_pitch = 2 * T, out_pitch = ((T / 50 + 4096 + 63) / 64) * 64;      // out_pitch: s16 samples
     // a short final block: whole 1024-sample chunks of the shortest stream (the chain objects take a ragged LAST block only)
     auto pass = [&](const uint8_t *d_in, uint8_t *d_out, size_t nproc) {
-        const long na = nfm ? csdr_amd_nfm_process(n.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch) : csdr_amd_wfm_process(w.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch);
+        const long na = amssb ? (long)csdr_amd_amssb_process(a.get(), d_in, in_pitch, (long long)nproc, (int16_t *)d_out, nullptr, out_pitch) :
+                        nfm ? csdr_amd_nfm_process(n.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch) : csdr_amd_wfm_process(w.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch);
         MUST(na);
         return (size_t)na * 2;
     };
@@ -215,7 +235,7 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, bool nfm)
         while (lines.feed(ctl_fd[0])) while (const char *line = lines.next()) {
             int st = -1; float rv = 0;
             if (sscanf(line, "%d %g", &st, &rv) != 2 || st < 0 || st >= S) continue;
-            MUST(nfm ? csdr_amd_nfm_set_rate(n.get(), st, rv) : csdr_amd_wfm_set_rate(w.get(), st, rv));
+            MUST(amssb ? csdr_amd_amssb_set_rate(a.get(), st, rv) : nfm ? csdr_amd_nfm_set_rate(n.get(), st, rv) : csdr_amd_wfm_set_rate(w.get(), st, rv));
             fprintf(stderr, "csdr %s: stream %d reinitialized to %g\n", g_cmd, st, rv);
         }
     };

@@ -898,6 +898,64 @@ long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, s
 /* the chain's front end object (kernel name / profiling: csdr_amd_ddc_kernel_name, csdr_amd_ddc_set_profiling, csdr_amd_ddc_kernel_time) */
 csdr_amd_ddc *csdr_amd_nfm_front_end(csdr_amd_nfm *w);
 
+/* ------------------------------------------------------------------ the AM and SSB receive chains (amssb.hip)
+ * README.md:95   ... | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16
+ * README.md:110  ... | bandpass_fir_fft_cc lo hi tbw | realpart_cf | agc_ff | limit_ff | convert_f_s16
+ * for n_channels channels: the parameters are shared, each channel has its own state {last_dc, last_gain}, kept on the device between calls.  The tail works on
+ * whole blocks of `block` samples, 2 .. 16384: fastdcblock_ff's buffer and agc_ff's call length, the CLI's situation when fastdcblock_ff announces its buffer size and
+ * agc_ff adopts it (in SSB only the AGC's call length).  Every float operation is the reference's, in its order (amssb_dev.hpp); only the order of fastdcblock_ff's
+ * block sum, which the reference leaves to its compiler, is fixed here.  A stream in one call and any cut of it into calls (0 samples included), any pitch,
+ * any set_lanes and either kernel give the same bits as csdr_amd_debug_amssb_walk.
+ * params_default: mode, block 1024, agc_ff's CLI defaults (csdr.c:1342-1361: hang_time 200, reference 0.2, attack_rate 0.01, decay_rate 0.0001, max_gain 65536,
+ * attack_wait_time 0, gain_filter_alpha 0.999) and limit_max 1.
+ * create_cf32: the input is decimated complex baseband (the output of csdr_amd_fastddc_bank, csdr_amd_ddc_process, csdr_amd_fir_decimate_cc), in_pitch in complex
+ * samples.  create / create_rates: the input is wideband u8 IQ per channel through an owned csdr_amd_ddc (one shift rate, or one per channel; ddc_taps: the real
+ * decimation filter), in_pitch in bytes, n_in in complex samples with that object's rules; set_rate / get_rate forward to it, front_end returns it.
+ * taps, taps_length, fft_size (SSB only; taps_length 0: no filter): host complex taps of an owned csdr_amd_fftfilt in front of realpart_cf, one passband per object.
+ * max_samples_per_call: the most n_in of a call.
+ * process: in (device), n_in new samples per channel.  Carried per channel between calls: the state, the complex samples short of a whole block and the filter's
+ * input short of one input_size.  Writes the whole blocks that became available to audio_s16 and, when it is not NULL, the float samples in front of agc_ff to
+ * pre_agc_f (both device, out_pitch elements apart) and returns their count per channel: a multiple of block, possibly 0.  Nothing is written beyond the count.
+ * Asynchronous on the context's stream.  reset_channel / set_channel touch the two state words only.
+ * set_lanes: channels per wave, 0 = automatic .. 64.  kernel_name: "k_amssb_tiled<AM>" / "k_amssb_tiled<SSB>" (staged through LDS in coalesced tiles; block a
+ * multiple of 64 and 8-byte aligned input) or "k_amssb_generic<AM>" / "k_amssb_generic<SSB>" (one lane per channel on global memory; force_generic(1)). */
+enum { CSDR_AMD_AMSSB_AM = 0, CSDR_AMD_AMSSB_SSB = 1 };
+typedef struct csdr_amd_amssb_params {
+    int mode, block;
+    float reference, attack_rate, decay_rate, max_gain;
+    short hang_time, attack_wait_time;
+    float gain_filter_alpha, limit_max;
+} csdr_amd_amssb_params;
+typedef struct csdr_amd_amssb_chan { float last_dc, last_gain; } csdr_amd_amssb_chan;
+typedef struct csdr_amd_amssb csdr_amd_amssb;
+int  csdr_amd_amssb_params_default(csdr_amd_amssb_params *p, int mode);
+csdr_amd_amssb *csdr_amd_amssb_create_cf32(csdr_amd_ctx *ctx, const csdr_amd_amssb_params *params, int n_channels, const csdr_complexf *taps, int taps_length,
+                                           int fft_size, size_t max_samples_per_call);
+csdr_amd_amssb *csdr_amd_amssb_create(csdr_amd_ctx *ctx, const csdr_amd_amssb_params *params, int n_channels, float shift_rate, int decimation,
+                                      const float *ddc_taps, int ddc_taps_length, const csdr_complexf *taps, int taps_length, int fft_size,
+                                      size_t max_samples_per_call);
+csdr_amd_amssb *csdr_amd_amssb_create_rates(csdr_amd_ctx *ctx, const csdr_amd_amssb_params *params, int n_channels, const float *shift_rates, int decimation,
+                                            const float *ddc_taps, int ddc_taps_length, const csdr_complexf *taps, int taps_length, int fft_size,
+                                            size_t max_samples_per_call);
+long long csdr_amd_amssb_process(csdr_amd_amssb *p, const void *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *pre_agc_f, size_t out_pitch);
+long long csdr_amd_amssb_max_out(const csdr_amd_amssb *p, long long n_in);
+int  csdr_amd_amssb_set_rate(csdr_amd_amssb *p, int channel, float shift_rate);
+float csdr_amd_amssb_get_rate(const csdr_amd_amssb *p, int channel);
+csdr_amd_ddc *csdr_amd_amssb_front_end(csdr_amd_amssb *p);
+int  csdr_amd_amssb_reset(csdr_amd_amssb *p);
+int  csdr_amd_amssb_reset_channel(csdr_amd_amssb *p, int channel);
+int  csdr_amd_amssb_get_channel(csdr_amd_amssb *p, int channel, csdr_amd_amssb_chan *out);
+int  csdr_amd_amssb_set_channel(csdr_amd_amssb *p, int channel, const csdr_amd_amssb_chan *state);
+int  csdr_amd_amssb_set_lanes(csdr_amd_amssb *p, int lanes);
+int  csdr_amd_amssb_lanes(const csdr_amd_amssb *p);
+int  csdr_amd_amssb_force_generic(csdr_amd_amssb *p, int on);
+const char *csdr_amd_amssb_kernel_name(const csdr_amd_amssb *p);
+void csdr_amd_amssb_destroy(csdr_amd_amssb *p);
+/* the kernels' functions on the host for one channel (params->mode: which chain): in holds n_blocks * params->block complex samples; state_io (may be NULL: a fresh
+ * channel) carries the state in and out; either output may be NULL.  Returns n_blocks * block or a negative code. */
+long long csdr_amd_debug_amssb_walk(const csdr_amd_amssb_params *params, const csdr_complexf *in, int n_blocks, csdr_amd_amssb_chan *state_io, int16_t *s16_out,
+                                    float *pre_agc_out);
+
 /* Test hook: one tile of the WFM chain kernel (k_wfm_mfma_seq: phase-independent weight set, post factors, chunk-boundary handling) on the CPU.
  * n0: window base sample (multiple of 8); window: 512 raw bytes; ctab2: (cos, sin) of chunks n0>>10, +1; out16: 16 rows. */
 int csdr_amd_debug_wfm_seq_tile(int D, int L, int F, float shift_rate, const float *taps, long long n0, const uint8_t *window,
