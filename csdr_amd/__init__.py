@@ -210,6 +210,10 @@ def lib():
     L.csdr_amd_amssb_set_rate.argtypes = [vp, i, fl]
     L.csdr_amd_amssb_get_rate.restype = fl; L.csdr_amd_amssb_get_rate.argtypes = [vp, i]
     L.csdr_amd_amssb_front_end.restype = vp; L.csdr_amd_amssb_front_end.argtypes = [vp]
+    if hasattr(L, "csdr_amd_amssb_set_passband"):         # (absent from older builds selected with CSDR_AMD_LIB for A/B runs, like the per-stream filter below)
+        L.csdr_amd_amssb_set_passband.argtypes = [vp, i, fl, fl, i]
+        L.csdr_amd_amssb_set_channel_taps.argtypes = [vp, i, vp, i]
+        L.csdr_amd_amssb_get_passband.argtypes = [vp, i, vp, vp]
     L.csdr_amd_amssb_reset.argtypes = [vp]
     L.csdr_amd_amssb_reset_channel.argtypes = [vp, i]
     L.csdr_amd_amssb_get_channel.argtypes = [vp, i, vp]
@@ -275,6 +279,11 @@ def lib():
     L.csdr_amd_fracdec_set_where.restype = None; L.csdr_amd_fracdec_set_where.argtypes = [vp, fl]
     L.csdr_amd_fracdec_get_where.restype = fl; L.csdr_amd_fracdec_get_where.argtypes = [vp]
     L.csdr_amd_fftfilt_create.restype = vp; L.csdr_amd_fftfilt_create.argtypes = [vp, i, vp, i, i, i]
+    L.csdr_amd_fftfilt_set_taps.argtypes = [vp, vp, i]
+    if hasattr(L, "csdr_amd_fftfilt_create_per_stream"):
+        L.csdr_amd_fftfilt_create_per_stream.restype = vp; L.csdr_amd_fftfilt_create_per_stream.argtypes = [vp, i, vp, i, i, i]
+        L.csdr_amd_fftfilt_set_stream_taps.argtypes = [vp, i, vp, i]
+        L.csdr_amd_fftfilt_per_stream.argtypes = [vp]
     L.csdr_amd_fftfilt_destroy.argtypes = [vp]
     L.csdr_amd_fftfilt_input_size.argtypes = [vp]
     L.csdr_amd_fftfilt_reset.argtypes = [vp]
@@ -1098,6 +1107,67 @@ class Carrier(_Handle, _ChannelState, _Lanes):
 AMSSB_MODES = {"am": 0, "ssb": 1}
 
 
+def _fftfilt_taps(taps, n_streams):
+    """complex64 taps, [taps_length] or [n_streams, taps_length]; ValueError on any other shape (before a device is touched)"""
+    taps = np.ascontiguousarray(taps, c64)
+    if taps.ndim == 2 and taps.shape[0] != n_streams:
+        raise ValueError("taps: %d rows for %d streams" % (taps.shape[0], n_streams))
+    if taps.ndim not in (1, 2) or taps.shape[-1] < 1:
+        raise ValueError("taps: need [taps_length] or [n_streams, taps_length], got shape %s" % (taps.shape,))
+    return taps
+
+
+class FftFilt(_Handle):
+    """csdr_amd_fftfilt: bandpass_fir_fft_cc for n_streams streams, the overlap carried between calls.  taps 1-D: one passband for all streams; 2-D: a passband per
+    stream (one-pass path only).  set_stream_taps turns a shared filter per-stream in place."""
+
+    def __init__(self, ctx, fft_size, taps, n_streams=1, max_blocks=1):
+        self.taps = _fftfilt_taps(taps, n_streams)
+        self.n_streams, self.taps_length = n_streams, self.taps.shape[-1]
+        create = ctx.L.csdr_amd_fftfilt_create if self.taps.ndim == 1 else ctx.L.csdr_amd_fftfilt_create_per_stream
+        _Handle.__init__(self, ctx, "fftfilt", create(ctx.h, fft_size, _hp(self.taps), self.taps_length, n_streams, max_blocks))
+        self.input_size = self._fn("input_size")(self.h)
+
+    def per_stream(self):
+        return bool(self._fn("per_stream")(self.h))
+
+    def window(self):
+        return self._fn("window")(self.h)
+
+    def _row(self, taps):
+        taps = np.ascontiguousarray(taps, c64)
+        if taps.ndim != 1:
+            raise ValueError("taps: need one row, got shape %s" % (taps.shape,))
+        return taps
+
+    def set_taps(self, taps):
+        taps = self._row(taps)
+        self._call("set_taps", _hp(taps), taps.size)
+
+    def set_stream_taps(self, stream, taps):
+        taps = self._row(taps)
+        self._call("set_stream_taps", int(stream), _hp(taps), taps.size)
+
+    def process(self, x, calls=None):
+        """x: [n_streams, n] complex samples; calls: blocks per call (default: all whole blocks in one call) -> the filtered whole blocks [n_streams, m]"""
+        x = np.ascontiguousarray(x, c64)
+        s, n = x.shape
+        if s != self.n_streams:
+            raise ValueError("x has %d rows for %d streams" % (s, self.n_streams))
+        inp = self.input_size
+        calls = [n // inp] if calls is None else [int(k) for k in calls]
+        if sum(calls) * inp > n:
+            raise ValueError("%d blocks of %d samples from %d samples" % (sum(calls), inp, n))
+        di = self.ctx.upload(x); do = self.ctx.alloc(x.nbytes + 64)
+        b = 0
+        self.kernels = []                                # the one-pass kernel every call ran ("": the full-size path)
+        for k in calls:
+            self._call("process", di.at(8 * b * inp), do.at(8 * b * inp), k, n, n)
+            self.kernels.append(self.kernel_name())
+            b += k
+        return self.ctx.download(do, c64, s * n).reshape(s, n)[:, :b * inp].copy()
+
+
 class AmSsbParams(C.Structure):
     """csdr_amd_amssb_params"""
     _fields_ = [("mode", C.c_int), ("block", C.c_int), ("reference", C.c_float), ("attack_rate", C.c_float), ("decay_rate", C.c_float), ("max_gain", C.c_float),
@@ -1135,13 +1205,24 @@ def amssb_debug_walk(params, x, state=None):
     return s16, pre
 
 
+def _passband_list(passbands, n_channels):
+    """[(low, high)] * n_channels as floats; ValueError on any other shape (before a device is touched)"""
+    pb = np.asarray(passbands, np.float64)
+    if pb.ndim != 2 or pb.shape != (n_channels, 2):
+        raise ValueError("passbands: need %d (low, high) pairs, got shape %s" % (n_channels, pb.shape))
+    return [(float(lo), float(hi)) for lo, hi in pb]
+
+
 class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
     """csdr_amd_amssb: the AM / SSB receive chain's demodulator and audio tail for n_channels channels; input "cf32" (decimated complex baseband) or "u8"
     (wideband u8 IQ through an owned front end: shift_rate one float or one per channel, decimation, ddc_taps); taps / fft_size: SSB's band-pass filter."""
     _chan = AmSsbChan
 
     def __init__(self, ctx, params, n_channels=1, in_format="cf32", taps=None, fft_size=0, max_samples_per_call=1 << 20, shift_rate=0.0, decimation=50,
-                 ddc_taps=None):
+                 ddc_taps=None, passbands=None, window=WINDOWS["HAMMING"]):
+        """passbands: [(low, high), ...], one pair per channel, set (set_passband) on the fresh object; taps still give the length and the channels' start"""
+        if passbands is not None:
+            passbands = _passband_list(passbands, n_channels)
         self.n_channels, self.params, self.in_format = n_channels, params, in_format
         self.taps = np.ascontiguousarray(taps, c64) if taps is not None else np.zeros(0, c64)
         tp, tn = (_hp(self.taps), self.taps.size) if self.taps.size else (None, 0)
@@ -1157,6 +1238,24 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
                 h = ctx.L.csdr_amd_amssb_create_rates(ctx.h, C.byref(params), n_channels, _hp(rates), decimation, _hp(self.ddc_taps), self.ddc_taps.size, tp,
                                                       tn, fft_size, max_samples_per_call)
         _Handle.__init__(self, ctx, "amssb", h)
+        for ch, (lo, hi) in enumerate(passbands or []):
+            self.set_passband(ch, lo, hi, window)
+
+    def set_passband(self, ch, low, high, window=WINDOWS["HAMMING"]):
+        """channel ch's filter becomes firdes_bandpass_c(low, high) at the object's taps length, from the first sample the filter has not consumed yet"""
+        self._call("set_passband", int(ch), float(low), float(high), int(window))
+
+    def get_passband(self, ch):
+        """(low, high) as set_passband gave them last; (nan, nan) when the channel's taps came from create or set_channel_taps"""
+        lo, hi = C.c_float(), C.c_float()
+        self._call("get_passband", int(ch), C.byref(lo), C.byref(hi))
+        return lo.value, hi.value
+
+    def set_channel_taps(self, ch, taps):
+        taps = np.ascontiguousarray(taps, c64)
+        if taps.ndim != 1 or taps.size != self.taps.size:
+            raise ValueError("a channel's taps have the object's length (%d), got shape %s" % (self.taps.size, taps.shape))
+        self._call("set_channel_taps", int(ch), _hp(taps), taps.size)
 
     def set_rate(self, ch, rate):
         self._call("set_rate", int(ch), rate)
@@ -1174,7 +1273,7 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
     def process(self, x, calls=None, with_pre=True, in_pitch=None, out_pitch=None, in_offset=0, retunes=None):
         """x: [n_channels, n] complex samples (or [n_channels, 2n] u8 IQ bytes); calls: per-call sample counts (default one call); in_pitch: row pitch in
         samples (bytes for u8); out_pitch in samples; in_offset: bytes by which the input's base is moved off its allocation; retunes: {call index:
-        [(channel, rate), ...]} -> (s16 [n_channels, na], pre_agc [n_channels, na] or None, the counts of the calls)"""
+        [(channel, rate) or (channel, "bp", low, high) or (channel, "taps", taps), ...]} -> (s16 [n_channels, na], pre_agc [n_channels, na] or None, the counts of the calls)"""
         u8 = self.in_format == "u8"
         x = np.ascontiguousarray(x, np.uint8 if u8 else c64)
         if x.ndim == 1:
@@ -1196,8 +1295,11 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
         at = 0
         for ci, k in enumerate(calls):
             self.ctx.check(self.ctx.L.csdr_amd_memset(self.ctx.h, ds.ptr, 0x55, 2 * op * s + 256), "memset")      # (what a call leaves alone is checked below)
-            for ch, r in (retunes or {}).get(ci, []):
-                self.set_rate(ch, r)
+            for ch, r, *more in (retunes or {}).get(ci, []):
+                if isinstance(r, str):
+                    self.set_passband(ch, *more) if r == "bp" else self.set_channel_taps(ch, *more)
+                else:
+                    self.set_rate(ch, r)
             got = self.process_dev(di.at(in_offset + (2 if u8 else 8) * at), ip, k, ds.ptr, dp.ptr if with_pre else None, op)
             counts.append(got)
             y = self.ctx.download(ds, np.int16, op * s).reshape(s, op)
@@ -1757,7 +1859,11 @@ class Context:
 
     def ssb_bank(self, n_channels=1, block=1024, taps=None, fft_size=0, agc=None, limit_max=None, **kw):
         """csdr_amd_amssb in SSB mode (README.md:110's bandpass_fir_fft_cc | realpart_cf | agc_ff | limit_ff | convert_f_s16); taps: firdes_bandpass_c's, or
-        None for no filter"""
+        None for no filter; passbands=[(low, high), ...]: a passband per channel (designed at the taps' length), window: their window"""
+        if kw.get("passbands") is not None:
+            kw["passbands"] = _passband_list(kw["passbands"], n_channels)
+            if taps is None:
+                raise ValueError("passbands need taps: their length is the passbands' length")
         return AmSsb(self, amssb_params("ssb", block, agc, limit_max), n_channels, taps=taps, fft_size=fft_size, **kw)
 
     # ---- carrier recovery (carrier.hip)
@@ -1855,20 +1961,20 @@ class Context:
         x = np.ascontiguousarray(x, c64); di = self.upload(x); do = self.alloc(x.nbytes + 64)
         self.check(self.L.csdr_amd_fft_c2c(self.h, di.ptr, do.ptr, x.size, int(forward)), "fft"); return self.download(do, c64, x.size)
 
+    def fftfilt(self, fft_size, taps, n_streams=1, max_blocks=1):
+        """A csdr_amd_fftfilt object (FftFilt); taps 1-D: shared by the streams, 2-D [n_streams, taps_length]: a passband per stream"""
+        return FftFilt(self, fft_size, taps, n_streams, max_blocks)
+
     def bandpass_fir_fft_cc(self, x, taps, fft_size, blocks_per_call=None):
-        x2, squeeze = self._2d(x, c64); taps = np.ascontiguousarray(taps, c64)
+        """taps: 1-D for every stream of x, or 2-D with one row per stream"""
+        x2, squeeze = self._2d(x, c64)
         s, n = x2.shape
-        inp = fft_size - taps.size + 1; nb = n // inp
+        taps = _fftfilt_taps(taps, s)
+        inp = fft_size - taps.shape[-1] + 1; nb = n // inp
         per = nb if not blocks_per_call else blocks_per_call
-        with _Handle(self, "fftfilt", self.L.csdr_amd_fftfilt_create(self.h, fft_size, _hp(taps), taps.size, s, max(per, 1))) as f:
-            di = self.upload(x2); do = self.alloc(x2.nbytes + 64)
-            b = 0
-            while b < nb:
-                k = min(per, nb - b)
-                self.check(f._fn("process")(f.h, di.at(8 * b * inp), do.at(8 * b * inp), k, n, n), "fftfilt")
-                b += k
-            y = self.download(do, c64, s * n).reshape(s, n)[:, :nb * inp]
-        return y[0].copy() if squeeze else y.copy()
+        with FftFilt(self, fft_size, taps, s, max(per, 1)) as f:
+            y = f.process(x2, [per] * (nb // per) + ([nb % per] if nb % per else [])) if nb else np.zeros((s, 0), c64)
+        return y[0].copy() if squeeze else y
 
     def fastddc_init(self, tbw, decimation, shift_rate):
         d = FastDDC(); err = self.L.csdr_amd_fastddc_init(C.byref(d), tbw, decimation, shift_rate); return d, err

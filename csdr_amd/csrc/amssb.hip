@@ -16,6 +16,7 @@
 // Both run amssb_dev.hpp's functions on the same samples in the same order: the same bits, for every C, every cut into calls and every pitch, as the CPU hook.
 #include "common.hpp"
 #include "amssb_dev.hpp"
+#include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -222,7 +223,8 @@ struct csdr_amd_amssb {
     DevBuf<float> d_carry; int fill;                     // [n_ch][block] complex: the samples short of a whole block
     int inp; DevBuf<float> d_fin, d_filt; size_t f_pitch; int f_fill;      // SSB: the filter's input (what is short of one input_size in front) and output
     int D; DevBuf<float> d_y; size_t y_pitch;            // U8: the front end's decimation and output
-    Owned<csdr_amd_fftfilt, csdr_amd_fftfilt_destroy> filt;
+    Owned<csdr_amd_fftfilt, csdr_amd_fftfilt_destroy> filt; int taps_len;
+    std::vector<float> band;                             // [n_ch][2]: the edges set_passband gave a channel last (NaN: none, or taps of the caller's own)
     Owned<csdr_amd_ddc, csdr_amd_ddc_destroy> ddc;
 };
 
@@ -260,6 +262,7 @@ csdr_amd_amssb *create_impl(csdr_amd_ctx *c, const csdr_amd_amssb_params *params
         p->f_pitch = (p->inp + p->max_tail + 15) & ~(size_t)15;
         p->filt.reset(csdr_amd_fftfilt_create(c, fft_size, taps, taps_length, n_channels, (int)(p->f_pitch / p->inp) + 1));
         if (!p->filt) return nullptr;
+        p->taps_len = taps_length; p->band.assign((size_t)2 * n_channels, NAN);
         alloc(p->d_fin, sizeof(cf32) * p->f_pitch * n_channels);
         alloc(p->d_filt, sizeof(cf32) * p->f_pitch * n_channels);
         p->max_tail = p->f_pitch;
@@ -375,6 +378,44 @@ int csdr_amd_amssb_set_rate(csdr_amd_amssb *p, int channel, float shift_rate)
 }
 float csdr_amd_amssb_get_rate(const csdr_amd_amssb *p, int channel) { return p && p->ddc ? csdr_amd_ddc_get_rate(p->ddc.get(), channel) : 0.f; }
 csdr_amd_ddc *csdr_amd_amssb_front_end(csdr_amd_amssb *p) { return p ? p->ddc.get() : nullptr; }
+
+// A channel's passband.  The owned filter takes it from its next call on, that is from the first sample it has not consumed: what waits in d_fin (short of one
+// input_size) is filtered with the new taps already.
+static int passband_target(const csdr_amd_amssb *p, int channel)
+{
+    if (!p) return fail_msg(-3, "amssb: null object");
+    if (!p->filt) return fail_msg(-3, "amssb: a passband needs an SSB object with a filter (AM has none)");
+    if (channel < 0 || channel >= p->n_ch) return fail_msg(-3, "amssb: channel out of range");
+    return 0;
+}
+int csdr_amd_amssb_set_channel_taps(csdr_amd_amssb *p, int channel, const csdr_complexf *taps, int taps_length)
+{
+    if (const int rc = passband_target(p, channel)) return rc;
+    if (!taps || taps_length != p->taps_len) return fail_msg(-3, "amssb: a channel's taps have the object's length (%d)", p->taps_len);
+    const int rc = csdr_amd_fftfilt_set_stream_taps(p->filt.get(), channel, taps, taps_length);
+    if (rc < 0) return rc;
+    p->band[2 * (size_t)channel] = p->band[2 * (size_t)channel + 1] = NAN;
+    return 0;
+}
+int csdr_amd_amssb_set_passband(csdr_amd_amssb *p, int channel, float low, float high, int window)
+{
+    if (const int rc = passband_target(p, channel)) return rc;
+    if (!(low < high) || low < -0.5f || high > 0.5f) return fail_msg(-3, "amssb: need -0.5 <= low < high <= 0.5");
+    if (window < CSDR_WINDOW_BOXCAR || window > CSDR_WINDOW_HAMMING) return fail_msg(-3, "amssb: unknown window");
+    std::vector<csdr_complexf> taps((size_t)p->taps_len);
+    csdr_amd_firdes_bandpass_c(taps.data(), p->taps_len, low, high, window);
+    const int rc = csdr_amd_fftfilt_set_stream_taps(p->filt.get(), channel, taps.data(), p->taps_len);
+    if (rc < 0) return rc;
+    p->band[2 * (size_t)channel] = low; p->band[2 * (size_t)channel + 1] = high;
+    return 0;
+}
+int csdr_amd_amssb_get_passband(const csdr_amd_amssb *p, int channel, float *low, float *high)
+{
+    if (const int rc = passband_target(p, channel)) return rc;
+    if (low) *low = p->band[2 * (size_t)channel];
+    if (high) *high = p->band[2 * (size_t)channel + 1];
+    return 0;
+}
 
 // every channel back to last_dc = 0, last_gain = 1 (csdr.c:957, 1365), nothing waiting, the filter's overlap and the front end as created
 int csdr_amd_amssb_reset(csdr_amd_amssb *p)

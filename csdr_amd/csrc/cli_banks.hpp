@@ -133,12 +133,15 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
 //   csdr am_bank_u8_s16  <shift_rate> <in_0> <out_0> [<in_1> <out_1> ...]      the same through the AM chain object (README.md:95 defaults: decimation 50, tbw 0.005)
 //   csdr ssb_bank_u8_s16 [--lsb] <shift_rate> <in_0> <out_0> [...]             the same through the SSB chain object (README.md:110 defaults: passband 0 0.1 0.05;
 //                                                                              --lsb: -0.1 0)
+//   csdr ssb_bank_u8_s16 --passbands lo:hi[,lo:hi,...] <shift_rate> ...        one passband for all streams or one per stream (transition bandwidth 0.05 for all);
+//                                                                              not together with --lsb
 // in_k / out_k: a path (file or fifo) or fd:<n>.  Every pass reads one block of CSDR_AMD_BANK_BLOCK samples (default 262144, a multiple of 1024) from
 // EVERY input (the streams advance in lockstep, like the clients of one nmux), uploads them as the rows of one batch, runs the chain once and writes
 // each row's audio to its output.  The pass in which the first stream ends is the last one (lockstep streams end together).
 //   <shift_rate> may be a comma-separated list, one rate per stream (ddcd tunes every client on its own: ddcd_old.h:51-61);
 //   --ctl <fifo | fd:<n>> in front of it: control lines "<stream> <rate>\n", applied between two passes exactly as `shift_addition_cc --fifo` applies a new rate
-//   between two reads (csdr.c:881-923: the phase carries over).
+//   between two reads (csdr.c:881-923: the phase carries over).  ssb_bank_u8_s16 also takes "<stream> bp <low> <high>\n": that stream's passband, as a retuned
+//   `bandpass_fir_fft_cc --fifo` (csdr.c:1817-1881), from the first sample the bank's filter has not consumed yet.
 size_t bank_block() { size_t T = 262144; if (const char *e = getenv("CSDR_AMD_BANK_BLOCK")) { long v = atol(e); if (v >= 1024) T = (size_t)v; } return T; }
 
 // The lockstep loop of the stream banks.  specs: in_0 out_0 in_1 out_1 ... (S pairs).  Every pass reads T samples of u8 IQ from EVERY input into the rows of one batch
@@ -182,6 +185,23 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
     const bool nfm = kind == BANK_NFM, amssb = kind == BANK_AM || kind == BANK_SSB;
     bool lsb = false;
     if (kind == BANK_SSB && argc > 2 && !strcmp(argv[2], "--lsb")) { lsb = true; argv += 1; argc -= 1; }
+    std::vector<float> bands;                                          // --passbands: low_0, high_0, low_1, ...
+    if (kind == BANK_SSB && argc > 2 && !strcmp(argv[2], "--passbands")) {
+        if (lsb) return badsyntax("--lsb and --passbands exclude each other");
+        if (argc < 4) return badsyntax("--passbands needs lo:hi[,lo:hi,...]");
+        for (const char *q = argv[3]; ;) {
+            char *e1 = nullptr, *e2 = nullptr;
+            const float lo = strtof(q, &e1);
+            if (e1 == q || *e1 != ':') return badsyntax("--passbands: every passband is lo:hi");
+            const float hi = strtof(e1 + 1, &e2);
+            if (e2 == e1 + 1 || (*e2 && *e2 != ',') || !(lo < hi)) return badsyntax("--passbands: every passband is lo:hi with lo < hi");
+            bands.push_back(lo); bands.push_back(hi);
+            if (!*e2) break;
+            q = e2 + 1;
+        }
+        argv += 2; argc -= 2;
+        if (argc > 2 && !strcmp(argv[2], "--lsb")) return badsyntax("--lsb and --passbands exclude each other");
+    }
     Fds ctl_fd(1, -1);
     if (argc > 3 && !strcmp(argv[2], "--ctl")) {
         ctl_fd[0] = open_spec(argv[3], O_RDONLY | O_NONBLOCK);
@@ -194,6 +214,7 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
     std::vector<float> rates;
     for (const char *q = argv[2]; *q;) { char *end = nullptr; const float v = strtof(q, &end); if (end == q) return badsyntax("shift_rate must be a number or a comma-separated list"); rates.push_back(v); q = *end == ',' ? end + 1 : end; if (*end && *end != ',') return badsyntax("shift_rate must be a number or a comma-separated list"); }
     if (rates.size() != 1 && (int)rates.size() != S) return badsyntax("as many shift rates as streams (or one for all)");
+    if (bands.size() > 2 && (int)bands.size() != 2 * S) return badsyntax("as many passbands as streams (or one for all)");
     // (fewer than 16 streams: the rate-per-stream object also when they share one rate -- its kernel fills all 16 columns of a tile with time segments of ONE stream,
     // the shared-rate kernel needs 16 streams to fill them)
     const bool per_stream = rates.size() > 1 || ctl_fd[0] >= 0 || (S < 16 && !getenv("CSDR_AMD_CLI_SHARED"));
@@ -210,7 +231,8 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
         std::vector<csdr_complexf> bp; int fft = 0;
         if (kind == BANK_SSB) {                                       // bandpass_fir_fft_cc 0 0.1 0.05 (the transform's size as csdr.c:1834-1836 chooses it)
             const int bl = csdr_amd_firdes_filter_len(0.05f);
-            bp.resize(bl); csdr_amd_firdes_bandpass_c(bp.data(), bl, lsb ? -0.1f : 0.f, lsb ? 0.f : 0.1f, CSDR_WINDOW_HAMMING);
+            const float lo = !bands.empty() ? bands[0] : lsb ? -0.1f : 0.f, hi = !bands.empty() ? bands[1] : lsb ? 0.f : 0.1f;
+            bp.resize(bl); csdr_amd_firdes_bandpass_c(bp.data(), bl, lo, hi, CSDR_WINDOW_HAMMING);
             fft = csdr_amd_next_pow2(bl); if (fft - bl < 200) fft *= 2;
         }
         a.reset(per_stream ? csdr_amd_amssb_create_rates(c, &ap, S, rates.data(), D, taps.data(), nt, bp.data(), (int)bp.size(), fft, T)
@@ -221,6 +243,7 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
     else if (per_stream) w.reset(csdr_amd_wfm_create_rates(c, S, rates.data(), D, taps.data(), nt, 5, 50e-6f, 48000, T));
     else w.reset(csdr_amd_wfm_create(c, S, shift, D, taps.data(), nt, 5, 50e-6f, 48000, T));
     if (!w && !n && !a) die("bank create");
+    if (bands.size() > 2) for (int k = 0; k < S; k++) MUST(csdr_amd_amssb_set_passband(a.get(), k, bands[2 * k], bands[2 * k + 1], CSDR_WINDOW_HAMMING));
     const size_t in_pitch = 2 * T, out_pitch = ((T / 50 + 4096 + 63) / 64) * 64;      // out_pitch: s16 samples
     // a short final block: whole 1024-sample chunks of the shortest stream (the chain objects take a ragged LAST block only)
     auto pass = [&](const uint8_t *d_in, uint8_t *d_out, size_t nproc) {
@@ -233,7 +256,13 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
     LineSplitter lines;
     auto retunes = [&]() {
         while (lines.feed(ctl_fd[0])) while (const char *line = lines.next()) {
-            int st = -1; float rv = 0;
+            int st = -1; float rv = 0, lo = 0, hi = 0;
+            if (kind == BANK_SSB && sscanf(line, "%d bp %g %g", &st, &lo, &hi) == 3) {
+                if (st < 0 || st >= S || !(lo < hi)) continue;
+                MUST(csdr_amd_amssb_set_passband(a.get(), st, lo, hi, CSDR_WINDOW_HAMMING));
+                fprintf(stderr, "csdr %s: stream %d passband reinitialized to %g %g\n", g_cmd, st, lo, hi);
+                continue;
+            }
             if (sscanf(line, "%d %g", &st, &rv) != 2 || st < 0 || st >= S) continue;
             MUST(amssb ? csdr_amd_amssb_set_rate(a.get(), st, rv) : nfm ? csdr_amd_nfm_set_rate(n.get(), st, rv) : csdr_amd_wfm_set_rate(w.get(), st, rv));
             fprintf(stderr, "csdr %s: stream %d reinitialized to %g\n", g_cmd, st, rv);

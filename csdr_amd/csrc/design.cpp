@@ -32,7 +32,8 @@ void csdr_amd_firdes_lowpass_f(float *taps, int length, float cutoff_rate, int w
     for (int k = 1; k <= mid; k++) {
         const float arg = 2 * PI_F * cutoff_rate * k;
         const float v = (float)((sin((double)arg) / k) * window_value(window, (float)k / mid));
-        taps[mid + k] = v; taps[mid - k] = v;
+        if (mid + k < length) taps[mid + k] = v;          // (an even length has no tap mid + mid; the reference writes one float past its buffer there)
+        taps[mid - k] = v;
     }
     float dc = 0;
     for (int k = 0; k < length; k++) dc += taps[k];

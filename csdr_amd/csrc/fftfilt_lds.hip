@@ -22,6 +22,10 @@
 #include "fft_butterflies.hpp"
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
+#include <stdint.h>
+#include <algorithm>
+#include <unordered_map>
 #include <vector>
 
 using namespace csdr_amd;
@@ -262,11 +266,15 @@ __device__ __forceinline__ void ffl_prefetch_ready(ffl_f32x2 (&nx)[16])
 // with 128: room for the next window's 32 input samples per thread in flight under this window's butterflies (PF), half as many waves at every barrier.  Counters of the
 // 1024-thread form (profiles/r6_fftfilt_pmc_issue.json): the vector ALU busy 46 % of the kernel's time, every wave parked (barrier / waitcnt) 52 % of its life -- one
 // workgroup per CU whose memory phase and butterflies do not overlap at all.
-template <int N, bool PF, int MINWG, bool HOIST, int LPT = 1>
+// ROWS (a taps spectrum per stream): hperm_all holds n_streams tables h_stride apart and a window of stream s reads table s.  s is uniform in the workgroup, so the
+// table's address stays in scalar registers.  HOIST cannot keep a table in registers across windows then: the centre phase fetches the window's own table (the
+// tables of the few streams a workgroup's consecutive windows belong to are served by the XCD's L2).  ROWS = false is the kernel as it was: h_stride is not read.
+template <int N, bool PF, int MINWG, bool HOIST, int LPT = 1, bool ROWS = false>
 __global__ __launch_bounds__(N / 16 / LPT, MINWG) void k_fftfilt_lds(const float2 *__restrict__ in, size_t in_pitch, const float2 *__restrict__ hist, int k1p, int m_new,
-                                                        int n_chunks, int n_windows, float2 *__restrict__ out, size_t out_pitch, const float2 *hperm,
-                                                        const float2 *__restrict__ g_tw1, const float2 *__restrict__ g_tws)
+                                                        int n_chunks, int n_windows, float2 *__restrict__ out, size_t out_pitch, const float2 *hperm_all,
+                                                        const float2 *__restrict__ g_tw1, const float2 *__restrict__ g_tws, size_t h_stride)
 {
+    const float2 *hperm = hperm_all;
     using G = FflGeom<N>;
     constexpr int TP = G::T / LPT;                                      // physical threads
     extern __shared__ float4 ffl_raw[];
@@ -289,6 +297,7 @@ __global__ __launch_bounds__(N / 16 / LPT, MINWG) void k_fftfilt_lds(const float
     }
     for (; w < w_end; w += stride) {
         const int s = w / n_chunks, c = w - s * n_chunks;
+        if (ROWS) hperm = hperm_all + (size_t)s * h_stride;
         if (!HOIST) {                                                   // keep the loop-invariant twiddle powers and taps spectrum OUT of registers (residency over reuse)
 #pragma unroll
             for (int h = 0; h < LPT; h++) asm volatile("" : "+v"(w1[h].x), "+v"(w1[h].y));
@@ -597,9 +606,11 @@ __device__ __forceinline__ void fw_pin(fw_pk2 (&v)[64])
 // Windows are dealt like the 256-thread kernel's: every XCD a contiguous range, consecutive waves consecutive windows (the taps - 1 samples two neighbours share come
 // from that XCD's L2).  Edges by the buffer range check: samples in front of the call's input come from the history (second descriptor, the stream's first window only),
 // samples behind its end read as zero, results outside [0, m_new) are dropped.  m_new is even (fw_launch), so a 16-byte access never straddles an edge.
+// ROWS: a taps spectrum per stream, h_stride apart; the window's stream is wave-uniform, so is the descriptor pass 1 builds from its table's address.
+template <bool ROWS>
 __global__ __launch_bounds__(64 * FW_WAVES, 2) void k_fftfilt_wave(const float2 *__restrict__ in, size_t in_pitch, const float2 *__restrict__ hist, int k1p, int m_new,
                                                                     int n_chunks, int n_windows, float2 *__restrict__ out, size_t out_pitch, const float2 *__restrict__ hw,
-                                                                    const float2 *__restrict__ g_tw)
+                                                                    const float2 *__restrict__ g_tw, size_t h_stride)
 {
     extern __shared__ float4 ffl_raw[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (wave-uniform: window, stream and descriptors stay in scalar registers)
@@ -645,7 +656,7 @@ __global__ __launch_bounds__(64 * FW_WAVES, 2) void k_fftfilt_wave(const float2 
         FW_T(1)
         fw_transpose(v, L, lane);
         FW_T(2)
-        fw_pass1_dev(v, hw, lane);
+        fw_pass1_dev(v, ROWS ? hw + (size_t)s * h_stride : hw, lane);
         FW_T(3)
         fw_pk_dft64<true>(v); fw_twiddle_lds<true>(v, tl);
         FW_T(4)
@@ -814,6 +825,8 @@ struct FftfiltLds {
     const char *last;                               // the window kernel the last call ran (a call's size and parity pick it)
     DevBuf<float2> d_hw, d_twl, d_tw2; bool wave, team;  // the tables of the wave-per-window kernel (4096-point windows) / of the team kernel (8192, 16384)
     int mode;                                       // CSDR_AMD_FFTFILT_LDS_MODE (A/B: 5 = the kernels of rounds 2-5, 6 = the wave kernel at every call size), read at create
+    int rows;                                       // 1: one taps spectrum for all streams; n_streams: d_hperm and d_hw hold a table of n points per stream, row s at s * n
+    bool per_stream;
 };
 
 // window size for a filter of taps_len taps: the smallest plan that keeps >= 3/4 of every window as output; 0 = none fits (the caller keeps its other paths)
@@ -831,32 +844,104 @@ void fftfilt_lds_destroy(FftfiltLds *p)
     delete p;
 }
 
-int fftfilt_lds_set_taps(FftfiltLds *p, hipStream_t st, const cf32 *taps, int taps_len)
+// row 0 of a table of n points to the rows 1 .. rows - 1 behind it
+static __global__ __launch_bounds__(256) void k_fftfilt_rows_fill(float2 *tab, int n, int rows)
 {
-    std::vector<float2> hperm, tw1, tws;
-    if (p->wave) {
-        std::vector<float2> hw, twl; fw_host_tables(taps, taps_len, hw, twl);
-        CSDR_HIP(hipStreamSynchronize(st));
-        CSDR_HIP(hipMemcpy(p->d_hw.get(), hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_twl.get(), twl.data(), sizeof(float2) * twl.size(), hipMemcpyHostToDevice));
-    }                                                                   // (and the 256-thread kernel's tables: it takes the calls with an odd sample count)
-    if (p->team) {
-        std::vector<float2> hw, t1, t2;
-        if (p->n == 8192) ft_host_tables<2>(taps, taps_len, hw, t1, t2); else ft_host_tables<4>(taps, taps_len, hw, t1, t2);
-        CSDR_HIP(hipStreamSynchronize(st));
-        CSDR_HIP(hipMemcpy(p->d_hw.get(), hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_twl.get(), t1.data(), sizeof(float2) * t1.size(), hipMemcpyHostToDevice));
-        CSDR_HIP(hipMemcpy(p->d_tw2.get(), t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float2 v = tab[i];
+    for (int r = 1 + blockIdx.y; r < rows; r += gridDim.y) tab[(size_t)r * n + i] = v;
+}
+
+// the spectrum tables of `rows` sets of taps (row r = taps + r * taps_len) in the kernels' orders, row r at r * n, and the twiddle tables (common to all rows);
+// every row by the functions that build a shared filter's tables.  A row whose taps equal an earlier row's (a bank's channels mostly share a few passbands) copies
+// that row's tables instead of transforming the taps again.
+static void lds_host_tables(const FftfiltLds *p, const cf32 *taps, int taps_len, int rows, std::vector<float2> &hperm, std::vector<float2> &hw, std::vector<float2> &tw1,
+                            std::vector<float2> &tws, std::vector<float2> &twl, std::vector<float2> &tw2)
+{
+    const size_t n = (size_t)p->n;
+    hperm.resize(n * rows); if (p->wave || p->team) hw.resize(n * rows);
+    std::vector<float2> h;
+    std::unordered_map<uint64_t, int> seen;                              // FNV-1a of a row's bytes -> the first row with it
+    for (int r = 0; r < rows; r++) {
+        const cf32 *t = taps + (size_t)r * taps_len;
+        if (rows > 1) {
+            uint64_t key = 1469598103934665603ull;
+            const unsigned char *b = reinterpret_cast<const unsigned char *>(t);
+            for (size_t i = 0; i < sizeof(cf32) * taps_len; i++) key = (key ^ b[i]) * 1099511628211ull;
+            const auto it = seen.find(key);
+            if (it != seen.end() && !memcmp(t, taps + (size_t)it->second * taps_len, sizeof(cf32) * taps_len)) {
+                std::copy(hperm.begin() + it->second * n, hperm.begin() + (it->second + 1) * n, hperm.begin() + r * n);
+                if (p->wave || p->team) std::copy(hw.begin() + it->second * n, hw.begin() + (it->second + 1) * n, hw.begin() + r * n);
+                continue;
+            }
+            if (it == seen.end()) seen[key] = r;
+        }
+        if (p->n == 4096) ffl_host_tables<4096>(t, taps_len, h, tw1, tws);
+        else if (p->n == 8192) ffl_host_tables<8192>(t, taps_len, h, tw1, tws);
+        else ffl_host_tables<16384>(t, taps_len, h, tw1, tws);
+        std::copy(h.begin(), h.end(), hperm.begin() + r * n);
+        if (p->wave) fw_host_tables(t, taps_len, h, twl);                // (the 256-thread kernel's tables as well: it takes the calls with an odd sample count)
+        else if (p->team) { if (p->n == 8192) ft_host_tables<2>(t, taps_len, h, twl, tw2); else ft_host_tables<4>(t, taps_len, h, twl, tw2); }
+        if (p->wave || p->team) std::copy(h.begin(), h.end(), hw.begin() + r * n);
     }
-    if (p->n == 4096) ffl_host_tables<4096>(taps, taps_len, hperm, tw1, tws);
-    else if (p->n == 8192) ffl_host_tables<8192>(taps, taps_len, hperm, tw1, tws);
-    else ffl_host_tables<16384>(taps, taps_len, hperm, tw1, tws);
+}
+
+// tables of `rows` consecutive streams from `first` on (rows = 1, first = 0 on a shared filter) to the device, the twiddle tables with them
+static int lds_upload(FftfiltLds *p, hipStream_t st, const cf32 *taps, int taps_len, int first, int rows)
+{
+    std::vector<float2> hperm, hw, tw1, tws, twl, tw2;
+    lds_host_tables(p, taps, taps_len, rows, hperm, hw, tw1, tws, twl, tw2);
     CSDR_HIP(hipStreamSynchronize(st));
-    CSDR_HIP(hipMemcpy(p->d_hperm.get(), hperm.data(), sizeof(float2) * hperm.size(), hipMemcpyHostToDevice));
+    const size_t off = (size_t)first * p->n;
+    if (p->wave || p->team) {
+        CSDR_HIP(hipMemcpy(p->d_hw.get() + off, hw.data(), sizeof(float2) * hw.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(p->d_twl.get(), twl.data(), sizeof(float2) * twl.size(), hipMemcpyHostToDevice));
+    }
+    if (p->team) CSDR_HIP(hipMemcpy(p->d_tw2.get(), tw2.data(), sizeof(float2) * tw2.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(p->d_hperm.get() + off, hperm.data(), sizeof(float2) * hperm.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(p->d_tw1.get(), tw1.data(), sizeof(float2) * tw1.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(p->d_tws.get(), tws.data(), sizeof(float2) * tws.size(), hipMemcpyHostToDevice));
     return 0;
 }
+
+static int lds_rows_fill(FftfiltLds *p, hipStream_t st)
+{
+    if (p->rows < 2) return 0;
+    const dim3 grid(cdiv(p->n, 256), (unsigned)std::min(p->rows - 1, 1024));
+    hipLaunchKernelGGL(k_fftfilt_rows_fill, grid, dim3(256), 0, st, p->d_hperm.get(), p->n, p->rows); CSDR_LAUNCH_CHECK();
+    if (p->wave || p->team) { hipLaunchKernelGGL(k_fftfilt_rows_fill, grid, dim3(256), 0, st, p->d_hw.get(), p->n, p->rows); CSDR_LAUNCH_CHECK(); }
+    return 0;
+}
+
+// one set of taps for every stream (on a per-stream filter: every row)
+int fftfilt_lds_set_taps(FftfiltLds *p, hipStream_t st, const cf32 *taps, int taps_len)
+{
+    const int rc = lds_upload(p, st, taps, taps_len, 0, 1);
+    return rc ? rc : lds_rows_fill(p, st);
+}
+
+// One stream's taps.  The first call on a shared filter makes room for a table per stream and fills every row with the current one, device to device; the history
+// (input samples, not taps) stays as it is.  Nothing of the object changes when an allocation fails.
+int fftfilt_lds_set_stream_taps(FftfiltLds *p, hipStream_t st, int stream, const cf32 *taps, int taps_len)
+{
+    if (!p->per_stream) {
+        const size_t bytes = sizeof(float2) * (size_t)p->n * p->n_streams;
+        DevBuf<float2> hperm, hw;
+        hipError_t e = dev_alloc(hperm, bytes);
+        if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(hw, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail_msg(-2, "fftfilt: out of device memory for %d streams' taps spectra", p->n_streams); }
+        CSDR_HIP(hipStreamSynchronize(st));
+        CSDR_HIP(hipMemcpy(hperm.get(), p->d_hperm.get(), sizeof(float2) * p->n, hipMemcpyDeviceToDevice));
+        if (hw) CSDR_HIP(hipMemcpy(hw.get(), p->d_hw.get(), sizeof(float2) * p->n, hipMemcpyDeviceToDevice));
+        p->d_hperm.swap(hperm); if (hw) p->d_hw.swap(hw);
+        p->per_stream = true; p->rows = p->n_streams;
+        const int rc = lds_rows_fill(p, st); if (rc) return rc;
+    }
+    return lds_upload(p, st, taps, taps_len, stream, 1);
+}
+
+int fftfilt_lds_per_stream(const FftfiltLds *p) { return p->per_stream; }
 
 int fftfilt_lds_reset(FftfiltLds *p, hipStream_t st)
 {
@@ -866,34 +951,35 @@ int fftfilt_lds_reset(FftfiltLds *p, hipStream_t st)
     return 0;
 }
 
-FftfiltLds *fftfilt_lds_create(hipStream_t st, int n, const cf32 *taps, int taps_len, int n_streams)
+// per_stream: taps holds n_streams rows of taps_len, one upload for all of them
+FftfiltLds *fftfilt_lds_create(hipStream_t st, int n, const cf32 *taps, int taps_len, int n_streams, bool per_stream)
 {
     std::unique_ptr<FftfiltLds> p(new FftfiltLds());
     p->n = n; p->taps_len = taps_len; p->k1p = (taps_len - 1 + 15) & ~15; p->n_streams = n_streams; p->flip = 0;
     p->mode = getenv("CSDR_AMD_FFTFILT_LDS_MODE") ? atoi(getenv("CSDR_AMD_FFTFILT_LDS_MODE")) : 0;
-    p->last = nullptr;
+    p->last = nullptr; p->per_stream = per_stream; p->rows = per_stream ? n_streams : 1;
     p->wave = n == 4096 && (p->mode == 0 || p->mode == 6);        // 4096-point windows: one wave per window; CSDR_AMD_FFTFILT_LDS_MODE=5 (A/B): the 256-thread kernel of rounds 2-5
     p->team = (n == 8192 || n == 16384) && (p->mode == 0 || p->mode == 6);      // a team of 2 / 4 waves per window; CSDR_AMD_FFTFILT_LDS_MODE=5: the 512-thread kernels of rounds 2-6
-    hipError_t e = dev_alloc(p->d_hperm, sizeof(float2) * n);
-    if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(p->d_hw, sizeof(float2) * n);
+    hipError_t e = dev_alloc(p->d_hperm, sizeof(float2) * n * p->rows);
+    if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(p->d_hw, sizeof(float2) * n * p->rows);
     if ((p->wave || p->team) && e == hipSuccess) e = dev_alloc(p->d_twl, sizeof(float2) * FW_TWE * (n / 64));
     if (p->team && e == hipSuccess) e = dev_alloc(p->d_tw2, sizeof(float2) * FW_TWE * 4);
     if (e == hipSuccess) e = dev_alloc(p->d_tw1, sizeof(float2) * (n / 16));
     if (e == hipSuccess) e = dev_alloc(p->d_tws, sizeof(float2) * (n / 16));
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = dev_alloc(p->d_hist[i], sizeof(float2) * (size_t)n_streams * (p->k1p + 16));
     if (e != hipSuccess) { fail(e, "hipMalloc(fftfilt_lds)", __FILE__, __LINE__); return nullptr; }
-    if (fftfilt_lds_set_taps(p.get(), st, taps, taps_len) || fftfilt_lds_reset(p.get(), st)) return nullptr;
+    if (lds_upload(p.get(), st, taps, taps_len, 0, p->rows) || fftfilt_lds_reset(p.get(), st)) return nullptr;
     return p.release();
 }
 
 const char *fftfilt_lds_kernel_name(const FftfiltLds *p) { return p->last ? p->last : p->wave ? "k_fftfilt_wave" : p->team ? (p->n == 8192 ? "k_fftfilt_team<2>" : "k_fftfilt_team<4>") : p->n == 4096 ? "k_fftfilt_lds<4096>" : p->n == 8192 ? "k_fftfilt_lds<8192>" : "k_fftfilt_lds<16384>"; }
 int fftfilt_lds_window(const FftfiltLds *p) { return p->n; }
 
-template <int N, bool PF, int MINWG, bool HOIST, int LPT = 1>
+template <int N, bool PF, int MINWG, bool HOIST, int LPT = 1, bool ROWS = false>
 static int ffl_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pitch, long m_new, cf32 *out, size_t out_pitch)
 {
     using G = FflGeom<N>;
-    int rc = lds_attr_once((const void *)k_fftfilt_lds<N, PF, MINWG, HOIST, LPT>, G::LDS_BYTES); if (rc) return rc;
+    int rc = lds_attr_once((const void *)k_fftfilt_lds<N, PF, MINWG, HOIST, LPT, ROWS>, G::LDS_BYTES); if (rc) return rc;
     const int V = N - p->k1p;
     const int n_chunks = (int)((m_new + V - 1) / V);
     const long n_windows = (long)n_chunks * p->n_streams;
@@ -903,17 +989,18 @@ static int ffl_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_p
     long grid = (long)current_device_cu_count() * (by_regs < by_lds ? by_regs : by_lds);
     if (grid > n_windows) grid = n_windows;
     grid = (grid + 7) & ~7L;
-    hipLaunchKernelGGL((k_fftfilt_lds<N, PF, MINWG, HOIST, LPT>), dim3((unsigned)grid), dim3(G::T / LPT), G::LDS_BYTES, st, (const float2 *)in, in_pitch,
+    hipLaunchKernelGGL((k_fftfilt_lds<N, PF, MINWG, HOIST, LPT, ROWS>), dim3((unsigned)grid), dim3(G::T / LPT), G::LDS_BYTES, st, (const float2 *)in, in_pitch,
                        (const float2 *)p->d_hist[p->flip].get(), p->k1p, (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hperm.get(),
-                       (const float2 *)p->d_tw1.get(), (const float2 *)p->d_tws.get());
+                       (const float2 *)p->d_tw1.get(), (const float2 *)p->d_tws.get(), ROWS ? (size_t)N : (size_t)0);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
 
+template <bool ROWS>
 static int fw_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pitch, long m_new, cf32 *out, size_t out_pitch)
 {
     constexpr size_t lds_bytes = (size_t)FW_WAVES * 64 * FW_LP * sizeof(float) + (size_t)FW_TWE * 64 * sizeof(float2);      // transposes + the workgroup's twiddle table
-    int rc = lds_attr_once((const void *)k_fftfilt_wave, lds_bytes); if (rc) return rc;
+    int rc = lds_attr_once((const void *)k_fftfilt_wave<ROWS>, lds_bytes); if (rc) return rc;
     const int V = FW_N - p->k1p;
     const int n_chunks = (int)((m_new + V - 1) / V);
     const long n_windows = (long)n_chunks * p->n_streams;
@@ -922,17 +1009,17 @@ static int fw_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pi
     const long need = (n_windows + FW_WAVES - 1) / FW_WAVES;
     if (grid > need) grid = need;
     grid = (grid + 7) & ~7L;
-    hipLaunchKernelGGL(k_fftfilt_wave, dim3((unsigned)grid), dim3(64 * FW_WAVES), lds_bytes, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
-                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get());
+    hipLaunchKernelGGL(k_fftfilt_wave<ROWS>, dim3((unsigned)grid), dim3(64 * FW_WAVES), lds_bytes, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
+                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get(), ROWS ? (size_t)FW_N : (size_t)0);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
 
-template <int M>
+template <int M, bool ROWS>
 static int ft_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pitch, long m_new, cf32 *out, size_t out_pitch)
 {
     using G = FtGeom<M>;
-    int rc = lds_attr_once((const void *)k_fftfilt_team<M>, G::LDS_BYTES); if (rc) return rc;
+    int rc = lds_attr_once((const void *)k_fftfilt_team<M, ROWS>, G::LDS_BYTES); if (rc) return rc;
     const int V = G::N - p->k1p;
     const int n_chunks = (int)((m_new + V - 1) / V);
     const long n_windows = (long)n_chunks * p->n_streams;
@@ -940,8 +1027,9 @@ static int ft_launch(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in_pi
     long grid = (long)current_device_cu_count() * (8 / M);             // eight waves per CU: two per SIMD at 256 registers
     if (grid > n_windows) grid = n_windows;
     grid = (grid + 7) & ~7L;
-    hipLaunchKernelGGL(k_fftfilt_team<M>, dim3((unsigned)grid), dim3(64 * M), G::LDS_BYTES, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
-                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get(), (const float2 *)p->d_tw2.get());
+    hipLaunchKernelGGL((k_fftfilt_team<M, ROWS>), dim3((unsigned)grid), dim3(64 * M), G::LDS_BYTES, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(), p->k1p,
+                       (int)m_new, n_chunks, (int)n_windows, (float2 *)out, out_pitch, (const float2 *)p->d_hw.get(), (const float2 *)p->d_twl.get(), (const float2 *)p->d_tw2.get(),
+                       ROWS ? (size_t)G::N : (size_t)0);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -956,14 +1044,17 @@ int fftfilt_lds_process(FftfiltLds *p, hipStream_t st, const cf32 *in, size_t in
     const bool wave_pays = p->wave && (p->mode == 6 || (m_new + (FW_N - p->k1p) - 1) / (FW_N - p->k1p) * p->n_streams >= 8192);
     const char *old_name = p->n == 4096 ? "k_fftfilt_lds<4096>" : p->n == 8192 ? "k_fftfilt_lds<8192>" : "k_fftfilt_lds<16384>";
     p->last = p->wave && !(m_new & 1) && wave_pays ? "k_fftfilt_wave" : p->team && !(m_new & 1) ? (p->n == 8192 ? "k_fftfilt_team<2>" : "k_fftfilt_team<4>") : old_name;
-    if (p->wave && !(m_new & 1) && wave_pays) rc = fw_launch(p, st, in, in_pitch, m_new, out, out_pitch);      // (16-byte accesses: an even sample count; odd ones take the 256-thread kernel)
-    else if (p->team && !(m_new & 1)) rc = p->n == 8192 ? ft_launch<2>(p, st, in, in_pitch, m_new, out, out_pitch) : ft_launch<4>(p, st, in, in_pitch, m_new, out, out_pitch);
+    const bool R = p->per_stream;                                       // a spectrum per stream: the ROWS instance of the same kernel
+#define FFL_GO(F, ...) (R ? F<__VA_ARGS__, true>(p, st, in, in_pitch, m_new, out, out_pitch) : F<__VA_ARGS__, false>(p, st, in, in_pitch, m_new, out, out_pitch))
+    if (p->wave && !(m_new & 1) && wave_pays) rc = R ? fw_launch<true>(p, st, in, in_pitch, m_new, out, out_pitch) : fw_launch<false>(p, st, in, in_pitch, m_new, out, out_pitch);      // (16-byte accesses: an even sample count; odd ones take the 256-thread kernel)
+    else if (p->team && !(m_new & 1)) rc = p->n == 8192 ? FFL_GO(ft_launch, 2) : FFL_GO(ft_launch, 4);
     // The kernels of rounds 2-5 (odd sample counts, small calls at 4096 points, CSDR_AMD_FFTFILT_LDS_MODE=5), each in the one form that measured best (profiles/r2_notes.md,
     // r6_notes.md; the prefetch / residency variants that lost -- modes 1-4 of earlier rounds -- are gone): 4096 points: four resident workgroups per CU, no register
     // prefetch; 8192: one 512-thread workgroup that prefetches the next window and keeps twiddle powers and spectrum in registers; 16384: 512 threads x two logical threads.
-    else if (p->n == 4096) rc = ffl_launch<4096, false, 4, false>(p, st, in, in_pitch, m_new, out, out_pitch);
-    else if (p->n == 8192) rc = ffl_launch<8192, true, 1, true>(p, st, in, in_pitch, m_new, out, out_pitch);
-    else rc = ffl_launch<16384, false, 1, false, 2>(p, st, in, in_pitch, m_new, out, out_pitch);
+    else if (p->n == 4096) rc = FFL_GO(ffl_launch, 4096, false, 4, false, 1);
+    else if (p->n == 8192) rc = FFL_GO(ffl_launch, 8192, true, 1, true, 1);
+    else rc = FFL_GO(ffl_launch, 16384, false, 1, false, 2);
+#undef FFL_GO
     if (rc) return rc;
     if (p->k1p > 0) {
         hipLaunchKernelGGL(k_fftfilt_hist, dim3(cdiv(p->k1p, 256), p->n_streams), dim3(256), 0, st, (const float2 *)in, in_pitch, (const float2 *)p->d_hist[p->flip].get(),

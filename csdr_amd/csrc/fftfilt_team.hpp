@@ -130,10 +130,11 @@ template <int ROWB, int H> __device__ __forceinline__ void ft_pass3_half(fw_pk2 
 
 // One team per window; windows dealt like the other kernels' (every XCD a contiguous range, consecutive teams consecutive windows).  Edges by the buffer range check.
 // tw1[e T + p]: the bases of W_N^(t k_a) for thread p (t = ft_logical(p)); tw2[e M + m]: those of W_T^(m k_c); hw: the spectrum in ft_h_index order.
-template <int M>
+// ROWS: hw holds a spectrum per stream, h_stride apart, and the descriptor of the window's own table is built per window (the stream is uniform in the team).
+template <int M, bool ROWS = false>
 __global__ __launch_bounds__(64 * M, 2) void k_fftfilt_team(const float2 *__restrict__ in, size_t in_pitch, const float2 *__restrict__ hist, int k1p, int m_new,
                                                             int n_chunks, int n_windows, float2 *__restrict__ out, size_t out_pitch, const float2 *__restrict__ hw,
-                                                            const float2 *__restrict__ g_tw1, const float2 *__restrict__ g_tw2)
+                                                            const float2 *__restrict__ g_tw1, const float2 *__restrict__ g_tw2, size_t h_stride)
 {
     using G = FtGeom<M>;
     constexpr int T = G::T, N = G::N, ROWB = G::ROWB;
@@ -157,8 +158,11 @@ __global__ __launch_bounds__(64 * M, 2) void k_fftfilt_team(const float2 *__rest
         const unsigned long long bx = (unsigned long long)(in + (size_t)s * in_pitch);
         return FwRows{ffl_i32x4{(int)(unsigned)bx, (int)((bx >> 32) & 0xffffu), m_new * 8, 0x00020000}, (c * V - k1p + n_lane) * 8};
     };
-    const unsigned long long bh = (unsigned long long)hw;
-    const ffl_i32x4 rh = {(int)(unsigned)bh, (int)((bh >> 32) & 0xffffu), N * 8, 0x00020000};
+    auto h_rows = [&](int s) {
+        const unsigned long long bh = (unsigned long long)(ROWS ? hw + (size_t)s * h_stride : hw);
+        return ffl_i32x4{(int)(unsigned)bh, (int)((bh >> 32) & 0xffffu), N * 8, 0x00020000};
+    };
+    const ffl_i32x4 rh0 = h_rows(0);
     ffl_f32x4 nx[32];
     {
         const FwRows x0 = rows_in(w);
@@ -183,6 +187,7 @@ __global__ __launch_bounds__(64 * M, 2) void k_fftfilt_team(const float2 *__rest
             fw_pk_twiddle<false>(v, tw);
         }
         ft_exchange<M, false>(v, xa, xb);
+        const ffl_i32x4 rh = ROWS ? h_rows(s) : rh0;
         ffl_f32x4 ha[4], hb[4];
         {
             fw_pk2 tw[FW_TWE];

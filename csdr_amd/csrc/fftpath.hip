@@ -313,7 +313,9 @@ int csdr_amd_scale_add(csdr_amd_ctx *c, csdr_complexf *io, size_t n, float scale
 namespace csdr_amd {
 struct FftfiltLds;
 int fftfilt_lds_pick(int taps_len);
-FftfiltLds *fftfilt_lds_create(hipStream_t st, int n, const cf32 *taps, int taps_len, int n_streams);
+FftfiltLds *fftfilt_lds_create(hipStream_t st, int n, const cf32 *taps, int taps_len, int n_streams, bool per_stream);
+int fftfilt_lds_set_stream_taps(FftfiltLds *p, hipStream_t st, int stream, const cf32 *taps, int taps_len);
+int fftfilt_lds_per_stream(const FftfiltLds *p);
 void fftfilt_lds_destroy(FftfiltLds *p);
 int fftfilt_lds_set_taps(FftfiltLds *p, hipStream_t st, const cf32 *taps, int taps_len);
 int fftfilt_lds_reset(FftfiltLds *p, hipStream_t st);
@@ -367,7 +369,7 @@ int csdr_amd_fftfilt_set_taps(csdr_amd_fftfilt *f, const csdr_complexf *host_tap
     return 0;
 }
 
-csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const csdr_complexf *host_taps, int taps_length, int n_streams, int max_blocks)
+static csdr_amd_fftfilt *fftfilt_create_impl(csdr_amd_ctx *ctx, int fft_size, const csdr_complexf *host_taps, int taps_length, int n_streams, int max_blocks, bool per_stream)
 {
     if (fft_size < 4 || (fft_size & (fft_size - 1)) || taps_length < 1 || taps_length > fft_size || n_streams < 1 || max_blocks < 1) {
         fail_msg(-3, "fftfilt: need power-of-two fft_size >= taps_length"); return nullptr; }
@@ -375,10 +377,11 @@ csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const
     f->ctx = ctx; f->fft = fft_size; f->taps_len = taps_length; f->inp = fft_size - taps_length + 1; f->ovl = taps_length - 1;
     f->n_streams = n_streams; f->max_blocks = max_blocks; f->flip = 0; f->plan_batch_n = 0;
     if (const int win = fftfilt_lds_pick(taps_length)) {
-        f->lds.reset(fftfilt_lds_create(ctx->stream, win, host_taps, taps_length, n_streams));
+        f->lds.reset(fftfilt_lds_create(ctx->stream, win, host_taps, taps_length, n_streams, per_stream));
         if (!f->lds) return nullptr;
         return f.release();
     }
+    if (per_stream) { fail_msg(-3, "fftfilt: taps per stream need the one-pass path (%d taps are served by the full-size transform)", taps_length); return nullptr; }
     const size_t tot = (size_t)n_streams * max_blocks * fft_size;
     hipError_t e = dev_alloc(f->d_taps_fft, sizeof(cf32) * fft_size);
     if (e == hipSuccess) e = dev_alloc(f->d_pad, sizeof(cf32) * tot);
@@ -398,6 +401,31 @@ csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const
     if (csdr_amd_fftfilt_set_taps(f.get(), host_taps, taps_length) || csdr_amd_fftfilt_reset(f.get())) return nullptr;
     return f.release();
 }
+
+csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const csdr_complexf *host_taps, int taps_length, int n_streams, int max_blocks)
+{
+    return fftfilt_create_impl(ctx, fft_size, host_taps, taps_length, n_streams, max_blocks, false);
+}
+
+/* host_taps: n_streams rows of taps_length, stream s filtered with row s */
+csdr_amd_fftfilt *csdr_amd_fftfilt_create_per_stream(csdr_amd_ctx *ctx, int fft_size, const csdr_complexf *host_taps, int taps_length, int n_streams, int max_blocks)
+{
+    if (!host_taps) { fail_msg(-3, "fftfilt: no taps"); return nullptr; }
+    return fftfilt_create_impl(ctx, fft_size, host_taps, taps_length, n_streams, max_blocks, true);
+}
+
+/* Stream `stream` alone gets new taps, from the next process on, over the history carried so far (what set_taps does for all streams).  The first call on a filter
+   created with shared taps gives every stream a table of its own, filled with the current one.  One-pass path only. */
+int csdr_amd_fftfilt_set_stream_taps(csdr_amd_fftfilt *f, int stream, const csdr_complexf *host_taps, int taps_length)
+{
+    if (!f || !host_taps) return fail_msg(-3, "fftfilt: null argument");
+    if (taps_length != f->taps_len) return fail_msg(-3, "fftfilt: taps_length changed (%d -> %d); create a new filter", f->taps_len, taps_length);
+    if (stream < 0 || stream >= f->n_streams) return fail_msg(-3, "fftfilt: stream %d out of range (0 .. %d)", stream, f->n_streams - 1);
+    if (!f->lds) return fail_msg(-3, "fftfilt: taps per stream need the one-pass path; this filter runs the full-size transform");
+    return fftfilt_lds_set_stream_taps(f->lds.get(), f->ctx->stream, stream, host_taps, taps_length);
+}
+
+int csdr_amd_fftfilt_per_stream(const csdr_amd_fftfilt *f) { return f && f->lds ? fftfilt_lds_per_stream(f->lds.get()) : 0; }
 
 void csdr_amd_fftfilt_destroy(csdr_amd_fftfilt *f)
 {

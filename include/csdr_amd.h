@@ -576,6 +576,18 @@ csdr_amd_fftfilt *csdr_amd_fftfilt_create(csdr_amd_ctx *ctx, int fft_size, const
                                           int taps_length, int n_streams, int max_blocks);
 void csdr_amd_fftfilt_destroy(csdr_amd_fftfilt *f);
 int  csdr_amd_fftfilt_set_taps(csdr_amd_fftfilt *f, const csdr_complexf *host_taps, int taps_length);
+/* A passband per stream (one-pass path only, i.e. <= 4096 taps and the path not switched off; the full-size transforms keep one taps spectrum and refuse with a
+ * negative status, staying usable).  The taps LENGTH, and with it input_size, the window and the carried history, is common to the object: streams differ in their
+ * taps, not in their number.
+ * create_per_stream: host_taps holds n_streams rows of taps_length; stream s is filtered with row s.
+ * set_stream_taps: new taps for one stream, from the next process on, over the input history carried so far (what set_taps does for all streams).  The first call on
+ * a filter created with shared taps gives every stream a spectrum table of its own (2 x window x 8 bytes per stream on the device), filled with the current one; the
+ * history is not touched.  set_taps on a per-stream filter sets every stream.  per_stream: 0 / 1.
+ * A wrong taps_length, a stream out of range or a filter on the full-size path: negative status, message in csdr_amd_last_error, the object unchanged. */
+csdr_amd_fftfilt *csdr_amd_fftfilt_create_per_stream(csdr_amd_ctx *ctx, int fft_size, const csdr_complexf *host_taps,
+                                                     int taps_length, int n_streams, int max_blocks);
+int  csdr_amd_fftfilt_set_stream_taps(csdr_amd_fftfilt *f, int stream, const csdr_complexf *host_taps, int taps_length);
+int  csdr_amd_fftfilt_per_stream(const csdr_amd_fftfilt *f);
 int  csdr_amd_fftfilt_input_size(const csdr_amd_fftfilt *f);
 /* Taps short enough for windows that fit a CU's LDS (<= 4096 taps) are served by ONE pass over HBM (fftfilt_lds.hip: overlap-save with 4096 / 8192 / 16384-point
  * transforms in LDS; same samples out, same framing at this interface): its kernel name and window size, or "" / 0 when the full-size transform path runs. */
@@ -911,7 +923,14 @@ csdr_amd_ddc *csdr_amd_nfm_front_end(csdr_amd_nfm *w);
  * create_cf32: the input is decimated complex baseband (the output of csdr_amd_fastddc_bank, csdr_amd_ddc_process, csdr_amd_fir_decimate_cc), in_pitch in complex
  * samples.  create / create_rates: the input is wideband u8 IQ per channel through an owned csdr_amd_ddc (one shift rate, or one per channel; ddc_taps: the real
  * decimation filter), in_pitch in bytes, n_in in complex samples with that object's rules; set_rate / get_rate forward to it, front_end returns it.
- * taps, taps_length, fft_size (SSB only; taps_length 0: no filter): host complex taps of an owned csdr_amd_fftfilt in front of realpart_cf, one passband per object.
+ * taps, taps_length, fft_size (SSB only; taps_length 0: no filter): host complex taps of an owned csdr_amd_fftfilt in front of realpart_cf, the passband of every
+ * channel until one is given its own.
+ * set_passband: channel's taps become firdes_bandpass_c(taps_length, low, high, window), as bandpass_fir_fft_cc designs them (the length is the object's: one
+ * transition bandwidth for the bank).  set_channel_taps: any taps of that length.  get_passband: the edges last set for the channel; NaN after set_channel_taps and
+ * before any set_passband (the object does not know what its creation taps pass).  All three need an SSB object with a filter (AM has none: negative status).
+ * A change lands at the first sample the owned filter has not consumed yet: the object holds back input short of one input_size = fft_size - taps_length + 1, and
+ * those samples, like all later ones, are filtered with the new taps (over the history of the old input, as a retuned bandpass_fir_fft_cc --fifo does).
+ * reset and reset_channel keep every channel's passband.
  * max_samples_per_call: the most n_in of a call.
  * process: in (device), n_in new samples per channel.  Carried per channel between calls: the state, the complex samples short of a whole block and the filter's
  * input short of one input_size.  Writes the whole blocks that became available to audio_s16 and, when it is not NULL, the float samples in front of agc_ff to
@@ -942,6 +961,9 @@ long long csdr_amd_amssb_max_out(const csdr_amd_amssb *p, long long n_in);
 int  csdr_amd_amssb_set_rate(csdr_amd_amssb *p, int channel, float shift_rate);
 float csdr_amd_amssb_get_rate(const csdr_amd_amssb *p, int channel);
 csdr_amd_ddc *csdr_amd_amssb_front_end(csdr_amd_amssb *p);
+int  csdr_amd_amssb_set_passband(csdr_amd_amssb *p, int channel, float low, float high, int window);
+int  csdr_amd_amssb_set_channel_taps(csdr_amd_amssb *p, int channel, const csdr_complexf *taps, int taps_length);
+int  csdr_amd_amssb_get_passband(const csdr_amd_amssb *p, int channel, float *low, float *high);
 int  csdr_amd_amssb_reset(csdr_amd_amssb *p);
 int  csdr_amd_amssb_reset_channel(csdr_amd_amssb *p, int channel);
 int  csdr_amd_amssb_get_channel(csdr_amd_amssb *p, int channel, csdr_amd_amssb_chan *out);
