@@ -152,6 +152,22 @@ def lib():
     L.csdr_amd_differential_decoder_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, vp]
     L.csdr_amd_duplicate_samples_ntimes_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i, i]
     L.csdr_amd_debug_psk31tx_walk.restype = ll; L.csdr_amd_debug_psk31tx_walk.argtypes = [i, i, i, i, vp, ll, vp, i, vp, vp]
+    L.csdr_amd_pulsetx_create.restype = vp; L.csdr_amd_pulsetx_create.argtypes = [vp, i, i, i, vp, i, i, i]
+    L.csdr_amd_pulsetx_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
+    L.csdr_amd_pulsetx_max_out.restype = ll; L.csdr_amd_pulsetx_max_out.argtypes = [vp, ll]
+    L.csdr_amd_pulsetx_reset.argtypes = [vp]
+    L.csdr_amd_pulsetx_force_generic.argtypes = [vp, i]
+    L.csdr_amd_pulsetx_kernel_name.restype = C.c_char_p; L.csdr_amd_pulsetx_kernel_name.argtypes = [vp]
+    L.csdr_amd_pulsetx_tile.argtypes = [vp]
+    L.csdr_amd_pulsetx_destroy.argtypes = [vp]; L.csdr_amd_pulsetx_destroy.restype = None
+    L.csdr_amd_debug_pulsetx_walk.restype = ll; L.csdr_amd_debug_pulsetx_walk.argtypes = [i, i, vp, i, i, i, vp, ll, vp, i, vp]
+    L.csdr_amd_generic_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
+    L.csdr_amd_plain_interpolate_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
+    L.csdr_amd_pack_bits_1to8_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
+    L.csdr_amd_pack_bits_8to1_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
+    L.csdr_amd_apply_real_fir_cc.argtypes = [vp, vp, vp, i, i, sz, sz, vp, i]
+    L.csdr_amd_firdes_rrc_f.argtypes = [vp, i, i, fl]
+    L.csdr_amd_firdes_cosine_f.argtypes = [vp, i, i]
     L.csdr_amd_rtty_create.restype = vp; L.csdr_amd_rtty_create.argtypes = [vp, vp, i, i, i]
     L.csdr_amd_rtty_process.argtypes = [vp, vp, ll, sz, vp, sz, vp]
     L.csdr_amd_rtty_max_out.restype = ll; L.csdr_amd_rtty_max_out.argtypes = [vp, ll]
@@ -824,6 +840,94 @@ class Psk31Tx(_Handle, _MaxOut, _ChannelState):
             dn = self.ctx.upload(ic)
         res = [r[0] for r in _counted_calls(self, x, calls, d_in_counts=dn.ptr if dn else None)]
         return res[0] if squeeze else res
+
+
+PULSETX_STAGES = {"mod": 0, "shape": 1}
+
+
+def _pulsetx_stage(s):
+    return PULSETX_STAGES[s] if isinstance(s, str) else int(s)
+
+
+def firdes_rrc_f(taps_length, samples_per_symbol, beta):
+    """firdes_rrc_f (libcsdr.c:2482-2497, csdr_amd_firdes_rrc_f): root raised cosine taps, taps_length odd -> float32"""
+    t = np.zeros(taps_length, f32)
+    if lib().csdr_amd_firdes_rrc_f(_hp(t), int(taps_length), int(samples_per_symbol), float(beta)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return t
+
+
+def firdes_cosine_f(samples_per_symbol, taps_length=None):
+    """firdes_cosine_f (libcsdr.c:2473-2480, csdr_amd_firdes_cosine_f): raised cosine pulse of 2 samples_per_symbol + 1 taps (the end taps 0) -> float32"""
+    n = 2 * int(samples_per_symbol) + 1 if taps_length is None else int(taps_length)
+    t = np.zeros(max(n, 1), f32)
+    if lib().csdr_amd_firdes_cosine_f(_hp(t), n, int(samples_per_symbol)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return t
+
+
+def pulsetx_debug_walk(x, taps, n_psk=4, interpolation=8, first="mod", last="shape", cuts=()):
+    """CPU run of the pulse-shaping transmit object's definition for one channel (csdr_amd_debug_pulsetx_walk): x cut into calls of `cuts` items and the
+    rest -> the outputs of all calls, concatenated"""
+    f, l = _pulsetx_stage(first), _pulsetx_stage(last)
+    x = np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, c64 if f == 1 else np.uint8)
+    t = None if taps is None else np.ascontiguousarray(taps, f32)
+    out = np.zeros(x.size * (max(int(interpolation), 1) if l == 1 else 1) + 16, c64)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_pulsetx_walk(n_psk, interpolation, _hp(t) if t is not None else None, t.size if t is not None else 0, f, l, _hp(x), x.size,
+                                          _hp(cu) if cu.size else None, cu.size, _hp(out))
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out[:k]
+
+
+class PulseTx(_Handle, _MaxOut):
+    """csdr_amd_pulsetx: psk_modulator_u8_c n_psk | plain_interpolate_cc interpolation | pulse_shaping_filter_cc (taps) for n_channels channels, stages
+    first..last ("mod", "shape"); the symbols behind the last call are kept on the device."""
+
+    def __init__(self, ctx, n_channels=1, n_psk=4, interpolation=8, taps=None, first="mod", last="shape"):
+        self.n_channels, self.n_psk, self.interpolation = n_channels, n_psk, interpolation
+        self.first, self.last = _pulsetx_stage(first), _pulsetx_stage(last)
+        self.in_dtype = c64 if self.first == 1 else np.uint8
+        t = None if taps is None else np.ascontiguousarray(taps, f32)
+        _Handle.__init__(self, ctx, "pulsetx", ctx.L.csdr_amd_pulsetx_create(ctx.h, n_channels, n_psk, interpolation, _hp(t) if t is not None else None,
+                                                                             t.size if t is not None else 0, self.first, self.last))
+
+    def tile(self):
+        """symbols per tile of k_pulsetx_poly"""
+        return int(self._fn("tile")(self.h))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch):
+        """device pointers -> the outputs per channel of this call.  Asynchronous."""
+        k = C.c_longlong(0)
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, C.byref(k))
+        return k.value
+
+    def process(self, x, calls=None):
+        """x: [n_channels, n] (or [n]) host symbols (bytes, or complex64 from "shape"); calls: per-call symbol counts (default one call) ->
+        [n_channels, n_out] complex64, the outputs of all calls concatenated"""
+        x = np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, self.in_dtype)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        if sum(calls) != n or min(calls, default=0) < 0:
+            raise ValueError("calls do not add up to the %d symbols" % n)
+        isz = x.dtype.itemsize
+        di = self.ctx.upload(x) if n else self.ctx.alloc(256)
+        pitch = max(self.max_out(max(calls, default=0)), 1)
+        do = self.ctx.alloc(8 * pitch * s + 256)
+        parts, pos = [], 0
+        for m in calls:
+            k = self.process_dev(di.at(pos * isz), m, max(n, 1), do.ptr, pitch)
+            if k:
+                parts.append(self.ctx.download(do, c64, pitch * s).reshape(s, pitch)[:, :k].copy())
+            pos += m
+        y = np.concatenate(parts, axis=1) if parts else np.zeros((s, 0), c64)
+        return y[0] if squeeze else y
 
 
 class RttyParams(C.Structure):
@@ -1822,6 +1926,49 @@ class Context:
         self.check(self.L.csdr_amd_duplicate_samples_ntimes_u8_u8(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(m, 1), sample_size_bytes, ntimes),
                    "duplicate_samples_ntimes_u8_u8")
         y = self.download(do, np.uint8, max(m, 1) * s).reshape(s, max(m, 1))[:, :m]
+        return y[0].copy() if squeeze else y.copy()
+
+    # ---- pulse-shaped symbol modem (modem.hip)
+    def pulse_tx(self, n_channels=1, n_psk=4, interpolation=8, taps=None, first="mod", last="shape"):
+        """A batched pulse-shaping transmit object (PulseTx)"""
+        return PulseTx(self, n_channels, n_psk, interpolation, taps, first, last)
+
+    def _flat_rows(self, fn, name, x, dtype_in, dtype_out, n_out, *extra):
+        x = np.ascontiguousarray(x, dtype_in)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        m = n_out(n)
+        di = self.upload(x) if n else self.alloc(256)
+        do = self.alloc(np.dtype(dtype_out).itemsize * max(m, 1) * s + 256)
+        self.check(fn(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(m, 1), *extra), name)
+        y = self.download(do, dtype_out, max(m, 1) * s).reshape(s, max(m, 1))[:, :m]
+        return y[0].copy() if squeeze else y.copy()
+
+    def generic_slicer_f_u8(self, x, n_symbols):
+        """generic_slicer_f_u8 (libcsdr.c:1731-1765) on [n_streams, n] (or [n]) floats; NaN gives 0"""
+        return self._flat_rows(self.L.csdr_amd_generic_slicer_f_u8, "generic_slicer_f_u8", x, f32, np.uint8, lambda n: n, int(n_symbols))
+
+    def plain_interpolate_cc(self, x, interpolation):
+        """plain_interpolate_cc (libcsdr.c:2499-2506) on [n_streams, n] (or [n]) complex samples -> n * interpolation each"""
+        return self._flat_rows(self.L.csdr_amd_plain_interpolate_cc, "plain_interpolate_cc", x, c64, c64, lambda n: n * max(int(interpolation), 0), int(interpolation))
+
+    def pack_bits_1to8(self, x):
+        """pack_bits_1to8_u8_u8 (libcsdr.c:1810-1815) on [n_streams, n] (or [n]) bytes -> 8 n bytes each, LSB first"""
+        return self._flat_rows(self.L.csdr_amd_pack_bits_1to8_u8_u8, "pack_bits_1to8_u8_u8", x, np.uint8, np.uint8, lambda n: 8 * n)
+
+    def pack_bits_8to1(self, x):
+        """pack_bits_8to1_u8_u8 (libcsdr.c:1818-1827) on every group of eight of [n_streams, n] (or [n]) bytes, n a multiple of 8 -> n / 8 bytes each, MSB first"""
+        return self._flat_rows(self.L.csdr_amd_pack_bits_8to1_u8_u8, "pack_bits_8to1_u8_u8", x, np.uint8, np.uint8, lambda n: n // 8)
+
+    def apply_real_fir_cc(self, x, taps):
+        """apply_real_fir_cc (libcsdr.c:2276-2291) on [n_streams, n] (or [n]) complex samples -> n - len(taps) + 1 each"""
+        x2, squeeze = self._2d(x, c64); taps = np.ascontiguousarray(taps, f32)
+        s, n = x2.shape
+        di = self.upload(x2) if n else self.alloc(256); dt = self.upload(taps); do = self.alloc(8 * s * max(n, 1) + 64)
+        no = self.check(self.L.csdr_amd_apply_real_fir_cc(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(n, 1), dt.ptr, taps.size), "apply_real_fir_cc")
+        y = self.download(do, c64, s * max(n, 1)).reshape(s, max(n, 1))[:, :no]
         return y[0].copy() if squeeze else y.copy()
 
     # ---- RTTY receive chain (rtty.hip)

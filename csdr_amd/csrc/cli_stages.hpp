@@ -307,6 +307,103 @@ struct BinarySlicer : Stage {   // binary_slicer_f_u8 csdr.c:2475-2487
     { *cons = n; MUST(csdr_amd_binary_slicer_f_u8(c, (const float *)i, (uint8_t *)o, 1, (long long)n, n, n)); return (long)n; }
 };
 
+// ---- the pulse-shaped symbol modem (modem.hip)
+// pulse_shaping_filter_cc / firdes_pulse_shaping_filter_f (csdr.c:3159-3199): (RRC <samples_per_symbol> <num_taps> <beta> | COSINE <samples_per_symbol>), the checks in
+// the reference's order; the designed taps into *taps.  false (message given) on bad syntax.
+bool parse_pulse_filter(int argc, char **argv, std::vector<float> *taps)
+{
+    if (argc <= 2) { badsyntax("required parameter <pulse_shaping_filter_type> is missing."); return false; }
+    const bool cosine = !strcmp(argv[2], "COSINE");                 // matched_filter_get_type_from_string: anything else is RRC
+    int samples_per_symbol = 0, num_taps = 0; float beta = 0;
+    if (argc <= 3) { badsyntax("required parameter <samples_per_symbol> is missing."); return false; }
+    sscanf(argv[3], "%d", &samples_per_symbol);
+    if (!cosine) {
+        if (argc <= 4) { badsyntax("required parameter <num_taps> is missing."); return false; }
+        sscanf(argv[4], "%d", &num_taps);
+        if (argc <= 5) { badsyntax("required parameter <beta> is missing."); return false; }
+        sscanf(argv[5], "%f", &beta);
+    } else num_taps = 2 * samples_per_symbol + 1;
+    if (samples_per_symbol <= 0) { badsyntax("samples_per_symbol should be >0"); return false; }
+    if (num_taps <= 0 || (!cosine && num_taps % 2 == 0)) { badsyntax("num_taps should be odd (and >0)"); return false; }
+    taps->assign(num_taps, 0.f);
+    const int rc = cosine ? csdr_amd_firdes_cosine_f(taps->data(), num_taps, samples_per_symbol) : csdr_amd_firdes_rrc_f(taps->data(), num_taps, samples_per_symbol, beta);
+    if (rc < 0) { badsyntax(csdr_amd_last_error()); return false; }
+    return true;
+}
+bool parse_plain_interpolate(int argc, char **argv, int *interpolation)
+{   // csdr.c:3238-3243
+    if (argc <= 2) { badsyntax("required parameter <interpolation> is missing."); return false; }
+    *interpolation = 0; sscanf(argv[2], "%d", interpolation);
+    if (*interpolation <= 0) { badsyntax("interpolation should be >0"); return false; }
+    return true;
+}
+
+struct PulseTx : Stage {   // [psk_modulator_u8_c n_psk |] plain_interpolate_cc I | pulse_shaping_filter_cc ...: one object for the run (`chain` fuses it); the symbols
+                          // behind the last call live on the device.  The stream is the filter applied to the whole zero-stuffed stream.
+    Owned<csdr_amd_pulsetx, csdr_amd_pulsetx_destroy> p; int I;
+    PulseTx(csdr_amd_ctx *c, int n_psk, int interpolation, const std::vector<float> &taps, int f) : I(interpolation)
+    {
+        p.reset(csdr_amd_pulsetx_create(c, 1, n_psk, interpolation, taps.data(), (int)taps.size(), f, CSDR_AMD_PULSETX_SHAPE)); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = f == CSDR_AMD_PULSETX_SHAPE ? 8 : 1; out_elem = 8;
+        max_block = std::max<size_t>(1024, ((size_t)64 << 20) / ((size_t)interpolation * out_elem) / 1024 * 1024);       // a pass writes at most 64 MiB
+        fprintf(stderr, "csdr pulse_tx: one fused pulse-shaping transmit object\n");
+    }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_pulsetx_max_out(p.get(), (long long)n) + 16; }
+    int next_bufsize(int b) override { return b * I; }               // csdr.c:3243
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        long long k = 0;
+        MUST(csdr_amd_pulsetx_process(p.get(), i, (long long)n, n, o, cap, &k));
+        return (long)k;
+    }
+};
+struct PlainInterpolate : Stage {   // plain_interpolate_cc csdr.c:3238-3254
+    int I;
+    PlainInterpolate(int interpolation) : I(interpolation)
+    { in_elem = 8; out_elem = 8; max_block = std::max<size_t>(1024, ((size_t)64 << 20) / ((size_t)interpolation * 8) / 1024 * 1024); }
+    size_t out_capacity(size_t n) override { return n * (size_t)I + 16; }
+    int next_bufsize(int b) override { return b * I; }               // csdr.c:3243
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    { *cons = n; MUST(csdr_amd_plain_interpolate_cc(c, (const csdr_complexf *)i, (csdr_complexf *)o, 1, (long long)n, n, cap, I)); return (long)(n * I); }
+};
+struct PulseFilter : Stage {   // pulse_shaping_filter_cc csdr.c:3159-3219: apply_real_fir_cc over the stream, the unconsumed tail presented again
+    int ntaps; CtxBuf<float> d_taps;
+    PulseFilter(csdr_amd_ctx *c, const std::vector<float> &taps) : ntaps((int)taps.size())
+    {
+        in_elem = 8; out_elem = 8; min_block = (size_t)ntaps;
+        d_taps = ctx_alloc<float>(c, 4 * taps.size(), "malloc");
+        MUST(csdr_amd_h2d(c, d_taps.get(), taps.data(), 4 * taps.size()));
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        const long no = csdr_amd_apply_real_fir_cc(c, (const csdr_complexf *)i, (csdr_complexf *)o, 1, (int)n, n, cap, d_taps.get(), ntaps);
+        MUST(no);
+        *cons = (size_t)no;                                        // the rest is re-presented (csdr.c:3216-3217)
+        return no;
+    }
+};
+struct GenericSlicer : Stage {   // generic_slicer_f_u8 csdr.c:3221-3236
+    int n_symbols;
+    GenericSlicer(int n) : n_symbols(n) { in_elem = 4; out_elem = 1; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    { *cons = n; MUST(csdr_amd_generic_slicer_f_u8(c, (const float *)i, (uint8_t *)o, 1, (long long)n, n, n, n_symbols)); return (long)n; }
+};
+struct PackBits : Stage {   // pack_bits_1to8_u8_u8 csdr.c:2749-2763 (a byte -> 8 bytes) / pack_bits_8to1_u8_u8 csdr.c:2765-2778 (8 bytes -> a byte; a partial group at EOF is dropped)
+    bool expand;
+    PackBits(bool e) : expand(e)
+    { in_elem = 1; out_elem = 1; if (!e) { granule = 8; flush_partial = false; } else max_block = (size_t)8 << 20; }
+    size_t out_capacity(size_t n) override { return (expand ? 8 * n : n / 8) + 16; }
+    int next_bufsize(int b) override { return expand ? b * 8 : 1; }  // csdr.c:2752, 2768
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        if (expand) { *cons = n; MUST(csdr_amd_pack_bits_1to8_u8_u8(c, (const uint8_t *)i, (uint8_t *)o, 1, (long long)n, n, cap)); return (long)(8 * n); }
+        const size_t m = n / 8 * 8; *cons = m;
+        if (m) MUST(csdr_amd_pack_bits_8to1_u8_u8(c, (const uint8_t *)i, (uint8_t *)o, 1, (long long)m, m, cap));
+        return (long)(m / 8);
+    }
+};
+
 struct Squelch : Stage {   // squelch_and_smeter_cc csdr.c:2192-2243: blocks of the_bufsize samples counted from the start of the stream, however many a pass moves;
                           // a new level (control channel, polled in front of every pass) applies from the next block; block k's power goes to the out fifo as "%g\n"
                           // when k mod (report_every_nth + 2) == report_every_nth + 1, written non-blocking as the reference does
@@ -959,6 +1056,44 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         }
         g_cmd = keep;
     }
+    if (!strcmp(argv[1], "pulse_tx")) {                                             // `chain`'s fused pulse-shaping run: argv[2..] are its commands, one per argument
+        int n_psk = 2, interpolation = 1, first = CSDR_AMD_PULSETX_SHAPE; std::vector<float> taps;
+        for (int k = 2; k < argc; k++) {
+            std::vector<std::string> words = split_chain(argv[k])[0]; std::vector<char *> av = argv_of(words);
+            g_cmd = av[1];
+            if (!strcmp(av[1], "psk_modulator_u8_c")) { int unused = 1; if (parse_psk31tx((int)av.size(), av.data(), &n_psk, &unused) < 0) return nullptr; first = CSDR_AMD_PULSETX_MOD; }
+            else if (!strcmp(av[1], "plain_interpolate_cc")) { if (!parse_plain_interpolate((int)av.size(), av.data(), &interpolation)) return nullptr; }
+            else if (!parse_pulse_filter((int)av.size(), av.data(), &taps)) return nullptr;
+        }
+        g_cmd = argv[1];
+        if (taps.empty()) { badsyntax("pulse_tx: the run ends with pulse_shaping_filter_cc"); return nullptr; }
+        return new PulseTx(c, n_psk, interpolation, taps, first);
+    }
+    if (!strcmp(argv[1], "plain_interpolate_cc")) {
+        const char *keep = g_cmd; g_cmd = argv[1];
+        int interpolation = 0;
+        if (!parse_plain_interpolate(argc, argv, &interpolation)) return nullptr;
+        g_cmd = keep;
+        return new PlainInterpolate(interpolation);
+    }
+    if (!strcmp(argv[1], "pulse_shaping_filter_cc")) {
+        const char *keep = g_cmd; g_cmd = argv[1];
+        std::vector<float> taps;
+        if (!parse_pulse_filter(argc, argv, &taps)) return nullptr;
+        g_cmd = keep;
+        return new PulseFilter(c, taps);
+    }
+    if (!strcmp(argv[1], "generic_slicer_f_u8")) {                                  // csdr.c:3221-3225
+        const char *keep = g_cmd; g_cmd = argv[1];
+        int n_symbols = 0;
+        if (argc <= 2) { badsyntax("required parameter <n_symbols> is missing."); return nullptr; }
+        sscanf(argv[2], "%d", &n_symbols);
+        if (n_symbols < 2 || n_symbols > 256) { badsyntax("n_symbols should be between 2 and 256"); return nullptr; }
+        g_cmd = keep;
+        return new GenericSlicer(n_symbols);
+    }
+    if (!strcmp(argv[1], "pack_bits_1to8_u8_u8")) return new PackBits(true);
+    if (!strcmp(argv[1], "pack_bits_8to1_u8_u8")) return new PackBits(false);
     g_cmd = argv[1];
     const std::string cmd = argv[1];
     const bool has_ctl = ctl && ctl->open_from(argc, argv);

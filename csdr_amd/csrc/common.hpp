@@ -100,6 +100,7 @@ int fastagc_ff_s16(struct ::csdr_amd_ctx *c, const float *in, float *out, int16_
                    size_t in_pitch, size_t out_pitch, size_t s16_pitch, float reference, float *state_io, bool have_peaks = false);
 float *fastagc_peaks_buffer(struct ::csdr_amd_ctx *c, int n_streams, int n_blocks);      // [n_streams][n_blocks + 2]; entries 2.. = peak |x| of the call's new blocks
 void set_audio_last_path(const char *path);                          // audio.hip: what csdr_amd_audio_last_path() reports for the calling thread
+void firdes_rrc_below(float *taps, int taps_length, int samples_per_symbol, float beta);   // modem.hip: firdes_rrc_f for any taps_length >= 1, writing indexes < taps_length only
 struct ShiftAhead;                                                   // shift.hip
 struct ShiftAheadDel { void operator()(ShiftAhead *a) const; };
 

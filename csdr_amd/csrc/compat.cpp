@@ -5,6 +5,7 @@
 // to state bookkeeping, setup-time table generation and format plumbing around the copies.
 #include "common.hpp"
 #include "carrier_dev.hpp"
+#include "modem_dev.hpp"
 #include "../../include/libcsdr_amd_compat.h"
 #include <math.h>
 #include <stdio.h>
@@ -517,6 +518,57 @@ complexf psk31_interpolate_sine_cc(complexf *in, complexf *out, int n, int inter
     fetch(out, dout, mo);
     return in[n - 1];
 }
+
+// ------------------------------------------------------------------ pulse-shaped symbol modem (modem.hip)
+int firdes_rrc_f(float *taps, int taps_length, int samples_per_symbol, float beta)
+{   // libcsdr.c:2482-2497, on the host; an even taps_length is designed as the reference does, without its write to taps[taps_length]
+    if (taps_length >= 1) firdes_rrc_below(taps, taps_length, samples_per_symbol, beta);
+    return 0;
+}
+int firdes_cosine_f(float *taps, int taps_length, int samples_per_symbol)
+{   // libcsdr.c:2473-2480, on the host
+    (void)csdr_amd_firdes_cosine_f(taps, taps_length, samples_per_symbol);
+    return 0;
+}
+matched_filter_type_t matched_filter_get_type_from_string(char *input)
+{   // libcsdr.c:2508-2516
+    if (!strcmp("RRC", input)) return MATCHED_FILTER_RRC;
+    if (!strcmp("COSINE", input)) return MATCHED_FILTER_COSINE;
+    return MATCHED_FILTER_DEFAULT;
+}
+int apply_real_fir_cc(complexf *in, complexf *out, int n, float *taps, int taps_length)
+{   // libcsdr.c:2276-2291
+    if (taps_length < 1 || n < taps_length) return 0;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); float *dt = stage_in<float>(6, taps, taps_length);
+    cf32 *dout = stage_out<cf32>(5, n - taps_length + 1);
+    const int produced = csdr_amd_apply_real_fir_cc(ctx(), din, dout, 1, n, n, n - taps_length + 1, dt, taps_length);
+    if (produced < 0) die("apply_real_fir_cc", produced);
+    fetch((cf32 *)out, dout, produced);
+    return produced;
+}
+void generic_slicer_f_u8(float *input, unsigned char *output, int input_size, int n_symbols)
+{   // libcsdr.c:1731-1765
+    if (input_size <= 0 || n_symbols < 2 || n_symbols > 256) return;
+    float *din = stage_in<float>(4, input, input_size); unsigned char *dout = stage_out<unsigned char>(5, input_size);
+    MUST(csdr_amd_generic_slicer_f_u8(ctx(), din, dout, 1, input_size, input_size, input_size, n_symbols));
+    fetch(output, dout, input_size);
+}
+void plain_interpolate_cc(complexf *in, complexf *out, int n, int interpolation)
+{   // libcsdr.c:2499-2506
+    if (n <= 0 || interpolation <= 0) return;
+    const size_t m = (size_t)n * interpolation;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); cf32 *dout = stage_out<cf32>(5, m);
+    MUST(csdr_amd_plain_interpolate_cc(ctx(), din, dout, 1, n, n, m, interpolation));
+    fetch((cf32 *)out, dout, m);
+}
+void pack_bits_1to8_u8_u8(unsigned char *in, unsigned char *out, int n)
+{   // libcsdr.c:1810-1815
+    if (n <= 0) return;
+    unsigned char *din = stage_in<unsigned char>(4, in, n); unsigned char *dout = stage_out<unsigned char>(5, 8 * (size_t)n);
+    MUST(csdr_amd_pack_bits_1to8_u8_u8(ctx(), din, dout, 1, n, n, 8 * (size_t)n));
+    fetch(out, dout, 8 * (size_t)n);
+}
+unsigned char pack_bits_8to1_u8_u8(unsigned char *input) { return pack_bits_8to1_step(input); }   // libcsdr.c:1818-1827: eight bytes, on the host
 
 // ------------------------------------------------------------------ RTTY receive (rtty.hip)
 int bfsk_demod_cf(complexf *in, float *out, int n, complexf *mark_filter, complexf *space_filter, int taps_length)

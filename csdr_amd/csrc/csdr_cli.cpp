@@ -138,6 +138,24 @@ const char *const PSK31_RUN[4] = {"simple_agc_cc", "timing_recovery_cc", "dbpsk_
 const char *const RTTY_RUN[3] = {"bfsk_demod_cf", "serial_line_decoder_f_u8", "rtty_baudot2ascii_u8_u8"};
 const char *const PSK31TX_RUN[4] = {"psk31_varicode_encoder_u8_u8", "differential_encoder_u8_u8", "psk_modulator_u8_c", "psk31_interpolate_sine_cc"};
 
+// [psk_modulator_u8_c n |] plain_interpolate_cc I | pulse_shaping_filter_cc ... -> one `pulse_tx` command (arguments: the run's commands, one per argument)
+bool fuse_pulsetx(std::vector<std::vector<std::string>> &cmds)
+{
+    auto is = [&](size_t k, const char *name) { return k < cmds.size() && cmds[k].size() > 1 && cmds[k][1] == name; };
+    bool any = false;
+    for (size_t m = 0; m + 1 < cmds.size(); m++) {
+        if (!is(m, "plain_interpolate_cc") || !is(m + 1, "pulse_shaping_filter_cc")) continue;
+        const size_t a = m > 0 && is(m - 1, "psk_modulator_u8_c") ? m - 1 : m, b = m + 2;
+        std::vector<std::string> fused = {"csdr", "pulse_tx"};
+        for (size_t k = a; k < b; k++) { std::string w; for (size_t t = 1; t < cmds[k].size(); t++) w += (t > 1 ? " " : "") + cmds[k][t]; fused.push_back(w); }
+        fprintf(stderr, "csdr chain: %s .. %s recognised -> one fused pulse-shaping transmit object (pulse_tx: k_pulsetx_poly)\n", cmds[a][1].c_str(), cmds[b - 1][1].c_str());
+        cmds.erase(cmds.begin() + a, cmds.begin() + b);
+        cmds.insert(cmds.begin() + a, fused);
+        m = a; any = true;
+    }
+    return any;
+}
+
 // convert_u8_f | shift_addition_cc r | fir_decimate_cc D [tbw [window]] at the head of a chain -> one ddc_u8_cc command
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
 {
@@ -169,6 +187,8 @@ int main(int argc, char **argv)
                         "simple_agc_cc timing_recovery_cc (needs |mu| * max_error <= 1) dbpsk_decoder_c_u8 psk31_varicode_decoder_u8_u8 "
                         "psk31_varicode_encoder_u8_u8 differential_encoder_u8_u8 differential_decoder_u8_u8 psk_modulator_u8_c (<n_psk>) psk31_interpolate_sine_cc (<interpolation>) "
                         "duplicate_samples_ntimes_u8_u8 (<sample_size_bytes> <ntimes>) "
+                        "plain_interpolate_cc (<interpolation>) pulse_shaping_filter_cc / firdes_pulse_shaping_filter_f (RRC <samples_per_symbol> <num_taps> <beta> | COSINE <samples_per_symbol>) "
+                        "generic_slicer_f_u8 (<n_symbols>) pack_bits_1to8_u8_u8 pack_bits_8to1_u8_u8 "
                         "bfsk_demod_cf serial_line_decoder_f_u8 rtty_baudot2ascii_u8_u8 rtty_line_decoder_u8_u8 binary_slicer_f_u8 firdes_peak_c "
                         "squelch_and_smeter_cc (--fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>) bpsk_costas_loop_cc (<loop_bandwidth> <damping_factor> [--dd | --decision_directed] [--output_error | --output_dphase | --output_nco | --output_combined <error_file> <dphase_file> <nco_file>]) pll_cc (1 [alpha] | 2 [bandwidth [damping_factor [ko [kd]]]]) amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf dsb_fc ([q_value]) fmmod_fc add_dcoffset_cc fixed_amplitude_cc (<new_amplitude>) convert_f_samplerf (<wait_for_this_sample>) fft_cc logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 / am_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], ssb_bank_u8_s16 [--lsb | --passbands lo:hi[,lo:hi,...]] <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
@@ -223,6 +243,13 @@ int main(int argc, char **argv)
         if (octave) { fflush(stdout); getchar(); }                   // keep octave's window open until the user closes the pipe
         return 0;
     }
+    if (cmd == "firdes_pulse_shaping_filter_f") {                     // csdr.c:3159-3205: print the designed taps, "%f " each
+        std::vector<float> t;
+        if (!parse_pulse_filter(argc, argv, &t)) return -1;
+        for (float v : t) printf("%f ", v);
+        fflush(stdout);
+        return 0;
+    }
     if ((cmd == "rational_resampler_ff" || cmd == "suboptimal_rational_resampler_ff") && argc > 3) {   // csdr.c:1427: 1/1 copies input to output
         int I = 0, D = 0; sscanf(argv[2], "%d", &I); sscanf(argv[3], "%d", &D); if (I == 1 && D == 1) return passthrough(true, 0);
     }
@@ -259,6 +286,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "csdr chain: convert_u8_f | shift_addition_cc | fir_decimate_cc recognised -> fused matrix-core front end\n");
         }
         fuse_run(cmds, PSK31_RUN, 4, "psk31_rx", "csdr chain: %s .. %s recognised -> one fused BPSK31 object (k_psk31)\n");
+        fuse_pulsetx(cmds);                                             // (in front of the BPSK31 transmit run: psk_modulator_u8_c belongs to both)
         fuse_run(cmds, PSK31TX_RUN, 4, "psk31_tx", "csdr chain: %s .. %s recognised -> one fused BPSK31 transmit object (psk31_tx)\n");
         fuse_run(cmds, RTTY_RUN, 3, "rtty_rx", "csdr chain: %s .. %s recognised -> one fused RTTY object (rtty_rx: k_bfsk_mfma + k_rtty_walk)\n");
     } else {

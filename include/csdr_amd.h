@@ -315,6 +315,59 @@ int  csdr_amd_duplicate_samples_ntimes_u8_u8(csdr_amd_ctx *ctx, const unsigned c
 long long csdr_amd_debug_psk31tx_walk(int n_psk, int interpolation, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
                                       int n_cuts, void *out, csdr_amd_psk31tx_chan *state_io);
 
+/* ------------------------------------------------------------------ pulse-shaped symbol modem (modem.hip)
+ * Transmit: psk_modulator_u8_c n_psk libcsdr.c:1772-1782 | plain_interpolate_cc I libcsdr.c:2499-2506 | pulse_shaping_filter_cc = apply_real_fir_cc
+ * libcsdr.c:2276-2291 (csdr.c:3159-3254), for n_channels channels with the same n_psk (1..256), interpolation I (>= 1) and T real taps (host pointer, copied).
+ * With c[m] a channel's symbols since its last reset, x[j] = c[j / I] where I divides j and 0 elsewhere, the stream is y[i] = sum over t < T of x[i + t] *
+ * taps[t]: after n symbols in total it holds exactly the outputs i = 0 .. n I - T (the zeros behind the last symbol are input), max(0, n I - T + 1) of them.
+ * The nonzero products of an output (t = (-i) mod I, + I, ...) are accumulated in ascending t with fmaf; a phase without a tap (T < I) gives 0 + 0i.  The
+ * output does not depend on how the stream is cut into calls (0- and 1-symbol calls included) nor on where a channel sits in the batch.
+ * The object runs the stages first_stage .. last_stage: MOD .. MOD is psk_modulator_u8_c alone (taps may be NULL); SHAPE .. SHAPE takes complexf symbols (any
+ * constellation).  Symbols: the table of csdr_amd_psk31tx_tables.  State: the number of symbols taken (the same for every channel) and, on the device, each
+ * channel's last ceil((T - 1) / I) symbols.
+ * process: n_in symbols per channel, in_pitch items apart (bytes from MOD, complexf from SHAPE); out: complexf, out_pitch apart, at least max_out(n_in) = n_in
+ * (x I to SHAPE), at most 2^31 - 1: a smaller out_pitch is an error and consumes nothing.  *n_out (host) receives the outputs per channel of this call;
+ * nothing is written at or beyond it.  Asynchronous on the context's stream.
+ * kernel_name: "k_pulsetx_poly" (taps and a tile's symbols within 63 KiB of LDS: 4 K I + 8 (4096 / I + K + 4) bytes, K = ceil(T / I)) or "k_pulsetx_generic"
+ * (every other shape, MOD .. MOD, and after force_generic(1)).  Both give the same bits.  tile: the symbols per tile of k_pulsetx_poly, max(1, 4096 / I). */
+enum { CSDR_AMD_PULSETX_MOD = 0, CSDR_AMD_PULSETX_SHAPE = 1 };
+typedef struct csdr_amd_pulsetx csdr_amd_pulsetx;
+csdr_amd_pulsetx *csdr_amd_pulsetx_create(csdr_amd_ctx *ctx, int n_channels, int n_psk, int interpolation, const float *host_taps, int taps_length,
+                                          int first_stage, int last_stage);
+int  csdr_amd_pulsetx_process(csdr_amd_pulsetx *p, const void *in, long long n_in, size_t in_pitch, void *out, size_t out_pitch, long long *n_out);
+long long csdr_amd_pulsetx_max_out(const csdr_amd_pulsetx *p, long long n_in);
+int  csdr_amd_pulsetx_reset(csdr_amd_pulsetx *p);
+int  csdr_amd_pulsetx_force_generic(csdr_amd_pulsetx *p, int on);
+const char *csdr_amd_pulsetx_kernel_name(const csdr_amd_pulsetx *p);
+int  csdr_amd_pulsetx_tile(const csdr_amd_pulsetx *p);
+void csdr_amd_pulsetx_destroy(csdr_amd_pulsetx *p);
+/* CPU run of the object's definition (the same step functions) for one channel, the n items cut into calls of cuts[0..n_cuts) items and the rest; outputs
+ * concatenated.  Returns the output count. */
+long long csdr_amd_debug_pulsetx_walk(int n_psk, int interpolation, const float *taps, int taps_length, int first_stage, int last_stage, const void *in,
+                                      long long n, const long long *cuts, int n_cuts, void *out);
+/* generic_slicer_f_u8 libcsdr.c:1731-1765 on n_streams streams of n floats, n_symbols 2..256: symbol j's centre is -1 + j d with d = (float)(2.0 / (n_symbols - 1)),
+ * its limits centre -/+ d / 2, all in float as the reference computes them; the first symbol has no lower and the last no upper limit.  An input that no symbol
+ * claims gives 0: NaN (the reference leaves that output byte unwritten), and a value in a rounding gap between two neighbours' limits. */
+int  csdr_amd_generic_slicer_f_u8(csdr_amd_ctx *ctx, const float *in, unsigned char *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                                  int n_symbols);
+/* plain_interpolate_cc libcsdr.c:2499-2506: out[i I] = in[i], zeros between; n inputs, n I outputs per stream.  out must not be in. */
+int  csdr_amd_plain_interpolate_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                                   int interpolation);
+/* pack_bits_1to8_u8_u8 libcsdr.c:1810-1815: n bytes -> 8 n bytes per stream, a byte's bits LSB first.  pack_bits_8to1_u8_u8 libcsdr.c:1818-1827 applied to
+ * every group of eight: n bytes (a multiple of 8) -> n / 8 bytes per stream, the first byte of a group the MSB, each byte taken as !!byte.  (They are not
+ * inverses of each other.)  out must not be in. */
+int  csdr_amd_pack_bits_1to8_u8_u8(csdr_amd_ctx *ctx, const unsigned char *in, unsigned char *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch);
+int  csdr_amd_pack_bits_8to1_u8_u8(csdr_amd_ctx *ctx, const unsigned char *in, unsigned char *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch);
+/* apply_real_fir_cc libcsdr.c:2276-2291: csdr_amd_fir_decimate_cc at decimation 1.  taps: DEVICE pointer.  Returns input_size - taps_length + 1 outputs per
+ * stream (0 when input_size < taps_length) or a negative error. */
+int  csdr_amd_apply_real_fir_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, int n_streams, int input_size, size_t in_pitch, size_t out_pitch,
+                                const float *taps, int taps_length);
+/* firdes_rrc_f libcsdr.c:2482-2497 and firdes_cosine_f libcsdr.c:2473-2480 (host), normalize_fir_f included.  RRC: taps_length odd, otherwise an error (for an
+ * even length the reference writes taps[taps_length]).  Cosine: meant for taps_length = 2 samples_per_symbol + 1; the taps the reference never writes (the two
+ * end taps of that length) are 0. */
+int  csdr_amd_firdes_rrc_f(float *taps, int taps_length, int samples_per_symbol, float beta);
+int  csdr_amd_firdes_cosine_f(float *taps, int taps_length, int samples_per_symbol);
+
 /* ------------------------------------------------------------------ RTTY receive chain (rtty.hip)
  * bfsk_demod_cf libcsdr.c:2335-2350 (csdr.c:3271-3300) | serial_line_decoder_f_u8 libcsdr.c:1662-1728 (csdr.c:2490-2528) | rtty_baudot2ascii_u8_u8 csdr.c:2461-2473,
  * for n_channels channels, all with the same parameters.  The object runs the stages first_stage .. last_stage (CSDR_AMD_RTTY_*) and keeps each channel's

@@ -117,6 +117,20 @@ void duplicate_samples_ntimes_u8_u8(unsigned char *input, unsigned char *output,
 complexf psk31_interpolate_sine_cc(complexf *input, complexf *output, int input_size, int interpolation, complexf last_input);
 void psk31_varicode_encoder_u8_u8(unsigned char *input, unsigned char *output, int input_size, int output_max_size, int *input_processed, int *output_size);
 unsigned char differential_codec(unsigned char *input, unsigned char *output, int input_size, int encode, unsigned char state);
+/* The pulse-shaped symbol modem, libcsdr.h:393-411 and libcsdr.c:1731-1765, 1810-1827, 2276-2291, 2473-2516.  The designs and pack_bits_8to1_u8_u8 (eight
+ * bytes) run on the host, the others on the device.  firdes_rrc_f writes only indexes below taps_length (the reference writes taps[taps_length] for an even
+ * length); firdes_cosine_f writes 0 into the taps the reference leaves unwritten; both return 0.  generic_slicer_f_u8 writes 0 for an input that no symbol
+ * claims (NaN: the reference leaves that byte unwritten) and does nothing for n_symbols outside 2..256. */
+typedef enum matched_filter_type_e { MATCHED_FILTER_RRC, MATCHED_FILTER_COSINE } matched_filter_type_t;
+#define MATCHED_FILTER_DEFAULT MATCHED_FILTER_RRC
+int firdes_cosine_f(float *taps, int taps_length, int samples_per_symbol);
+int firdes_rrc_f(float *taps, int taps_length, int samples_per_symbol, float beta);
+matched_filter_type_t matched_filter_get_type_from_string(char *input);
+int apply_real_fir_cc(complexf *input, complexf *output, int input_size, float *taps, int taps_length);
+void generic_slicer_f_u8(float *input, unsigned char *output, int input_size, int n_symbols);
+void plain_interpolate_cc(complexf *input, complexf *output, int input_size, int interpolation);
+void pack_bits_1to8_u8_u8(unsigned char *input, unsigned char *output, int input_size);
+unsigned char pack_bits_8to1_u8_u8(unsigned char *input);
 /* RTTY receive, libcsdr.h:236-289, 412.  bfsk_demod_cf and serial_line_decoder_f_u8 run on the device (one library call = one window, as the reference);
  * serial_line_decoder_f_u8 writes unsigned char, short or unsigned outputs for databits <= 8, <= 16, above.  The Baudot functions run on the host. */
 typedef struct rtty_baudot_item_s { unsigned long long code; unsigned char ascii_letter; unsigned char ascii_figure; } rtty_baudot_item_t;
