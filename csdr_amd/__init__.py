@@ -99,67 +99,41 @@ def lib():
     L.csdr_amd_compress_fft_adpcm_f_u8.argtypes = [vp, vp, vp, i, i]
     L.csdr_amd_waterfall_create.restype = vp; L.csdr_amd_waterfall_create.argtypes = [vp, i, i, i, i, fl, i, i, i, sz]
     L.csdr_amd_waterfall_process.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(i)]
-    L.csdr_amd_waterfall_reset.argtypes = [vp]
-    L.csdr_amd_waterfall_kernel_name.restype = C.c_char_p; L.csdr_amd_waterfall_kernel_name.argtypes = [vp]
-    L.csdr_amd_waterfall_force_generic.argtypes = [vp, i]
-    L.csdr_amd_waterfall_destroy.argtypes = [vp]; L.csdr_amd_waterfall_destroy.restype = None
     ll = C.c_longlong
+    # csdr_amd_<pre>_<member>, the entry points the stateful objects share (what _Handle and its mixins below call; on the C side csrc/bank.hpp holds the
+    # bodies): every object has `common`, the table lists which of the others
+    members = {"reset": (i, [vp]), "force_generic": (i, [vp, i]), "kernel_name": (C.c_char_p, [vp]), "destroy": (None, [vp]), "max_out": (ll, [vp, ll]),
+               "reset_channel": (i, [vp, i]), "get_channel": (i, [vp, i, vp]), "set_channel": (i, [vp, i, vp]), "set_lanes": (i, [vp, i]), "lanes": (i, [vp])}
+    common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
+    for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
+                       ("pulsetx", max_out), ("rtty", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
+                       ("txbank", max_out)):
+        for m in common + extra:
+            f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
+            f.restype, f.argtypes = members[m]
     L.csdr_amd_resampler_create.restype = vp; L.csdr_amd_resampler_create.argtypes = [vp, i, i, vp, i, i]
     L.csdr_amd_resampler_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
-    L.csdr_amd_resampler_max_out.restype = ll; L.csdr_amd_resampler_max_out.argtypes = [vp, ll]
-    L.csdr_amd_resampler_reset.argtypes = [vp]
     L.csdr_amd_resampler_set_cli_bufsize.argtypes = [vp, i]
     L.csdr_amd_resampler_set_last_taps_delay.argtypes = [vp, i]
-    L.csdr_amd_resampler_force_generic.argtypes = [vp, i]
-    L.csdr_amd_resampler_kernel_name.restype = C.c_char_p; L.csdr_amd_resampler_kernel_name.argtypes = [vp]
-    L.csdr_amd_resampler_destroy.argtypes = [vp]; L.csdr_amd_resampler_destroy.restype = None
     L.csdr_amd_resampler_window.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_interp_create.restype = vp; L.csdr_amd_interp_create.argtypes = [vp, i, vp, i, i]
     L.csdr_amd_interp_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
-    L.csdr_amd_interp_max_out.restype = ll; L.csdr_amd_interp_max_out.argtypes = [vp, ll]
-    L.csdr_amd_interp_reset.argtypes = [vp]
     L.csdr_amd_interp_set_cli_bufsize.argtypes = [vp, i]
-    L.csdr_amd_interp_force_generic.argtypes = [vp, i]
-    L.csdr_amd_interp_kernel_name.restype = C.c_char_p; L.csdr_amd_interp_kernel_name.argtypes = [vp]
-    L.csdr_amd_interp_destroy.argtypes = [vp]; L.csdr_amd_interp_destroy.restype = None
     L.csdr_amd_psk31_create.restype = vp; L.csdr_amd_psk31_create.argtypes = [vp, vp, i, i, i]
     L.csdr_amd_psk31_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, vp, vp]
-    L.csdr_amd_psk31_max_out.restype = ll; L.csdr_amd_psk31_max_out.argtypes = [vp, ll]
-    L.csdr_amd_psk31_reset.argtypes = [vp]
-    L.csdr_amd_psk31_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_psk31_get_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_psk31_set_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_psk31_set_lanes.argtypes = [vp, i]
-    L.csdr_amd_psk31_force_generic.argtypes = [vp, i]
-    L.csdr_amd_psk31_lanes.argtypes = [vp]
-    L.csdr_amd_psk31_kernel_name.restype = C.c_char_p; L.csdr_amd_psk31_kernel_name.argtypes = [vp]
-    L.csdr_amd_psk31_destroy.argtypes = [vp]; L.csdr_amd_psk31_destroy.restype = None
     L.csdr_amd_simple_agc_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, C.c_float, C.c_float, C.c_float, vp]
     L.csdr_amd_psk31_varicode_decoder_push.restype = C.c_char; L.csdr_amd_psk31_varicode_decoder_push.argtypes = [vp, C.c_ubyte]
     L.csdr_amd_psk31_varicode_table.restype = None; L.csdr_amd_psk31_varicode_table.argtypes = [vp]
     L.csdr_amd_debug_psk31_walk.restype = ll; L.csdr_amd_debug_psk31_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
     L.csdr_amd_psk31tx_create.restype = vp; L.csdr_amd_psk31tx_create.argtypes = [vp, i, i, i, i, i]
     L.csdr_amd_psk31tx_process.argtypes = [vp, vp, ll, vp, sz, vp, sz, vp]
-    L.csdr_amd_psk31tx_max_out.restype = ll; L.csdr_amd_psk31tx_max_out.argtypes = [vp, ll]
-    L.csdr_amd_psk31tx_reset.argtypes = [vp]
-    L.csdr_amd_psk31tx_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_psk31tx_get_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_psk31tx_set_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_psk31tx_force_generic.argtypes = [vp, i]
-    L.csdr_amd_psk31tx_kernel_name.restype = C.c_char_p; L.csdr_amd_psk31tx_kernel_name.argtypes = [vp]
-    L.csdr_amd_psk31tx_destroy.argtypes = [vp]; L.csdr_amd_psk31tx_destroy.restype = None
     L.csdr_amd_psk31tx_tables.argtypes = [i, i, vp, vp]
     L.csdr_amd_differential_decoder_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, vp]
     L.csdr_amd_duplicate_samples_ntimes_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i, i]
     L.csdr_amd_debug_psk31tx_walk.restype = ll; L.csdr_amd_debug_psk31tx_walk.argtypes = [i, i, i, i, vp, ll, vp, i, vp, vp]
     L.csdr_amd_pulsetx_create.restype = vp; L.csdr_amd_pulsetx_create.argtypes = [vp, i, i, i, vp, i, i, i]
     L.csdr_amd_pulsetx_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
-    L.csdr_amd_pulsetx_max_out.restype = ll; L.csdr_amd_pulsetx_max_out.argtypes = [vp, ll]
-    L.csdr_amd_pulsetx_reset.argtypes = [vp]
-    L.csdr_amd_pulsetx_force_generic.argtypes = [vp, i]
-    L.csdr_amd_pulsetx_kernel_name.restype = C.c_char_p; L.csdr_amd_pulsetx_kernel_name.argtypes = [vp]
     L.csdr_amd_pulsetx_tile.argtypes = [vp]
-    L.csdr_amd_pulsetx_destroy.argtypes = [vp]; L.csdr_amd_pulsetx_destroy.restype = None
     L.csdr_amd_debug_pulsetx_walk.restype = ll; L.csdr_amd_debug_pulsetx_walk.argtypes = [i, i, vp, i, i, i, vp, ll, vp, i, vp]
     L.csdr_amd_generic_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
     L.csdr_amd_plain_interpolate_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
@@ -170,12 +144,6 @@ def lib():
     L.csdr_amd_firdes_cosine_f.argtypes = [vp, i, i]
     L.csdr_amd_rtty_create.restype = vp; L.csdr_amd_rtty_create.argtypes = [vp, vp, i, i, i]
     L.csdr_amd_rtty_process.argtypes = [vp, vp, ll, sz, vp, sz, vp]
-    L.csdr_amd_rtty_max_out.restype = ll; L.csdr_amd_rtty_max_out.argtypes = [vp, ll]
-    L.csdr_amd_rtty_reset.argtypes = [vp]
-    L.csdr_amd_rtty_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_rtty_force_generic.argtypes = [vp, i]
-    L.csdr_amd_rtty_kernel_name.restype = C.c_char_p; L.csdr_amd_rtty_kernel_name.argtypes = [vp]
-    L.csdr_amd_rtty_destroy.argtypes = [vp]; L.csdr_amd_rtty_destroy.restype = None
     L.csdr_amd_bfsk_demod_cf.argtypes = [vp, vp, vp, i, ll, sz, sz, vp, vp, i, i]
     L.csdr_amd_bfsk_last_kernel.restype = C.c_char_p; L.csdr_amd_bfsk_last_kernel.argtypes = []
     L.csdr_amd_binary_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
@@ -192,11 +160,6 @@ def lib():
     L.csdr_amd_squelch_get_level.restype = fl; L.csdr_amd_squelch_get_level.argtypes = [vp, i]
     L.csdr_amd_squelch_block_index.restype = ll; L.csdr_amd_squelch_block_index.argtypes = [vp, i]
     L.csdr_amd_squelch_max_blocks.argtypes = [vp]
-    L.csdr_amd_squelch_reset.argtypes = [vp]
-    L.csdr_amd_squelch_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_squelch_force_generic.argtypes = [vp, i]
-    L.csdr_amd_squelch_kernel_name.restype = C.c_char_p; L.csdr_amd_squelch_kernel_name.argtypes = [vp]
-    L.csdr_amd_squelch_destroy.argtypes = [vp]; L.csdr_amd_squelch_destroy.restype = None
     L.csdr_amd_get_power_c.argtypes = [vp, vp, i, i, i, i, sz, vp]
     L.csdr_amd_get_power_f.argtypes = [vp, vp, i, i, i, i, sz, vp]
     L.csdr_amd_squelch_report_due.argtypes = [i, ll]
@@ -207,22 +170,12 @@ def lib():
     L.csdr_amd_pll_params_pi.argtypes = [fl, fl, fl, fl, vp]
     L.csdr_amd_carrier_create.restype = vp; L.csdr_amd_carrier_create.argtypes = [vp, vp, i]
     L.csdr_amd_carrier_process.argtypes = [vp, vp, ll, sz, vp, vp, vp, vp, sz]
-    L.csdr_amd_carrier_reset.argtypes = [vp]
-    L.csdr_amd_carrier_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_carrier_get_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_carrier_set_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_carrier_set_lanes.argtypes = [vp, i]
-    L.csdr_amd_carrier_lanes.argtypes = [vp]
-    L.csdr_amd_carrier_force_generic.argtypes = [vp, i]
-    L.csdr_amd_carrier_kernel_name.restype = C.c_char_p; L.csdr_amd_carrier_kernel_name.argtypes = [vp]
-    L.csdr_amd_carrier_destroy.argtypes = [vp]; L.csdr_amd_carrier_destroy.restype = None
     L.csdr_amd_debug_carrier_walk.restype = ll; L.csdr_amd_debug_carrier_walk.argtypes = [vp, vp, ll, vp, i, vp, vp, vp, vp, vp]
     L.csdr_amd_amssb_params_default.argtypes = [vp, i]
     L.csdr_amd_amssb_create_cf32.restype = vp; L.csdr_amd_amssb_create_cf32.argtypes = [vp, vp, i, vp, i, i, sz]
     L.csdr_amd_amssb_create.restype = vp; L.csdr_amd_amssb_create.argtypes = [vp, vp, i, fl, i, vp, i, vp, i, i, sz]
     L.csdr_amd_amssb_create_rates.restype = vp; L.csdr_amd_amssb_create_rates.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, i, sz]
     L.csdr_amd_amssb_process.restype = ll; L.csdr_amd_amssb_process.argtypes = [vp, vp, sz, ll, vp, vp, sz]
-    L.csdr_amd_amssb_max_out.restype = ll; L.csdr_amd_amssb_max_out.argtypes = [vp, ll]
     L.csdr_amd_amssb_set_rate.argtypes = [vp, i, fl]
     L.csdr_amd_amssb_get_rate.restype = fl; L.csdr_amd_amssb_get_rate.argtypes = [vp, i]
     L.csdr_amd_amssb_front_end.restype = vp; L.csdr_amd_amssb_front_end.argtypes = [vp]
@@ -230,15 +183,6 @@ def lib():
         L.csdr_amd_amssb_set_passband.argtypes = [vp, i, fl, fl, i]
         L.csdr_amd_amssb_set_channel_taps.argtypes = [vp, i, vp, i]
         L.csdr_amd_amssb_get_passband.argtypes = [vp, i, vp, vp]
-    L.csdr_amd_amssb_reset.argtypes = [vp]
-    L.csdr_amd_amssb_reset_channel.argtypes = [vp, i]
-    L.csdr_amd_amssb_get_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_amssb_set_channel.argtypes = [vp, i, vp]
-    L.csdr_amd_amssb_set_lanes.argtypes = [vp, i]
-    L.csdr_amd_amssb_lanes.argtypes = [vp]
-    L.csdr_amd_amssb_force_generic.argtypes = [vp, i]
-    L.csdr_amd_amssb_kernel_name.restype = C.c_char_p; L.csdr_amd_amssb_kernel_name.argtypes = [vp]
-    L.csdr_amd_amssb_destroy.argtypes = [vp]; L.csdr_amd_amssb_destroy.restype = None
     L.csdr_amd_debug_amssb_walk.restype = ll; L.csdr_amd_debug_amssb_walk.argtypes = [vp, vp, i, vp, vp, vp]
     L.csdr_amd_fmmod_fc.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_dsb_fc.argtypes = [vp, vp, vp, sz, fl]
@@ -250,11 +194,6 @@ def lib():
     L.csdr_amd_txbank_process.argtypes = [vp, vp, sz, ll, vp, sz, C.POINTER(ll)]
     L.csdr_amd_txbank_set_rate.argtypes = [vp, i, fl]
     L.csdr_amd_txbank_get_rate.restype = fl; L.csdr_amd_txbank_get_rate.argtypes = [vp, i]
-    L.csdr_amd_txbank_reset.argtypes = [vp]
-    L.csdr_amd_txbank_max_out.restype = ll; L.csdr_amd_txbank_max_out.argtypes = [vp, ll]
-    L.csdr_amd_txbank_force_generic.argtypes = [vp, i]
-    L.csdr_amd_txbank_kernel_name.restype = C.c_char_p; L.csdr_amd_txbank_kernel_name.argtypes = [vp]
-    L.csdr_amd_txbank_destroy.argtypes = [vp]; L.csdr_amd_txbank_destroy.restype = None
     L.csdr_amd_rational_resampler_get_lowpass_f.restype = None; L.csdr_amd_rational_resampler_get_lowpass_f.argtypes = [vp, i, i, i, i]
     L.csdr_amd_debug_resampler_schedule.argtypes = [i, i, i, i, i, vp]
     L.csdr_amd_logaveragepower_cf.argtypes = [vp, vp, vp, i, i, i, fl]

@@ -14,7 +14,7 @@
 //   k_amssb_generic<MODE>   one lane per channel, straight from and to global memory, float by float: any pointer alignment, any block size.  force_generic(1)
 //                           takes it always.
 // Both run amssb_dev.hpp's functions on the same samples in the same order: the same bits, for every C, every cut into calls and every pitch, as the CPU hook.
-#include "common.hpp"
+#include "bank.hpp"
 #include "amssb_dev.hpp"
 #include <math.h>
 #include <string.h>
@@ -216,13 +216,12 @@ inline dim3 copy_grid(long long count, int n_ch) { return dim3(cdiv((size_t)(2 *
 
 } // namespace
 
-struct csdr_amd_amssb {
-    csdr_amd_ctx *c; AmSsbCfg cfg; int n_ch, lanes; bool force_generic; const char *last_kernel;
+struct csdr_amd_amssb : ChanBank<AmSsbChan> {
+    AmSsbCfg cfg;
     size_t max_in, max_tail;                             // most samples per call at the interface and in front of the tail
-    DevBuf<AmSsbChan> d_st;
-    DevBuf<float> d_carry; int fill;                     // [n_ch][block] complex: the samples short of a whole block
-    int inp; DevBuf<float> d_fin, d_filt; size_t f_pitch; int f_fill;      // SSB: the filter's input (what is short of one input_size in front) and output
-    int D; DevBuf<float> d_y; size_t y_pitch;            // U8: the front end's decimation and output
+    DevBuf<float> d_carry; int fill = 0;                 // [n_ch][block] complex: the samples short of a whole block
+    int inp = 0; DevBuf<float> d_fin, d_filt; size_t f_pitch = 0; int f_fill = 0;      // SSB: the filter's input (what is short of one input_size in front) and output
+    int D = 1; DevBuf<float> d_y; size_t y_pitch = 0;    // U8: the front end's decimation and output
     Owned<csdr_amd_fftfilt, csdr_amd_fftfilt_destroy> filt; int taps_len;
     std::vector<float> band;                             // [n_ch][2]: the edges set_passband gave a channel last (NaN: none, or taps of the caller's own)
     Owned<csdr_amd_ddc, csdr_amd_ddc_destroy> ddc;
@@ -234,15 +233,11 @@ csdr_amd_amssb *create_impl(csdr_amd_ctx *c, const csdr_amd_amssb_params *params
                             const float *ddc_taps, int ddc_taps_length, const csdr_complexf *taps, int taps_length, int fft_size, size_t max_samples_per_call)
 {
     AmSsbCfg cfg;
-    if (!c) { fail_msg(-3, "amssb: null context"); return nullptr; }
-    if (n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "amssb: n_channels should be 1 .. 4194304"); return nullptr; }
-    if (check_params(params, &cfg) < 0) return nullptr;
+    if (bank_create_check("amssb", c, n_channels) < 0 || check_params(params, &cfg) < 0) return nullptr;
     if (taps_length < 0 || (taps_length > 0 && (!taps || cfg.mode != AMSSB_SSB))) { fail_msg(-3, "amssb: taps belong to SSB mode"); return nullptr; }
     if (max_samples_per_call < 1 || max_samples_per_call > ((size_t)1 << 30)) { fail_msg(-3, "amssb: max_samples_per_call should be 1 .. 2^30"); return nullptr; }
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "amssb: hipSetDevice"); return nullptr; }
     Owned<csdr_amd_amssb, csdr_amd_amssb_destroy> p(new csdr_amd_amssb());
-    p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->lanes = 0; p->force_generic = false; p->last_kernel = "";
-    p->fill = 0; p->inp = 0; p->f_pitch = 0; p->f_fill = 0; p->y_pitch = 0; p->D = 1;
+    p->c = c; p->cfg = cfg; p->n_ch = n_channels;
     p->max_in = max_samples_per_call; p->max_tail = max_samples_per_call;
     hipError_t e = hipSuccess;
     auto alloc = [&](auto &b, size_t bytes) { if (e == hipSuccess) e = dev_alloc(b, bytes); };
@@ -312,16 +307,13 @@ long long run_tail(csdr_amd_amssb *p, const float *x, size_t xp, long long n, in
         a.s16 = s16; a.pre = pre; a.out_pitch = out_pitch;
         const bool am = p->cfg.mode == AMSSB_AM;
         if (!p->force_generic && B % AT == 0 && !((uintptr_t)x & 7)) {
-            const int C = std::min(p->lanes ? p->lanes : default_lanes(p->n_ch, true), ACMAX);
-            a.lanes = C;
+            const int C = a.lanes = bank_launch_lanes(p, am ? "k_amssb_tiled<AM>" : "k_amssb_tiled<SSB>", default_lanes(p->n_ch, true), ACMAX);
             if (am) hipLaunchKernelGGL(k_amssb_tiled<AMSSB_AM>, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C), st, a, C);
             else hipLaunchKernelGGL(k_amssb_tiled<AMSSB_SSB>, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C), st, a, C);
-            p->last_kernel = am ? "k_amssb_tiled<AM>" : "k_amssb_tiled<SSB>";
         } else {
-            a.lanes = p->lanes ? p->lanes : default_lanes(p->n_ch, false);
+            a.lanes = bank_launch_lanes(p, am ? "k_amssb_generic<AM>" : "k_amssb_generic<SSB>", default_lanes(p->n_ch, false));
             if (am) hipLaunchKernelGGL(k_amssb_generic<AMSSB_AM>, dim3(cdiv(p->n_ch, a.lanes)), dim3(64), 0, st, a);
             else hipLaunchKernelGGL(k_amssb_generic<AMSSB_SSB>, dim3(cdiv(p->n_ch, a.lanes)), dim3(64), 0, st, a);
-            p->last_kernel = am ? "k_amssb_generic<AM>" : "k_amssb_generic<SSB>";
         }
         CSDR_LAUNCH_CHECK();
     }
@@ -430,42 +422,19 @@ int csdr_amd_amssb_reset(csdr_amd_amssb *p)
 }
 
 // one channel's two state words back to their start; its samples short of a block stay
-int csdr_amd_amssb_reset_channel(csdr_amd_amssb *p, int ch)
-{
-    const csdr_amd_amssb_chan z = {0.f, 1.f};
-    return csdr_amd_amssb_set_channel(p, ch, &z);
-}
+int csdr_amd_amssb_reset_channel(csdr_amd_amssb *p, int ch) { return bank_reset_channel(p, "amssb", ch, AmSsbChan{0.f, 1.f}); }
+int csdr_amd_amssb_get_channel(csdr_amd_amssb *p, int ch, csdr_amd_amssb_chan *out) { return bank_get_channel(p, "amssb", ch, out); }
+int csdr_amd_amssb_set_channel(csdr_amd_amssb *p, int ch, const csdr_amd_amssb_chan *s) { return bank_set_channel(p, "amssb", ch, s, [] { return 0; }); }
 
-int csdr_amd_amssb_get_channel(csdr_amd_amssb *p, int ch, csdr_amd_amssb_chan *out)
-{
-    if (!p || !out || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "amssb: channel out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_d2h(p->c, out, p->d_st.get() + ch, sizeof(AmSsbChan));
-}
-
-int csdr_amd_amssb_set_channel(csdr_amd_amssb *p, int ch, const csdr_amd_amssb_chan *s)
-{
-    if (!p || !s || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "amssb: channel out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_h2d(p->c, p->d_st.get() + ch, s, sizeof(AmSsbChan));
-}
-
-int csdr_amd_amssb_set_lanes(csdr_amd_amssb *p, int lanes)
-{
-    if (!p || lanes < 0 || lanes > 64) return fail_msg(-3, "amssb: channels per wave is 0 (automatic) .. 64");
-    p->lanes = lanes;
-    return 0;
-}
-
+int csdr_amd_amssb_set_lanes(csdr_amd_amssb *p, int lanes) { return bank_set_lanes(p, "amssb", lanes); }
 int csdr_amd_amssb_lanes(const csdr_amd_amssb *p)
 {
     if (!p) return 0;
-    if (p->force_generic) return p->lanes ? p->lanes : default_lanes(p->n_ch, false);
-    return std::min(p->lanes ? p->lanes : default_lanes(p->n_ch, true), ACMAX);
+    return p->force_generic ? bank_lanes(p, default_lanes(p->n_ch, false)) : bank_lanes(p, default_lanes(p->n_ch, true), ACMAX);
 }
 
-int csdr_amd_amssb_force_generic(csdr_amd_amssb *p, int on) { if (!p) return fail_msg(-3, "amssb: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_amssb_kernel_name(const csdr_amd_amssb *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_amssb_force_generic(csdr_amd_amssb *p, int on) { return bank_force_generic(p, "amssb", on); }
+const char *csdr_amd_amssb_kernel_name(const csdr_amd_amssb *p) { return bank_kernel_name(p); }
 
 void csdr_amd_amssb_destroy(csdr_amd_amssb *p) { destroy_on_stream(p); }
 

@@ -7,7 +7,7 @@
 //                     and all lanes write every requested output tile back coalesced.  An output that was not asked for is neither stored to LDS nor written.
 //   k_carrier         one lane per channel, straight from and to global memory, float by float: any pointer alignment.  force_generic(1) takes it always.
 // Both run carrier_dev.hpp's step function on the same samples in the same order: the same bits, for every C, every batch position and every cut into calls.
-#include "common.hpp"
+#include "bank.hpp"
 #include "carrier_dev.hpp"
 #include <string.h>
 #include <algorithm>
@@ -133,9 +133,8 @@ int check_chan(const csdr_amd_carrier_chan *s)
 
 } // namespace
 
-struct csdr_amd_carrier {
-    csdr_amd_ctx *c; CarrierCfg cfg; int n_ch, lanes; bool force_generic; const char *last_kernel;
-    DevBuf<CarrierChan> d_st;
+struct csdr_amd_carrier : ChanBank<CarrierChan> {
+    CarrierCfg cfg;
 };
 
 extern "C" {
@@ -169,61 +168,32 @@ int csdr_amd_pll_params_pi(float bandwidth, float ko, float kd, float damping, c
 csdr_amd_carrier *csdr_amd_carrier_create(csdr_amd_ctx *c, const csdr_amd_carrier_params *params, int n_channels)
 {
     CarrierCfg cfg;
-    if (!c) { fail_msg(-3, "carrier: null context"); return nullptr; }
-    if (n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "carrier: n_channels should be 1 .. 4194304"); return nullptr; }
-    if (check_params(params, &cfg) < 0) return nullptr;
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "carrier: hipSetDevice"); return nullptr; }
+    if (bank_create_check("carrier", c, n_channels) < 0 || check_params(params, &cfg) < 0) return nullptr;
     Owned<csdr_amd_carrier, csdr_amd_carrier_destroy> p(new csdr_amd_carrier());
-    p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->lanes = 0; p->force_generic = false; p->last_kernel = "";
+    p->c = c; p->cfg = cfg; p->n_ch = n_channels;
     if (dev_alloc(p->d_st, sizeof(CarrierChan) * n_channels) != hipSuccess) { fail_msg(-2, "carrier: out of device memory"); return nullptr; }
     if (csdr_amd_carrier_reset(p.get()) < 0) return nullptr;
     return p.release();
 }
 
-// every channel back to phase = dphase = freq = 0 (what the reference's init functions leave)
-int csdr_amd_carrier_reset(csdr_amd_carrier *p)
-{
-    if (!p) return fail_msg(-3, "carrier: null object");
-    return csdr_amd_memset(p->c, p->d_st.get(), 0, sizeof(CarrierChan) * p->n_ch);      // (on the context's stream, in order with the calls)
-}
-
-int csdr_amd_carrier_reset_channel(csdr_amd_carrier *p, int ch)
-{
-    const csdr_amd_carrier_chan z = {0.f, 0.f, 0.f};
-    return csdr_amd_carrier_set_channel(p, ch, &z);
-}
-
-int csdr_amd_carrier_get_channel(csdr_amd_carrier *p, int ch, csdr_amd_carrier_chan *out)
-{
-    if (!p || !out || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "carrier: channel out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_d2h(p->c, out, p->d_st.get() + ch, sizeof(CarrierChan));
-}
-
+// every channel back to phase = dphase = freq = 0 (what the reference's init functions leave): zero bytes, on the context's stream in order with the calls
+int csdr_amd_carrier_reset(csdr_amd_carrier *p) { return bank_reset(p, "carrier", nullptr); }
+int csdr_amd_carrier_reset_channel(csdr_amd_carrier *p, int ch) { return bank_reset_channel(p, "carrier", ch, CarrierChan{0.f, 0.f, 0.f}); }
+int csdr_amd_carrier_get_channel(csdr_amd_carrier *p, int ch, csdr_amd_carrier_chan *out) { return bank_get_channel(p, "carrier", ch, out); }
 int csdr_amd_carrier_set_channel(csdr_amd_carrier *p, int ch, const csdr_amd_carrier_chan *s)
 {
-    if (!p || !s || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "carrier: channel out of range");
-    if (check_chan(s) < 0) return -3;
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_h2d(p->c, p->d_st.get() + ch, s, sizeof(CarrierChan));
+    return bank_set_channel(p, "carrier", ch, s, [&] { return check_chan(s); });
 }
 
-int csdr_amd_carrier_set_lanes(csdr_amd_carrier *p, int lanes)
-{
-    if (!p || lanes < 0 || lanes > 64) return fail_msg(-3, "carrier: channels per wave is 0 (automatic) .. 64");
-    p->lanes = lanes;
-    return 0;
-}
-
+int csdr_amd_carrier_set_lanes(csdr_amd_carrier *p, int lanes) { return bank_set_lanes(p, "carrier", lanes); }
 int csdr_amd_carrier_lanes(const csdr_amd_carrier *p)
 {
     if (!p) return 0;
-    if (p->force_generic) return p->lanes ? p->lanes : default_lanes(p->n_ch, false);
-    return std::min(p->lanes ? p->lanes : default_lanes(p->n_ch, true), CMAX);
+    return p->force_generic ? bank_lanes(p, default_lanes(p->n_ch, false)) : bank_lanes(p, default_lanes(p->n_ch, true), CMAX);
 }
 
-int csdr_amd_carrier_force_generic(csdr_amd_carrier *p, int on) { if (!p) return fail_msg(-3, "carrier: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_carrier_kernel_name(const csdr_amd_carrier *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_carrier_force_generic(csdr_amd_carrier *p, int on) { return bank_force_generic(p, "carrier", on); }
+const char *csdr_amd_carrier_kernel_name(const csdr_amd_carrier *p) { return bank_kernel_name(p); }
 
 void csdr_amd_carrier_destroy(csdr_amd_carrier *p) { destroy_on_stream(p); }
 
@@ -242,15 +212,12 @@ int csdr_amd_carrier_process(csdr_amd_carrier *p, const csdr_complexf *in, long 
     a.out = (float *)out; a.err = error; a.dph = dphase; a.nco = (float *)nco; a.out_pitch = out_pitch;
     const bool aligned = !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)nco) & 7);
     if (!p->force_generic && aligned) {
-        const int C = std::min(p->lanes ? p->lanes : default_lanes(p->n_ch, true), CMAX);
-        a.lanes = C;
+        const int C = a.lanes = bank_launch_lanes(p, "k_carrier_tiled", default_lanes(p->n_ch, true), CMAX);
         if (tiled_lds(C) > 64 * 1024 && lds_attr_once((const void *)k_carrier_tiled, tiled_lds(CMAX)) < 0) return -2;
         hipLaunchKernelGGL(k_carrier_tiled, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C), p->c->stream, a, C);
-        p->last_kernel = "k_carrier_tiled";
     } else {
-        a.lanes = p->lanes ? p->lanes : default_lanes(p->n_ch, false);
+        a.lanes = bank_launch_lanes(p, "k_carrier", default_lanes(p->n_ch, false));
         hipLaunchKernelGGL(k_carrier, dim3(cdiv(p->n_ch, a.lanes)), dim3(64), 0, p->c->stream, a);
-        p->last_kernel = "k_carrier";
     }
     CSDR_LAUNCH_CHECK();
     return 0;
@@ -267,9 +234,7 @@ long long csdr_amd_debug_carrier_walk(const csdr_amd_carrier_params *params, con
     if (cfg.mode >= CARRIER_PLL_P && (out || error)) return fail_msg(-3, "carrier: the PLL modes give nco and dphase only");
     CarrierChan s{0.f, 0.f, 0.f};
     if (state_io) { if (check_chan(state_io) < 0) return -3; memcpy(&s, state_io, sizeof s); }
-    long long done = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        const long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
         CarrierChan t = s;                               // a call: state in, samples, state out
         for (long long j = done; j < done + m; j++) {
             CarrierSample o;
@@ -280,8 +245,7 @@ long long csdr_amd_debug_carrier_walk(const csdr_amd_carrier_params *params, con
             if (nco) { nco[j].i = o.nco.x; nco[j].q = o.nco.y; }
         }
         s = t;
-        done += m;
-    }
+    });
     if (state_io) memcpy(state_io, &s, sizeof s);
     return n;
 }

@@ -13,7 +13,7 @@
 //   k_pulsetx_generic  one thread per output, symbols and taps from global memory (modem_dev.hpp's pulsetx_output); every stage range and shape.
 //   k_pulsetx_hist     the H symbols behind the call into the other half of the history buffer.
 // Both output kernels add the same products in the same order (ascending t, fmaf), so they give the same bits.
-#include "common.hpp"
+#include "bank.hpp"
 #include "modem_dev.hpp"
 #include <limits.h>
 #include <math.h>
@@ -276,10 +276,10 @@ void csdr_amd::firdes_rrc_below(float *taps, int taps_length, int samples_per_sy
     for (int i = 0; i < taps_length; i++) taps[i] = taps[i] / sum;
 }
 
-struct csdr_amd_pulsetx {
-    csdr_amd_ctx *c; PulseTxCfg cfg; int n_ch; bool fits, force_generic; const char *last_kernel;
-    long long total;                                              // symbols every channel has taken since the last reset
-    int cur;                                                      // the half of d_hist that holds the history
+struct csdr_amd_pulsetx : Bank {
+    PulseTxCfg cfg; bool fits;
+    long long total = 0;                                          // symbols every channel has taken since the last reset
+    int cur = 0;                                                  // the half of d_hist that holds the history
     DevBuf<float2> d_sym, d_hist; DevBuf<float> d_taps;           // d_hist: 2 x n_ch x H
     size_t hist_half() const { return (size_t)n_ch * cfg.H; }
 };
@@ -289,15 +289,13 @@ extern "C" {
 csdr_amd_pulsetx *csdr_amd_pulsetx_create(csdr_amd_ctx *c, int n_channels, int n_psk, int interpolation, const float *host_taps, int taps_length, int first_stage,
                                           int last_stage)
 {
-    if (!c || n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "pulsetx: need a context and 1 <= n_channels <= 4194304"); return nullptr; }
+    if (bank_create_check("pulsetx", c, n_channels) < 0) return nullptr;
     if (first_stage == PULSETX_MOD && last_stage == PULSETX_MOD) { if (taps_length < 1) taps_length = 1; if (interpolation < 1) interpolation = 1; host_taps = nullptr; }
     else if (!host_taps) { fail_msg(-3, "pulsetx: taps are required up to the stage SHAPE"); return nullptr; }
     if (check_cfg(n_psk, interpolation, taps_length, first_stage, last_stage) < 0) return nullptr;
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "pulsetx: hipSetDevice"); return nullptr; }
     Owned<csdr_amd_pulsetx, csdr_amd_pulsetx_destroy> p(new csdr_amd_pulsetx());
-    p->c = c; p->cfg = make_cfg(interpolation, taps_length, first_stage, last_stage); p->n_ch = n_channels; p->last_kernel = "";
+    p->c = c; p->cfg = make_cfg(interpolation, taps_length, first_stage, last_stage); p->n_ch = n_channels;
     p->fits = last_stage == PULSETX_SHAPE && poly_lds_bytes(p->cfg.I, p->cfg.K) <= (size_t)POLY_LDS;
-    p->force_generic = false; p->total = 0; p->cur = 0;
     csdr_complexf sym[256];
     if (csdr_amd_psk31tx_tables(n_psk, 1, sym, nullptr) < 0) return nullptr;
     if (dev_alloc(p->d_sym, sizeof sym) != hipSuccess || dev_alloc(p->d_taps, sizeof(float) * taps_length) != hipSuccess ||
@@ -373,8 +371,8 @@ int csdr_amd_pulsetx_process(csdr_amd_pulsetx *p, const void *in, long long n_in
     return 0;
 }
 
-int csdr_amd_pulsetx_force_generic(csdr_amd_pulsetx *p, int on) { if (!p) return fail_msg(-3, "pulsetx: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_pulsetx_kernel_name(const csdr_amd_pulsetx *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_pulsetx_force_generic(csdr_amd_pulsetx *p, int on) { return bank_force_generic(p, "pulsetx", on); }
+const char *csdr_amd_pulsetx_kernel_name(const csdr_amd_pulsetx *p) { return bank_kernel_name(p); }
 
 void csdr_amd_pulsetx_destroy(csdr_amd_pulsetx *p) { destroy_on_stream(p); }
 
@@ -396,10 +394,9 @@ long long csdr_amd_debug_pulsetx_walk(int n_psk, int interpolation, const float 
     std::vector<float2> hist(std::max(g.H, 1), make_float2(0.f, 0.f)), next(hist);
     const size_t isz = first_stage == PULSETX_SHAPE ? sizeof(float2) : 1;
     float2 *y = (float2 *)out;
-    long long done = 0, w = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        const long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
-        if (!m) continue;
+    long long w = 0;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
+        if (!m) return;
         const char *x = (const char *)in + done * isz;
         const PulseTxCall k = make_call(g, done, m);
         const PulseTxSrc s{hist.data(), first_stage == PULSETX_MOD ? (const uint8_t *)x : nullptr, first_stage == PULSETX_SHAPE ? (const float2 *)x : nullptr, sym};
@@ -409,8 +406,7 @@ long long csdr_amd_debug_pulsetx_walk(int n_psk, int interpolation, const float 
             for (int h = 0; h < g.H; h++) next[h] = pulsetx_next_hist(g, k, s, h);
             hist.swap(next);
         }
-        done += m;
-    }
+    });
     return w;
 }
 

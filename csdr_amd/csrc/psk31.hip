@@ -9,7 +9,7 @@
 // of the AGC is computed there by all lanes, and one lane per channel is left with the gain recurrence and the per-symbol work.  Every other stage range,
 // and a decimation whose ring does not fit in LDS, runs on k_psk31 (one lane per channel, straight from global memory).  Both give the same bits.
 // csdr_amd_psk31_set_lanes sets the channels per wave, csdr_amd_psk31_force_generic(1) takes k_psk31 always.
-#include "common.hpp"
+#include "bank.hpp"
 #include "psk31_dev.hpp"
 #include <math.h>
 #include <string.h>
@@ -226,9 +226,9 @@ Psk31Chan fresh_chan() { Psk31Chan s; memset(&s, 0, sizeof s); s.gain = 1.f; ret
 
 } // namespace
 
-struct csdr_amd_psk31 {
-    csdr_amd_ctx *c; Psk31Cfg cfg; int n_ch, tail_cap, lanes, cus, ring; bool force_generic; const char *last_kernel;
-    DevBuf<Psk31Chan> d_st; DevBuf<float2> d_tail; DevBuf<uint8_t> d_dec;
+struct csdr_amd_psk31 : ChanBank<Psk31Chan> {
+    Psk31Cfg cfg; int tail_cap, cus, ring;
+    DevBuf<float2> d_tail; DevBuf<uint8_t> d_dec;
 };
 
 extern "C" {
@@ -236,14 +236,12 @@ extern "C" {
 csdr_amd_psk31 *csdr_amd_psk31_create(csdr_amd_ctx *c, const csdr_amd_psk31_params *params, int n_channels, int first_stage, int last_stage)
 {
     Psk31Cfg cfg;
-    if (!c || n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "psk31: need a context and 1 <= n_channels <= 4194304"); return nullptr; }
-    if (make_cfg(params, first_stage, last_stage, &cfg) < 0) return nullptr;
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "psk31: hipSetDevice"); return nullptr; }
+    if (bank_create_check("psk31", c, n_channels) < 0 || make_cfg(params, first_stage, last_stage, &cfg) < 0) return nullptr;
     Owned<csdr_amd_psk31, csdr_amd_psk31_destroy> p(new csdr_amd_psk31());
-    p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->last_kernel = "";
+    p->c = c; p->cfg = cfg; p->n_ch = n_channels;
     const bool timing = first_stage <= PSK31_TIMING && last_stage >= PSK31_TIMING;
     p->tail_cap = timing ? 3 * cfg.hb + 1 : 1;
-    p->lanes = 0; p->cus = current_device_cu_count(); p->force_generic = false;
+    p->cus = current_device_cu_count();
     p->ring = first_stage == PSK31_AGC && last_stage >= PSK31_TIMING ? tiled_ring(cfg.hb) : 0;     // 0: the stage range runs on k_psk31
     if (dev_alloc(p->d_st, sizeof(Psk31Chan) * n_channels) != hipSuccess || dev_alloc(p->d_tail, sizeof(float2) * (size_t)p->tail_cap * n_channels) != hipSuccess ||
         dev_alloc(p->d_dec, 1024) != hipSuccess) { fail_msg(-2, "psk31: out of device memory"); return nullptr; }
@@ -251,41 +249,19 @@ csdr_amd_psk31 *csdr_amd_psk31_create(csdr_amd_ctx *c, const csdr_amd_psk31_para
     return p.release();
 }
 
-int csdr_amd_psk31_reset(csdr_amd_psk31 *p)
-{
-    if (!p) return fail_msg(-3, "psk31: null object");
-    std::vector<Psk31Chan> h(p->n_ch, fresh_chan());
-    return csdr_amd_h2d(p->c, p->d_st.get(), h.data(), sizeof(Psk31Chan) * h.size());
-}
-
-int csdr_amd_psk31_reset_channel(csdr_amd_psk31 *p, int ch)
-{
-    if (!p || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31: channel out of range");
-    const Psk31Chan s = fresh_chan();
-    return csdr_amd_psk31_set_channel(p, ch, (const csdr_amd_psk31_chan *)&s);
-}
-
-int csdr_amd_psk31_get_channel(csdr_amd_psk31 *p, int ch, csdr_amd_psk31_chan *out)
-{
-    if (!p || !out || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31: channel out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_d2h(p->c, out, p->d_st.get() + ch, sizeof(Psk31Chan));
-}
+int csdr_amd_psk31_reset(csdr_amd_psk31 *p) { const Psk31Chan s = fresh_chan(); return bank_reset(p, "psk31", &s); }
+int csdr_amd_psk31_reset_channel(csdr_amd_psk31 *p, int ch) { return bank_reset_channel(p, "psk31", ch, fresh_chan()); }
+int csdr_amd_psk31_get_channel(csdr_amd_psk31 *p, int ch, csdr_amd_psk31_chan *out) { return bank_get_channel(p, "psk31", ch, out); }
 
 int csdr_amd_psk31_set_channel(csdr_amd_psk31 *p, int ch, const csdr_amd_psk31_chan *s)
 {
-    if (!p || !s || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31: channel out of range");
-    if (s->tail_len < 0 || s->tail_len > p->tail_cap - 1 || (s->tail_len && p->tail_cap == 1)) return fail_msg(-3, "psk31: tail_len out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_h2d(p->c, p->d_st.get() + ch, s, sizeof(Psk31Chan));
+    return bank_set_channel(p, "psk31", ch, s, [&] {
+        const bool ok = s->tail_len >= 0 && s->tail_len <= p->tail_cap - 1 && !(s->tail_len && p->tail_cap == 1);
+        return ok ? 0 : fail_msg(-3, "psk31: tail_len out of range");
+    });
 }
 
-int csdr_amd_psk31_set_lanes(csdr_amd_psk31 *p, int lanes)
-{
-    if (!p || lanes < 0 || lanes > 64) return fail_msg(-3, "psk31: lanes per wave is 0 (automatic) .. 64");
-    p->lanes = lanes;
-    return 0;
-}
+int csdr_amd_psk31_set_lanes(csdr_amd_psk31 *p, int lanes) { return bank_set_lanes(p, "psk31", lanes); }
 
 long long csdr_amd_psk31_max_out(const csdr_amd_psk31 *p, long long n_in)
 {
@@ -306,32 +282,24 @@ int csdr_amd_psk31_process(csdr_amd_psk31 *p, const void *in, long long n_in, si
     csdr_amd_ctx *c = p->c;
     int C = 0;
     if (p->ring && !p->force_generic) {
-        C = std::min(p->lanes ? p->lanes : default_lanes(p->cus, p->n_ch, true), 16);      // (k_psk31_tiled holds one sample per channel ahead: 16 at most)
+        C = bank_launch_lanes(p, "k_psk31_tiled", default_lanes(p->cus, p->n_ch, true), 16);      // (k_psk31_tiled holds one sample per channel ahead: 16 at most)
         while (C > 0 && tiled_lds(C, p->ring) > (size_t)TILED_LDS) C--;
     }
     if (C > 0) {
         hipLaunchKernelGGL(k_psk31_tiled, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C, p->ring), c->stream, p->cfg, p->d_st.get(), p->d_tail.get(), p->tail_cap,
                            p->n_ch, C, p->ring, (const float2 *)in, n_in, in_pitch, out, out_pitch, counts, err, idx, p->d_dec.get());
-        p->last_kernel = "k_psk31_tiled";
     } else {
-        const int lanes = p->lanes ? p->lanes : default_lanes(p->cus, p->n_ch, false);
+        const int lanes = bank_launch_lanes(p, "k_psk31", default_lanes(p->cus, p->n_ch, false));
         hipLaunchKernelGGL(k_psk31, dim3(cdiv(p->n_ch, lanes)), dim3(64), 0, c->stream, p->cfg, p->d_st.get(), p->d_tail.get(), p->tail_cap, p->n_ch, lanes,
                            in, n_in, in_pitch, out, out_pitch, counts, err, idx, p->d_dec.get());
-        p->last_kernel = "k_psk31";
     }
     CSDR_LAUNCH_CHECK();
     return 0;
 }
 
-int csdr_amd_psk31_force_generic(csdr_amd_psk31 *p, int on) { if (!p) return fail_msg(-3, "psk31: null object"); p->force_generic = on != 0; return 0; }
-
-int csdr_amd_psk31_lanes(const csdr_amd_psk31 *p)
-{
-    if (!p) return 0;
-    if (p->lanes) return p->lanes;
-    return default_lanes(p->cus, p->n_ch, p->ring && !p->force_generic);
-}
-const char *csdr_amd_psk31_kernel_name(const csdr_amd_psk31 *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_psk31_force_generic(csdr_amd_psk31 *p, int on) { return bank_force_generic(p, "psk31", on); }
+int csdr_amd_psk31_lanes(const csdr_amd_psk31 *p) { return p ? bank_lanes(p, default_lanes(p->cus, p->n_ch, p->ring && !p->force_generic)) : 0; }
+const char *csdr_amd_psk31_kernel_name(const csdr_amd_psk31 *p) { return bank_kernel_name(p); }
 
 void csdr_amd_psk31_destroy(csdr_amd_psk31 *p) { destroy_on_stream(p); }
 
@@ -364,16 +332,14 @@ long long csdr_amd_debug_psk31_walk(const csdr_amd_psk31_params *params, int fir
     std::vector<float2> tail(3 * (size_t)cfg.hb + 2);
     if (s.tail_len < 0 || (size_t)s.tail_len >= tail.size()) return fail_msg(-3, "debug_psk31_walk: tail_len out of range");
     const size_t isz = first_stage == PSK31_VARICODE ? 1 : sizeof(float2), osz = last_stage <= PSK31_TIMING ? sizeof(float2) : 1;
-    long long done = 0, k = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
+    long long k = 0;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
         const char *x = (const char *)in + done * isz;
         Psk31Out o{nullptr, nullptr, err ? err + k : nullptr, idx ? idx + k : nullptr};
         if (last_stage <= PSK31_TIMING) o.c = (float2 *)((char *)out + k * osz); else o.b = (uint8_t *)out + k;
         k += psk31_walk(cfg, s, tail.data(), first_stage <= PSK31_DBPSK ? (const float2 *)x : nullptr, first_stage == PSK31_VARICODE ? (const uint8_t *)x : nullptr,
                         m, o, varicode_dec().t);
-        done += m;
-    }
+    });
     if (state_io) memcpy(state_io, &s, sizeof s);
     return k;
 }

@@ -15,7 +15,7 @@
 //                    Workgroups past a channel's count leave without storing.
 // The fused path needs both tables and the states of a tile in LDS: 8 I + 4 (TILE_S / 32 + 8) bytes within 63 KiB, that is I <= FUSED_MAX_I = 7904; a
 // larger I takes the generic path, as does a grid of more than 2^31 - 1 workgroups.  Both paths give the same bits.
-#include "common.hpp"
+#include "bank.hpp"
 #include "psk31tx_dev.hpp"
 #include <limits.h>
 #include <math.h>
@@ -228,6 +228,8 @@ struct HostTab {
     Psk31TxTab tab() const { return Psk31TxTab{vc, sym, rate.data(), rate1m.data()}; }
 };
 
+const Psk31TxChan FRESH = {};      // state 0 (csdr.c:2823), last symbol 0 + 0i (csdr.c:2736-2738); static storage: the padding bytes are 0 too
+
 long long max_out_of(int first, int last, int I, long long n_in)
 {
     long long m = n_in;
@@ -238,10 +240,10 @@ long long max_out_of(int first, int last, int I, long long n_in)
 
 } // namespace
 
-struct csdr_amd_psk31tx {
-    csdr_amd_ctx *c; Psk31TxCfg cfg; int n_ch, n_psk; bool fused, force_generic; const char *last_kernel; float2 sym0, sym1;
-    DevBuf<Psk31TxChan> d_st; DevBuf<uint16_t> d_vc; DevBuf<float2> d_sym; DevBuf<float> d_rate;      // d_rate: rate[I] then rate1m[I]
-    DevBuf<uint32_t> d_bits; size_t bits_pitch; DevBuf<float2> d_prev;                                // the plan kernel's rows, grown on demand
+struct csdr_amd_psk31tx : ChanBank<Psk31TxChan> {
+    Psk31TxCfg cfg; int n_psk; bool fused; float2 sym0, sym1;
+    DevBuf<uint16_t> d_vc; DevBuf<float2> d_sym; DevBuf<float> d_rate;                                // d_rate: rate[I] then rate1m[I]
+    DevBuf<uint32_t> d_bits; size_t bits_pitch = 0; DevBuf<float2> d_prev;                            // the plan kernel's rows, grown on demand
     Psk31TxTab tab() const { return Psk31TxTab{d_vc.get(), d_sym.get(), d_rate.get(), d_rate.get() + cfg.I}; }
 };
 
@@ -249,13 +251,10 @@ extern "C" {
 
 csdr_amd_psk31tx *csdr_amd_psk31tx_create(csdr_amd_ctx *c, int n_channels, int n_psk, int interpolation, int first_stage, int last_stage)
 {
-    if (!c || n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "psk31tx: need a context and 1 <= n_channels <= 4194304"); return nullptr; }
-    if (check_cfg(n_psk, interpolation, first_stage, last_stage) < 0) return nullptr;
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "psk31tx: hipSetDevice"); return nullptr; }
+    if (bank_create_check("psk31tx", c, n_channels) < 0 || check_cfg(n_psk, interpolation, first_stage, last_stage) < 0) return nullptr;
     Owned<csdr_amd_psk31tx, csdr_amd_psk31tx_destroy> p(new csdr_amd_psk31tx());
-    p->c = c; p->cfg = Psk31TxCfg{first_stage, last_stage, interpolation}; p->n_ch = n_channels; p->n_psk = n_psk; p->last_kernel = "";
+    p->c = c; p->cfg = Psk31TxCfg{first_stage, last_stage, interpolation}; p->n_ch = n_channels; p->n_psk = n_psk;
     p->fused = first_stage == PSK31TX_VARICODE && last_stage == PSK31TX_SHAPE && interpolation <= FUSED_MAX_I;
-    p->force_generic = false; p->bits_pitch = 0;
     const HostTab h(n_psk, interpolation);
     p->sym0 = h.sym[0]; p->sym1 = h.sym[1];
     const size_t I = (size_t)interpolation;
@@ -268,36 +267,18 @@ csdr_amd_psk31tx *csdr_amd_psk31tx_create(csdr_amd_ctx *c, int n_channels, int n
     return p.release();
 }
 
-int csdr_amd_psk31tx_reset(csdr_amd_psk31tx *p)
-{
-    if (!p) return fail_msg(-3, "psk31tx: null object");
-    std::vector<Psk31TxChan> h(p->n_ch);
-    memset(h.data(), 0, sizeof(Psk31TxChan) * h.size());          // state 0 (csdr.c:2823), last symbol 0 + 0i (csdr.c:2736-2738)
-    return csdr_amd_h2d(p->c, p->d_st.get(), h.data(), sizeof(Psk31TxChan) * h.size());
-}
-
-int csdr_amd_psk31tx_reset_channel(csdr_amd_psk31tx *p, int ch)
-{
-    if (!p || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31tx: channel out of range");
-    csdr_amd_psk31tx_chan s; memset(&s, 0, sizeof s);
-    return csdr_amd_psk31tx_set_channel(p, ch, &s);
-}
-
-int csdr_amd_psk31tx_get_channel(csdr_amd_psk31tx *p, int ch, csdr_amd_psk31tx_chan *out)
-{
-    if (!p || !out || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31tx: channel out of range");
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_d2h(p->c, out, p->d_st.get() + ch, sizeof(Psk31TxChan));
-}
+int csdr_amd_psk31tx_reset(csdr_amd_psk31tx *p) { return bank_reset(p, "psk31tx", &FRESH); }
+int csdr_amd_psk31tx_reset_channel(csdr_amd_psk31tx *p, int ch) { return bank_reset_channel(p, "psk31tx", ch, FRESH); }
+int csdr_amd_psk31tx_get_channel(csdr_amd_psk31tx *p, int ch, csdr_amd_psk31tx_chan *out) { return bank_get_channel(p, "psk31tx", ch, out); }
 
 int csdr_amd_psk31tx_set_channel(csdr_amd_psk31tx *p, int ch, const csdr_amd_psk31tx_chan *s)
 {
-    if (!p || !s || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "psk31tx: channel out of range");
-    if (p->fused && s->diff_state > 1) return fail_msg(-3, "psk31tx: diff_state is 0 or 1 for the range VARICODE .. SHAPE");   // (its packed states hold one bit)
-    Psk31TxChan h; memset(&h, 0, sizeof h);                       // (padding bytes defined)
-    h.diff_state = s->diff_state; h.last_i = s->last_i; h.last_q = s->last_q;
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_h2d(p->c, p->d_st.get() + ch, &h, sizeof h);
+    Psk31TxChan h; memset(&h, 0, sizeof h);                       // (what is uploaded: the caller's fields, padding bytes defined)
+    return bank_set_channel(p, "psk31tx", ch, s, [&] {
+        if (p->fused && s->diff_state > 1) return fail_msg(-3, "psk31tx: diff_state is 0 or 1 for the range VARICODE .. SHAPE");   // (its packed states hold one bit)
+        h.diff_state = s->diff_state; h.last_i = s->last_i; h.last_q = s->last_q;
+        return 0;
+    }, &h);
 }
 
 long long csdr_amd_psk31tx_max_out(const csdr_amd_psk31tx *p, long long n_in)
@@ -344,8 +325,8 @@ int csdr_amd_psk31tx_process(csdr_amd_psk31tx *p, const void *in, long long n_in
     return 0;
 }
 
-int csdr_amd_psk31tx_force_generic(csdr_amd_psk31tx *p, int on) { if (!p) return fail_msg(-3, "psk31tx: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_psk31tx_kernel_name(const csdr_amd_psk31tx *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_psk31tx_force_generic(csdr_amd_psk31tx *p, int on) { return bank_force_generic(p, "psk31tx", on); }
+const char *csdr_amd_psk31tx_kernel_name(const csdr_amd_psk31tx *p) { return bank_kernel_name(p); }
 
 void csdr_amd_psk31tx_destroy(csdr_amd_psk31tx *p) { destroy_on_stream(p); }
 
@@ -402,17 +383,15 @@ long long csdr_amd_debug_psk31tx_walk(int n_psk, int interpolation, int first_st
     const HostTab h(n_psk, interpolation);
     const Psk31TxCfg cfg{first_stage, last_stage, interpolation};
     const Psk31TxTab t = h.tab();
-    Psk31TxChan s; memset(&s, 0, sizeof s);
+    Psk31TxChan s = FRESH;
     if (state_io) { s.diff_state = state_io->diff_state; s.last_i = state_io->last_i; s.last_q = state_io->last_q; }
     const size_t isz = first_stage == PSK31TX_SHAPE ? sizeof(float2) : 1, osz = last_stage >= PSK31TX_MOD ? sizeof(float2) : 1;
-    long long done = 0, k = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        const long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
+    long long k = 0;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
         const char *x = (const char *)in + done * isz;
         char *y = (char *)out + k * osz;
         k += psk31tx_walk(cfg, s, t, (const uint8_t *)x, (const float2 *)x, m, (uint8_t *)y, (float2 *)y);
-        done += m;
-    }
+    });
     if (state_io) { state_io->diff_state = s.diff_state; state_io->last_i = s.last_i; state_io->last_q = s.last_q; }
     return k;
 }

@@ -20,7 +20,7 @@
 // i I + I - 1 + T <= total I.  k_interp_poly: one thread per position, the positions' input staged in LDS, the phases in wave-uniform chunks of IC (taps are
 // scalar loads); each chunk's outputs are staged through LDS and written row by row, so consecutive lanes store consecutive complex values (for I <= 8 the
 // tile's output is one contiguous run).  k_interp_generic: one thread per output.  Same summation order (k ascending, fmaf per component) in both.
-#include "common.hpp"
+#include "bank.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -225,8 +225,8 @@ int upload_table(csdr_amd_ctx *c, DevBuf<RrSeg> &buf, int &cap, const std::vecto
 
 } // namespace
 
-struct csdr_amd_resampler {
-    csdr_amd_ctx *c; int I, D, T, n_streams, P, Dg, H, cli_bufsize; bool force_generic; const char *last_kernel;
+struct csdr_amd_resampler : Bank {                        // (n_ch: the streams)
+    int I, D, T, P, Dg, H, cli_bufsize = 0;
     int M, Cp; size_t lds;                                                // k_rr_poly's tile (M = 0: the shape runs on k_rr_generic)
     long long total;                                                      // input samples per stream seen since the last reset
     long long s_next; int d_next;                                         // streaming: the next output (absolute input index, tap phase)
@@ -236,8 +236,8 @@ struct csdr_amd_resampler {
     int Kpad; int cur; DevBuf<float> d_hist[2], d_taps, d_tpm; DevBuf<int> d_offt; DevBuf<RrSeg> d_tab; int tab_cap;
 };
 
-struct csdr_amd_interp {
-    csdr_amd_ctx *c; int I, T, n_streams, H, Kmax, cli_bufsize; bool force_generic; const char *last_kernel;
+struct csdr_amd_interp : Bank {                           // (n_ch: the streams)
+    int I, T, H, Kmax, cli_bufsize = 0;
     long long total, pos_next;
     int cur; DevBuf<float2> d_hist[2]; DevBuf<float> d_taps;
 };
@@ -248,7 +248,7 @@ int rr_alloc_hist(csdr_amd_resampler *r)
 {
     const int need = std::max({r->T / r->I + 2, r->D / r->I + 3, r->cli_bufsize}) + 2;      // (a capped output waits up to D/I + 1 samples back)
     r->H = (need + 3) & ~3;
-    for (auto &h : r->d_hist) CSDR_HIP(dev_alloc(h, sizeof(float) * (size_t)r->H * r->n_streams + 256));
+    for (auto &h : r->d_hist) CSDR_HIP(dev_alloc(h, sizeof(float) * (size_t)r->H * r->n_ch + 256));
     return 0;
 }
 
@@ -256,7 +256,7 @@ int ip_alloc_hist(csdr_amd_interp *p)
 {
     const int need = p->T / p->I + 3 + p->cli_bufsize;
     p->H = (need + 3) & ~3;
-    for (auto &h : p->d_hist) CSDR_HIP(dev_alloc(h, sizeof(float2) * (size_t)p->H * p->n_streams + 256));
+    for (auto &h : p->d_hist) CSDR_HIP(dev_alloc(h, sizeof(float2) * (size_t)p->H * p->n_ch + 256));
     return 0;
 }
 
@@ -301,9 +301,9 @@ csdr_amd_resampler *csdr_amd_resampler_create(csdr_amd_ctx *c, int interpolation
         return nullptr;
     }
     Owned<csdr_amd_resampler, csdr_amd_resampler_destroy> r(new csdr_amd_resampler());
-    r->c = c; r->I = interpolation; r->D = decimation; r->T = taps_length; r->n_streams = n_streams;
+    r->c = c; r->I = interpolation; r->D = decimation; r->T = taps_length; r->n_ch = n_streams;
     const int g = std::gcd(interpolation, decimation);
-    r->P = interpolation / g; r->Dg = decimation / g; r->cli_bufsize = 0; r->cli_pmin = 1; r->force_generic = false; r->last_kernel = ""; r->tab_cap = 0;
+    r->P = interpolation / g; r->Dg = decimation / g; r->cli_pmin = 1; r->tab_cap = 0;
     // k_rr_poly's tile: the largest M (a multiple of 64) whose LDS fits the budget
     const int Kmax = taps_length / interpolation;
     r->M = 0; r->Cp = 0; r->lds = 0;
@@ -335,7 +335,7 @@ int csdr_amd_resampler_reset(csdr_amd_resampler *r)
     if (!r) return fail_msg(-3, "resampler: null object");
     r->total = 0; r->s_next = 0; r->d_next = 0; r->emitted = 0; r->win_a = 0; r->win_L = 0; r->cur = 0;
     // (positions before the stream's start are never read)
-    return csdr_amd_memset(r->c, r->d_hist[0].get(), 0, sizeof(float) * (size_t)r->H * r->n_streams) < 0 ? -5 : 0;
+    return csdr_amd_memset(r->c, r->d_hist[0].get(), 0, sizeof(float) * (size_t)r->H * r->n_ch) < 0 ? -5 : 0;
 }
 
 int csdr_amd_resampler_set_cli_bufsize(csdr_amd_resampler *r, int the_bufsize)
@@ -368,8 +368,8 @@ int csdr_amd_resampler_window(int I, int D, int T, int input_size, int last_taps
     return 0;
 }
 
-int csdr_amd_resampler_force_generic(csdr_amd_resampler *r, int on) { if (!r) return -3; r->force_generic = on != 0; return 0; }
-const char *csdr_amd_resampler_kernel_name(const csdr_amd_resampler *r) { return r ? r->last_kernel : ""; }
+int csdr_amd_resampler_force_generic(csdr_amd_resampler *r, int on) { return bank_force_generic(r, "resampler", on); }
+const char *csdr_amd_resampler_kernel_name(const csdr_amd_resampler *r) { return bank_kernel_name(r); }
 
 void csdr_amd_resampler_destroy(csdr_amd_resampler *r) { destroy_on_stream(r); }
 
@@ -420,17 +420,17 @@ int csdr_amd_resampler_process(csdr_amd_resampler *r, const float *in, long long
                 for (int t = 0; (long long)t * per < g.count; t++)
                     tiles.push_back(RrSeg{g.s + t * r->M * r->Dg, g.d0, g.out0 + t * per, std::min(per, g.count - t * per)});
             if (upload_table(c, r->d_tab, r->tab_cap, tiles) < 0) return -5;
-            hipLaunchKernelGGL(k_rr_poly, dim3((unsigned)tiles.size(), r->n_streams), dim3(RR_THREADS), r->lds, c->stream, r->d_hist[r->cur].get(), r->H, (size_t)r->H,
+            hipLaunchKernelGGL(k_rr_poly, dim3((unsigned)tiles.size(), r->n_ch), dim3(RR_THREADS), r->lds, c->stream, r->d_hist[r->cur].get(), r->H, (size_t)r->H,
                                in, in_pitch, n_in, out, out_pitch, r->d_tab.get(), r->I, r->D, r->T, r->P, r->Dg, r->M, r->Cp, r->d_tpm.get(), r->Kpad, r->d_offt.get());
         } else {
             if (upload_table(c, r->d_tab, r->tab_cap, segs) < 0) return -5;
-            hipLaunchKernelGGL(k_rr_generic, dim3(cdiv(n, 256), r->n_streams), dim3(256), 0, c->stream, r->d_hist[r->cur].get(), r->H, (size_t)r->H,
+            hipLaunchKernelGGL(k_rr_generic, dim3(cdiv(n, 256), r->n_ch), dim3(256), 0, c->stream, r->d_hist[r->cur].get(), r->H, (size_t)r->H,
                                in, in_pitch, n_in, out, out_pitch, r->d_tab.get(), (int)segs.size(), (int)n, r->I, r->D, r->T, r->d_taps.get());
         }
         CSDR_LAUNCH_CHECK();
         r->last_kernel = poly ? "k_rr_poly" : "k_rr_generic";
     }
-    if (hist_advance(c, r->d_hist[r->cur].get(), r->d_hist[r->cur ^ 1].get(), r->H, (size_t)r->H, in, in_pitch, n_in, r->n_streams) < 0) return -5;
+    if (hist_advance(c, r->d_hist[r->cur].get(), r->d_hist[r->cur ^ 1].get(), r->H, (size_t)r->H, in, in_pitch, n_in, r->n_ch) < 0) return -5;
     r->cur ^= 1;
     r->total = total_after;
     if (n_out) *n_out = n;
@@ -445,7 +445,7 @@ csdr_amd_interp *csdr_amd_interp_create(csdr_amd_ctx *c, int interpolation, cons
         return nullptr;
     }
     Owned<csdr_amd_interp, csdr_amd_interp_destroy> p(new csdr_amd_interp());
-    p->c = c; p->I = interpolation; p->T = taps_length; p->n_streams = n_streams; p->cli_bufsize = 0; p->force_generic = false; p->last_kernel = "";
+    p->c = c; p->I = interpolation; p->T = taps_length; p->n_ch = n_streams;
     p->Kmax = 0;
     for (int ip = 0; ip < interpolation; ip++) p->Kmax = std::max(p->Kmax, interp_taps(taps_length, interpolation, ip));
     if (sizeof(float2) * (256 * 9 + (size_t)p->Kmax) <= (size_t)IP_LDS_BUDGET) {
@@ -462,7 +462,7 @@ int csdr_amd_interp_reset(csdr_amd_interp *p)
 {
     if (!p) return fail_msg(-3, "interp: null object");
     p->total = p->cli_bufsize; p->pos_next = 0; p->cur = 0;                 // cli_bufsize mode: the CLI's first pass runs over a buffer of zeros (csdr.c:1218-1221)
-    return csdr_amd_memset(p->c, p->d_hist[0].get(), 0, sizeof(float2) * (size_t)p->H * p->n_streams) < 0 ? -5 : 0;
+    return csdr_amd_memset(p->c, p->d_hist[0].get(), 0, sizeof(float2) * (size_t)p->H * p->n_ch) < 0 ? -5 : 0;
 }
 
 int csdr_amd_interp_set_cli_bufsize(csdr_amd_interp *p, int the_bufsize)
@@ -475,8 +475,8 @@ int csdr_amd_interp_set_cli_bufsize(csdr_amd_interp *p, int the_bufsize)
     return csdr_amd_interp_reset(p);
 }
 
-int csdr_amd_interp_force_generic(csdr_amd_interp *p, int on) { if (!p) return -3; p->force_generic = on != 0; return 0; }
-const char *csdr_amd_interp_kernel_name(const csdr_amd_interp *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_interp_force_generic(csdr_amd_interp *p, int on) { return bank_force_generic(p, "interp", on); }
+const char *csdr_amd_interp_kernel_name(const csdr_amd_interp *p) { return bank_kernel_name(p); }
 
 void csdr_amd_interp_destroy(csdr_amd_interp *p) { destroy_on_stream(p); }
 
@@ -506,19 +506,19 @@ int csdr_amd_interp_process(csdr_amd_interp *p, const csdr_complexf *in, long lo
         const size_t lds = sizeof(float2) * (256 * (1 + (size_t)IC) + (size_t)p->Kmax);
         const bool poly = sizeof(float2) * (256 * 9 + (size_t)p->Kmax) <= (size_t)IP_LDS_BUDGET && !p->force_generic;
         if (poly) {
-            const dim3 grid(cdiv(n_pos, 256), p->n_streams);
+            const dim3 grid(cdiv(n_pos, 256), p->n_ch);
 #define IP_LAUNCH(ICV) hipLaunchKernelGGL(k_interp_poly<ICV>, grid, dim3(256), lds, c->stream, h, p->H, (size_t)p->H, x, in_pitch, n_in, o, out_pitch, pos0, (int)n_pos, p->I, p->T, p->Kmax, p->d_taps.get())
             if (IC == 8) IP_LAUNCH(8); else if (IC == 4) IP_LAUNCH(4); else if (IC == 2) IP_LAUNCH(2); else IP_LAUNCH(1);
 #undef IP_LAUNCH
         } else {
-            hipLaunchKernelGGL(k_interp_generic, dim3(cdiv(n, 256), p->n_streams), dim3(256), 0, c->stream, h, p->H, (size_t)p->H, x, in_pitch, n_in, o, out_pitch,
+            hipLaunchKernelGGL(k_interp_generic, dim3(cdiv(n, 256), p->n_ch), dim3(256), 0, c->stream, h, p->H, (size_t)p->H, x, in_pitch, n_in, o, out_pitch,
                                pos0, (int)n_pos, p->I, p->T, p->d_taps.get());
         }
         CSDR_LAUNCH_CHECK();
         p->last_kernel = poly ? "k_interp_poly" : "k_interp_generic";
         p->pos_next += n_pos;
     }
-    if (hist_advance(c, (const float2 *)p->d_hist[p->cur].get(), p->d_hist[p->cur ^ 1].get(), p->H, (size_t)p->H, (const float2 *)in, in_pitch, n_in, p->n_streams) < 0) return -5;
+    if (hist_advance(c, (const float2 *)p->d_hist[p->cur].get(), p->d_hist[p->cur ^ 1].get(), p->H, (size_t)p->H, (const float2 *)in, in_pitch, n_in, p->n_ch) < 0) return -5;
     p->cur ^= 1;
     p->total = total_after;
     if (n_out) *n_out = n;

@@ -12,7 +12,7 @@
 // The serial decoder walks each channel's windows with one wave per channel (k_rtty_walk): the start-edge scan takes 64 samples per step, the bit sums
 // and the reference's index arithmetic run in the shared step function; the remainder of a channel's window (< B samples) and its complex history
 // (< L samples) stay on the device between calls.
-#include "common.hpp"
+#include "bank.hpp"
 #include "rtty_dev.hpp"
 #include <math.h>
 #include <string.h>
@@ -331,9 +331,9 @@ const char *launch_bfsk(hipStream_t stream, bool generic, const float2 *in, size
 
 } // namespace
 
-struct csdr_amd_rtty {
-    csdr_amd_ctx *c; RttyCfg cfg; int n_ch, hist_cap, cus; bool force_generic; const char *last_kernel; size_t mid_cap;
-    DevBuf<RttyChan> d_st; DevBuf<float2> d_hist; DevBuf<float> d_rem, d_mid; DevBuf<float2> d_taps; DevBuf<int> d_mid_cnt;
+struct csdr_amd_rtty : ChanBank<RttyChan> {
+    RttyCfg cfg; int hist_cap, cus; size_t mid_cap = 0;
+    DevBuf<float2> d_hist; DevBuf<float> d_rem, d_mid; DevBuf<float2> d_taps; DevBuf<int> d_mid_cnt;
 };
 
 extern "C" {
@@ -341,11 +341,9 @@ extern "C" {
 csdr_amd_rtty *csdr_amd_rtty_create(csdr_amd_ctx *c, const csdr_amd_rtty_params *params, int n_channels, int first_stage, int last_stage)
 {
     RttyCfg cfg;
-    if (!c || n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "rtty: need a context and 1 <= n_channels <= 4194304"); return nullptr; }
-    if (make_cfg(params, first_stage, last_stage, &cfg) < 0) return nullptr;
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "rtty: hipSetDevice"); return nullptr; }
+    if (bank_create_check("rtty", c, n_channels) < 0 || make_cfg(params, first_stage, last_stage, &cfg) < 0) return nullptr;
     Owned<csdr_amd_rtty, csdr_amd_rtty_destroy> p(new csdr_amd_rtty());
-    p->c = c; p->cfg = cfg; p->n_ch = n_channels; p->force_generic = false; p->last_kernel = ""; p->mid_cap = 0;
+    p->c = c; p->cfg = cfg; p->n_ch = n_channels;
     p->cus = current_device_cu_count();
     const bool bfsk = first_stage == RTTY_BFSK, serial = first_stage <= RTTY_SERIAL && last_stage >= RTTY_SERIAL;
     p->hist_cap = bfsk ? std::max(1, cfg.L - 1) : 1;
@@ -363,20 +361,8 @@ csdr_amd_rtty *csdr_amd_rtty_create(csdr_amd_ctx *c, const csdr_amd_rtty_params 
     return p.release();
 }
 
-int csdr_amd_rtty_reset(csdr_amd_rtty *p)
-{
-    if (!p) return fail_msg(-3, "rtty: null object");
-    std::vector<RttyChan> h(p->n_ch, fresh_chan());
-    return csdr_amd_h2d(p->c, p->d_st.get(), h.data(), sizeof(RttyChan) * h.size());
-}
-
-int csdr_amd_rtty_reset_channel(csdr_amd_rtty *p, int ch)
-{
-    if (!p || ch < 0 || ch >= p->n_ch) return fail_msg(-3, "rtty: channel out of range");
-    const RttyChan s = fresh_chan();
-    if (csdr_amd_ctx_sync(p->c) < 0) return -5;
-    return csdr_amd_h2d(p->c, p->d_st.get() + ch, &s, sizeof s);
-}
+int csdr_amd_rtty_reset(csdr_amd_rtty *p) { const RttyChan s = fresh_chan(); return bank_reset(p, "rtty", &s); }
+int csdr_amd_rtty_reset_channel(csdr_amd_rtty *p, int ch) { return bank_reset_channel(p, "rtty", ch, fresh_chan()); }
 
 long long csdr_amd_rtty_max_out(const csdr_amd_rtty *p, long long n_in)
 {
@@ -431,8 +417,8 @@ int csdr_amd_rtty_process(csdr_amd_rtty *p, const void *in, long long n_in, size
     return 0;
 }
 
-int csdr_amd_rtty_force_generic(csdr_amd_rtty *p, int on) { if (!p) return fail_msg(-3, "rtty: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_rtty_kernel_name(const csdr_amd_rtty *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_rtty_force_generic(csdr_amd_rtty *p, int on) { return bank_force_generic(p, "rtty", on); }
+const char *csdr_amd_rtty_kernel_name(const csdr_amd_rtty *p) { return bank_kernel_name(p); }
 
 void csdr_amd_rtty_destroy(csdr_amd_rtty *p) { destroy_on_stream(p); }
 
@@ -509,9 +495,8 @@ long long csdr_amd_debug_rtty_walk(const csdr_amd_rtty_params *params, int first
     std::vector<float2> hist(std::max(1, cfg.L)), ms;
     if (first_stage == RTTY_BFSK) bfsk_taps(params, ms);
     const size_t isz = first_stage == RTTY_BFSK ? 8 : first_stage == RTTY_SERIAL ? 4 : 1, osz = rtty_out_elem(cfg);
-    long long done = 0, k = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        const long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
+    long long k = 0;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
         const char *x = (const char *)in + done * isz;
         uint8_t *o = (uint8_t *)out + k * osz;
         const float *xf = (const float *)x;
@@ -526,15 +511,14 @@ long long csdr_amd_debug_rtty_walk(const csdr_amd_rtty_params *params, int first
             const int h2 = (int)std::min((long long)(cfg.L - 1), nV);
             for (int j = 0; j < h2; j++) { const long long p = nV - h2 + j; hist[j] = V(p); }
             s.hist_len = h2;
-            if (last_stage == RTTY_BFSK) { k += no; done += m; continue; }
+            if (last_stage == RTTY_BFSK) { k += no; return; }
             xf = dst; nx = no;
         }
         Emit e{&cfg, o, 0, &s.fig_mode};
         if (first_stage == RTTY_BAUDOT) for (long long j = 0; j < m; j++) e(((const uint8_t *)x)[j]);
         else { auto r = [&](long long q) { return xf[q]; }; serial_walk(cfg, s, rem.data(), r, nx, e); }
         k += e.k;
-        done += m;
-    }
+    });
     return k;
 }
 

@@ -9,7 +9,7 @@
 //   k_squelch_generic   two passes over global memory, any B, any pitch or alignment, blocks that begin in the samples held from earlier calls
 // All of them evaluate squelch_dev.hpp's order (512 chains by sample index, then the tree): the same bits.  16-byte loads and stores in the one-pass kernels,
 // zeros included.  What is left of a channel behind its last whole block (< B samples) stays in the object (k_squelch_carry).
-#include "common.hpp"
+#include "bank.hpp"
 #include "squelch_dev.hpp"
 #include <string.h>
 #include <algorithm>
@@ -185,8 +185,8 @@ constexpr int SQ_WAVE_MAX = 128 * 16;          // the largest block of one wave
 
 } // namespace
 
-struct csdr_amd_squelch {
-    csdr_amd_ctx *c; int n_ch, B, d; long long max_n; bool force_generic, lv_dirty; const char *last_kernel;
+struct csdr_amd_squelch : Bank {
+    int B, d; long long max_n; bool lv_dirty;
     std::vector<int> rem; std::vector<long long> blk; std::vector<float> lv, lv_started;
     bool uniform;                    // every channel holds rem[0] samples: the kernels need no per-channel counts
     DevBuf<float2> d_carry; DevBuf<float> d_lv; DevBuf<int> d_rem;
@@ -196,14 +196,12 @@ extern "C" {
 
 csdr_amd_squelch *csdr_amd_squelch_create(csdr_amd_ctx *c, int n_channels, int block_size, int use_every_nth, const float *levels, long long max_samples_per_call)
 {
-    if (!c) { fail_msg(-3, "squelch: null context"); return nullptr; }
-    if (n_channels < 1 || n_channels > (1 << 22)) { fail_msg(-3, "squelch: n_channels should be 1 .. 4194304"); return nullptr; }
+    if (bank_create_check("squelch", c, n_channels) < 0) return nullptr;
     if (block_size < 1 || block_size > (1 << 24)) { fail_msg(-3, "squelch: block_size should be 1 .. 16777216"); return nullptr; }
     if (use_every_nth < 1) { fail_msg(-3, "squelch: use_every_nth <= 0 is invalid"); return nullptr; }
     if (max_samples_per_call < 1 || max_samples_per_call > (1LL << 30)) { fail_msg(-3, "squelch: max_samples_per_call should be 1 .. 2^30"); return nullptr; }
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "squelch: hipSetDevice"); return nullptr; }
     Owned<csdr_amd_squelch, csdr_amd_squelch_destroy> p(new csdr_amd_squelch());
-    p->c = c; p->n_ch = n_channels; p->B = block_size; p->d = use_every_nth; p->max_n = max_samples_per_call; p->force_generic = false; p->last_kernel = "";
+    p->c = c; p->n_ch = n_channels; p->B = block_size; p->d = use_every_nth; p->max_n = max_samples_per_call;
     p->lv.assign(n_channels, 0.f);
     if (levels) p->lv.assign(levels, levels + n_channels);
     if (dev_alloc(p->d_carry, sizeof(float2) * (size_t)block_size * n_channels) != hipSuccess || dev_alloc(p->d_lv, sizeof(float) * 2 * n_channels) != hipSuccess ||
@@ -252,8 +250,8 @@ int csdr_amd_squelch_set_level(csdr_amd_squelch *p, int ch, float level)
 float csdr_amd_squelch_get_level(const csdr_amd_squelch *p, int ch) { return p && ch >= 0 && ch < p->n_ch ? p->lv[ch] : 0.f; }
 long long csdr_amd_squelch_block_index(const csdr_amd_squelch *p, int ch) { return p && ch >= 0 && ch < p->n_ch ? p->blk[ch] : -1; }
 int csdr_amd_squelch_max_blocks(const csdr_amd_squelch *p) { return p ? (int)((p->max_n + p->B - 1) / p->B) : 0; }
-int csdr_amd_squelch_force_generic(csdr_amd_squelch *p, int on) { if (!p) return fail_msg(-3, "squelch: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_squelch_kernel_name(const csdr_amd_squelch *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_squelch_force_generic(csdr_amd_squelch *p, int on) { return bank_force_generic(p, "squelch", on); }
+const char *csdr_amd_squelch_kernel_name(const csdr_amd_squelch *p) { return bank_kernel_name(p); }
 
 void csdr_amd_squelch_destroy(csdr_amd_squelch *p) { destroy_on_stream(p); }
 

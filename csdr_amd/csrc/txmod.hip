@@ -19,7 +19,7 @@
 //                 run of 16 outputs then takes the run's checkpoint, steps the recurrence and rotates the staged values in place; and all lanes convert and store
 //                 them in 16-byte pieces: each output byte is written once, coalesced.
 //   k_tx_up_generic   one output per lane straight from and to global memory, any pointer and pitch.  The same operations in the same order: the same bits.
-#include "common.hpp"
+#include "bank.hpp"
 #include "txmod_dev.hpp"
 #include "seeds.hpp"
 #include <string.h>
@@ -346,11 +346,9 @@ int check_ew(const char *name, const void *in, const void *out, size_t n)
 
 } // namespace
 
-struct csdr_amd_txbank {
-    csdr_amd_ctx *c;
-    int n_streams, mode, I, T, K, Ipad, u8; float gain, q_value; size_t max_in;
-    long long hist;                                       // samples the interpolator holds in front of the next call: min(total, K)
-    bool force_generic; const char *last_kernel;
+struct csdr_amd_txbank : Bank {                           // (n_ch: the streams)
+    int mode, I, T, K, Ipad, u8; float gain, q_value; size_t max_in;
+    long long hist = 0;                                   // samples the interpolator holds in front of the next call: min(total, K)
     std::vector<float> h_rates;
     size_t bb_pitch, seed_pitch;
     DevBuf<float2> d_bb, d_ckpt, d_sdcd;
@@ -428,9 +426,7 @@ long long csdr_amd_debug_fmmod_walk(const float *in, long long n, const long lon
 {
     if (n < 0 || (n > 0 && !in) || n_cuts < 0 || (n_cuts && !cuts)) return fail_msg(-3, "debug_fmmod_walk: bad arguments");
     float s = state_io ? *state_io : 0.f;
-    long long done = 0;
-    for (int ci = 0; ci <= n_cuts; ci++) {
-        const long long m = ci < n_cuts ? std::min(std::max(cuts[ci], 0LL), n - done) : n - done;
+    for_each_call(n, cuts, n_cuts, [&](long long done, long long m) {
         float p = s;                                     // a call: last_phase in, samples, last_phase out
         for (long long j = done; j < done + m; j++) {
             p = fmmod_phase_step(p, fmmod_delta(in[j]));
@@ -438,8 +434,7 @@ long long csdr_amd_debug_fmmod_walk(const float *in, long long n, const long lon
             if (out) { const float2 o = fmmod_output(p); out[j].i = o.x; out[j].q = o.y; }
         }
         s = p;
-        done += m;
-    }
+    });
     if (state_io) *state_io = s;
     return n;
 }
@@ -448,8 +443,7 @@ long long csdr_amd_debug_fmmod_walk(const float *in, long long n, const long lon
 csdr_amd_txbank *csdr_amd_txbank_create(csdr_amd_ctx *c, int n_streams, int mode, float gain, float q_value, int interpolation, const float *host_taps,
                                         int taps_length, const float *shift_rates, int out_format, size_t max_in_samples)
 {
-    if (!c) { fail_msg(-3, "txbank: null context"); return nullptr; }
-    if (n_streams < 1 || n_streams > 65535) { fail_msg(-3, "txbank: n_streams should be 1 .. 65535"); return nullptr; }
+    if (bank_create_check("txbank", c, n_streams, 65535, "n_streams") < 0) return nullptr;
     if (mode < CSDR_TX_FM || mode > CSDR_TX_DSB) { fail_msg(-3, "txbank: mode is 0 (FM), 1 (AM) or 2 (DSB)"); return nullptr; }
     if (out_format != CSDR_TX_OUT_CF32 && out_format != CSDR_TX_OUT_U8) { fail_msg(-3, "txbank: out_format is 0 (cf32) or 1 (u8)"); return nullptr; }
     if (!(fabsf(gain) <= 1e30f) || !(fabsf(q_value) <= 1e30f)) { fail_msg(-3, "txbank: gain and q_value should be finite"); return nullptr; }
@@ -460,11 +454,10 @@ csdr_amd_txbank *csdr_amd_txbank_create(csdr_amd_ctx *c, int n_streams, int mode
     if (!shift_rates) { fail_msg(-3, "txbank: shift_rates is required (n_streams floats)"); return nullptr; }
     for (int s = 0; s < n_streams; s++) if (check_rate(shift_rates[s]) < 0) return nullptr;
     if (max_in_samples < 1 || max_in_samples * (size_t)I > ((size_t)1 << 30)) { fail_msg(-3, "txbank: max_in_samples should be 1 .. 2^30 / interpolation"); return nullptr; }
-    if (hipSetDevice(c->device) != hipSuccess) { fail_msg(-2, "txbank: hipSetDevice"); return nullptr; }
 
     Owned<csdr_amd_txbank, csdr_amd_txbank_destroy> p(new csdr_amd_txbank());
-    p->c = c; p->n_streams = n_streams; p->mode = mode; p->I = I; p->T = T; p->K = K; p->Ipad = (I + 7) & ~7; p->u8 = out_format == CSDR_TX_OUT_U8;
-    p->gain = gain; p->q_value = q_value; p->max_in = max_in_samples; p->hist = 0; p->force_generic = false; p->last_kernel = "";
+    p->c = c; p->n_ch = n_streams; p->mode = mode; p->I = I; p->T = T; p->K = K; p->Ipad = (I + 7) & ~7; p->u8 = out_format == CSDR_TX_OUT_U8;
+    p->gain = gain; p->q_value = q_value; p->max_in = max_in_samples;
     p->h_rates.assign(shift_rates, shift_rates + n_streams);
     p->bb_pitch = ((size_t)K + max_in_samples + 1) & ~(size_t)1;
     p->seed_pitch = (max_in_samples * I + 1023) / 1024 + 2;
@@ -493,7 +486,7 @@ csdr_amd_txbank *csdr_amd_txbank_create(csdr_amd_ctx *c, int n_streams, int mode
 int csdr_amd_txbank_reset(csdr_amd_txbank *p)
 {
     if (!p) return fail_msg(-3, "txbank: null object");
-    const size_t ns = p->n_streams;
+    const size_t ns = p->n_ch;
     p->hist = 0;
     if (int rc = csdr_amd_memset(p->c, p->d_fm_phase.get(), 0, sizeof(float) * ns)) return rc;
     if (int rc = csdr_amd_memset(p->c, p->d_rot_phase.get(), 0, sizeof(float) * ns)) return rc;
@@ -502,7 +495,7 @@ int csdr_amd_txbank_reset(csdr_amd_txbank *p)
 
 int csdr_amd_txbank_set_rate(csdr_amd_txbank *p, int stream, float rate)
 {
-    if (!p || stream < 0 || stream >= p->n_streams) return fail_msg(-3, "txbank: stream out of range");
+    if (!p || stream < 0 || stream >= p->n_ch) return fail_msg(-3, "txbank: stream out of range");
     if (int rc = check_rate(rate)) return rc;
     CSDR_HIP(hipSetDevice(p->c->device));
     float sd, cd;
@@ -515,13 +508,13 @@ int csdr_amd_txbank_set_rate(csdr_amd_txbank *p, int stream, float rate)
 
 float csdr_amd_txbank_get_rate(const csdr_amd_txbank *p, int stream)
 {
-    if (!p || stream < 0 || stream >= p->n_streams) { fail_msg(-3, "txbank: stream out of range"); return 0.f; }
+    if (!p || stream < 0 || stream >= p->n_ch) { fail_msg(-3, "txbank: stream out of range"); return 0.f; }
     return p->h_rates[stream];
 }
 
 long long csdr_amd_txbank_max_out(const csdr_amd_txbank *p, long long n_in) { return p && n_in > 0 ? n_in * p->I : 0; }
-int csdr_amd_txbank_force_generic(csdr_amd_txbank *p, int on) { if (!p) return fail_msg(-3, "txbank: null object"); p->force_generic = on != 0; return 0; }
-const char *csdr_amd_txbank_kernel_name(const csdr_amd_txbank *p) { return p ? p->last_kernel : ""; }
+int csdr_amd_txbank_force_generic(csdr_amd_txbank *p, int on) { return bank_force_generic(p, "txbank", on); }
+const char *csdr_amd_txbank_kernel_name(const csdr_amd_txbank *p) { return bank_kernel_name(p); }
 
 void csdr_amd_txbank_destroy(csdr_amd_txbank *p) { destroy_on_stream(p); }
 
@@ -538,7 +531,7 @@ int csdr_amd_txbank_process(csdr_amd_txbank *p, const int16_t *in_s16, size_t in
     if (no > 0 && !p->u8 && ((uintptr_t)out & 3)) return fail_msg(-3, "txbank: a cf32 output must be 4-byte aligned");
     CSDR_HIP(hipSetDevice(p->c->device));
     hipStream_t st = p->c->stream;
-    const int ns = p->n_streams;
+    const int ns = p->n_ch;
 
     // 1. modulate at the audio rate, behind the history: row = [K - hist, K) history, [K, K + n_in) new
     if (p->mode == CSDR_TX_FM) {
