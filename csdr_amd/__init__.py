@@ -106,7 +106,7 @@ def lib():
                "reset_channel": (i, [vp, i]), "get_channel": (i, [vp, i, vp]), "set_channel": (i, [vp, i, vp]), "set_lanes": (i, [vp, i]), "lanes": (i, [vp])}
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
-                       ("pulsetx", max_out), ("rtty", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
+                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
                        ("txbank", max_out)):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
@@ -135,6 +135,9 @@ def lib():
     L.csdr_amd_pulsetx_process.argtypes = [vp, vp, ll, sz, vp, sz, C.POINTER(ll)]
     L.csdr_amd_pulsetx_tile.argtypes = [vp]
     L.csdr_amd_debug_pulsetx_walk.restype = ll; L.csdr_amd_debug_pulsetx_walk.argtypes = [i, i, vp, i, i, i, vp, ll, vp, i, vp]
+    L.csdr_amd_pulserx_create.restype = vp; L.csdr_amd_pulserx_create.argtypes = [vp, vp, i, i, i]
+    L.csdr_amd_pulserx_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, vp, vp]
+    L.csdr_amd_debug_pulserx_walk.restype = ll; L.csdr_amd_debug_pulserx_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
     L.csdr_amd_generic_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
     L.csdr_amd_plain_interpolate_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
     L.csdr_amd_pack_bits_1to8_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
@@ -867,6 +870,86 @@ class PulseTx(_Handle, _MaxOut):
             pos += m
         y = np.concatenate(parts, axis=1) if parts else np.zeros((s, 0), c64)
         return y[0] if squeeze else y
+
+
+class PulseRxParams(C.Structure):
+    """csdr_amd_pulserx_params; `taps` points into the array kept as `_taps`"""
+    _fields_ = [("taps", C.c_void_p), ("taps_length", C.c_int), ("algorithm", C.c_int), ("decimation", C.c_int), ("loop_gain", C.c_float),
+                ("max_error", C.c_float), ("use_q", C.c_int), ("gain", C.c_float), ("n_symbols", C.c_int), ("slice_q", C.c_int)]
+
+
+class PulseRxChan(C.Structure):
+    """csdr_amd_pulserx_chan: one channel's state (its raw tail stays on the device)"""
+    _fields_ = [("tail_len", C.c_int), ("correction_offset", C.c_int), ("base", C.c_uint)]
+
+
+PULSERX_STAGES = {"filter": 0, "timing": 1, "slice": 2}
+
+
+def _pulserx_stage(s):
+    return PULSERX_STAGES[s] if isinstance(s, str) else int(s)
+
+
+def pulserx_params(taps=None, algorithm="GARDNER", decimation=8, loop_gain=0.5, max_error=2.0, use_q=True, gain=1.0, n_symbols=2, slice_q=False):
+    """the receive object's parameters: `pulse_shaping_filter_cc` taps | `timing_recovery_cc algorithm decimation loop_gain max_error [--add_q]` |
+    [`realpart_cf` |] `gain_ff gain | generic_slicer_f_u8 n_symbols` (slice_q: no realpart_cf, two bytes per symbol)"""
+    alg = TIMING_ALGORITHMS[algorithm] if isinstance(algorithm, str) else int(algorithm)
+    t = None if taps is None else np.ascontiguousarray(taps, f32)
+    p = PulseRxParams(t.ctypes.data if t is not None and t.size else None, t.size if t is not None else 0, alg, decimation, loop_gain, max_error,
+                      int(bool(use_q)), gain, n_symbols, int(bool(slice_q)))
+    p._taps = t
+    return p
+
+
+def pulserx_debug_walk(params, first="filter", last="slice", x=None, cuts=(), state=None, with_extras=False):
+    """CPU run of the receive object's walk for one channel (csdr_amd_debug_pulserx_walk): x cut into calls of `cuts` samples and the rest -> outputs
+    (and, with_extras, the timing errors and indexes).  state: a PulseRxChan carried in and out (without a tail on the way in)."""
+    f, l = _pulserx_stage(first), _pulserx_stage(last)
+    x = np.ascontiguousarray(x, c64)
+    n = x.size
+    cap = (2 * n // max(params.decimation, 1) + 3 * len(cuts) + 16) * 2
+    out = np.zeros(cap, c64 if l == 1 else np.uint8)
+    err = np.zeros(cap, f32) if with_extras else None
+    idx = np.zeros(cap, np.uint32) if with_extras else None
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_pulserx_walk(C.byref(params), f, l, _hp(x), n, _hp(cu) if cu.size else None, cu.size, _hp(out),
+                                          _hp(err) if with_extras else None, _hp(idx) if with_extras else None, C.byref(state) if state is not None else None)
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return (out[:k], err[:k], idx[:k]) if with_extras else out[:k]
+
+
+class PulseRx(_Handle, _MaxOut, _ChannelState, _Lanes):
+    """csdr_amd_pulserx: pulse_shaping_filter_cc (matched filter) | timing_recovery_cc | [realpart_cf |] gain_ff | generic_slicer_f_u8 for n_channels
+    channels, stages first ("filter", "timing") .. last ("timing", "slice"), state kept on the device between calls."""
+    _chan = PulseRxChan
+
+    def __init__(self, ctx, params, n_channels=1, first="filter", last="slice"):
+        self.n_channels, self.params = n_channels, params
+        self.first, self.last = _pulserx_stage(first), _pulserx_stage(last)
+        self.in_dtype, self.out_dtype = c64, (c64 if self.last == 1 else np.uint8)
+        _Handle.__init__(self, ctx, "pulserx", ctx.L.csdr_amd_pulserx_create(ctx.h, C.byref(params), n_channels, self.first, self.last))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err=None, d_idx=None):
+        """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_err, d_idx)
+
+    def process(self, x, calls=None, with_extras=False):
+        """x: [n_channels, n] (or [n]) host samples; calls: per-call sample counts (default one call) -> a list of per-channel output arrays
+        (or one array for 1-D x); with_extras (last == "timing"): (symbols, errors, indexes) per channel."""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        if with_extras:
+            res = _counted_calls(self, x, calls, (("d_err", f32), ("d_idx", np.uint32)))
+        else:
+            res = [r[0] for r in _counted_calls(self, x, calls)]
+        return res[0] if squeeze else res
 
 
 class RttyParams(C.Structure):
@@ -1871,6 +1954,15 @@ class Context:
     def pulse_tx(self, n_channels=1, n_psk=4, interpolation=8, taps=None, first="mod", last="shape"):
         """A batched pulse-shaping transmit object (PulseTx)"""
         return PulseTx(self, n_channels, n_psk, interpolation, taps, first, last)
+
+    def pulse_rx(self, params, n_channels=1, first="filter", last="slice"):
+        """A batched pulse-shaped receive object (PulseRx); params from pulserx_params()"""
+        return PulseRx(self, params, n_channels, first, last)
+
+    @staticmethod
+    def pulserx_debug_walk(params, first="filter", last="slice", x=None, cuts=(), state=None, with_extras=False):
+        """pulserx_debug_walk: the CPU run of the receive object's walk for one channel"""
+        return pulserx_debug_walk(params, first, last, x, cuts, state, with_extras)
 
     def _flat_rows(self, fn, name, x, dtype_in, dtype_out, n_out, *extra):
         x = np.ascontiguousarray(x, dtype_in)

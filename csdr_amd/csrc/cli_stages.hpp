@@ -383,6 +383,26 @@ struct PulseFilter : Stage {   // pulse_shaping_filter_cc csdr.c:3159-3219: appl
         return no;
     }
 };
+struct PulseRx : Stage {   // pulse_shaping_filter_cc ... | timing_recovery_cc ... [[| realpart_cf] | gain_ff g | generic_slicer_f_u8 n]: one object for the run (`chain` fuses
+                          // it); the unconsumed tail and the loop's state live on the device.  The filter is evaluated only where the timing loop reads it.
+    Owned<csdr_amd_pulserx, csdr_amd_pulserx_destroy> p; int D; CtxBuf<int> d_count;
+    PulseRx(csdr_amd_ctx *c, const csdr_amd_pulserx_params &pr, int last) : D(pr.decimation)
+    {
+        p.reset(csdr_amd_pulserx_create(c, &pr, 1, CSDR_AMD_PULSERX_FILTER, last)); if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        in_elem = 8; out_elem = last == CSDR_AMD_PULSERX_TIMING ? 8 : 1;
+        d_count = ctx_alloc<int>(c, 64, "malloc");
+        fprintf(stderr, "csdr pulse_rx: one fused pulse-shaped receive object\n");
+    }
+    size_t out_capacity(size_t n) override { return (size_t)csdr_amd_pulserx_max_out(p.get(), (long long)n) + 16; }
+    int next_bufsize(int b) override { return b / D; }               // csdr.c:2620 (the other commands of the run pass their buffer size on)
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        MUST(csdr_amd_pulserx_process(p.get(), (const csdr_complexf *)i, (long long)n, n, o, cap, d_count.get(), nullptr, nullptr));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count.get(), sizeof k));
+        return k;
+    }
+};
 struct GenericSlicer : Stage {   // generic_slicer_f_u8 csdr.c:3221-3236
     int n_symbols;
     GenericSlicer(int n) : n_symbols(n) { in_elem = 4; out_elem = 1; }
@@ -1068,6 +1088,31 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         g_cmd = argv[1];
         if (taps.empty()) { badsyntax("pulse_tx: the run ends with pulse_shaping_filter_cc"); return nullptr; }
         return new PulseTx(c, n_psk, interpolation, taps, first);
+    }
+    if (!strcmp(argv[1], "pulse_rx")) {                                             // `chain`'s fused receive run: argv[2..] are its commands, one per argument
+        std::vector<float> taps; csdr_amd_psk31_params tr; memset(&tr, 0, sizeof tr);
+        csdr_amd_pulserx_params pr; memset(&pr, 0, sizeof pr);
+        bool realpart = false, sliced = false;
+        for (int k = 2; k < argc; k++) {
+            std::vector<std::string> words = split_chain(argv[k])[0]; std::vector<char *> av = argv_of(words);
+            g_cmd = av[1];
+            if (!strcmp(av[1], "pulse_shaping_filter_cc")) { if (!parse_pulse_filter((int)av.size(), av.data(), &taps)) return nullptr; }
+            else if (!strcmp(av[1], "timing_recovery_cc")) { int extra = 0; if (parse_psk31((int)av.size(), av.data(), &tr, &extra) < 0) return nullptr; }
+            else if (!strcmp(av[1], "realpart_cf")) realpart = true;
+            else if (!strcmp(av[1], "gain_ff")) { if (av.size() <= 2) { badsyntax("need required parameter (gain)"); return nullptr; } sscanf(av[2], "%g", &pr.gain); }
+            else if (!strcmp(av[1], "generic_slicer_f_u8")) {                       // csdr.c:3221-3225
+                if (av.size() <= 2) { badsyntax("required parameter <n_symbols> is missing."); return nullptr; }
+                sscanf(av[2], "%d", &pr.n_symbols);
+                if (pr.n_symbols < 2 || pr.n_symbols > 256) { badsyntax("n_symbols should be between 2 and 256"); return nullptr; }
+                sliced = true;
+            }
+        }
+        g_cmd = argv[1];
+        if (taps.empty() || !tr.decimation) { badsyntax("pulse_rx: the run starts with pulse_shaping_filter_cc | timing_recovery_cc"); return nullptr; }
+        pr.taps = taps.data(); pr.taps_length = (int)taps.size();
+        pr.algorithm = tr.algorithm; pr.decimation = tr.decimation; pr.loop_gain = tr.loop_gain; pr.max_error = tr.max_error; pr.use_q = tr.use_q;
+        pr.slice_q = sliced && !realpart;
+        return new PulseRx(c, pr, sliced ? CSDR_AMD_PULSERX_SLICE : CSDR_AMD_PULSERX_TIMING);
     }
     if (!strcmp(argv[1], "plain_interpolate_cc")) {
         const char *keep = g_cmd; g_cmd = argv[1];

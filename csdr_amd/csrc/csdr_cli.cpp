@@ -156,6 +156,30 @@ bool fuse_pulsetx(std::vector<std::vector<std::string>> &cmds)
     return any;
 }
 
+// pulse_shaping_filter_cc ... | timing_recovery_cc ... [[| realpart_cf] | gain_ff g | generic_slicer_f_u8 n] -> one `pulse_rx` command (arguments: the run's commands, one
+// per argument).  A timing_recovery_cc with an option behind --add_q (--output_error, --output_indexes, the Octave plots) writes something else: the run stays as it is.
+bool fuse_pulserx(std::vector<std::vector<std::string>> &cmds)
+{
+    auto is = [&](size_t k, const char *name) { return k < cmds.size() && cmds[k].size() > 1 && cmds[k][1] == name; };
+    bool any = false;
+    for (size_t a = 0; a + 1 < cmds.size(); a++) {
+        if (!is(a, "pulse_shaping_filter_cc") || !is(a + 1, "timing_recovery_cc")) continue;
+        const std::vector<std::string> &t = cmds[a + 1];                // csdr timing_recovery_cc <algorithm> <decimation> [loop_gain [max_error [--add_q [option]]]]
+        const size_t plain = 6 + (t.size() > 6 && t[6] == "--add_q");
+        if (t.size() > plain) continue;
+        size_t b = a + 2;
+        if (is(b, "realpart_cf") && is(b + 1, "gain_ff") && is(b + 2, "generic_slicer_f_u8")) b += 3;
+        else if (is(b, "gain_ff") && is(b + 1, "generic_slicer_f_u8")) b += 2;
+        std::vector<std::string> fused = {"csdr", "pulse_rx"};
+        for (size_t k = a; k < b; k++) { std::string w; for (size_t u = 1; u < cmds[k].size(); u++) w += (u > 1 ? " " : "") + cmds[k][u]; fused.push_back(w); }
+        fprintf(stderr, "csdr chain: %s .. %s recognised -> one fused pulse-shaped receive object (pulse_rx)\n", cmds[a][1].c_str(), cmds[b - 1][1].c_str());
+        cmds.erase(cmds.begin() + a, cmds.begin() + b);
+        cmds.insert(cmds.begin() + a, fused);
+        any = true;
+    }
+    return any;
+}
+
 // convert_u8_f | shift_addition_cc r | fir_decimate_cc D [tbw [window]] at the head of a chain -> one ddc_u8_cc command
 bool fuse_front_end(std::vector<std::vector<std::string>> &cmds)
 {
@@ -287,6 +311,7 @@ int main(int argc, char **argv)
         }
         fuse_run(cmds, PSK31_RUN, 4, "psk31_rx", "csdr chain: %s .. %s recognised -> one fused BPSK31 object (k_psk31)\n");
         fuse_pulsetx(cmds);                                             // (in front of the BPSK31 transmit run: psk_modulator_u8_c belongs to both)
+        fuse_pulserx(cmds);                                             // (behind both: a filter that shapes a transmit run, or a timing loop a BPSK31 run took, is theirs)
         fuse_run(cmds, PSK31TX_RUN, 4, "psk31_tx", "csdr chain: %s .. %s recognised -> one fused BPSK31 transmit object (psk31_tx)\n");
         fuse_run(cmds, RTTY_RUN, 3, "rtty_rx", "csdr chain: %s .. %s recognised -> one fused RTTY object (rtty_rx: k_bfsk_mfma + k_rtty_walk)\n");
     } else {

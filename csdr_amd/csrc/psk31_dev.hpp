@@ -106,32 +106,48 @@ struct Psk31Tail {
     }
 };
 
-// timing_recovery_cc's sample positions of the symbol at cbi (libcsdr.c:2002-2026); resets the incoming correction_offset as the reference does
-__host__ __device__ inline void psk31_positions(const Psk31Cfg &c, long long cbi, int *corr, long long *pl, long long *pm, long long *pr)
+// timing_recovery_cc's sample positions of the symbol at cbi (libcsdr.c:2002-2026); resets the incoming correction_offset as the reference does.
+// I: the caller's index type (long long; int where a call's stream is known to stay below 2^31 samples)
+template <class I> __host__ __device__ inline void psk31_positions(const Psk31Cfg &c, I cbi, int *corr, I *pl, I *pm, I *pr)
 {
     if (*corr <= c.reset_lo || *corr >= c.reset_hi) *corr = 0;
     if (c.algorithm == 1) { *pr = cbi + c.wing * 3; *pl = cbi + c.wing - *corr; *pm = cbi + c.hb; }
     else { *pr = cbi + c.hb * 3; *pl = cbi + c.hb; *pm = cbi + c.hb * 2; }
 }
 
-// One symbol from the (AGC'd) samples at its three positions: written at stage `last`; returns the next correction_offset (libcsdr.c:2027-2069)
-__host__ __device__ inline int psk31_symbol(const Psk31Cfg &c, Psk31Chan &s, Psk31Tail &t, const Psk31Out &o, float2 xl, float2 xm, float2 xr, long long po)
+// The timing error of one symbol from the samples at its three positions, unclamped (libcsdr.c:2027-2040)
+__host__ __device__ inline float psk31_timing_error(const Psk31Cfg &c, float2 xl, float2 xm, float2 xr)
 {
-    const float2 xo = c.algorithm == 1 ? xm : xl;
     float error = (xr.x - xl.x) * xm.x;
     if (c.use_q) {
         error += (xr.y - xl.y) * xm.y;
         error /= 2;
     }
+    return error;
+}
+
+// The next correction_offset from a symbol's timing error (libcsdr.c:2064-2069).  A NaN error (an inf or NaN sample) corrects by 0: the conversion of a
+// NaN to int is not defined, gives 0 on the device and INT_MIN on an x86 host, and the latter would walk the symbol start backwards out of the tail.
+__host__ __device__ inline int psk31_correction(const Psk31Cfg &c, float error)
+{
+    if (!(error == error)) error = 0.f;
+    if (error > c.max_error) error = c.max_error;
+    if (error < -c.max_error) error = -c.max_error;
+    return (int)((error * c.loop_gain) * c.hb_sign);
+}
+
+// One symbol from the (AGC'd) samples at its three positions: written at stage `last`; returns the next correction_offset (libcsdr.c:2027-2069)
+__host__ __device__ inline int psk31_symbol(const Psk31Cfg &c, Psk31Chan &s, Psk31Tail &t, const Psk31Out &o, float2 xl, float2 xm, float2 xr, long long po)
+{
+    const float2 xo = c.algorithm == 1 ? xm : xl;
+    const float error = psk31_timing_error(c, xl, xm, xr);
     if (c.last == PSK31_TIMING) {
         o.c[t.k] = xo;
         if (o.err) o.err[t.k] = error;
         if (o.idx) o.idx[t.k] = s.base + (uint32_t)po;
         t.k++;
     } else t.symbol(xo.x, xo.y);
-    if (error > c.max_error) error = c.max_error;
-    if (error < -c.max_error) error = -c.max_error;
-    return (int)((error * c.loop_gain) * c.hb_sign);
+    return psk31_correction(c, error);
 }
 
 // The stream V = tail ++ in that timing recovery reads, and the AGC walker over it: g is the gain in front of sample pos.  Symbol positions only grow, except

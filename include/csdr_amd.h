@@ -345,6 +345,57 @@ void csdr_amd_pulsetx_destroy(csdr_amd_pulsetx *p);
  * concatenated.  Returns the output count. */
 long long csdr_amd_debug_pulsetx_walk(int n_psk, int interpolation, const float *taps, int taps_length, int first_stage, int last_stage, const void *in,
                                       long long n, const long long *cuts, int n_cuts, void *out);
+/* Receive: pulse_shaping_filter_cc as the matched filter (apply_real_fir_cc libcsdr.c:2276-2291) | timing_recovery_cc libcsdr.c:1977-2072 | [realpart_cf |]
+ * gain_ff libcsdr.c:1139-1142 | generic_slicer_f_u8 libcsdr.c:1731-1765, for n_channels channels with the same parameters.  With x a channel's complexf input
+ * since its last reset: FILTER gives f[i] = sum over t < T of x[i + t] taps[t], i = 0 .. n - T (no zeros in front); from first_stage TIMING on, f = x with its
+ * bits kept and the taps are not read.  TIMING is timing_recovery_cc applied once to the whole of f (GARDNER 0 / EARLYLATE 1, use_q, loop_gain, max_error with
+ * |loop_gain| max_error <= 1, decimation >= 2: the library function's range, wider than the command line's).  SLICE: slice_q 0 is realpart_cf |
+ * gain_ff gain | generic_slicer_f_u8 n_symbols, one byte per symbol; slice_q 1 is gain_ff | generic_slicer_f_u8 on the complexf symbols read as interleaved floats, two bytes per symbol (I, Q).
+ * f is never stored: it is evaluated only at the three positions the timing loop reads per symbol.  The order of the T products is part of the definition (a
+ * float is truncated to an int in the loop): 16 partial sums over t = r (mod 16), each in ascending t with fmaf from 0, then p[r] += p[r + s] for r < s,
+ * s = 8, 4, 2, 1.  Both kernels and the debug walk run that order and give the same bits.  The output does not depend on how the stream is cut into calls
+ * (0- and 1-sample calls included) nor on where a channel sits in the batch.  State per channel: the raw unconsumed tail (from the current symbol start on,
+ * at most 3 D/2 + T - 1 samples, kept on the device), its length, correction_offset, and base, the absolute index of the tail's first sample.
+ * process: n_in complexf per channel, in_pitch items apart; out: complexf symbols (last_stage TIMING) or bytes (SLICE), out_pitch items apart, at least
+ * max_out(n_in): a smaller out_pitch is an error and consumes nothing.  counts (device, n_channels ints) receives each channel's output count (bytes from
+ * SLICE).  err / idx (device, optional, last_stage TIMING only): the unclamped timing error and the absolute sample index per symbol.  Asynchronous.
+ * kernel_name: "k_pulserx_tiled" (a one-wave workgroup per 16, 8, 4, 2 or 1 channels with 4, 8 or 16 lanes per channel; per channel a ring of the next
+ * power of two >= 3 D/2 + T + 127 samples, with the taps and the byte staging within 63 KiB of LDS) or "k_pulserx_generic" (one lane per channel; every
+ * other shape and after force_generic(1)).  set_lanes(n): channels per wave, 0 automatic; k_pulserx_tiled takes the largest of 16, 8, 4, 2, 1 within n,
+ * the next smaller of them where the rings do not fit.  Every choice gives the same bits. */
+enum { CSDR_AMD_PULSERX_FILTER = 0, CSDR_AMD_PULSERX_TIMING = 1, CSDR_AMD_PULSERX_SLICE = 2 };
+typedef struct csdr_amd_pulserx_params {
+    const float *taps; int taps_length;                  /* host taps (copied); not read from first_stage TIMING on */
+    int algorithm, decimation;
+    float loop_gain, max_error;
+    int use_q;
+    float gain;                                          /* gain_ff's factor in front of the slicer */
+    int n_symbols, slice_q;                              /* generic_slicer_f_u8's n_symbols (2..256); both needed to last_stage SLICE only */
+} csdr_amd_pulserx_params;
+typedef struct csdr_amd_pulserx_chan {
+    int tail_len;
+    int correction_offset;
+    unsigned base;
+} csdr_amd_pulserx_chan;
+typedef struct csdr_amd_pulserx csdr_amd_pulserx;
+csdr_amd_pulserx *csdr_amd_pulserx_create(csdr_amd_ctx *ctx, const csdr_amd_pulserx_params *params, int n_channels, int first_stage, int last_stage);
+int  csdr_amd_pulserx_process(csdr_amd_pulserx *p, const csdr_complexf *in, long long n_in, size_t in_pitch, void *out, size_t out_pitch, int *counts, float *err,
+                              unsigned *idx);
+long long csdr_amd_pulserx_max_out(const csdr_amd_pulserx *p, long long n_in);
+int  csdr_amd_pulserx_reset(csdr_amd_pulserx *p);
+int  csdr_amd_pulserx_reset_channel(csdr_amd_pulserx *p, int channel);
+int  csdr_amd_pulserx_get_channel(csdr_amd_pulserx *p, int channel, csdr_amd_pulserx_chan *state);
+int  csdr_amd_pulserx_set_channel(csdr_amd_pulserx *p, int channel, const csdr_amd_pulserx_chan *state);
+int  csdr_amd_pulserx_set_lanes(csdr_amd_pulserx *p, int lanes);
+int  csdr_amd_pulserx_lanes(const csdr_amd_pulserx *p);
+int  csdr_amd_pulserx_force_generic(csdr_amd_pulserx *p, int on);
+const char *csdr_amd_pulserx_kernel_name(const csdr_amd_pulserx *p);
+void csdr_amd_pulserx_destroy(csdr_amd_pulserx *p);
+/* CPU run of the object's walk (the same step functions) for one channel, the n samples cut into calls of cuts[0..n_cuts) samples and the rest; outputs
+ * concatenated.  state_io (may be NULL: a fresh channel) carries the channel state in and out; a state with a tail cannot be carried in (the tail is not
+ * part of the record).  Returns the output count. */
+long long csdr_amd_debug_pulserx_walk(const csdr_amd_pulserx_params *params, int first_stage, int last_stage, const csdr_complexf *in, long long n,
+                                      const long long *cuts, int n_cuts, void *out, float *err, unsigned *idx, csdr_amd_pulserx_chan *state_io);
 /* generic_slicer_f_u8 libcsdr.c:1731-1765 on n_streams streams of n floats, n_symbols 2..256: symbol j's centre is -1 + j d with d = (float)(2.0 / (n_symbols - 1)),
  * its limits centre -/+ d / 2, all in float as the reference computes them; the first symbol has no lower and the last no upper limit.  An input that no symbol
  * claims gives 0: NaN (the reference leaves that output byte unwritten), and a value in a rounding gap between two neighbours' limits. */
