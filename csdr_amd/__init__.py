@@ -106,7 +106,7 @@ def lib():
                "reset_channel": (i, [vp, i]), "get_channel": (i, [vp, i, vp]), "set_channel": (i, [vp, i, vp]), "set_lanes": (i, [vp, i]), "lanes": (i, [vp])}
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
-                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
+                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
                        ("txbank", max_out)):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
@@ -157,6 +157,14 @@ def lib():
     L.csdr_amd_firdes_add_peak_c.restype = None; L.csdr_amd_firdes_add_peak_c.argtypes = [vp, i, C.c_float, i, i, i]
     L.csdr_amd_firdes_peak_c.restype = None; L.csdr_amd_firdes_peak_c.argtypes = [vp, i, C.c_float, i]
     L.csdr_amd_debug_rtty_walk.restype = ll; L.csdr_amd_debug_rtty_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp]
+    L.csdr_amd_cfir_create.restype = vp; L.csdr_amd_cfir_create.argtypes = [vp, i, i]
+    L.csdr_amd_cfir_set_taps.argtypes = [vp, i, vp]
+    L.csdr_amd_cfir_set_peaks.argtypes = [vp, i, vp, i, i]
+    L.csdr_amd_cfir_process.argtypes = [vp, vp, ll, sz, vp, sz, vp]
+    L.csdr_amd_apply_fir_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, vp, sz, i, i]
+    L.csdr_amd_apply_fir_last_kernel.restype = C.c_char_p; L.csdr_amd_apply_fir_last_kernel.argtypes = []
+    L.csdr_amd_firdes_peaks_c.restype = None; L.csdr_amd_firdes_peaks_c.argtypes = [vp, i, vp, i, i]
+    L.csdr_amd_debug_cfir_walk.restype = ll; L.csdr_amd_debug_cfir_walk.argtypes = [vp, i, vp, ll, vp, i, vp]
     L.csdr_amd_squelch_create.restype = vp; L.csdr_amd_squelch_create.argtypes = [vp, i, i, i, vp, ll]
     L.csdr_amd_squelch_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, sz, vp, vp]
     L.csdr_amd_squelch_set_level.argtypes = [vp, i, fl]
@@ -1039,6 +1047,88 @@ class Rtty(_Handle, _MaxOut, _PerChannel):
         """x: [n_channels, n] (or [n]) host items; calls: per-call item counts (default one call) -> a list of per-channel output arrays
         (or one array for 1-D x)"""
         x = np.ascontiguousarray(x, self.in_dtype)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        calls = [n] if calls is None else list(calls)
+        res = [r[0] for r in _counted_calls(self, x, calls)]
+        return res[0] if squeeze else res
+
+
+def _window(window):
+    return WINDOWS[window] if isinstance(window, str) else int(window)
+
+
+def firdes_peaks_c(length, rates, window="HAMMING"):
+    """the taps of peaks_fir_cc (csdr.c:2997-3002): firdes_add_peak_c of every rate into zeroed taps, normalised with the last -> complex64 taps"""
+    r = np.ascontiguousarray(np.atleast_1d(rates), f32)
+    if int(length) < 1 or r.size < 1:
+        raise ValueError("firdes_peaks_c needs length >= 1 and at least one rate")
+    t = np.zeros(int(length), c64)
+    lib().csdr_amd_firdes_peaks_c(_hp(t), int(length), _hp(r), r.size, _window(window))
+    return t
+
+
+def cfir_debug_walk(taps, x, cuts=()):
+    """CPU run of the CFir walk for one channel (csdr_amd_debug_cfir_walk): x cut into calls of `cuts` samples and the rest -> the concatenated outputs"""
+    taps = np.ascontiguousarray(taps, c64); x = np.ascontiguousarray(x, c64)
+    out = np.zeros(x.size + 16, c64)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_cfir_walk(_hp(taps) if taps.size else None, taps.size, _hp(x), x.size, _hp(cu) if cu.size else None, cu.size, _hp(out))
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out[:k]
+
+
+def apply_fir_cc(x, taps, ctx=None, force_generic=False):
+    """apply_fir_cc (libcsdr.c:2261-2273) on the device: Context.apply_fir_cc on `ctx`, or on a context of device 0 opened for the call"""
+    if ctx is not None:
+        return ctx.apply_fir_cc(x, taps, force_generic)
+    own = Context(0)
+    try:
+        return own.apply_fir_cc(x, taps, force_generic)
+    finally:
+        own.close()
+
+
+class CFir(_Handle, _MaxOut, _PerChannel):
+    """csdr_amd_cfir: the complex-tap FIR (apply_fir_cc) for n_channels channels, each with its own taps_length taps (zero until set) and its history on the
+    device: the calls' outputs are the valid filter output of each channel's whole stream."""
+    in_dtype = out_dtype = c64
+
+    def __init__(self, ctx, n_channels=1, taps_length=101):
+        self.n_channels, self.taps_length = n_channels, taps_length
+        _Handle.__init__(self, ctx, "cfir", ctx.L.csdr_amd_cfir_create(ctx.h, n_channels, taps_length))
+
+    def set_taps(self, taps, channel=-1):
+        """taps: taps_length complex taps for `channel` (-1: every channel), or [n_channels, taps_length] for all of them"""
+        taps = np.ascontiguousarray(taps, c64)
+        if taps.ndim == 2 and channel == -1:
+            if taps.shape != (self.n_channels, self.taps_length):
+                raise ValueError("taps should be [%d, %d]" % (self.n_channels, self.taps_length))
+            for ch in range(self.n_channels):
+                self._call("set_taps", ch, _hp(taps[ch]))
+            return
+        if taps.shape != (self.taps_length,):
+            raise ValueError("taps should be %d complex values" % self.taps_length)
+        self._call("set_taps", int(channel), _hp(taps))
+
+    def set_peaks(self, rates, channel=-1, window="HAMMING"):
+        """the taps of peaks_fir_cc at `rates` (one or more) for `channel` (-1: every channel)"""
+        r = np.ascontiguousarray(np.atleast_1d(rates), f32)
+        self._call("set_peaks", int(channel), _hp(r) if r.size else None, r.size, _window(window))
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts):
+        """device pointers; counts (n_channels int32) receives each channel's output count.  Asynchronous."""
+        self._call("process", d_in, n_in, in_pitch, d_out, out_pitch, d_counts)
+
+    def process(self, x, calls=None):
+        """x: [n_channels, n] (or [n]) complex samples; calls: per-call sample counts (default one call) -> a list of per-channel output arrays
+        (or one array for 1-D x)"""
+        x = np.ascontiguousarray(x, c64)
         squeeze = x.ndim == 1
         if squeeze:
             x = x[None]
@@ -2022,6 +2112,25 @@ class Context:
         self.check(self.L.csdr_amd_bfsk_demod_cf(self.h, di.ptr, do.ptr, s, n, n, max(no, 1), dt.ptr, dt.at(8 * L), L, int(force_generic)), "bfsk_demod_cf")
         y = self.download(do, f32, max(no, 1) * s).reshape(s, max(no, 1))[:, :no].copy()
         self.last_bfsk_kernel = self.L.csdr_amd_bfsk_last_kernel().decode()
+        return y[0] if squeeze else y
+
+    # ---- complex-tap FIR (cfir.hip)
+    def cfir(self, n_channels=1, taps_length=101):
+        """A batched complex-tap FIR object (CFir)"""
+        return CFir(self, n_channels, taps_length)
+
+    def apply_fir_cc(self, x, taps, force_generic=False):
+        """apply_fir_cc (libcsdr.c:2261-2273) on [n_streams, n] (or [n]) complex samples; taps [T] for all streams or [n_streams, T] -> [n_streams, n - T + 1]"""
+        x2, squeeze = self._2d(x, c64); taps = np.ascontiguousarray(taps, c64)
+        s, n = x2.shape
+        if taps.ndim not in (1, 2) or (taps.ndim == 2 and taps.shape[0] != s):
+            raise ValueError("taps should be [T] or [%d, T]" % s)
+        T = taps.shape[-1]
+        no = max(n - T + 1, 0)
+        di = self.upload(x2) if n else self.alloc(256); dt = self.upload(taps) if taps.size else self.alloc(256); do = self.alloc(8 * s * max(no, 1) + 64)
+        self.check(self.L.csdr_amd_apply_fir_cc(self.h, di.ptr, do.ptr, s, n, max(n, 1), max(no, 1), dt.ptr, T if taps.ndim == 2 else 0, T, int(force_generic)), "apply_fir_cc")
+        y = self.download(do, c64, s * max(no, 1)).reshape(s, max(no, 1))[:, :no].copy()
+        self.last_apply_fir_kernel = self.L.csdr_amd_apply_fir_last_kernel().decode()
         return y[0] if squeeze else y
 
     # ---- squelch and S-meter (squelch.hip)

@@ -383,6 +383,25 @@ struct PulseFilter : Stage {   // pulse_shaping_filter_cc csdr.c:3159-3219: appl
         return no;
     }
 };
+struct PeaksFir : Stage {   // peaks_fir_cc csdr.c:2975-3016: apply_fir_cc over the stream with the taps of its peak rates, the unconsumed tail (taps_length - 1
+                           // samples) presented again: the valid filter output of the whole stream, whatever the block size
+    int ntaps; CtxBuf<csdr_complexf> d_taps;
+    PeaksFir(csdr_amd_ctx *c, int taps_length, const std::vector<float> &rates) : ntaps(taps_length)
+    {
+        in_elem = 8; out_elem = 8; min_block = (size_t)ntaps;
+        std::vector<csdr_complexf> taps((size_t)ntaps);
+        csdr_amd_firdes_peaks_c(taps.data(), ntaps, rates.data(), (int)rates.size(), CSDR_WINDOW_HAMMING);      // WINDOW_DEFAULT, csdr.c:2991
+        d_taps = ctx_alloc<csdr_complexf>(c, 8 * taps.size(), "malloc");
+        MUST(csdr_amd_h2d(c, d_taps.get(), taps.data(), 8 * taps.size()));
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        const long no = n >= (size_t)ntaps ? (long)(n - ntaps + 1) : 0;
+        MUST(csdr_amd_apply_fir_cc(c, (const csdr_complexf *)i, (csdr_complexf *)o, 1, (long long)n, n, cap, d_taps.get(), 0, ntaps, 0));
+        *cons = (size_t)no;                                        // the rest is re-presented (csdr.c:3013-3014)
+        return no;
+    }
+};
 struct PulseRx : Stage {   // pulse_shaping_filter_cc ... | timing_recovery_cc ... [[| realpart_cf] | gain_ff g | generic_slicer_f_u8 n]: one object for the run (`chain` fuses
                           // it); the unconsumed tail and the loop's state live on the device.  The filter is evaluated only where the timing loop reads it.
     Owned<csdr_amd_pulserx, csdr_amd_pulserx_destroy> p; int D; CtxBuf<int> d_count;
@@ -1127,6 +1146,18 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         if (!parse_pulse_filter(argc, argv, &taps)) return nullptr;
         g_cmd = keep;
         return new PulseFilter(c, taps);
+    }
+    if (!strcmp(argv[1], "peaks_fir_cc")) {                                         // csdr.c:2975-2995, its checks in its order
+        const char *keep = g_cmd; g_cmd = argv[1];
+        if (argc <= 2) { badsyntax("need required parameter (taps_length)"); return nullptr; }
+        int taps_length = 0; sscanf(argv[2], "%d", &taps_length);
+        std::vector<float> rates;
+        for (int k = 3; k < argc; k++) { float r = 0; sscanf(argv[k], "%f", &r); rates.push_back(r); }
+        if (rates.empty()) { badsyntax("need required parameter (peak_rate) once or multiple times"); return nullptr; }
+        if (the_bufsize - taps_length <= 0) { badsyntax("taps_length is below buffer size, decrease taps_length"); return nullptr; }
+        if (taps_length < 1) { badsyntax("taps_length should be at least 1"); return nullptr; }
+        g_cmd = keep;
+        return new PeaksFir(c, taps_length, rates);
     }
     if (!strcmp(argv[1], "generic_slicer_f_u8")) {                                  // csdr.c:3221-3225
         const char *keep = g_cmd; g_cmd = argv[1];

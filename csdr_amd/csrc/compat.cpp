@@ -583,6 +583,17 @@ int bfsk_demod_cf(complexf *in, float *out, int n, complexf *mark_filter, comple
     return no;
 }
 
+int apply_fir_cc(complexf *in, complexf *out, int n, complexf *taps, int taps_length)
+{   // libcsdr.c:2261-2273
+    const int no = n - taps_length + 1;
+    if (no <= 0 || taps_length < 1) return 0;
+    cf32 *din = stage_in<cf32>(4, (const cf32 *)in, n); cf32 *dout = stage_out<cf32>(5, no);
+    cf32 *dt = stage_in<cf32>(6, (const cf32 *)taps, taps_length);
+    MUST(csdr_amd_apply_fir_cc(ctx(), din, dout, 1, n, n, no, dt, 0, taps_length, 0));
+    fetch((cf32 *)out, dout, no);
+    return no;
+}
+
 void firdes_add_peak_c(complexf *output, int length, float rate, window_t window, int add, int normalize)
 {   // libcsdr.c:2219-2257, on the host
     csdr_amd_firdes_add_peak_c((cf32 *)output, length, rate, (int)window, add, normalize);

@@ -484,6 +484,43 @@ void csdr_amd_firdes_peak_c(csdr_complexf *taps, int length, float rate, int win
 long long csdr_amd_debug_rtty_walk(const csdr_amd_rtty_params *params, int first_stage, int last_stage, const void *in, long long n, const long long *cuts,
                                    int n_cuts, void *out);
 
+/* ------------------------------------------------------------------ complex-tap FIR (cfir.hip)
+ * apply_fir_cc libcsdr.c:2261-2273: y[o] = sum_{t < T} x[o + t] h[t], complex x complex; n samples give n - T + 1 outputs (none below that, no zero
+ * history).  Each part of an output is ONE fmaf chain over the 2 T interleaved tap floats, from 0 (cfir_dev.hpp): the matrix-core kernel, the generic
+ * kernel and the CPU walk give the same bits for finite inputs, however a stream is cut into calls and whatever a channel's position in the batch.  (On
+ * the matrix cores an Inf or NaN sample also reaches outputs of its group of 16 that do not use it: the tap band's zeros multiply it there.)
+ * Stateless call: n_streams rows of n samples, in_pitch / out_pitch samples apart (rows 8-byte aligned); taps: DEVICE, taps_length complexf per row,
+ * taps_pitch samples apart, taps_pitch == 0: one row for all streams.  taps_length 1 .. 65536.  Returns 0 or a negative error.
+ * kernel names: "k_cfir_mfma" (the fp32 matrix cores, up to 256 taps), "k_cfir_generic" (one thread per output; force_generic takes it always). */
+int  csdr_amd_apply_fir_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, int n_streams, long long n, size_t in_pitch, size_t out_pitch,
+                           const csdr_complexf *taps, size_t taps_pitch, int taps_length, int force_generic);
+const char *csdr_amd_apply_fir_last_kernel(void);
+/* The bank: n_channels channels, each with its own taps_length taps (all zero after create) and the last < taps_length samples of its stream on the
+ * device, so the outputs of successive calls are the valid filter output of the whole stream since the last reset.  taps_length 1 .. 65536 and
+ * n_channels x taps_length <= 2^27 (the taps and the history are device buffers of that many samples).
+ * set_taps: taps_length HOST complexf for `channel` (-1: every channel).  set_peaks: the taps of peaks_fir_cc (csdr.c:2997-3002): firdes_add_peak_c of every
+ * rate (n_rates >= 1) into zeroed taps, normalised with the last.  Both are ordered with the calls on the context's stream and keep the history: new taps
+ * apply to every output of the calls that follow, the output stream has no gap and no repeat.
+ * process: n_in new samples per channel -> held + n_in - taps_length + 1 outputs (0 if fewer), at most max_out(n_in) = n_in; counts (device, n_channels ints,
+ * may be NULL) receives each channel's count.  Asynchronous.  reset / reset_channel drop the history and keep the taps. */
+typedef struct csdr_amd_cfir csdr_amd_cfir;
+csdr_amd_cfir *csdr_amd_cfir_create(csdr_amd_ctx *ctx, int n_channels, int taps_length);
+int  csdr_amd_cfir_set_taps(csdr_amd_cfir *f, int channel, const csdr_complexf *host_taps);
+int  csdr_amd_cfir_set_peaks(csdr_amd_cfir *f, int channel, const float *rates, int n_rates, int window);
+int  csdr_amd_cfir_process(csdr_amd_cfir *f, const csdr_complexf *in, long long n_in, size_t in_pitch, csdr_complexf *out, size_t out_pitch, int *counts);
+long long csdr_amd_cfir_max_out(const csdr_amd_cfir *f, long long n_in);
+int  csdr_amd_cfir_reset(csdr_amd_cfir *f);
+int  csdr_amd_cfir_reset_channel(csdr_amd_cfir *f, int channel);
+int  csdr_amd_cfir_force_generic(csdr_amd_cfir *f, int on);
+const char *csdr_amd_cfir_kernel_name(const csdr_amd_cfir *f);
+void csdr_amd_cfir_destroy(csdr_amd_cfir *f);
+/* the taps of peaks_fir_cc on the host: length complexf */
+void csdr_amd_firdes_peaks_c(csdr_complexf *taps, int length, const float *rates, int n_rates, int window);
+/* CPU run of the bank's walk (the same step functions) for one channel with HOST taps, the n samples cut into calls of cuts[0..n_cuts) samples and the
+ * rest; outputs concatenated.  Returns the output count (< 0: refused, the reason in csdr_amd_last_error()). */
+long long csdr_amd_debug_cfir_walk(const csdr_complexf *taps, int taps_length, const csdr_complexf *in, long long n, const long long *cuts, int n_cuts,
+                                   csdr_complexf *out);
+
 /* ------------------------------------------------------------------ squelch and S-meter (squelch.hip)
  * squelch_and_smeter_cc csdr.c:2192-2243 with get_power_c libcsdr.c:1154-1162, for n_channels channels.  Each channel's stream is cut into blocks of
  * block_size (B) samples counted from its start (the last reset).  A block's power is P = sum over its samples 0, d, 2d, .. of (i*i + q*q) / B with

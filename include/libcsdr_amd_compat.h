@@ -158,6 +158,7 @@ void serial_line_decoder_f_u8(serial_line_t *s, float *input, unsigned char *out
 void binary_slicer_f_u8(float *input, unsigned char *output, int input_size);
 int bfsk_demod_cf(complexf *input, float *output, int input_size, complexf *mark_filter, complexf *space_filter, int taps_length);
 void firdes_add_peak_c(complexf *output, int length, float rate, window_t window, int add, int normalize);
+int apply_fir_cc(complexf *input, complexf *output, int input_size, complexf *taps, int taps_length);      /* libcsdr.h:382: the complex-tap FIR, on the device */
 void rational_resampler_get_lowpass_f(float *output, int output_size, int interpolation, int decimation, window_t window);
 
 typedef struct shift_table_data_s { float *table; int table_size; } shift_table_data_t;     /* libcsdr.h:180-184 */
