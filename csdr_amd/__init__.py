@@ -165,6 +165,30 @@ def lib():
     L.csdr_amd_apply_fir_last_kernel.restype = C.c_char_p; L.csdr_amd_apply_fir_last_kernel.argtypes = []
     L.csdr_amd_firdes_peaks_c.restype = None; L.csdr_amd_firdes_peaks_c.argtypes = [vp, i, vp, i, i]
     L.csdr_amd_debug_cfir_walk.restype = ll; L.csdr_amd_debug_cfir_walk.argtypes = [vp, i, vp, ll, vp, i, vp]
+    ull = C.c_ulonglong
+    L.csdr_amd_noise_create.restype = vp; L.csdr_amd_noise_create.argtypes = [vp, i, i, ull, vp]
+    L.csdr_amd_noise_generate.argtypes = [vp, vp, ll, sz]
+    L.csdr_amd_noise_awgn_cc.argtypes = [vp, vp, ll, sz, vp, sz, vp]
+    L.csdr_amd_noise_set_snr_db.argtypes = [vp, i, fl]
+    L.csdr_amd_noise_set_snrs.argtypes = [vp, vp]
+    L.csdr_amd_noise_get_gains.argtypes = [vp, i, C.POINTER(fl), C.POINTER(fl)]
+    L.csdr_amd_noise_position.restype = ll; L.csdr_amd_noise_position.argtypes = [vp, i]
+    L.csdr_amd_noise_set_position.argtypes = [vp, i, ll]
+    L.csdr_amd_noise_get_channel.argtypes = [vp, i, vp]
+    L.csdr_amd_noise_reset.argtypes = [vp]
+    L.csdr_amd_noise_reset_channel.argtypes = [vp, i]
+    L.csdr_amd_noise_kernel_name.restype = C.c_char_p; L.csdr_amd_noise_kernel_name.argtypes = [vp]
+    L.csdr_amd_noise_destroy.restype = None; L.csdr_amd_noise_destroy.argtypes = [vp]
+    L.csdr_amd_awgn_gains.restype = None; L.csdr_amd_awgn_gains.argtypes = [fl, C.POINTER(fl), C.POINTER(fl)]
+    L.csdr_amd_awgn_cc.argtypes = [vp, vp, vp, vp, i, ll, sz, sz, sz, vp, vp]
+    L.csdr_amd_total_logpower_cf.argtypes = [vp, vp, i, ll, sz, vp]
+    L.csdr_amd_normalized_timing_variance_u32_f.argtypes = [vp, vp, sz, i, vp, i, i, i, vp]
+    L.csdr_amd_count_errors_u8.argtypes = [vp, vp, sz, ll, vp, sz, ll, i, vp, vp, vp]
+    L.csdr_amd_debug_philox.restype = None; L.csdr_amd_debug_philox.argtypes = [vp, vp, vp]
+    L.csdr_amd_debug_noise_words.argtypes = [i, vp, ll, vp]
+    L.csdr_amd_debug_noise_walk.restype = ll; L.csdr_amd_debug_noise_walk.argtypes = [i, ull, C.c_uint, ll, ll, vp, i, vp, fl, vp]
+    L.csdr_amd_debug_awgn_cc.argtypes = [vp, vp, ll, fl, vp]
+    L.csdr_amd_debug_timing_variance.restype = fl; L.csdr_amd_debug_timing_variance.argtypes = [vp, i, i, i]
     L.csdr_amd_squelch_create.restype = vp; L.csdr_amd_squelch_create.argtypes = [vp, i, i, i, vp, ll]
     L.csdr_amd_squelch_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, sz, vp, vp]
     L.csdr_amd_squelch_set_level.argtypes = [vp, i, fl]
@@ -1138,6 +1162,146 @@ class CFir(_Handle, _MaxOut, _PerChannel):
         calls = [n] if calls is None else list(calls)
         res = [r[0] for r in _counted_calls(self, x, calls)]
         return res[0] if squeeze else res
+
+
+NOISE_KINDS = {"gaussian": 0, "uniform": 1}
+
+
+def _noise_kind(kind):
+    return NOISE_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 of the library (csdr_amd_debug_philox): 4 counter words, 2 key words -> 4 uint32"""
+    c = np.ascontiguousarray(ctr, np.uint32); k = np.ascontiguousarray(key, np.uint32); o = np.zeros(4, np.uint32)
+    if c.shape != (4,) or k.shape != (2,):
+        raise ValueError("philox4x32_10 takes 4 counter words and 2 key words")
+    lib().csdr_amd_debug_philox(_hp(c), _hp(k), _hp(o))
+    return o
+
+
+def noise_from_words(kind, words):
+    """CPU run of the words-to-samples transform (csdr_amd_debug_noise_words): 2 n words -> n complex Gaussian samples, or n words -> n uniform floats"""
+    kind = _noise_kind(kind); w = np.ascontiguousarray(words, np.uint32).reshape(-1)
+    n = w.size // 2 if kind == 0 else w.size
+    out = np.zeros(n, c64 if kind == 0 else f32)
+    if lib().csdr_amd_debug_noise_words(kind, _hp(w), n, _hp(out)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out
+
+
+def noise_debug_walk(kind, seed, stream_id=0, position=0, n=0, cuts=(), x=None, snr_db=0.0):
+    """CPU run of one channel of a Noise object (csdr_amd_debug_noise_walk): samples position .. position + n - 1 of stream `stream_id`, cut into calls of
+    `cuts` samples and the rest; with x (Gaussian): awgn_cc of x at snr_db, n = len(x)"""
+    kind = _noise_kind(kind)
+    if x is not None:
+        x = np.ascontiguousarray(x, c64); n = x.size
+    out = np.zeros(int(n), c64 if kind == 0 else f32)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    k = lib().csdr_amd_debug_noise_walk(kind, int(seed), int(stream_id), int(position), int(n), _hp(cu) if cu.size else None, cu.size,
+                                        _hp(x) if x is not None else None, float(snr_db), _hp(out))
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out
+
+
+def awgn_gains(snr_db):
+    """(a_signal, a_noise * 0.707) of awgn_cc <snr_db> as float32 (csdr.c:3050-3052, :3079)"""
+    a, g = C.c_float(0), C.c_float(0)
+    lib().csdr_amd_awgn_gains(float(snr_db), C.byref(a), C.byref(g))
+    return f32(a.value), f32(g.value)
+
+
+def awgn_debug_mix(x, noise, snr_db):
+    """CPU run of the flat awgn_cc (csdr_amd_debug_awgn_cc): x and the caller's noise at snr_db"""
+    x = np.ascontiguousarray(x, c64); noise = np.ascontiguousarray(noise, c64)
+    if x.shape != noise.shape or x.ndim != 1:
+        raise ValueError("x and noise should be two rows of one length")
+    out = np.zeros(x.size, c64)
+    if lib().csdr_amd_debug_awgn_cc(_hp(x), _hp(noise), x.size, float(snr_db), _hp(out)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out
+
+
+def debug_timing_variance(idx, samples_per_symbol, initial_sample_offset):
+    """CPU run of normalized_timing_variance_u32_f on one row of sample indexes"""
+    idx = np.ascontiguousarray(idx, np.uint32)
+    return f32(lib().csdr_amd_debug_timing_variance(_hp(idx) if idx.size else None, idx.size, int(samples_per_symbol), int(initial_sample_offset)))
+
+
+class Noise(_Handle, _PerChannel):
+    """csdr_amd_noise: uniform_noise_f / gaussian_noise_c for n_channels channels and, on a Gaussian object, the fused awgn_cc.  A channel's stream is a
+    function of (seed, its stream id, sample index): positions are 64-bit sample indexes, settable per channel."""
+
+    def __init__(self, ctx, n_channels=1, kind="gaussian", seed=0, stream_ids=None, snr_db=None):
+        self.n_channels, self.kind, self.seed = int(n_channels), _noise_kind(kind), int(seed)
+        self.dtype = c64 if self.kind == 0 else f32
+        ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32)
+        if ids is not None and ids.shape != (self.n_channels,):
+            raise ValueError("stream_ids should be %d ids" % self.n_channels)
+        _Handle.__init__(self, ctx, "noise", ctx.L.csdr_amd_noise_create(ctx.h, self.n_channels, self.kind, self.seed, _hp(ids) if ids is not None else None))
+        if snr_db is not None:
+            self.set_snrs(snr_db)
+
+    def force_generic(self, on=True):
+        raise CsdrAmdError("noise: one kernel per call form, nothing to force")
+
+    def set_snr_db(self, ch, snr_db):
+        self._call("set_snr_db", int(ch), float(snr_db))
+
+    def set_snrs(self, snr_db):
+        """one SNR for all channels or n_channels of them, in dB"""
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(snr_db, f32), (self.n_channels,)), f32)
+        self._call("set_snrs", _hp(v))
+
+    def get_gains(self, ch):
+        a, g = C.c_float(0), C.c_float(0)
+        self._call("get_gains", int(ch), C.byref(a), C.byref(g))
+        return f32(a.value), f32(g.value)
+
+    def position(self, ch=0):
+        p = int(self._fn("position")(self.h, int(ch)))
+        if p < 0:
+            raise CsdrAmdError(self.ctx.err())
+        return p
+
+    def set_position(self, ch, pos):
+        self._call("set_position", int(ch), int(pos))
+
+    def generate_dev(self, d_out, n, out_pitch):
+        """device pointer; n samples per channel, rows out_pitch items apart.  Asynchronous."""
+        self._call("generate", d_out, int(n), int(out_pitch))
+
+    def awgn_cc_dev(self, d_in, n, in_pitch, d_out, out_pitch, d_snr=None):
+        self._call("awgn_cc", d_in, int(n), int(in_pitch), d_out, int(out_pitch), d_snr)
+
+    def generate(self, n, out_pitch=None):
+        """n samples per channel -> [n_channels, n] (float32 or complex64)"""
+        n = int(n); pitch = max(n, 1) if out_pitch is None else int(out_pitch)
+        size = self.n_channels * pitch
+        do = self.ctx.upload(np.zeros(size, self.dtype))
+        self.generate_dev(do.ptr, n, pitch)
+        return self.ctx.download(do, self.dtype, size).reshape(self.n_channels, pitch)[:, :n].copy()
+
+    def awgn_cc(self, x, with_snr=False, in_place=False, in_pitch=None, out_pitch=None):
+        """x: [n_channels, n] (or [n]) complex samples -> the same shape with each channel's noise added at its SNR; with_snr: also the n_channels SNRs in dB
+        that --snrshow would print for this call"""
+        x = np.ascontiguousarray(x, c64)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        ip = max(n, 1) if in_pitch is None else int(in_pitch); op = ip if in_place else (max(n, 1) if out_pitch is None else int(out_pitch))
+        xi = np.zeros((s, ip), c64); xi[:, :n] = x
+        di = self.ctx.upload(xi)
+        do = di if in_place else self.ctx.upload(np.zeros(s * op, c64))
+        ds = self.ctx.upload(np.zeros(s, f32)) if with_snr else None
+        self.awgn_cc_dev(di.ptr, n, ip, do.ptr, op, ds.ptr if ds else None)
+        y = self.ctx.download(do, c64, s * op).reshape(s, op)[:, :n].copy()
+        y = y[0] if squeeze else y
+        return (y, self.ctx.download(ds, f32, s)) if with_snr else y
 
 
 def squelch_report_due(report_every_nth, block_index):
@@ -2132,6 +2296,57 @@ class Context:
         y = self.download(do, c64, s * max(no, 1)).reshape(s, max(no, 1))[:, :no].copy()
         self.last_apply_fir_kernel = self.L.csdr_amd_apply_fir_last_kernel().decode()
         return y[0] if squeeze else y
+
+    # ---- noise sources, AWGN channel and link measurements (noise.hip)
+    def noise(self, n_channels=1, kind="gaussian", seed=0, stream_ids=None, snr_db=None):
+        """A batched noise source / AWGN channel (Noise)"""
+        return Noise(self, n_channels, kind, seed, stream_ids, snr_db)
+
+    def awgn_cc(self, x, noise, a_signal, a_noise_scaled):
+        """the flat awgn_cc on the caller's noise rows: x, noise [n_channels, n] (or [n]); gains per channel or one for all -> x * a_signal + noise * a_noise_scaled"""
+        x2, squeeze = self._2d(x, c64); nz, _ = self._2d(noise, c64)
+        s, n = x2.shape
+        if nz.shape != x2.shape:
+            raise ValueError("x and noise should have one shape")
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a_signal, f32), (s,)), f32); g = np.ascontiguousarray(np.broadcast_to(np.asarray(a_noise_scaled, f32), (s,)), f32)
+        di = self.upload(x2) if n else self.alloc(256); dn = self.upload(nz) if n else self.alloc(256); do = self.alloc(8 * s * max(n, 1)); da = self.upload(a); dg = self.upload(g)
+        self.check(self.L.csdr_amd_awgn_cc(self.h, di.ptr, dn.ptr, do.ptr, s, n, max(n, 1), max(n, 1), max(n, 1), da.ptr, dg.ptr), "awgn_cc")
+        y = self.download(do, c64, s * max(n, 1)).reshape(s, max(n, 1))[:, :n].copy()
+        return y[0] if squeeze else y
+
+    def total_logpower_cf(self, x):
+        """total_logpower_cf of each row of [n_rows, n] (or [n]) complex samples, in dB"""
+        x2, squeeze = self._2d(x, c64)
+        s, n = x2.shape
+        di = self.upload(x2); do = self.alloc(4 * s)
+        self.check(self.L.csdr_amd_total_logpower_cf(self.h, di.ptr, s, n, n, do.ptr), "total_logpower_cf")
+        y = self.download(do, f32, s)
+        return y[0] if squeeze else y
+
+    def normalized_timing_variance_u32_f(self, idx, samples_per_symbol, initial_sample_offset, counts=None):
+        """normalized_timing_variance_u32_f of each row of [n_rows, n] sample indexes (row r: its first counts[r]) -> n_rows floats"""
+        idx = np.ascontiguousarray(idx, np.uint32)
+        if idx.ndim == 1:
+            idx = idx[None]
+        s, n = idx.shape
+        di = self.upload(idx) if n else self.alloc(256); do = self.alloc(4 * s)
+        dc = self.upload(np.ascontiguousarray(counts, np.int32)) if counts is not None else None
+        self.check(self.L.csdr_amd_normalized_timing_variance_u32_f(self.h, di.ptr, max(n, 1), n, dc.ptr if dc else None, s, int(samples_per_symbol),
+                                                                    int(initial_sample_offset), do.ptr), "normalized_timing_variance_u32_f")
+        return self.download(do, f32, s)
+
+    def count_errors_u8(self, a, b, lags=None, counts=None):
+        """per row c the number of i < counts[c] with a[c][lags[c] + i] != b[c][i] (a, b: [n_channels, len] bytes) -> n_channels ints"""
+        a = np.ascontiguousarray(a, np.uint8); b = np.ascontiguousarray(b, np.uint8)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+            raise ValueError("a and b should be [n_channels, len] with one n_channels")
+        s = a.shape[0]
+        da = self.upload(a) if a.size else self.alloc(256); db_ = self.upload(b) if b.size else self.alloc(256); de = self.alloc(4 * s)
+        dl = self.upload(np.ascontiguousarray(lags, np.int32)) if lags is not None else None
+        dc = self.upload(np.ascontiguousarray(counts, np.int32)) if counts is not None else None
+        self.check(self.L.csdr_amd_count_errors_u8(self.h, da.ptr, max(a.shape[1], 1), a.shape[1], db_.ptr, max(b.shape[1], 1), b.shape[1], s,
+                                                   dl.ptr if dl else None, dc.ptr if dc else None, de.ptr), "count_errors_u8")
+        return self.download(de, np.int32, s)
 
     # ---- squelch and S-meter (squelch.hip)
     def squelch(self, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):

@@ -924,6 +924,117 @@ struct WaterfallStage : Stage {
     }
 };
 
+// ------------------------------------------------------------------ noise sources, AWGN channel, timing variance (csdr.c:3035-3146)
+// --seed S, or eight bytes read once from /dev/urandom
+unsigned long long noise_seed_arg(int argc, char **argv, int from)
+{
+    for (int k = from; k + 1 < argc; k++) if (!strcmp(argv[k], "--seed")) return strtoull(argv[k + 1], nullptr, 0);
+    unsigned long long seed = 0;
+    FILE *f = fopen("/dev/urandom", "r");
+    if (!f || fread(&seed, sizeof seed, 1, f) != 1) { badsyntax("failed to read a seed from /dev/urandom"); exit(255); }
+    fclose(f);
+    return seed;
+}
+
+struct Awgn : Stage {   // awgn_cc csdr.c:3035-3091.  Without --awgnfile the noise is the seeded stream of one csdr_amd_noise channel, added in the generating kernel:
+                       // the output does not depend on how the passes cut the stream.  With it, the file's whole blocks of the_bufsize samples cycle as in the
+                       // reference (a short read rewinds: the partial tail is never used): stream sample k takes noise sample k mod (whole blocks x the_bufsize).
+                       // --snrshow: one "SNR = %f dB" line per the_bufsize samples, as the reference prints (file mode: from the powers of the unscaled rows and the gains).
+    Owned<csdr_amd_noise, csdr_amd_noise_destroy> p; CtxBuf<csdr_complexf> d_noise; CtxBuf<float> d_g, d_snr; size_t period = 0, at = 0; int B; bool snrshow; float a_signal, g_noise;
+    Awgn(csdr_amd_ctx *c, float snr_db, const char *awgnfile, bool show, unsigned long long seed, int the_bufsize) : B(the_bufsize), snrshow(show)
+    {
+        in_elem = 8; out_elem = 8;
+        if (show) granule = (size_t)the_bufsize;
+        csdr_amd_awgn_gains(snr_db, &a_signal, &g_noise);
+        const float a_noise = g_noise / 0.707f;
+        fprintf(stderr, "csdr %s: a_signal = %f, a_noise = %f\n", g_cmd, a_signal, a_noise);
+        d_snr = ctx_alloc<float>(c, 64, "malloc");
+        if (!awgnfile) {
+            p.reset(csdr_amd_noise_create(c, 1, CSDR_AMD_NOISE_GAUSSIAN, seed, nullptr)); if (!p) die("noise_create");
+            MUST(csdr_amd_noise_set_snr_db(p.get(), 0, snr_db));
+            return;
+        }
+        FILE *f = fopen(awgnfile, "r");
+        if (!f) { badsyntax("failed to open the --awgnfile"); exit(255); }
+        std::vector<csdr_complexf> h;
+        std::vector<csdr_complexf> blk((size_t)the_bufsize);
+        while (fread(blk.data(), sizeof(csdr_complexf), blk.size(), f) == blk.size()) h.insert(h.end(), blk.begin(), blk.end());
+        fclose(f);
+        if (h.empty()) { badsyntax("the --awgnfile holds less than one buffer of samples"); exit(255); }
+        period = h.size();
+        d_noise = ctx_alloc<csdr_complexf>(c, 8 * period, "malloc");
+        MUST(csdr_amd_h2d(c, d_noise.get(), h.data(), 8 * period));
+        d_g = ctx_alloc<float>(c, 64, "malloc");
+        const float gains[2] = {a_signal, g_noise};
+        MUST(csdr_amd_h2d(c, d_g.get(), gains, sizeof gains));
+    }
+    float fetch(csdr_amd_ctx *c) { float v = 0; MUST(csdr_amd_d2h(c, &v, d_snr.get(), 4)); return v; }
+    // one run of m samples whose noise is contiguous
+    void piece(csdr_amd_ctx *c, const csdr_complexf *x, csdr_complexf *y, size_t m, bool with_snr)
+    {
+        if (p) {
+            MUST(csdr_amd_noise_awgn_cc(p.get(), x, (long long)m, m, y, m, with_snr ? d_snr.get() : nullptr));
+            if (with_snr) fprintf(stderr, "csdr %s: SNR = %f dB\n", g_cmd, fetch(c));
+            return;
+        }
+        if (with_snr) {
+            MUST(csdr_amd_total_logpower_cf(c, x, 1, (long long)m, m, d_snr.get()));
+            const float ps = fetch(c) + 20 * log10f(a_signal);
+            MUST(csdr_amd_total_logpower_cf(c, d_noise.get() + at, 1, (long long)m, m, d_snr.get()));
+            fprintf(stderr, "csdr %s: SNR = %f dB\n", g_cmd, ps - (fetch(c) + 20 * log10f(g_noise)));
+        }
+        MUST(csdr_amd_awgn_cc(c, x, d_noise.get() + at, y, 1, (long long)m, m, m, m, d_g.get(), d_g.get() + 1));
+        at = (at + m) % period;
+    }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        const csdr_complexf *x = (const csdr_complexf *)i; csdr_complexf *y = (csdr_complexf *)o;
+        for (size_t done = 0; done < n;) {
+            size_t m = n - done;
+            if (snrshow) m = std::min(m, (size_t)B);
+            if (!p) m = std::min(m, period - at);
+            piece(c, x + done, y + done, m, snrshow);
+            done += m;
+        }
+        return (long)n;
+    }
+};
+
+struct TimingVariance : Stage {   // normalized_timing_variance_u32_f csdr.c:3121-3146: one float per the_bufsize indexes (a partial last buffer gives one of its own)
+    int B, sps, offset; CtxBuf<float> d_out; std::vector<float> h;
+    TimingVariance(int the_bufsize, int s, int off) : B(the_bufsize), sps(s), offset(off) { in_elem = 4; out_elem = 4; granule = (size_t)the_bufsize; }
+    size_t out_capacity(size_t n) override { return n / B + 16; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        const size_t rows = n / B, rest = n % B;
+        if (rows) MUST(csdr_amd_normalized_timing_variance_u32_f(c, (const unsigned *)i, (size_t)B, B, nullptr, (int)rows, sps, offset, (float *)o));
+        if (rest) MUST(csdr_amd_normalized_timing_variance_u32_f(c, (const unsigned *)i + rows * B, rest, (int)rest, nullptr, 1, sps, offset, (float *)o + rows));
+        const size_t k = rows + (rest ? 1 : 0);
+        h.resize(k);
+        if (k) MUST(csdr_amd_d2h(c, h.data(), o, 4 * k));
+        for (float v : h) fprintf(stderr, "csdr %s: normalized variance = %f\n", g_cmd, v);
+        return (long)k;
+    }
+};
+
+// `csdr uniform_noise_f [--seed S]` / `csdr gaussian_noise_c [--seed S]` (csdr.c:3093-3119): sources, they write until the reader goes away
+int run_noise_source(csdr_amd_ctx *c, int argc, char **argv, bool gaussian)
+{
+    const unsigned long long seed = noise_seed_arg(argc, argv, 2);
+    Owned<csdr_amd_noise, csdr_amd_noise_destroy> p(csdr_amd_noise_create(c, 1, gaussian ? CSDR_AMD_NOISE_GAUSSIAN : CSDR_AMD_NOISE_UNIFORM, seed, nullptr));
+    if (!p) die("noise_create");
+    const size_t elem = gaussian ? 8 : 4, n = std::max((size_t)unitround(g_dynamic ? 1024 : g_fixed), (size_t)65536);
+    const auto d = ctx_alloc<char>(c, elem * n, "malloc");
+    std::vector<char> h(elem * n);
+    for (;;) {
+        MUST(csdr_amd_noise_generate(p.get(), d.get(), (long long)n, n));
+        MUST(csdr_amd_d2h(c, h.data(), d.get(), h.size()));
+        if (fwrite(h.data(), 1, h.size(), stdout) != h.size() || fflush(stdout)) return 0;
+    }
+}
+
 // Build the operator for one command line.  `block` = the largest input this stage will be handed in one call.
 // ctl: opened when the command line carries --fifo/--fd (single-command mode only).  Returns nullptr after printing why.
 // the BPSK31 commands: stage index, parameters into *pr, *extra = 1 / 2 for --output_error / --output_indexes; -1 (message given) on bad syntax
@@ -1229,6 +1340,24 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
             fprintf(stderr, "csdr %s: bw=%f damping=%f ko=%f kd=%f alpha=%f beta=%f\n", g_cmd, bandwidth, damping, ko, kd, pr.alpha, pr.beta);
         } else { badsyntax("invalid pll_type. Valid values are:\n\t1: PLL_P_CONTROLLER\n\t2: PLL_PI_CONTROLLER"); return nullptr; }
         return new Carrier(c, pr, Carrier::NCO);
+    }
+    if (cmd == "awgn_cc") {                                                         // csdr.c:3035-3049: <snr_db> [--awgnfile F] [--snrshow]; [--seed S] is ours
+        if (argc <= 2) { badsyntax("required parameter <snr_db> is missing."); return nullptr; }
+        float snr_db = 0; sscanf(argv[2], "%f", &snr_db);
+        const char *file = nullptr; bool show = false;
+        for (int k = 3; k < argc; k++) {
+            if (!strcmp(argv[k], "--awgnfile") && k + 1 < argc) file = argv[++k];
+            else if (!strcmp(argv[k], "--snrshow")) show = true;
+            else if (!strcmp(argv[k], "--seed") && k + 1 < argc) k++;
+        }
+        return new Awgn(c, snr_db, file, show, file ? 0 : noise_seed_arg(argc, argv, 3), unitround(the_bufsize));
+    }
+    if (cmd == "normalized_timing_variance_u32_f") {                                // csdr.c:3121-3132 (--debug, its stderr trace, is not offered)
+        if (argc <= 2) { badsyntax("required parameter <samples_per_symbol> is missing."); return nullptr; }
+        if (argc <= 3) { badsyntax("required parameter <initial_sample_offset> is missing."); return nullptr; }
+        int sps = 0, off = 0; sscanf(argv[2], "%d", &sps); sscanf(argv[3], "%d", &off);
+        if (sps < 1) { badsyntax("samples_per_symbol should be at least 1"); return nullptr; }
+        return new TimingVariance(unitround(the_bufsize), sps, off);
     }
     if (cmd == "convert_u8_f") return new Convert(0, 1, 4);
     if (cmd == "convert_f_u8") return new Convert(1, 4, 1);

@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "carrier_dev.hpp"
 #include "modem_dev.hpp"
+#include "noise_dev.hpp"
 #include "../../include/libcsdr_amd_compat.h"
 #include <math.h>
 #include <stdio.h>
@@ -1005,6 +1006,44 @@ ima_adpcm_state_t decode_ima_adpcm_u8_i16(unsigned char *in, short *out, int n, 
     MUST(csdr_amd_decode_ima_adpcm_u8_i16(ctx(), din, dout, 1, n, n, 2 * (size_t)n, ds));
     fetch(out, dout, 2 * (size_t)n); fetch(&state.index, ds, 2);
     return state;
+}
+
+// ------------------------------------------------------------------ noise sources and link measurements (libcsdr.c:2444-2471, 2518-2521, 1316-1321, 2293-2317): host code
+FILE *init_get_random_samples_f(void) { return fopen("/dev/urandom", "r"); }
+void get_random_samples_f(float *output, int output_size, FILE *status)
+{
+    if (output_size <= 0) return;
+    fread((unsigned char *)output, sizeof(float), output_size, status);
+    for (int i = 0; i < output_size; i++) { uint32_t w; memcpy(&w, output + i, 4); output[i] = noise_uniform(w); }
+}
+void get_random_gaussian_samples_c(complexf *output, int output_size, FILE *status)
+{
+    if (output_size <= 0) return;
+    fread((unsigned char *)output, sizeof(complexf), output_size, status);
+    for (int i = 0; i < output_size; i++) {
+        uint32_t w[2]; memcpy(w, output + i, 8);
+        const float2 g = noise_gauss(w[0], w[1]);
+        memcpy(output + i, &g, 8);
+    }
+}
+int deinit_get_random_samples_f(FILE *status) { return fclose(status); }
+float *add_ff(float *input1, float *input2, float *output, int input_size)
+{
+    for (int i = 0; i < input_size; i++) output[i] = input1[i] + input2[i];
+    return output;
+}
+float total_logpower_cf(complexf *input, int input_size)
+{
+    const float *x = (const float *)input;
+    float acc = 0;
+    for (int i = 0; i < input_size; i++) acc += x[2 * i] * x[2 * i] + x[2 * i + 1] * x[2 * i + 1];
+    return 10 * log10(acc / input_size);
+}
+float normalized_timing_variance_u32_f(unsigned *input, float *temp, int input_size, int samples_per_symbol, int initial_sample_offset, int debug_print)
+{   // temp and debug_print: the reference's scratch and its stderr trace, neither needed here
+    (void)temp; (void)debug_print;
+    if (input_size <= 0 || samples_per_symbol < 1) return 0.f;
+    return timing_variance([&](int i) { return input[i]; }, input_size, samples_per_symbol, initial_sample_offset);
 }
 
 } // extern "C"

@@ -521,6 +521,72 @@ void csdr_amd_firdes_peaks_c(csdr_complexf *taps, int length, const float *rates
 long long csdr_amd_debug_cfir_walk(const csdr_complexf *taps, int taps_length, const csdr_complexf *in, long long n, const long long *cuts, int n_cuts,
                                    csdr_complexf *out);
 
+/* ------------------------------------------------------------------ noise sources, the AWGN channel and link measurements (noise.hip, noise_dev.hpp)
+ * uniform_noise_f, gaussian_noise_c and awgn_cc (csdr.c:3035-3119; get_random_samples_f / get_random_gaussian_samples_c libcsdr.c:2444-2466) for
+ * n_channels channels.  The reference turns 32-bit words from /dev/urandom into samples; here the words come from Philox4x32-10:
+ *   block(kind, s, j) = philox(ctr = (j lo, j hi, s, kind), key = (seed lo, seed hi))      s: the channel's stream id, kind 0 Gaussian / 1 uniform
+ *   Gaussian complex sample i takes words 2 (i & 1) and 2 (i & 1) + 1 of block(0, s, i >> 1), uniform float k word k & 3 of block(1, s, k >> 2)
+ * and the words become samples as in the reference (noise_dev.hpp), with ln, sin and cos written out so that the kernels and the CPU entry give the same
+ * bits.  A channel's stream is a function of (seed, stream id, sample index) alone: it does not depend on how calls cut it nor on the batch position.
+ * create: stream_ids = n_channels HOST ids, or NULL for 0 .. n_channels - 1.  Every channel starts at position 0 with a_signal 1 and no noise.
+ * generate: n samples per channel from its position on (float rows for a uniform object, complexf rows for a Gaussian one, out_pitch items apart).
+ * awgn_cc (Gaussian objects): out = in * a_signal + noise * a_noise_scaled, two rounded products and one rounded sum per part (gain_ff, gain_ff, add_ff of
+ * csdr.c:3078-3087), generated, scaled and added in one pass: the noise is not written anywhere.  out may be in.  snr_out (device, n_channels floats, may
+ * be NULL): what --snrshow prints for this call, total_logpower_cf(in * a_signal) - total_logpower_cf(noise * a_noise_scaled), the powers summed in the
+ * fixed order that noise.hip documents (float squares, double sums); a call of 0 samples leaves it alone.
+ * Both advance every channel's position by n; any n from 0 on, any position, positions may differ per channel.  Asynchronous.
+ * set_snr_db / set_snrs (HOST array): a_signal = spn / (spn + 1), a_noise = 1 / (spn + 1), a_noise_scaled = a_noise * 0.707 with spn = 10^(snr_db / 20)
+ * in the reference's types (csdr_amd_awgn_gains).  get_gains returns a_signal and a_noise_scaled.  reset / reset_channel: back to position 0; ids
+ * and gains stay.  kernel_name: "k_noise_gauss", "k_noise_uniform", "k_noise_gauss<awgn>", "k_noise_gauss<awgn+snr>". */
+enum { CSDR_AMD_NOISE_GAUSSIAN = 0, CSDR_AMD_NOISE_UNIFORM = 1 };
+typedef struct csdr_amd_noise_chan {
+    unsigned long long position;
+    unsigned stream_id;
+    float a_signal, a_noise_scaled;
+    unsigned reserved;
+} csdr_amd_noise_chan;
+typedef struct csdr_amd_noise csdr_amd_noise;
+csdr_amd_noise *csdr_amd_noise_create(csdr_amd_ctx *ctx, int n_channels, int kind, unsigned long long seed, const unsigned *stream_ids);
+int  csdr_amd_noise_generate(csdr_amd_noise *p, void *out, long long n, size_t out_pitch);
+int  csdr_amd_noise_awgn_cc(csdr_amd_noise *p, const csdr_complexf *in, long long n, size_t in_pitch, csdr_complexf *out, size_t out_pitch, float *snr_out);
+int  csdr_amd_noise_set_snr_db(csdr_amd_noise *p, int channel, float snr_db);
+int  csdr_amd_noise_set_snrs(csdr_amd_noise *p, const float *snr_db);
+int  csdr_amd_noise_get_gains(const csdr_amd_noise *p, int channel, float *a_signal, float *a_noise_scaled);
+long long csdr_amd_noise_position(csdr_amd_noise *p, int channel);
+int  csdr_amd_noise_set_position(csdr_amd_noise *p, int channel, long long position);
+int  csdr_amd_noise_get_channel(csdr_amd_noise *p, int channel, csdr_amd_noise_chan *state);
+int  csdr_amd_noise_reset(csdr_amd_noise *p);
+int  csdr_amd_noise_reset_channel(csdr_amd_noise *p, int channel);
+const char *csdr_amd_noise_kernel_name(const csdr_amd_noise *p);
+void csdr_amd_noise_destroy(csdr_amd_noise *p);
+/* the gains of awgn_cc <snr_db> on the host (either output may be NULL) */
+void csdr_amd_awgn_gains(float snr_db, float *a_signal, float *a_noise_scaled);
+/* awgn_cc on the caller's noise rows (the --awgnfile path): out = in * a_signal[ch] + noise * a_noise_scaled[ch] in the order above, bit-exact to the
+ * reference.  Rows of n complexf, pitches in samples; a_signal / a_noise_scaled: DEVICE, n_channels floats each.  out may be in. */
+int  csdr_amd_awgn_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, const csdr_complexf *noise, csdr_complexf *out, int n_channels, long long n, size_t in_pitch,
+                      size_t noise_pitch, size_t out_pitch, const float *a_signal, const float *a_noise_scaled);
+/* total_logpower_cf libcsdr.c:1316-1321 for n_rows rows of n >= 1 samples: out (device, n_rows floats) = 10 log10(sum (i*i + q*q) / n), the squares in
+ * float, the sum in double in the order of noise.hip. */
+int  csdr_amd_total_logpower_cf(csdr_amd_ctx *ctx, const csdr_complexf *in, int n_rows, long long n, size_t in_pitch, float *out);
+/* normalized_timing_variance_u32_f libcsdr.c:2293-2317 for n_rows rows of sample indexes (the idx output of csdr_amd_pulserx_process), pitch items apart:
+ * row r has counts[r] of them (device ints, clamped to 0 .. n; NULL: n each).  The reference's unsigned arithmetic and running mean, one lane per row.
+ * out: device, n_rows floats.  A row of one index divides 0 by 0 as the reference does and gives NaN; an empty row gives 0. */
+int  csdr_amd_normalized_timing_variance_u32_f(csdr_amd_ctx *ctx, const unsigned *idx, size_t pitch, int n, const int *counts, int n_rows, int samples_per_symbol,
+                                               int initial_sample_offset, float *out);
+/* errors[c] (device ints) = the number of i < n_c with a[c][lag_c + i] != b[c][i], exact.  n_c = counts[c] (device; NULL: b_len) cut to b_len and to
+ * a_len - lag_c, so that no read leaves a row; lag_c = lags[c] >= 0 (device; NULL: 0).  Rows a_pitch / b_pitch bytes apart. */
+int  csdr_amd_count_errors_u8(csdr_amd_ctx *ctx, const unsigned char *a, size_t a_pitch, long long a_len, const unsigned char *b, size_t b_pitch, long long b_len,
+                              int n_channels, const int *lags, const int *counts, int *errors);
+/* CPU entries (noise_dev.hpp on the host).  philox: ctr[4], key[2] -> out[4].  noise_words: kind 0, n complexf from 2 n words; kind 1, n floats from n
+ * words.  noise_walk: one channel's stream from `position`, cut into calls of cuts[0..n_cuts) samples and the rest; in == NULL: the noise, else (Gaussian)
+ * awgn_cc of in at snr_db.  Returns n (< 0: refused). */
+void csdr_amd_debug_philox(const unsigned *ctr, const unsigned *key, unsigned *out);
+int  csdr_amd_debug_noise_words(int kind, const unsigned *words, long long n, void *out);
+long long csdr_amd_debug_noise_walk(int kind, unsigned long long seed, unsigned stream_id, long long position, long long n, const long long *cuts, int n_cuts,
+                                    const csdr_complexf *in, float snr_db, void *out);
+int  csdr_amd_debug_awgn_cc(const csdr_complexf *in, const csdr_complexf *noise, long long n, float snr_db, csdr_complexf *out);   /* the flat awgn_cc on the host */
+float csdr_amd_debug_timing_variance(const unsigned *idx, int n, int samples_per_symbol, int initial_sample_offset);
+
 /* ------------------------------------------------------------------ squelch and S-meter (squelch.hip)
  * squelch_and_smeter_cc csdr.c:2192-2243 with get_power_c libcsdr.c:1154-1162, for n_channels channels.  Each channel's stream is cut into blocks of
  * block_size (B) samples counted from its start (the last reset).  A block's power is P = sum over its samples 0, d, 2d, .. of (i*i + q*q) / B with

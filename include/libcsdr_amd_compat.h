@@ -255,6 +255,17 @@ decimating_shift_addition_status_t fastddc_inv_cc(complexf *input, complexf *out
 void fastddc_print(fastddc_t *ddc, char *source);
 void fft_swap_sides(complexf *io, int fft_size);
 
+/* noise sources and link measurements, libcsdr.h:385-391, all on the host.  The random samples are functions of the 32-bit words read from `status`:
+ * any file of recorded words in place of /dev/urandom reproduces the reference (the Gaussian ones within the float32 gate of DESIGN.md 4s).
+ * add_ff returns output (the reference's has no return statement). */
+FILE *init_get_random_samples_f(void);
+void get_random_samples_f(float *output, int output_size, FILE *status);
+void get_random_gaussian_samples_c(complexf *output, int output_size, FILE *status);
+int deinit_get_random_samples_f(FILE *status);
+float *add_ff(float *input1, float *input2, float *output, int input_size);
+float total_logpower_cf(complexf *input, int input_size);
+float normalized_timing_variance_u32_f(unsigned *input, float *temp, int input_size, int samples_per_symbol, int initial_sample_offset, int debug_print);
+
 #ifdef __cplusplus
 }
 #endif
