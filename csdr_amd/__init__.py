@@ -94,6 +94,10 @@ def lib():
     L.csdr_amd_fftcc_create.restype = vp; L.csdr_amd_fftcc_create.argtypes = [vp, i, i, i, i]
     L.csdr_amd_fftcc_destroy.argtypes = [vp]; L.csdr_amd_fftcc_destroy.restype = None
     L.csdr_amd_fftcc_process.argtypes = [vp, vp, sz, vp, C.POINTER(sz)]
+    L.csdr_amd_fftfc_create.restype = vp; L.csdr_amd_fftfc_create.argtypes = [vp, i, i, i, sz]
+    L.csdr_amd_fftfc_destroy.argtypes = [vp]; L.csdr_amd_fftfc_destroy.restype = None
+    L.csdr_amd_fftfc_process.argtypes = [vp, vp, sz, vp]
+    L.csdr_amd_fft_one_side_ff.argtypes = [vp, vp, vp, i, i]
     L.csdr_amd_encode_ima_adpcm_i16_u8.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_decode_ima_adpcm_u8_i16.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_compress_fft_adpcm_f_u8.argtypes = [vp, vp, vp, i, i]
@@ -523,13 +527,18 @@ def _counted_calls(obj, x, calls, extras=(), **inputs):
 
 
 class Waterfall(_Handle):
-    """csdr_amd_waterfall: n_streams streams in lockstep -> rows of fft_size float dB values (out_format "db") or (fft_size+10)/2 ADPCM bytes ("adpcm")."""
+    """csdr_amd_waterfall: n_streams streams in lockstep -> rows of fft_size float dB values (out_format "db") or (fft_size+10)/2 ADPCM bytes ("adpcm").
+    in_format "cf32" / "u8": complex samples, rows with the halves exchanged; "f32" / "s16": real samples, fft_size is the number of output bins (fft_fc's
+    fft_out_size), every_n and the sample counts are in real samples, rows are one-sided (DC first)."""
+    # in_format -> (CSDR_AMD_WF_IN_*, host dtype, host elements per sample, bytes per sample)
+    FORMATS = {"cf32": (0, c64, 1, 8), "u8": (1, np.uint8, 2, 2), "f32": (2, f32, 1, 4), "s16": (3, np.int16, 1, 2)}
 
     def __init__(self, ctx, fft_size, every_n, avgnumber, add_db, window, in_format, out_format, n_streams, max_samples_per_call):
         self.fft, self.every, self.avg, self.n_streams, self.max_in = fft_size, every_n, avgnumber, n_streams, int(max_samples_per_call)
         self.in_format, self.out_format = in_format, out_format
+        self._code, self._dtype, self._per, self._eb = self.FORMATS.get(in_format, self.FORMATS["cf32"])
         _Handle.__init__(self, ctx, "waterfall", ctx.L.csdr_amd_waterfall_create(ctx.h, fft_size, every_n, WINDOWS[window], avgnumber, add_db,
-                                                                                  1 if in_format == "u8" else 0, 1 if out_format == "adpcm" else 0, n_streams, self.max_in))
+                                                                                  self._code, 1 if out_format == "adpcm" else 0, n_streams, self.max_in))
         self.row_bytes = 4 * fft_size if out_format == "db" else (fft_size + 10) // 2
 
     def max_rows(self, n_in):
@@ -542,12 +551,13 @@ class Waterfall(_Handle):
         return rows.value
 
     def process(self, x, calls=None):
-        """x: [n_streams, ...] host samples (u8 IQ bytes or complex64); calls: list of per-call sample counts (default one call) -> [n_streams, rows, ...]"""
-        x = np.ascontiguousarray(x, np.uint8 if self.in_format == "u8" else c64)
+        """x: [n_streams, ...] host samples (u8 IQ bytes, complex64, float32 or int16 by in_format); calls: list of per-call sample counts (default one
+        call) -> [n_streams, rows, ...]"""
+        x = np.ascontiguousarray(x, self._dtype)
         if x.ndim == 1:
             x = x[None]
-        n = x.shape[1] // 2 if self.in_format == "u8" else x.shape[1]
-        eb = 2 if self.in_format == "u8" else 8
+        n = x.shape[1] // self._per
+        eb = self._eb
         calls = [n] if calls is None else list(calls)
         di = self.ctx.upload(x)
         opitch = (self.max_rows(max(calls)) * self.row_bytes + 255) // 256 * 256
@@ -2039,8 +2049,28 @@ class Context:
 
     # ---- the waterfall (waterfall.hip)
     def waterfall(self, fft_size, every_n, avgnumber, add_db=0.0, window="HAMMING", in_format="u8", out_format="db", n_streams=1, max_samples_per_call=1 << 20):
-        """A batched `[convert_u8_f |] fft_cc | logaveragepower_cf | fft_exchange_sides_ff [| compress_fft_adpcm_f_u8]` object (csdr_amd_waterfall)."""
+        """A batched `[convert_u8_f |] fft_cc | logaveragepower_cf | fft_exchange_sides_ff [| compress_fft_adpcm_f_u8]` object (csdr_amd_waterfall);
+        in_format "f32" / "s16": `[convert_s16_f |] fft_fc | logaveragepower_cf [| compress_fft_adpcm_f_u8]` on real samples, fft_size = output bins."""
         return Waterfall(self, fft_size, every_n, avgnumber, add_db, window, in_format, out_format, n_streams, max_samples_per_call)
+
+    def fft_fc(self, x, fft_out_size, every_n, window="HAMMING", calls=1):
+        """`csdr fft_fc` (csdr.c:3414-3498) on one stream of floats, cut into `calls` calls -> [spectra, fft_out_size] complex64"""
+        x = np.ascontiguousarray(x, f32).ravel()
+        per = max(1, (x.size + calls - 1) // calls)
+        frames_max = x.size // min(every_n, 2 * fft_out_size) + calls + 1
+        with _Handle(self, "fftfc", self.L.csdr_amd_fftfc_create(self.h, fft_out_size, every_n, WINDOWS[window], per)) as f:
+            di = self.upload(x); do = self.alloc(8 * fft_out_size * frames_max + 64)
+            total = 0
+            for at in range(0, x.size, per):
+                total += self.check(f._fn("process")(f.h, di.at(4 * at), min(per, x.size - at), do.at(8 * fft_out_size * total)), "fft_fc")
+            return self.download(do, c64, fft_out_size * total).reshape(total, fft_out_size)
+
+    def fft_one_side_ff(self, x, fft_size):
+        """`csdr fft_one_side_ff` (csdr.c:1717-1734): the first fft_size/2 floats of every row of fft_size -> [n_rows, fft_size/2]"""
+        x = np.ascontiguousarray(x, f32).ravel(); rows = x.size // fft_size
+        di = self.upload(x); do = self.alloc(4 * rows * (fft_size // 2) + 64)
+        self.check(self.L.csdr_amd_fft_one_side_ff(self.h, di.ptr, do.ptr, rows, fft_size), "fft_one_side_ff")
+        return self.download(do, f32, rows * (fft_size // 2)).reshape(rows, fft_size // 2)
 
     def logaveragepower_cf(self, x, fft_size, avgnumber, add_db=0.0):
         """x: n_rows*avgnumber spectra of fft_size bins -> [n_rows, fft_size] dB rows (csdr.c:1663-1695)"""

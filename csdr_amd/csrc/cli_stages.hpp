@@ -846,6 +846,39 @@ struct FftCc : Stage {         // csdr.c:1569-1641 (binary output; --octave text
     long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t, size_t *cons) override
     { size_t used = 0; int nf = csdr_amd_fftcc_process(f, (const csdr_complexf *)i, n, (csdr_complexf *)o, &used); MUST(nf); *cons = used; return (long)nf * fft; }
 };
+struct FftFc : Stage {         // csdr.c:3414-3498 (binary output): M complex bins per spectrum of 2M floats; the sliding buffer and the skip stay in the object
+    csdr_amd_fftfc *f; int fft, every; size_t chunk;
+    FftFc(csdr_amd_ctx *c, int fft_out_size, int every_n, int window, size_t block) : fft(fft_out_size), every(every_n)
+    {
+        in_elem = 4; out_elem = 8;
+        chunk = block + 64;
+        if (chunk > (size_t)32768 * every_n) chunk = (size_t)32768 * every_n;      // (the object frames at most 65535 spectra per call)
+        f = csdr_amd_fftfc_create(c, fft_out_size, every_n, window, chunk); if (!f) die("fftfc_create");
+    }
+    size_t out_capacity(size_t n) override { return (n / every + 2) * (size_t)fft; }
+    int next_bufsize(int) override { return fft; }                   // csdr.c:3447
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        *cons = n;
+        long nf = 0;
+        for (size_t at = 0; at < n; at += chunk) {
+            const int k = csdr_amd_fftfc_process(f, (const float *)i + at, n - at < chunk ? n - at : chunk, (csdr_complexf *)o + (size_t)nf * fft); MUST(k);
+            nf += k;
+        }
+        return nf * fft;
+    }
+};
+struct OneSide : Stage {       // csdr.c:1717-1734
+    int fft;
+    OneSide(int f) : fft(f) { granule = f; flush_partial = false; }
+    int next_bufsize(int) override { return fft; }                   // csdr.c:1723
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t, size_t *cons) override
+    {
+        const int nr = (int)(n / fft); *cons = (size_t)nr * fft;
+        if (nr) MUST(csdr_amd_fft_one_side_ff(c, (const float *)i, (float *)o, nr, fft));
+        return (long)nr * (fft / 2);
+    }
+};
 
 
 // ------------------------------------------------------------------ f3 commands (csdr.c:1745-1768, 1891-1919)
@@ -904,12 +937,14 @@ struct ExchangeSides : Stage {   // csdr.c:1697-1714
 };
 // `[convert_u8_f |] fft_cc N E [window] | logaveragepower_cf A N AVG | fft_exchange_sides_ff N [| compress_fft_adpcm_f_u8 N]` as ONE command (extension):
 //   csdr waterfall_u8 | waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>
+// and `[convert_s16_f |] fft_fc M E [window] | logaveragepower_cf A M AVG [| compress_fft_adpcm_f_u8 M]` on a real stream (one-sided rows, M = output bins):
+//   csdr waterfall_ff | waterfall_s16 <fft_out_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>
 struct WaterfallStage : Stage {
     csdr_amd_waterfall *w; int fft, every, avg; bool adpcm;
-    WaterfallStage(csdr_amd_ctx *c, bool u8, int f, int e, int window, float add_db, int a, bool ad, size_t block) : fft(f), every(e), avg(a), adpcm(ad)
+    WaterfallStage(csdr_amd_ctx *c, int in_format, int f, int e, int window, float add_db, int a, bool ad, size_t block) : fft(f), every(e), avg(a), adpcm(ad)
     {
-        in_elem = u8 ? 2 : 8; out_elem = ad ? 1 : 4;
-        w = csdr_amd_waterfall_create(c, f, e, window, a, add_db, u8 ? CSDR_AMD_WF_IN_U8 : CSDR_AMD_WF_IN_CF32, ad ? CSDR_AMD_WF_OUT_ADPCM : CSDR_AMD_WF_OUT_DB, 1, block + 64);
+        in_elem = in_format == CSDR_AMD_WF_IN_CF32 ? 8 : in_format == CSDR_AMD_WF_IN_F32 ? 4 : 2; out_elem = ad ? 1 : 4;
+        w = csdr_amd_waterfall_create(c, f, e, window, a, add_db, in_format, ad ? CSDR_AMD_WF_OUT_ADPCM : CSDR_AMD_WF_OUT_DB, 1, block + 64);
         if (!w) die("waterfall_create");
     }
     size_t row_elems() const { return adpcm ? (size_t)(fft + 10) / 2 : (size_t)fft; }
@@ -1523,12 +1558,27 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         if (csdr_amd_log2n(fft) < 1) { badsyntax("fft_size must be a power of two >= 2"); return nullptr; }
         return new ExchangeSides(fft);
     }
-    if (cmd == "waterfall_u8" || cmd == "waterfall_cc") {
+    if (cmd == "fft_fc") {
+        if (argc <= 3) { badsyntax("need required parameters (fft_out_size, out_of_every_n_samples)"); return nullptr; }
+        int fft = 0, every = 0; sscanf(argv[2], "%d", &fft); sscanf(argv[3], "%d", &every);
+        if (csdr_amd_log2n(fft) < 1) { badsyntax("fft_out_size should be power of 2 (>= 2 on the MI355X back end)"); return nullptr; }
+        if (every <= 0) { badsyntax("out_of_every_n_samples must be positive"); return nullptr; }
+        if (argc >= 6 && !strcmp(argv[5], "--octave")) { badsyntax("--octave text output is not offered by the MI355X back end"); return nullptr; }
+        return new FftFc(c, fft, every, argc >= 5 ? window_from(argv[4]) : CSDR_WINDOW_HAMMING, block);
+    }
+    if (cmd == "fft_one_side_ff") {
+        if (argc <= 2) { badsyntax("need required parameters (fft_size)"); return nullptr; }
+        int fft = 0; sscanf(argv[2], "%d", &fft);
+        if (fft < 2 || (fft & 1)) { badsyntax("fft_size must be even and >= 2"); return nullptr; }
+        return new OneSide(fft);
+    }
+    if (cmd == "waterfall_u8" || cmd == "waterfall_cc" || cmd == "waterfall_ff" || cmd == "waterfall_s16") {
         if (argc <= 7) { badsyntax("need required parameters (fft_size, every_n, window, add_db, avgnumber, db|adpcm)"); return nullptr; }
         int fft = 0, every = 0, avg = 0; float add_db = 0;
         sscanf(argv[2], "%d", &fft); sscanf(argv[3], "%d", &every); sscanf(argv[5], "%g", &add_db); sscanf(argv[6], "%d", &avg);
         if (csdr_amd_log2n(fft) < 1 || every <= 0 || avg <= 0) { badsyntax("fft_size must be a power of two >= 2, every_n and avgnumber positive"); return nullptr; }
-        return new WaterfallStage(c, cmd == "waterfall_u8", fft, every, window_from(argv[4]), add_db, avg, !strcmp(argv[7], "adpcm"), block);
+        const int in_format = cmd == "waterfall_u8" ? CSDR_AMD_WF_IN_U8 : cmd == "waterfall_cc" ? CSDR_AMD_WF_IN_CF32 : cmd == "waterfall_ff" ? CSDR_AMD_WF_IN_F32 : CSDR_AMD_WF_IN_S16;
+        return new WaterfallStage(c, in_format, fft, every, window_from(argv[4]), add_db, avg, !strcmp(argv[7], "adpcm"), block);
     }
     // the fused commands: `--fifo <path>` / `--fd <n>` stand where the shift rate stands, as in shift_addition_cc (csdr.c:881-893); the first rate is waited for
     if (cmd == "ddc_u8_cc" || cmd == "nfm_chain_u8_s16" || cmd == "wfm_chain_u8_s16") {

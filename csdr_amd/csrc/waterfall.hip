@@ -18,6 +18,16 @@
 // zeros of the reference's fresh sliding buffer.  All streams of an object advance in lockstep, so the schedule is host-side scalars; each stream keeps the
 // last N raw input samples (the overlap history) and its partial row (acc in device memory).
 //
+// Real input (CSDR_AMD_WF_IN_F32 / _S16): `[convert_s16_f |] fft_fc M E [window] | logaveragepower_cf A M AVG [| compress_fft_adpcm_f_u8 M]` (csdr.c:3414-3498).
+// fft_size is M, the number of output bins; a frame is 2M real samples, loaded as the M complex points z[n] = w[2n] x[2n] + i w[2n+1] x[2n+1].  The M-point
+// passes run unchanged on z; one more exchange through the same LDS (Z in natural order, every thread reads its bins' partners) untangles Z into the real
+// signal's spectrum, X[k] = 1/2 (Z[k] + conj Z[(M-k) mod M]) - (i/2) e^(-i pi k / M) (Z[k] - conj Z[(M-k) mod M]), k < M (the Nyquist bin is not formed, as
+// fft_fc does not write it).  Rows are in display order already: no exchange of halves.  The generic form packs the same way, runs the M-point hipFFT plan
+// and untangles in k_wf_post.  Frame schedule = fft_fc's, in real samples: E <= 2M: frame k covers [k E + E - 2M, k E + E); E > 2M: the reference's skip loop
+// reads complexf-sized items from the float stream (csdr.c:3466-3469), so it drops 2 (E - 2M) floats and frame k covers [k P, k P + 2M), P = 2 E - 2M.
+// The eight real instantiations take 181 - 240 VGPRs and no scratch (two waves per SIMD).  At M = 8192 a workgroup holds a CU alone, so its compressed rows
+// are not encoded by thread 0 inside the kernel but by k_wf_post's stand-alone mode over dB rows in scratch (run_onepass).
+//
 // The one-pass stages are __host__ __device__: csdr_amd_debug_waterfall_row runs them on the CPU thread by thread (same index maps, same accumulation order).
 #include "common.hpp"
 #include "convert_dev.hpp"
@@ -130,7 +140,9 @@ template <int N> WF_HD void wf_const(int t, const float2 *table, WfConst<N> &c)
     if constexpr (WfPlan<N>::NP > 3) WfPass<N, 3>::twiddles(t, table, c.w3);
 }
 
-template <int IN> constexpr int wf_elem() { return IN == CSDR_AMD_WF_IN_U8 ? 2 : 8; }
+// bytes per raw unit of the schedule: a complex sample (cf32, u8 IQ) or a real one (f32, s16)
+template <int IN> constexpr int wf_elem() { return IN == CSDR_AMD_WF_IN_U8 || IN == CSDR_AMD_WF_IN_S16 ? 2 : IN == CSDR_AMD_WF_IN_F32 ? 4 : 8; }
+template <int IN> constexpr bool wf_real() { return IN == CSDR_AMD_WF_IN_F32 || IN == CSDR_AMD_WF_IN_S16; }
 
 // one raw sample as a complex float: u8 IQ through convert_u8_f's arithmetic, or cf32
 template <int IN> WF_HD float2 wf_to_c(const void *p, long long idx)
@@ -170,6 +182,82 @@ template <int N, int IN> WF_HD void wf_load(const void *in, const void *hist, lo
 #pragma unroll
     for (int s = 0; s < 16; s++) v[s] = wf_windowed<IN>(in, hist, base, hist_len, start + WfPass<N, 0>::src(t, s), window[WfPass<N, 0>::src(t, s)]);
 }
+// ---- real input: one raw sample as a float (s16 through convert_s16_f's arithmetic), the packed load, the untangle
+WF_HD float wf_s16_f(int raw)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return to_float<2>(raw);
+#else
+    return (float)raw * (1.0f / 32767.0f);                               // libcsdr.c:2370 as the reference's -ffast-math build forms it (convert_dev.hpp)
+#endif
+}
+template <int IN> WF_HD float wf_to_r(const void *p, long long idx)
+{
+    if (IN == CSDR_AMD_WF_IN_S16) return wf_s16_f(((const int16_t *)p)[idx]);
+    return ((const float *)p)[idx];
+}
+// samples 2n and 2n+1 of p as one load (p aligned to a pair)
+template <int IN> WF_HD float2 wf_pair(const void *p, int n)
+{
+    if (IN == CSDR_AMD_WF_IN_S16) {
+        const uint32_t u = ((const uint32_t *)p)[n];
+        return make_float2(wf_s16_f((int16_t)(u & 0xffff)), wf_s16_f((int16_t)(u >> 16)));
+    }
+    return ((const float2 *)p)[n];
+}
+// packed point n of the frame that starts at real sample `start`: (w[2n] x[start + 2n], w[2n+1] x[start + 2n + 1]); positions as wf_windowed's
+template <int IN> WF_HD float2 wf_packed(const void *in, const void *hist, long long base, int hist_len, long long start, int n, const float *window)
+{
+    float x[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const long long p = start + 2 * n + e;
+        x[e] = p < 0 ? 0.f : p >= base ? wf_to_r<IN>(in, p - base) : wf_to_r<IN>(hist, p - base + hist_len);
+    }
+    const float2 w = reinterpret_cast<const float2 *>(window)[n];
+    return make_float2(x[0] * w.x, x[1] * w.y);
+}
+template <int N, int IN> WF_HD void wf_load_r(const void *in, const void *hist, long long base, int hist_len, long long start, int t, const float *window, float2 (&v)[16])
+{
+    if (start >= base) {                                                 // (uniform) the whole frame lies in this call's input
+        const char *x = (const char *)in + (size_t)(start - base + 2 * t) * wf_elem<IN>();
+        const float2 *wt = reinterpret_cast<const float2 *>(window) + t;
+        if (((size_t)x & (2 * wf_elem<IN>() - 1)) == 0) {                // (uniform: the threads' addresses differ by whole pairs) a pair per load
+#pragma unroll
+            for (int s = 0; s < 16; s++) {
+                const float2 y = wf_pair<IN>(x, WfPass<N, 0>::src_off(s)), w = wt[WfPass<N, 0>::src_off(s)];
+                v[s] = make_float2(y.x * w.x, y.y * w.y);
+            }
+            return;
+        }
+#pragma unroll
+        for (int s = 0; s < 16; s++) {
+            const float2 w = wt[WfPass<N, 0>::src_off(s)];
+            v[s] = make_float2(wf_to_r<IN>(x, 2 * WfPass<N, 0>::src_off(s)) * w.x, wf_to_r<IN>(x, 2 * WfPass<N, 0>::src_off(s) + 1) * w.y);
+        }
+        return;
+    }
+#pragma unroll
+    for (int s = 0; s < 16; s++) v[s] = wf_packed<IN>(in, hist, base, hist_len, start, WfPass<N, 0>::src(t, s), window);
+}
+// bin k of the real signal's spectrum from Z[k], zm = Z[(M - k) mod M] and h = e^(-i pi k / M)
+// (products and sums as written, in every kernel that inlines it: `fft_fc | logaveragepower_cf` then equals the generic form's rows bit for bit)
+WF_HD float2 wf_untangle1(float2 z, float2 zm, float2 h)
+{
+#pragma clang fp contract(off)
+    const float ax = 0.5f * (z.x + zm.x), ay = 0.5f * (z.y - zm.y), bx = 0.5f * (z.x - zm.x), by = 0.5f * (z.y + zm.y);
+    const float cx = h.x * bx - h.y * by, cy = h.x * by + h.y * bx;      // c = h b
+    return make_float2(ax + cy, ay - cx);                                // a - i c
+}
+// lds: Z in natural order (padded), written by the last pass's lds_write; every thread untangles the bins it holds
+template <int N> WF_HD void wf_untangle(const float2 *lds, int t, const float2 *half, float2 (&v)[16])
+{
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+        const int k = wf_bin<N>(t, s);
+        v[s] = wf_untangle1(v[s], lds[wf_pad((N - k) & (N - 1))], half[k]);
+    }
+}
 template <int N> WF_HD void wf_accumulate(const float2 (&v)[16], float (&acc)[16])
 {
 #pragma clang fp contract(off)
@@ -192,7 +280,7 @@ struct WfArgs {
     const void *in; size_t in_pitch;                                    // samples
     const void *hist; void *hist_new; int hist_len;                      // [stream][hist_len] raw samples: positions [base - hist_len, base)
     long long base; int every, off;
-    const float *window; const float2 *table;
+    const float *window; const float2 *table;                            // real input: window of 2N entries, table = [exp(-2 pi i m / N), m < N | exp(-i pi k / N), k < N]
     const float *acc_in; float *acc_out;                                 // [stream][N]: the partial row, natural bin order -- read from one buffer, written to the
                                                                          // other (the call's first segment reads it while its last one writes the next)
     void *out; size_t out_pitch; int out_format; float add_db;           // out_pitch: bytes
@@ -220,10 +308,11 @@ __device__ void wf_adpcm_row(const int16_t *q, int n, uint8_t *y)
 }
 
 template <int N, int IN>
-__global__ __launch_bounds__(N / 16) void k_wf_onepass(WfArgs a)
+__device__ __forceinline__ void wf_onepass(const WfArgs &a, float2 *wf_lds)
 {
-    extern __shared__ __attribute__((aligned(16))) float2 wf_lds[];
     constexpr int NP = WfPlan<N>::NP;
+    constexpr bool REAL = wf_real<IN>();
+    constexpr int SWAP = REAL ? 0 : N / 2;                               // a one-sided row is in display order already
     const int t = threadIdx.x, s = blockIdx.y;
     const WfSeg sg = a.segs[blockIdx.x];
     float2 w[8];                                                         // base twiddles of the pass at hand (re-read per frame: cache-resident, and registers are short)
@@ -236,7 +325,8 @@ __global__ __launch_bounds__(N / 16) void k_wf_onepass(WfArgs a)
     float2 v[16];
     for (int f = 0; f < sg.n; f++) {
         const long long start = (sg.k0 + f) * a.every + a.off;
-        wf_load<N, IN>(in, hist, a.base, a.hist_len, start, t, a.window, v);
+        if constexpr (REAL) wf_load_r<N, IN>(in, hist, a.base, a.hist_len, start, t, a.window, v);
+        else wf_load<N, IN>(in, hist, a.base, a.hist_len, start, t, a.window, v);
         WfPass<N, 0>::compute(v, w);
         WfPass<N, 0>::lds_write(wf_lds, t, v);
         __syncthreads();
@@ -257,6 +347,12 @@ __global__ __launch_bounds__(N / 16) void k_wf_onepass(WfArgs a)
             WfPass<N, 3>::twiddles(t, a.table, w);
             WfPass<N, 3>::compute(v, w);
         }
+        if constexpr (REAL) {
+            __syncthreads();
+            WfPass<N, NP - 1>::lds_write(wf_lds, t, v);                  // Z in natural order
+            __syncthreads();
+            wf_untangle<N>(wf_lds, t, a.table + N, v);
+        }
         wf_accumulate<N>(v, acc);
         __syncthreads();                                                 // (the next frame's first write)
     }
@@ -269,14 +365,27 @@ __global__ __launch_bounds__(N / 16) void k_wf_onepass(WfArgs a)
     if (a.out_format == CSDR_AMD_WF_OUT_DB) {
         float *o = (float *)orow + (size_t)sg.row * N;
 #pragma unroll
-        for (int k = 0; k < 16; k++) o[(wf_bin<N>(t, k) + N / 2) & (N - 1)] = wf_db(acc[k], a.add_db);
+        for (int k = 0; k < 16; k++) o[(wf_bin<N>(t, k) + SWAP) & (N - 1)] = wf_db(acc[k], a.add_db);
         return;
     }
     int16_t *q = reinterpret_cast<int16_t *>(wf_lds);
 #pragma unroll
-    for (int k = 0; k < 16; k++) q[(wf_bin<N>(t, k) + N / 2) & (N - 1)] = (int16_t)db_to_short(wf_db(acc[k], a.add_db));
+    for (int k = 0; k < 16; k++) q[(wf_bin<N>(t, k) + SWAP) & (N - 1)] = (int16_t)db_to_short(wf_db(acc[k], a.add_db));
     __syncthreads();
     if (t == 0) wf_adpcm_row(q, N, (uint8_t *)orow + (size_t)sg.row * ((N + 10) / 2));
+}
+template <int N, int IN>
+__global__ __launch_bounds__(N / 16) void k_wf_onepass(WfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float2 wf_lds[];
+    wf_onepass<N, IN>(a, wf_lds);
+}
+// the real-input form (N = output bins, IN = CSDR_AMD_WF_IN_F32 / _S16): a name of its own in traces
+template <int N, int IN>
+__global__ __launch_bounds__(N / 16) void k_wf_onepass_real(WfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float2 wf_lds[];
+    wf_onepass<N, IN>(a, wf_lds);
 }
 
 // new history = the last hist_len samples of [history | input]  (raw samples as 16-bit units: u8 rows may start on any even byte)
@@ -303,16 +412,19 @@ __global__ __launch_bounds__(256) void k_wf_frame(WfArgs a, int fft, long long k
     const long long start = (k_first + f) * a.every + a.off;
     float2 *y = frames + ((size_t)sl * n_frames + f) * fft;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < fft; i += gridDim.x * 256) {
-        y[i] = wf_windowed<IN>(in, hist, a.base, a.hist_len, start + i, a.window[i]);
+        if constexpr (wf_real<IN>()) y[i] = wf_packed<IN>(in, hist, a.base, a.hist_len, start, i, a.window);   // fft packed points of 2 fft real samples
+        else y[i] = wf_windowed<IN>(in, hist, a.base, a.hist_len, start + i, a.window[i]);
     }
 }
 
 // post-FFT pass: POWER = sum |X|^2 over the segment's spectra, log, optional swap, dB or compressed row; !POWER = float rows, swap only
 // (fft_exchange_sides_ff).  spectra: [stream][frame][fft], frames of segment = frame0 .. frame0 + n - 1.  One workgroup per (segment, stream).
 // segs == nullptr: the stand-alone operations, row r = frames r avg .. r avg + avg - 1
+// half_tw != nullptr (real input): the spectra are the transforms Z of packed frames; bin b of a frame is untangled from Z[b] and Z[(fft - b) mod fft]
 template <bool POWER>
 __global__ __launch_bounds__(256) void k_wf_post(const void *__restrict__ spectra, int fft, int n_frames, int avg, const WfSeg *__restrict__ segs, const float *__restrict__ acc_in, float *__restrict__ acc_out,
-                                                 void *__restrict__ out, size_t out_pitch, int out_format, float add_db, int swap, int s0, int16_t *__restrict__ q_scratch)
+                                                 void *__restrict__ out, size_t out_pitch, int out_format, float add_db, int swap, int s0, int16_t *__restrict__ q_scratch,
+                                                 const float2 *__restrict__ half_tw)
 {
 #pragma clang fp contract(off)
     const int sl = blockIdx.y, s = s0 + sl;
@@ -327,6 +439,11 @@ __global__ __launch_bounds__(256) void k_wf_post(const void *__restrict__ spectr
         if (POWER) {
             const float2 *x = (const float2 *)spectra + ((size_t)sl * n_frames + sg.frame0) * fft + b;
             float acc = (sg.flags & WF_LOAD) ? acc_in[(size_t)s * fft + b] : 0.f;
+            if (half_tw) {
+                const float2 *xm = x - b + ((fft - b) & (fft - 1));
+                const float2 h = half_tw[b];
+                for (int f = 0; f < sg.n; f++) { const float2 z = wf_untangle1(x[(size_t)f * fft], xm[(size_t)f * fft], h); acc += z.x * z.x + z.y * z.y; }
+            } else
             for (int f = 0; f < sg.n; f++) { const float2 z = x[(size_t)f * fft]; acc += z.x * z.x + z.y * z.y; }
             if (!(sg.flags & WF_EMIT)) { acc_out[(size_t)s * fft + b] = acc; continue; }
             v = wf_db(acc, add_db);
@@ -363,14 +480,31 @@ void twiddle_table(int n, std::vector<float2> &t)
     t.resize(n);
     for (int m = 0; m < n; m++) { const double a = -2.0 * M_PI * (double)m / n; t[m] = make_float2((float)cos(a), (float)sin(a)); }
 }
+// appends exp(-i pi k / n), k < n: the untangle's half-step twiddles
+void half_table(int n, std::vector<float2> &t)
+{
+    for (int k = 0; k < n; k++) { const double a = -M_PI * (double)k / n; t.push_back(make_float2((float)cos(a), (float)sin(a))); }
+}
+// transforms per hipFFT plan execution (about 2 Mi points): one fixed batch for every call of the generic form and of the stand-alone fft_fc
+int plan_batch(int n) { return n >= (1 << 21) ? 1 : (1 << 21) / n; }
 bool onepass_size(int n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192; }
 
-template <int N, int IN> void *onepass_kernel() { return (void *)&k_wf_onepass<N, IN>; }
+template <int N, int IN> void *onepass_kernel()
+{
+    if constexpr (wf_real<IN>()) return (void *)&k_wf_onepass_real<N, IN>;
+    else return (void *)&k_wf_onepass<N, IN>;
+}
+template <int N> void *onepass_kernel(int in_format)
+{
+    return in_format == CSDR_AMD_WF_IN_U8 ? onepass_kernel<N, 1>() : in_format == CSDR_AMD_WF_IN_F32 ? onepass_kernel<N, 2>() :
+           in_format == CSDR_AMD_WF_IN_S16 ? onepass_kernel<N, 3>() : onepass_kernel<N, 0>();
+}
 
 } // namespace
 
 struct csdr_amd_waterfall {
     csdr_amd_ctx *c; int fft, every, avg, in_format, out_format, n_streams; float add_db; size_t max_in;
+    int len, period, off;                                                // the schedule in raw units: frame k covers [k period + off, k period + off + len)
     bool onepass, force_generic; const char *last_kernel;
     long long total, frames_done;                                        // samples per stream seen, frames completed (lockstep)
     int hist_len, cur, acc_cur; DevBuf<> d_hist[2]; DevBuf<float> d_w; DevBuf<float2> d_tw; DevBuf<float> d_acc; DevBuf<WfSeg> d_segs; int segs_cap;   // d_acc: two [stream][N] buffers
@@ -379,13 +513,22 @@ struct csdr_amd_waterfall {
 
 namespace {
 
-int elem_bytes(int in_format) { return in_format == CSDR_AMD_WF_IN_U8 ? 2 : 8; }
+bool real_format(int in_format) { return in_format == CSDR_AMD_WF_IN_F32 || in_format == CSDR_AMD_WF_IN_S16; }
+bool known_format(int in_format) { return in_format == CSDR_AMD_WF_IN_CF32 || in_format == CSDR_AMD_WF_IN_U8 || real_format(in_format); }
+int elem_bytes(int in_format) { return in_format == CSDR_AMD_WF_IN_U8 || in_format == CSDR_AMD_WF_IN_S16 ? 2 : in_format == CSDR_AMD_WF_IN_F32 ? 4 : 8; }
 
-// frames completed by the first `total` samples: frame k ends at k E + off + N
-long long frames_by(const csdr_amd_waterfall *w, long long total)
+// fft_cc's schedule in complex samples, fft_fc's in real ones (the header of this file): len, period, off
+void wf_schedule(int fft, int every, bool real, int *len, int *period, int *off)
 {
-    const long long first_end = (long long)(w->every < w->fft ? w->every - w->fft : 0) + w->fft;
-    return total < first_end ? 0 : (total - first_end) / w->every + 1;
+    *len = real ? 2 * fft : fft;
+    *period = real && every > *len ? 2 * every - *len : every;
+    *off = every < *len ? every - *len : 0;
+}
+// frames completed by the first `total` units: frame k ends at k period + off + len
+long long frames_by(long long total, int len, int period, int off)
+{
+    const long long first_end = (long long)off + len;
+    return total < first_end ? 0 : (total - first_end) / period + 1;
 }
 
 // the call's frames [k0, k1) grouped by row
@@ -403,22 +546,43 @@ void make_segments(const csdr_amd_waterfall *w, long long k0, long long k1, std:
     }
 }
 
-int run_onepass(csdr_amd_waterfall *w, const WfArgs &a, int n_segs)
+int run_onepass(csdr_amd_waterfall *w, const WfArgs &a, int n_segs, int rows)
 {
     csdr_amd_ctx *c = w->c;
     void *k = nullptr;
-    const bool u8 = w->in_format == CSDR_AMD_WF_IN_U8;
+    // The compressor is one lane walking the row.  The real 8192-bin form's workgroup (8 waves at ~240 registers) holds a CU alone, so inside the kernel
+    // the rows of a CU are compressed one after the other (measured: 5.2 ms per step where the transform takes 0.2 ms); that form writes dB rows to
+    // scratch and k_wf_post's stand-alone mode compresses them, one small workgroup per row, many per CU -- the same db_to_short and encoder, the same bytes.
+    const bool split_tail = real_format(w->in_format) && w->fft == 8192 && w->out_format == CSDR_AMD_WF_OUT_ADPCM && rows > 0;
+    const size_t cells = (size_t)w->n_streams * rows * w->fft;
+    if (split_tail) {
+        if (4 * cells > w->frames_cap) {
+            w->d_frames.reset(); w->frames_cap = 4 * cells;
+            w->d_frames.reset((float2 *)csdr_amd_malloc(c, w->frames_cap));
+            if (!w->d_frames) { w->frames_cap = 0; return fail_msg(-2, "waterfall: row buffer allocation failed"); }
+        }
+        if (2 * cells > w->q_cap) {
+            w->d_q.reset(); w->q_cap = 2 * cells; w->d_q.reset((int16_t *)csdr_amd_malloc(c, w->q_cap));
+            if (!w->d_q) { w->q_cap = 0; return fail_msg(-2, "waterfall: scratch allocation failed"); }
+        }
+    }
     size_t lds = 0; int threads = w->fft / 16;
     switch (w->fft) {
-        case 1024: k = u8 ? onepass_kernel<1024, 1>() : onepass_kernel<1024, 0>(); lds = WfGeom<1024>::LDS_BYTES; break;
-        case 2048: k = u8 ? onepass_kernel<2048, 1>() : onepass_kernel<2048, 0>(); lds = WfGeom<2048>::LDS_BYTES; break;
-        case 4096: k = u8 ? onepass_kernel<4096, 1>() : onepass_kernel<4096, 0>(); lds = WfGeom<4096>::LDS_BYTES; break;
-        default:   k = u8 ? onepass_kernel<8192, 1>() : onepass_kernel<8192, 0>(); lds = WfGeom<8192>::LDS_BYTES; break;
+        case 1024: k = onepass_kernel<1024>(w->in_format); lds = WfGeom<1024>::LDS_BYTES; break;
+        case 2048: k = onepass_kernel<2048>(w->in_format); lds = WfGeom<2048>::LDS_BYTES; break;
+        case 4096: k = onepass_kernel<4096>(w->in_format); lds = WfGeom<4096>::LDS_BYTES; break;
+        default:   k = onepass_kernel<8192>(w->in_format); lds = WfGeom<8192>::LDS_BYTES; break;
     }
     if (lds_attr_once(k, lds) < 0) return -5;
     WfArgs aa = a;
+    if (split_tail) { aa.out = w->d_frames.get(); aa.out_pitch = 4 * (size_t)rows * w->fft; aa.out_format = CSDR_AMD_WF_OUT_DB; }
     void *args[] = {&aa};
     CSDR_HIP(hipLaunchKernel(k, dim3((unsigned)n_segs, (unsigned)w->n_streams), dim3(threads), args, lds, c->stream));
+    if (split_tail) {
+        hipLaunchKernelGGL(k_wf_post<false>, dim3(rows, w->n_streams), dim3(256), 0, c->stream, (const void *)w->d_frames.get(), w->fft, rows, 1, (const WfSeg *)nullptr,
+                           (const float *)nullptr, (float *)nullptr, a.out, a.out_pitch, (int)CSDR_AMD_WF_OUT_ADPCM, 0.f, 0, 0, w->d_q.get(), (const float2 *)nullptr);
+        CSDR_LAUNCH_CHECK();
+    }
     return 0;
 }
 
@@ -426,6 +590,7 @@ int run_generic(csdr_amd_waterfall *w, const WfArgs &a, long long k0, int n_fram
 {
     csdr_amd_ctx *c = w->c;
     const int N = w->fft;
+    const bool real = real_format(w->in_format);
     if (n_frames > 65535) return fail_msg(-3, "waterfall: %d frames in one call on the generic path (at most 65535: pass fewer samples per call)", n_frames);
     // streams per group: the frames of a group stay within ~256 MiB
     const size_t per_stream = (size_t)n_frames * N * 8;
@@ -433,7 +598,7 @@ int run_generic(csdr_amd_waterfall *w, const WfArgs &a, long long k0, int n_fram
     const int group = fit < 1 ? 1 : fit > (size_t)w->n_streams ? w->n_streams : (int)fit;
     // one plan of a fixed batch (about 2 Mi points per execution) for every call: hipFFT picks its kernels by batch count, and rows must not depend on how
     // the stream was cut into calls; the frame buffer is padded to whole plan batches (the padding's transforms are never read)
-    const int pb = N >= (1 << 21) ? 1 : (1 << 21) / N;
+    const int pb = plan_batch(N);
     const size_t need = ((size_t)group * n_frames + pb - 1) / pb * pb * N * 8;
     if (need > w->frames_cap) {
         w->d_frames.reset(); w->frames_cap = need;
@@ -457,6 +622,8 @@ int run_generic(csdr_amd_waterfall *w, const WfArgs &a, long long k0, int n_fram
         const int g = s0 + group <= w->n_streams ? group : w->n_streams - s0;
         const unsigned gx = cdiv(N, 256) > 16 ? 16 : cdiv(N, 256);
         if (w->in_format == CSDR_AMD_WF_IN_U8) hipLaunchKernelGGL(k_wf_frame<1>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
+        else if (w->in_format == CSDR_AMD_WF_IN_F32) hipLaunchKernelGGL(k_wf_frame<2>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
+        else if (w->in_format == CSDR_AMD_WF_IN_S16) hipLaunchKernelGGL(k_wf_frame<3>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
         else hipLaunchKernelGGL(k_wf_frame<0>, dim3(gx, n_frames, g), dim3(256), 0, c->stream, a, N, k0, n_frames, w->d_frames.get(), s0);
         CSDR_LAUNCH_CHECK();
         const size_t used = (size_t)g * n_frames, padded = (used + pb - 1) / pb * pb;
@@ -466,31 +633,33 @@ int run_generic(csdr_amd_waterfall *w, const WfArgs &a, long long k0, int n_fram
             if (hipfftExecC2C(w->plans[pb].get(), z, z, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "waterfall: hipfftExecC2C failed");
         }
         hipLaunchKernelGGL(k_wf_post<true>, dim3(n_segs, g), dim3(256), 0, c->stream, (const void *)w->d_frames.get(), N, n_frames, w->avg, a.segs, a.acc_in, a.acc_out, a.out, a.out_pitch,
-                           w->out_format, a.add_db, 1, s0, w->out_format == CSDR_AMD_WF_OUT_ADPCM ? w->d_q.get() : nullptr);
+                           w->out_format, a.add_db, real ? 0 : 1, s0, w->out_format == CSDR_AMD_WF_OUT_ADPCM ? w->d_q.get() : nullptr, real ? a.table + N : (const float2 *)nullptr);
         CSDR_LAUNCH_CHECK();
     }
     return 0;
 }
 
-// the CPU run of the one-pass stages for one row of a fresh stream (csdr_amd_debug_waterfall_row)
+// the CPU run of the one-pass stages for row `row` of a stream given from its start (csdr_amd_debug_waterfall_row / _row_at)
 template <int N, int IN>
-void host_row(int every, const float *window, int avg, float add_db, const void *in, float *db_row, float *power_row)
+void host_row(int period, int off, int row, const float *window, int avg, float add_db, const void *in, float *db_row, float *power_row)
 {
     constexpr int T = WfGeom<N>::T, NP = WfPlan<N>::NP;
+    constexpr bool REAL = wf_real<IN>();
     std::vector<float2> table; twiddle_table(N, table);
+    if (REAL) half_table(N, table);
     std::vector<float2> lds(WfGeom<N>::DATA);
     std::vector<WfConst<N>> cst(T);
     std::vector<std::array<float2, 16>> v(T);
     std::vector<std::array<float, 16>> acc(T);
     for (int t = 0; t < T; t++) { wf_const<N>(t, table.data(), cst[t]); acc[t].fill(0.f); }
-    const int off = every < N ? every - N : 0;
     auto as_regs = [](std::array<float2, 16> &a) -> float2 (&)[16] { return *reinterpret_cast<float2 (*)[16]>(a.data()); };
     for (int f = 0; f < avg; f++) {
-        const long long start = (long long)f * every + off;
+        const long long start = ((long long)row * avg + f) * period + off;
         for (int t = 0; t < T; t++) {
             float2 (&r)[16] = as_regs(v[t]);
             for (int s = 0; s < 16; s++) {
-                r[s] = wf_windowed<IN>(in, nullptr, 0, 0, start + WfPass<N, 0>::src(t, s), window[WfPass<N, 0>::src(t, s)]);
+                if constexpr (REAL) r[s] = wf_packed<IN>(in, nullptr, 0, 0, start, WfPass<N, 0>::src(t, s), window);
+                else r[s] = wf_windowed<IN>(in, nullptr, 0, 0, start + WfPass<N, 0>::src(t, s), window[WfPass<N, 0>::src(t, s)]);
             }
             WfPass<N, 0>::compute(r, cst[t].w1);
             WfPass<N, 0>::lds_write(lds.data(), t, r);
@@ -502,14 +671,27 @@ void host_row(int every, const float *window, int avg, float add_db, const void 
             for (int t = 0; t < T; t++) WfPass<N, 2>::lds_write(lds.data(), t, as_regs(v[t]));
             for (int t = 0; t < T; t++) { WfPass<N, 3>::lds_read(lds.data(), t, as_regs(v[t])); WfPass<N, 3>::compute(as_regs(v[t]), cst[t].w3); }
         }
+        if constexpr (REAL) {
+            for (int t = 0; t < T; t++) WfPass<N, NP - 1>::lds_write(lds.data(), t, as_regs(v[t]));
+            for (int t = 0; t < T; t++) wf_untangle<N>(lds.data(), t, table.data() + N, as_regs(v[t]));
+        }
         for (int t = 0; t < T; t++) wf_accumulate<N>(as_regs(v[t]), *reinterpret_cast<float (*)[16]>(acc[t].data()));
     }
     for (int t = 0; t < T; t++)
         for (int s = 0; s < 16; s++) {
-            const int o = (wf_bin<N>(t, s) + N / 2) & (N - 1);
+            const int o = (wf_bin<N>(t, s) + (REAL ? 0 : N / 2)) & (N - 1);
             if (db_row) db_row[o] = wf_db(acc[t][s], add_db);
             if (power_row) power_row[o] = acc[t][s];
         }
+}
+
+template <int N>
+void host_row_of(int in_format, int period, int off, int row, const float *window, int avg, float add_db, const void *in, float *db_row, float *power_row)
+{
+    if (in_format == CSDR_AMD_WF_IN_U8) host_row<N, 1>(period, off, row, window, avg, add_db, in, db_row, power_row);
+    else if (in_format == CSDR_AMD_WF_IN_F32) host_row<N, 2>(period, off, row, window, avg, add_db, in, db_row, power_row);
+    else if (in_format == CSDR_AMD_WF_IN_S16) host_row<N, 3>(period, off, row, window, avg, add_db, in, db_row, power_row);
+    else host_row<N, 0>(period, off, row, window, avg, add_db, in, db_row, power_row);
 }
 
 } // namespace
@@ -520,7 +702,7 @@ csdr_amd_waterfall *csdr_amd_waterfall_create(csdr_amd_ctx *c, int fft_size, int
                                               int n_streams, size_t max_samples_per_call)
 {
     if (fft_size < 2 || (fft_size & (fft_size - 1)) || every_n_samples <= 0 || avgnumber <= 0 || n_streams <= 0 || !max_samples_per_call ||
-        (in_format != CSDR_AMD_WF_IN_CF32 && in_format != CSDR_AMD_WF_IN_U8) || (out_format != CSDR_AMD_WF_OUT_DB && out_format != CSDR_AMD_WF_OUT_ADPCM)) {
+        every_n_samples > (1 << 29) || fft_size > (1 << 29) || !known_format(in_format) || (out_format != CSDR_AMD_WF_OUT_DB && out_format != CSDR_AMD_WF_OUT_ADPCM)) {
         fail_msg(-3, "waterfall: fft_size must be a power of two >= 2; every_n, avgnumber, n_streams, max_samples_per_call positive; formats CSDR_AMD_WF_*");
         return nullptr;
     }
@@ -528,16 +710,19 @@ csdr_amd_waterfall *csdr_amd_waterfall_create(csdr_amd_ctx *c, int fft_size, int
     w->c = c; w->fft = fft_size; w->every = every_n_samples; w->avg = avgnumber; w->in_format = in_format; w->out_format = out_format; w->n_streams = n_streams;
     w->add_db = (float)(add_db - 10.0 * log10((double)avgnumber));                // csdr.c:1678
     w->max_in = max_samples_per_call; w->onepass = onepass_size(fft_size); w->force_generic = false; w->last_kernel = "";
-    w->total = 0; w->frames_done = 0; w->cur = 0; w->hist_len = fft_size;
-    const size_t hb = (size_t)n_streams * fft_size * elem_bytes(in_format);
+    const bool real = real_format(in_format);
+    wf_schedule(fft_size, every_n_samples, real, &w->len, &w->period, &w->off);
+    w->total = 0; w->frames_done = 0; w->cur = 0; w->hist_len = w->len;
+    const size_t hb = (size_t)n_streams * w->len * elem_bytes(in_format);
     w->d_hist[0].reset(csdr_amd_malloc(c, hb + 256)); w->d_hist[1].reset(csdr_amd_malloc(c, hb + 256));
-    w->d_w.reset((float *)csdr_amd_malloc(c, 4 * (size_t)fft_size));
-    w->d_tw.reset((float2 *)csdr_amd_malloc(c, 8 * (size_t)fft_size));
+    w->d_w.reset((float *)csdr_amd_malloc(c, 4 * (size_t)w->len));
+    w->d_tw.reset((float2 *)csdr_amd_malloc(c, 8 * (size_t)w->len));
     w->d_acc.reset((float *)csdr_amd_malloc(c, 2 * 4 * (size_t)n_streams * fft_size));
     if (!w->d_hist[0] || !w->d_hist[1] || !w->d_w || !w->d_tw || !w->d_acc) return nullptr;
-    std::vector<float> win(fft_size); csdr_amd_precalculate_window(win.data(), fft_size, window);
+    std::vector<float> win(w->len); csdr_amd_precalculate_window(win.data(), w->len, window);
     std::vector<float2> tw; twiddle_table(fft_size, tw);
-    if (csdr_amd_h2d(c, w->d_w.get(), win.data(), 4 * (size_t)fft_size) < 0 || csdr_amd_h2d(c, w->d_tw.get(), tw.data(), 8 * (size_t)fft_size) < 0 ||
+    if (real) half_table(fft_size, tw);
+    if (csdr_amd_h2d(c, w->d_w.get(), win.data(), 4 * win.size()) < 0 || csdr_amd_h2d(c, w->d_tw.get(), tw.data(), 8 * tw.size()) < 0 ||
         csdr_amd_waterfall_reset(w.get()) < 0) return nullptr;
     return w.release();
 }
@@ -546,7 +731,7 @@ int csdr_amd_waterfall_reset(csdr_amd_waterfall *w)
 {
     // (history positions before the stream's start are read as zeros whatever the buffer holds: wf_windowed)
     w->total = 0; w->frames_done = 0; w->cur = 0; w->acc_cur = 0;
-    const size_t hb = (size_t)w->n_streams * w->fft * elem_bytes(w->in_format);
+    const size_t hb = (size_t)w->n_streams * w->len * elem_bytes(w->in_format);
     if (csdr_amd_memset(w->c, w->d_hist[0].get(), 0, hb) < 0) return -5;
     return 0;
 }
@@ -569,14 +754,14 @@ int csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_i
     if (!n_in) return 0;
     if (in_pitch < n_in) return fail_msg(-3, "waterfall: in_pitch must be >= n_in");
     csdr_amd_ctx *c = w->c;
-    const long long k0 = w->frames_done, k1 = frames_by(w, w->total + (long long)n_in);
+    const long long k0 = w->frames_done, k1 = frames_by(w->total + (long long)n_in, w->len, w->period, w->off);
     std::vector<WfSeg> segs; int rows = 0;
     make_segments(w, k0, k1, segs, &rows);
     const size_t row_bytes = w->out_format == CSDR_AMD_WF_OUT_DB ? 4 * (size_t)w->fft : (size_t)(w->fft + 10) / 2;
     if (rows && out_pitch < (size_t)rows * row_bytes && w->n_streams > 1) return fail_msg(-3, "waterfall: out_pitch %zu below the %d rows of %zu bytes of this call", out_pitch, rows, row_bytes);
     WfArgs a;
     a.in = in; a.in_pitch = in_pitch; a.hist = w->d_hist[w->cur].get(); a.hist_new = w->d_hist[w->cur ^ 1].get(); a.hist_len = w->hist_len;
-    a.base = w->total; a.every = w->every; a.off = w->every < w->fft ? w->every - w->fft : 0;
+    a.base = w->total; a.every = w->period; a.off = w->off;
     a.window = w->d_w.get(); a.table = w->d_tw.get();
     a.acc_in = w->d_acc.get() + (size_t)w->acc_cur * w->n_streams * w->fft; a.acc_out = w->d_acc.get() + (size_t)(w->acc_cur ^ 1) * w->n_streams * w->fft; a.out = out; a.out_pitch = out_pitch; a.out_format = w->out_format; a.add_db = w->add_db;
     if (!segs.empty()) {
@@ -591,10 +776,12 @@ int csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_i
         if (c->pinned_upload(w->d_segs.get(), sizeof(WfSeg) * segs.size()) < 0) return -5;
         a.segs = w->d_segs.get();
         const bool onepass = w->onepass && !w->force_generic;
-        const int rc = onepass ? run_onepass(w, a, (int)segs.size()) : run_generic(w, a, k0, (int)(k1 - k0), (int)segs.size());
+        const int rc = onepass ? run_onepass(w, a, (int)segs.size(), rows) : run_generic(w, a, k0, (int)(k1 - k0), (int)segs.size());
         if (rc < 0) return rc;
         w->acc_cur ^= 1;
-        w->last_kernel = !onepass ? "k_wf_post (generic: framing + hipFFT)" : w->in_format == CSDR_AMD_WF_IN_U8 ? "k_wf_onepass (u8)" : "k_wf_onepass (cf32)";
+        w->last_kernel = !onepass ? (real_format(w->in_format) ? "k_wf_post (generic real: framing + hipFFT + untangle)" : "k_wf_post (generic: framing + hipFFT)") :
+                         w->in_format == CSDR_AMD_WF_IN_U8 ? "k_wf_onepass (u8)" : w->in_format == CSDR_AMD_WF_IN_F32 ? "k_wf_onepass_real (f32)" :
+                         w->in_format == CSDR_AMD_WF_IN_S16 ? "k_wf_onepass_real (s16)" : "k_wf_onepass (cf32)";
     }
     // the history moves on by n_in samples (after every read of the old one: same stream)
     const size_t eb = elem_bytes(w->in_format), hb = (size_t)w->hist_len * eb;
@@ -614,7 +801,7 @@ int csdr_amd_logaveragepower_cf(csdr_amd_ctx *c, const csdr_complexf *in, float 
     const float a = (float)(add_db - 10.0 * log10((double)avgnumber));     // csdr.c:1678
     // one "stream" whose segments are the n_rows rows, no swap
     hipLaunchKernelGGL(k_wf_post<true>, dim3(n_rows, 1), dim3(256), 0, c->stream, (const void *)in, fft_size, n_rows * avgnumber, avgnumber, (const WfSeg *)nullptr,
-                       (const float *)nullptr, (float *)nullptr, (void *)out, (size_t)0, (int)CSDR_AMD_WF_OUT_DB, a, 0, 0, (int16_t *)nullptr);
+                       (const float *)nullptr, (float *)nullptr, (void *)out, (size_t)0, (int)CSDR_AMD_WF_OUT_DB, a, 0, 0, (int16_t *)nullptr, (const float2 *)nullptr);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -624,7 +811,7 @@ int csdr_amd_fft_exchange_sides_ff(csdr_amd_ctx *c, const float *in, float *out,
     if (n_rows <= 0) return 0;
     if (fft_size < 2 || (fft_size & (fft_size - 1))) return fail_msg(-3, "fft_exchange_sides_ff: fft_size must be a power of two >= 2");
     hipLaunchKernelGGL(k_wf_post<false>, dim3(n_rows, 1), dim3(256), 0, c->stream, (const void *)in, fft_size, n_rows, 1, (const WfSeg *)nullptr,
-                       (const float *)nullptr, (float *)nullptr, (void *)out, (size_t)0, (int)CSDR_AMD_WF_OUT_DB, 0.f, 1, 0, (int16_t *)nullptr);
+                       (const float *)nullptr, (float *)nullptr, (void *)out, (size_t)0, (int)CSDR_AMD_WF_OUT_DB, 0.f, 1, 0, (int16_t *)nullptr, (const float2 *)nullptr);
     CSDR_LAUNCH_CHECK();
     return 0;
 }
@@ -645,18 +832,129 @@ int csdr_amd_log_ff(csdr_amd_ctx *c, const float *in, float *out, size_t n, floa
 int csdr_amd_debug_waterfall_row(int fft_size, int every_n_samples, int window, int avgnumber, float add_db, int in_format, const void *in, long long n_in,
                                  float *db_row, float *power_row)
 {
-    if (!onepass_size(fft_size) || every_n_samples <= 0 || avgnumber <= 0 || (in_format != CSDR_AMD_WF_IN_CF32 && in_format != CSDR_AMD_WF_IN_U8)) return -3;
-    const long long off = every_n_samples < fft_size ? every_n_samples - fft_size : 0;
-    if (n_in < (long long)(avgnumber - 1) * every_n_samples + off + fft_size) return -3;   // the row's last frame must be complete
-    std::vector<float> win(fft_size); csdr_amd_precalculate_window(win.data(), fft_size, window);
+    return csdr_amd_debug_waterfall_row_at(fft_size, every_n_samples, window, avgnumber, add_db, in_format, in, n_in, 0, db_row, power_row);
+}
+
+int csdr_amd_debug_waterfall_row_at(int fft_size, int every_n_samples, int window, int avgnumber, float add_db, int in_format, const void *in, long long n_in,
+                                    int row, float *db_row, float *power_row)
+{
+    if (row < 0 || !onepass_size(fft_size) || every_n_samples <= 0 || every_n_samples > (1 << 29) || avgnumber <= 0 || !known_format(in_format)) return -3;
+    int len, period, off;
+    wf_schedule(fft_size, every_n_samples, real_format(in_format), &len, &period, &off);
+    if (n_in < ((long long)(row + 1) * avgnumber - 1) * period + off + len) return -3;   // the row's last frame must be complete
+    std::vector<float> win(len); csdr_amd_precalculate_window(win.data(), len, window);
     const float a = (float)(add_db - 10.0 * log10((double)avgnumber));
-    const bool u8 = in_format == CSDR_AMD_WF_IN_U8;
     switch (fft_size) {
-        case 1024: u8 ? host_row<1024, 1>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row) : host_row<1024, 0>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row); break;
-        case 2048: u8 ? host_row<2048, 1>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row) : host_row<2048, 0>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row); break;
-        case 4096: u8 ? host_row<4096, 1>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row) : host_row<4096, 0>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row); break;
-        default:   u8 ? host_row<8192, 1>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row) : host_row<8192, 0>(every_n_samples, win.data(), avgnumber, a, in, db_row, power_row); break;
+        case 1024: host_row_of<1024>(in_format, period, off, row, win.data(), avgnumber, a, in, db_row, power_row); break;
+        case 2048: host_row_of<2048>(in_format, period, off, row, win.data(), avgnumber, a, in, db_row, power_row); break;
+        case 4096: host_row_of<4096>(in_format, period, off, row, win.data(), avgnumber, a, in, db_row, power_row); break;
+        default:   host_row_of<8192>(in_format, period, off, row, win.data(), avgnumber, a, in, db_row, power_row); break;
     }
+    return 0;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ fft_fc and fft_one_side_ff as stand-alone stages (csdr.c:3414-3498, 1717-1734)
+namespace {
+
+// spectra of packed frames -> the first fft bins of the real frames' spectra: out[f][k] from Z[f][k] and Z[f][(fft - k) mod fft]
+__global__ __launch_bounds__(256) void k_fftfc_untangle(const float2 *__restrict__ z, float2 *__restrict__ out, int fft, const float2 *__restrict__ half)
+{
+    const float2 *zf = z + (size_t)blockIdx.y * fft;
+    float2 *o = out + (size_t)blockIdx.y * fft;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < fft; k += gridDim.x * 256) o[k] = wf_untangle1(zf[k], zf[(fft - k) & (fft - 1)], half[k]);
+}
+__global__ __launch_bounds__(256) void k_one_side(const float *__restrict__ in, float *__restrict__ out, int half_size, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = in[i / half_size * 2 * half_size + i % half_size];
+}
+
+} // namespace
+
+// one stream: the schedule, the sliding buffer (the last 2M floats) and the samples still to skip are the waterfall object's, without the row stage
+struct csdr_amd_fftfc {
+    csdr_amd_ctx *c; int fft, len, period, off, pb; size_t max_in, max_frames;
+    long long total, frames_done; int cur;
+    DevBuf<float> d_hist[2]; DevBuf<float> d_w; DevBuf<float2> d_half; DevBuf<float2> d_frames; FftPlan plan;
+};
+
+extern "C" {
+
+csdr_amd_fftfc *csdr_amd_fftfc_create(csdr_amd_ctx *c, int fft_out_size, int every_n_samples, int window, size_t max_samples_per_call)
+{
+    if (fft_out_size < 2 || (fft_out_size & (fft_out_size - 1)) || fft_out_size > (1 << 29) || every_n_samples <= 0 || every_n_samples > (1 << 29) || !max_samples_per_call) {
+        fail_msg(-3, "fft_fc: fft_out_size must be a power of two >= 2, every_n and max_samples_per_call positive");
+        return nullptr;
+    }
+    Owned<csdr_amd_fftfc, csdr_amd_fftfc_destroy> f(new csdr_amd_fftfc());
+    f->c = c; f->fft = fft_out_size; f->max_in = max_samples_per_call; f->total = 0; f->frames_done = 0; f->cur = 0;
+    wf_schedule(fft_out_size, every_n_samples, true, &f->len, &f->period, &f->off);
+    f->max_frames = (max_samples_per_call + f->period - 1) / f->period;
+    if (f->max_frames > 65535) { fail_msg(-3, "fft_fc: %zu frames per call (at most 65535: fewer samples per call)", f->max_frames); return nullptr; }
+    // the generic waterfall's plan (one fixed batch for every call: spectra must not depend on how the stream is cut into calls, and they are the
+    // spectra that object sums); the frame buffer holds whole batches
+    f->pb = plan_batch(fft_out_size);
+    const size_t frames_cap = (f->max_frames + f->pb - 1) / f->pb * f->pb * (size_t)f->fft;
+    f->d_hist[0].reset((float *)csdr_amd_malloc(c, 4 * (size_t)f->len)); f->d_hist[1].reset((float *)csdr_amd_malloc(c, 4 * (size_t)f->len));
+    f->d_w.reset((float *)csdr_amd_malloc(c, 4 * (size_t)f->len));
+    f->d_half.reset((float2 *)csdr_amd_malloc(c, 8 * (size_t)f->fft));
+    f->d_frames.reset((float2 *)csdr_amd_malloc(c, 8 * frames_cap));
+    if (!f->d_hist[0] || !f->d_hist[1] || !f->d_w || !f->d_half || !f->d_frames) return nullptr;
+    std::vector<float> win(f->len); csdr_amd_precalculate_window(win.data(), f->len, window);
+    std::vector<float2> half; half_table(f->fft, half);
+    if (csdr_amd_h2d(c, f->d_w.get(), win.data(), 4 * win.size()) < 0 || csdr_amd_h2d(c, f->d_half.get(), half.data(), 8 * half.size()) < 0 ||
+        csdr_amd_memset(c, f->d_hist[0].get(), 0, 4 * (size_t)f->len) < 0 || csdr_amd_memset(c, f->d_frames.get(), 0, 8 * frames_cap) < 0) return nullptr;
+    hipfftHandle h; int n[1] = {f->fft};
+    if (hipfftPlanMany(&h, 1, n, nullptr, 1, f->fft, nullptr, 1, f->fft, HIPFFT_C2C, f->pb) != HIPFFT_SUCCESS) { fail_msg(-5, "fft_fc: hipfftPlanMany(%d x %d) failed", f->fft, f->pb); return nullptr; }
+    f->plan.reset(h);
+    hipfftSetStream(h, c->stream);
+    return f.release();
+}
+
+void csdr_amd_fftfc_destroy(csdr_amd_fftfc *f)
+{
+    if (!f) return;
+    (void)hipSetDevice(f->c->device);
+    delete f;
+}
+
+int csdr_amd_fftfc_process(csdr_amd_fftfc *f, const float *in, size_t n_in, csdr_complexf *out)
+{
+    if (!f) return fail_msg(-3, "fft_fc: null object");
+    if (n_in > f->max_in) return fail_msg(-3, "fft_fc: %zu samples per call, the object was created for at most %zu", n_in, f->max_in);
+    if (!n_in) return 0;
+    csdr_amd_ctx *c = f->c;
+    const long long k0 = f->frames_done, k1 = frames_by(f->total + (long long)n_in, f->len, f->period, f->off);
+    const int n_frames = (int)(k1 - k0), M = f->fft;
+    if (n_frames > 0) {
+        WfArgs a = {};
+        a.in = in; a.in_pitch = n_in; a.hist = f->d_hist[f->cur].get(); a.hist_len = f->len; a.base = f->total; a.every = f->period; a.off = f->off; a.window = f->d_w.get();
+        const unsigned gx = cdiv(M, 256) > 16 ? 16 : cdiv(M, 256);
+        hipLaunchKernelGGL(k_wf_frame<CSDR_AMD_WF_IN_F32>, dim3(gx, n_frames, 1), dim3(256), 0, c->stream, a, M, k0, n_frames, f->d_frames.get(), 0);
+        CSDR_LAUNCH_CHECK();
+        for (int g = 0; g < n_frames; g += f->pb) {
+            hipfftComplex *z = (hipfftComplex *)(f->d_frames.get() + (size_t)g * M);
+            if (hipfftExecC2C(f->plan.get(), z, z, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail_msg(-5, "fft_fc: hipfftExecC2C failed");
+        }
+        hipLaunchKernelGGL(k_fftfc_untangle, dim3(gx, n_frames), dim3(256), 0, c->stream, (const float2 *)f->d_frames.get(), (float2 *)out, M, (const float2 *)f->d_half.get());
+        CSDR_LAUNCH_CHECK();
+    }
+    const size_t hb = 4 * (size_t)f->len;
+    hipLaunchKernelGGL(k_wf_hist, dim3(cdiv(hb / 2, 256) > 64 ? 64 : cdiv(hb / 2, 256), 1), dim3(256), 0, c->stream,
+                       (const uint8_t *)in, n_in * 4, (const uint8_t *)f->d_hist[f->cur].get(), (uint8_t *)f->d_hist[f->cur ^ 1].get(), hb, n_in * 4);
+    CSDR_LAUNCH_CHECK();
+    f->cur ^= 1;
+    f->total += (long long)n_in; f->frames_done = k1;
+    return n_frames;
+}
+
+int csdr_amd_fft_one_side_ff(csdr_amd_ctx *c, const float *in, float *out, int n_rows, int fft_size)
+{
+    if (n_rows <= 0) return 0;
+    if (fft_size < 2 || (fft_size & 1)) return fail_msg(-3, "fft_one_side_ff: fft_size must be even and >= 2");
+    const size_t n = (size_t)n_rows * (fft_size / 2);
+    hipLaunchKernelGGL(k_one_side, dim3(cdiv(n, 256) > 4096 ? 4096 : cdiv(n, 256)), dim3(256), 0, c->stream, in, out, fft_size / 2, n); CSDR_LAUNCH_CHECK();
     return 0;
 }
 

@@ -734,22 +734,42 @@ typedef struct csdr_amd_fftcc csdr_amd_fftcc;
 csdr_amd_fftcc *csdr_amd_fftcc_create(csdr_amd_ctx *ctx, int fft_size, int every_n_samples, int window, int max_frames);
 void csdr_amd_fftcc_destroy(csdr_amd_fftcc *f);
 int  csdr_amd_fftcc_process(csdr_amd_fftcc *f, const csdr_complexf *in, size_t n_in, csdr_complexf *out, size_t *consumed);
+/* `csdr fft_fc <fft_out_size> <out_of_every_n_samples> [window]` (csdr.c:3414-3498): the spectrum of a real signal.  M = fft_out_size (a power of two >= 2)
+ * is the number of complex bins written per spectrum, DC to M-1 (the Nyquist bin is not written); every transform takes 2M floats times
+ * precalculate_window(2M, window).  Schedule in floats, E = every_n_samples: E <= 2M: spectrum k covers stream floats [k E + E - 2M, k E + E), positions
+ * before 0 being the zeros of a fresh sliding buffer; E > 2M: the reference skips with complexf-sized reads on its float stream (csdr.c:3466-3469), i.e.
+ * 2 (E - 2M) floats, so spectrum k covers [k P, k P + 2M) with P = 2 E - 2M -- reproduced, so that a stream frames as the reference's does.
+ * The sliding buffer and the floats still to skip are carried inside the object: process consumes all n_in (<= max_samples_per_call) device floats and
+ * writes the spectra they complete, at most ceil(n_in / min(E, P)) of M csdr_complexf each, to the device array out.  Returns their number, or < 0.
+ * The reference's repeated last spectrum at end of stream is not produced. */
+typedef struct csdr_amd_fftfc csdr_amd_fftfc;
+csdr_amd_fftfc *csdr_amd_fftfc_create(csdr_amd_ctx *ctx, int fft_out_size, int every_n_samples, int window, size_t max_samples_per_call);
+void csdr_amd_fftfc_destroy(csdr_amd_fftfc *f);
+int  csdr_amd_fftfc_process(csdr_amd_fftfc *f, const float *in, size_t n_in, csdr_complexf *out);
+/* `csdr fft_one_side_ff <fft_size>` (csdr.c:1717-1734): the first fft_size/2 floats of each of n_rows rows of fft_size (device arrays; fft_size even) */
+int  csdr_amd_fft_one_side_ff(csdr_amd_ctx *ctx, const float *in, float *out, int n_rows, int fft_size);
 
 /* ------------------------------------------------------------------ the waterfall: `[convert_u8_f |] fft_cc N E [window] | logaveragepower_cf A N AVG |
  * fft_exchange_sides_ff N [| compress_fft_adpcm_f_u8 N]` (csdr.c:1569-1641, 1663-1714, 1745-1768) for n_streams streams per call.
  * fft_size 1024 / 2048 / 4096 / 8192: one kernel per row that reads the input once (k_wf_onepass); any other power of two >= 2: framing + hipFFT + one
  * post-FFT kernel.  The frame schedule is fft_cc's; the overlap history, the samples still to skip and the partial row are carried per stream between calls,
  * and only complete rows are written: rows of fft_size float dB values (CSDR_AMD_WF_OUT_DB, halves exchanged) or of (fft_size+10)/2 ADPCM bytes
- * (CSDR_AMD_WF_OUT_ADPCM, compress_fft_adpcm_f_u8 of the dB row).  add_db' = (float)(add_db - 10 log10(avgnumber)) as csdr.c:1678 forms it. */
+ * (CSDR_AMD_WF_OUT_ADPCM, compress_fft_adpcm_f_u8 of the dB row).  add_db' = (float)(add_db - 10 log10(avgnumber)) as csdr.c:1678 forms it.
+ * Real input, CSDR_AMD_WF_IN_F32 (floats) / CSDR_AMD_WF_IN_S16 (shorts through convert_s16_f's arithmetic): the object is
+ * `[convert_s16_f |] fft_fc M E [window] | logaveragepower_cf A M AVG [| compress_fft_adpcm_f_u8 M]`.  fft_size means M, the output bins, as in fft_fc;
+ * every_n_samples, max_samples_per_call, n_in and in_pitch count real samples, with fft_fc's schedule (above, its E > 2M period P = 2 E - 2M included);
+ * rows are M floats or (M+10)/2 bytes in display order (DC first, no exchange of halves).  M = 1024 / 2048 / 4096 / 8192: one kernel (k_wf_onepass_real:
+ * the M-point transform of the packed frame plus one untangling exchange); any other power of two >= 2: framing + hipFFT + k_wf_post. */
 typedef struct csdr_amd_waterfall csdr_amd_waterfall;
-enum { CSDR_AMD_WF_IN_CF32 = 0, CSDR_AMD_WF_IN_U8 = 1 };
+enum { CSDR_AMD_WF_IN_CF32 = 0, CSDR_AMD_WF_IN_U8 = 1, CSDR_AMD_WF_IN_F32 = 2, CSDR_AMD_WF_IN_S16 = 3 };
 enum { CSDR_AMD_WF_OUT_DB = 0, CSDR_AMD_WF_OUT_ADPCM = 1 };
 csdr_amd_waterfall *csdr_amd_waterfall_create(csdr_amd_ctx *ctx, int fft_size, int every_n_samples, int window, int avgnumber,
                                               float add_db, int in_format, int out_format, int n_streams, size_t max_samples_per_call);
 /* n_in new samples for every stream (device, in_pitch samples apart); writes *rows_out rows per stream (out_pitch bytes apart).  Returns the rows or < 0. */
 int  csdr_amd_waterfall_process(csdr_amd_waterfall *w, const void *in, size_t n_in, size_t in_pitch, void *out, size_t out_pitch, int *rows_out);
 int  csdr_amd_waterfall_reset(csdr_amd_waterfall *w);
-/* what the last call ran: "k_wf_onepass (u8)" / "k_wf_onepass (cf32)" or "k_wf_post (generic: framing + hipFFT)" */
+/* what the last call ran: "k_wf_onepass (u8)" / "k_wf_onepass (cf32)" or "k_wf_post (generic: framing + hipFFT)"; real input:
+ * "k_wf_onepass_real (f32)" / "k_wf_onepass_real (s16)" or "k_wf_post (generic real: framing + hipFFT + untangle)" */
 const char *csdr_amd_waterfall_kernel_name(const csdr_amd_waterfall *w);
 /* on != 0: the one-pass sizes take the generic path too (A/B comparisons) */
 int  csdr_amd_waterfall_force_generic(csdr_amd_waterfall *w, int on);
@@ -1204,10 +1224,14 @@ int  csdr_amd_debug_ddc_fold_plan(int pre_decimation, int n_blocks, int *tiles, 
  * Toeplitz digit table and accumulator classes as k_nfm_deemph_mfma combines them. */
 int csdr_amd_debug_nfm_deemph_tile(int audio_rate, float max_amp, const float *x, float *out16);
 /* Test hook: the one-pass waterfall kernel's stages (k_wf_onepass) on the CPU for the first row of a fresh stream (fft_size 1024 / 2048 / 4096 / 8192):
- * in holds n_in samples (cf32 or u8 IQ pairs) from the stream's start.  db_row: the row as the object writes it (halves exchanged); power_row (may be null):
+ * in holds n_in samples (cf32 or u8 IQ pairs; floats or shorts for the real formats, fft_size then being the output bins) from the stream's start.
+ * db_row: the row as the object writes it (halves exchanged; a real format's row is one-sided, DC first); power_row (may be null):
  * the summed |X|^2 in the same order.  Returns 0, or -3 when the row's frames are not all within n_in. */
 int csdr_amd_debug_waterfall_row(int fft_size, int every_n_samples, int window, int avgnumber, float add_db, int in_format, const void *in, long long n_in,
                                  float *db_row, float *power_row);
+/* the same for row `row` (0 = the first) of the stream that in holds from its start */
+int csdr_amd_debug_waterfall_row_at(int fft_size, int every_n_samples, int window, int avgnumber, float add_db, int in_format, const void *in, long long n_in,
+                                    int row, float *db_row, float *power_row);
 #ifdef __cplusplus
 }
 #endif
