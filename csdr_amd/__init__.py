@@ -110,7 +110,7 @@ def lib():
                "reset_channel": (i, [vp, i]), "get_channel": (i, [vp, i, vp]), "set_channel": (i, [vp, i, vp]), "set_lanes": (i, [vp, i]), "lanes": (i, [vp])}
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
-                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("amssb", max_out + chan + lanes),
+                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("shiftbank", chan), ("amssb", max_out + chan + lanes),
                        ("txbank", max_out)):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
@@ -210,6 +210,13 @@ def lib():
     L.csdr_amd_carrier_create.restype = vp; L.csdr_amd_carrier_create.argtypes = [vp, vp, i]
     L.csdr_amd_carrier_process.argtypes = [vp, vp, ll, sz, vp, vp, vp, vp, sz]
     L.csdr_amd_debug_carrier_walk.restype = ll; L.csdr_amd_debug_carrier_walk.argtypes = [vp, vp, ll, vp, i, vp, vp, vp, vp, vp]
+    L.csdr_amd_shiftbank_create.restype = vp; L.csdr_amd_shiftbank_create.argtypes = [vp, i, i, vp, i, i, i, sz]
+    L.csdr_amd_shiftbank_process.argtypes = [vp, vp, sz, vp, sz, sz]
+    L.csdr_amd_shiftbank_set_rate.argtypes = [vp, i, fl]
+    L.csdr_amd_shiftbank_get_rate.argtypes = [vp, i, C.POINTER(fl)]
+    L.csdr_amd_shiftbank_scans_ahead.restype = ll; L.csdr_amd_shiftbank_scans_ahead.argtypes = [vp]
+    L.csdr_amd_debug_shiftbank_walk.restype = ll; L.csdr_amd_debug_shiftbank_walk.argtypes = [i, fl, i, i, i, vp, ll, vp, i, vp, vp, vp]
+    L.csdr_amd_debug_shiftbank_chunk_phases.restype = None; L.csdr_amd_debug_shiftbank_chunk_phases.argtypes = [fl, fl, i, i, vp]
     L.csdr_amd_amssb_params_default.argtypes = [vp, i]
     L.csdr_amd_amssb_create_cf32.restype = vp; L.csdr_amd_amssb_create_cf32.argtypes = [vp, vp, i, vp, i, i, sz]
     L.csdr_amd_amssb_create.restype = vp; L.csdr_amd_amssb_create.argtypes = [vp, vp, i, fl, i, vp, i, vp, i, i, sz]
@@ -1494,6 +1501,88 @@ class Carrier(_Handle, _ChannelState, _Lanes):
         return {k: v[0] for k, v in res.items()} if squeeze else res
 
 
+class ShiftBankChan(C.Structure):
+    """csdr_amd_shiftbank_chan: one stream's state"""
+    _fields_ = [("rate", C.c_float), ("phase", C.c_float), ("c", C.c_float), ("s", C.c_float), ("pos", C.c_int), ("pending", C.c_int),
+                ("old_rate", C.c_float), ("pad", C.c_int)]
+
+
+SHIFTBANK_FORMATS = {"cf32": 0, "f32": 1}
+
+
+def shiftbank_debug_walk(variant, rate, x, chunk=1024, aux=0, in_format="cf32", cuts=(), call_rates=None, state=None):
+    """CPU run of the shifter bank's step functions for one stream (csdr_amd_debug_shiftbank_walk): x cut into calls of `cuts` samples and the rest -> the
+    shifted samples.  call_rates: one entry per call (len(cuts) + 1), a set_rate in front of that call where it is not None / NaN.  state: a ShiftBankChan
+    carried in and out."""
+    real = SHIFTBANK_FORMATS[in_format] == 1
+    x = np.ascontiguousarray(x, f32 if real else c64)
+    y = np.zeros(x.size, c64)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    cr = None
+    if call_rates is not None:
+        cr = np.array([np.nan if r is None else r for r in call_rates], f32)
+        if cr.size != cu.size + 1:
+            raise ValueError("call_rates has one entry per call: len(cuts) + 1")
+    rc = lib().csdr_amd_debug_shiftbank_walk(SHIFT[variant], float(rate), int(chunk), int(aux), SHIFTBANK_FORMATS[in_format], _hp(x), x.size,
+                                             _hp(cu) if cu.size else None, cu.size, _hp(cr) if cr is not None else None, _hp(y),
+                                             C.byref(state) if state is not None else None)
+    if rc < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return y
+
+
+def shiftbank_chunk_phases(rate, phase, chunk, n):
+    """ADDITION's chunk start phases as the bank's pre-pass steps them, host build (csdr_amd_debug_shiftbank_chunk_phases): the phases after 1 .. n chunks"""
+    out = np.zeros(n, f32)
+    lib().csdr_amd_debug_shiftbank_chunk_phases(float(rate), float(phase), int(chunk), int(n), _hp(out))
+    return out
+
+
+class ShiftBank(_Handle, _ChannelState):
+    """csdr_amd_shiftbank: shift_addition_cc / _fc, shift_math_cc or shift_table_cc for len(rates) streams, each with its own rate; every stream's phase
+    state stays on the device between calls and set_rate retunes one stream from the next call on."""
+
+    _chan = ShiftBankChan
+
+    def __init__(self, ctx, variant, rates, chunk=1024, aux=0, in_format="cf32", max_samples_per_call=1 << 20):
+        r = np.ascontiguousarray(np.atleast_1d(rates), f32)
+        self.n_streams, self.variant, self.real = r.size, variant, SHIFTBANK_FORMATS[in_format] == 1
+        _Handle.__init__(self, ctx, "shiftbank", ctx.L.csdr_amd_shiftbank_create(ctx.h, SHIFT[variant], r.size, _hp(r), int(chunk), int(aux),
+                                                                                  SHIFTBANK_FORMATS[in_format], int(max_samples_per_call)))
+
+    def process_dev(self, d_in, in_pitch, d_out, out_pitch, n):
+        """device pointers; in_pitch in elements, 0: one input row for every stream.  Asynchronous."""
+        self._call("process", d_in, in_pitch, d_out, out_pitch, n)
+
+    def process(self, x, calls=None):
+        """x: [n_streams, n], or [n]: one row shared by every stream; calls: per-call sample counts (default one call) -> [n_streams, n] complex64"""
+        x = np.ascontiguousarray(x, f32 if self.real else c64)
+        shared = x.ndim == 1
+        n = x.shape[-1]
+        if not shared and x.shape[0] != self.n_streams:
+            raise ValueError("x has %d rows for %d streams" % (x.shape[0], self.n_streams))
+        calls = [n] if calls is None else [int(k) for k in calls]
+        s, pitch = self.n_streams, max(n, 1)
+        di = self.ctx.upload(x) if n else self.ctx.alloc(256)
+        do = self.ctx.alloc(8 * pitch * s + 256)
+        at = 0
+        for k in calls:
+            self.process_dev(di.at(x.itemsize * at), 0 if shared else pitch, do.at(8 * at), pitch, k)
+            at += k
+        return self.ctx.download(do, c64, pitch * s).reshape(s, pitch)[:, :n]
+
+    def set_rate(self, stream, rate):
+        self._call("set_rate", int(stream), float(rate))
+
+    def get_rate(self, stream):
+        r = C.c_float(0)
+        self._call("get_rate", int(stream), C.byref(r))
+        return r.value
+
+    def scans_ahead(self):
+        return int(self._fn("scans_ahead")(self.h))
+
+
 AMSSB_MODES = {"am": 0, "ssb": 1}
 
 
@@ -2402,6 +2491,10 @@ class Context:
     def carrier(self, params, n_channels=1):
         """A batched bpsk_costas_loop_cc / pll_cc object (Carrier); params from costas_params() or pll_params()"""
         return Carrier(self, params, n_channels)
+
+    def shiftbank(self, variant, rates, **kw):
+        """A shifter bank with a rate per stream (ShiftBank)"""
+        return ShiftBank(self, variant, rates, **kw)
 
     def txbank(self, n_streams, mode, interpolation, taps, rates, **kw):
         """The fused transmit bank (TxBank): mode "fm", "am" or "dsb"; kw: gain, q_value, out_format ("cf32" / "u8"), max_in_samples"""

@@ -125,6 +125,61 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
     return 0;
 }
 
+// ------------------------------------------------------------------ one shifter per client on one wideband stream (csdr.c:881-923, ddcd_old.h:51-61) in one process
+//   csdr shift_bank_cc <addition|math|table[:size]> <ctl | -> <out_0> <rate_0> [<out_1> <rate_1> ...]
+// reads ONE complexf stream from stdin and writes N shifted streams through one csdr_amd_shiftbank (the input row shared by all streams).  out_k and ctl as in
+// fastddc_bank_cc; a control line "<channel> <rate>\n" retunes that channel from the next block on, as `shift_addition_cc --fifo` does between two reads.
+// Blocks are CSDR_AMD_BANK_BLOCK samples (default 262144, a multiple of 1024); out_k carries what `csdr shift_<variant>_cc <rate_k>` writes for the same input.
+size_t bank_block();
+int run_shift_bank(csdr_amd_ctx *c, int argc, char **argv)
+{
+    if (argc < 6 || (argc - 4) % 2) return badsyntax("usage: shift_bank_cc <addition|math|table[:size]> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]");
+    int variant = -1, aux = 0;
+    if (!strcmp(argv[2], "addition")) variant = CSDR_SHIFT_ADDITION;
+    else if (!strcmp(argv[2], "math")) variant = CSDR_SHIFT_MATH;
+    else if (!strncmp(argv[2], "table", 5) && (!argv[2][5] || argv[2][5] == ':')) { variant = CSDR_SHIFT_TABLE; aux = 65536; if (argv[2][5]) sscanf(argv[2] + 6, "%d", &aux); }   // csdr.c:731
+    if (variant < 0 || aux < 0) return badsyntax("the variant is addition, math or table[:size]");
+    const int n_ch = (argc - 4) / 2;
+    Fds ctl_fd(1, -1); LineSplitter lines;
+    if (strcmp(argv[3], "-")) {
+        ctl_fd[0] = open_spec(argv[3], O_RDONLY | O_NONBLOCK);
+        if (ctl_fd[0] < 0) return badsyntax("cannot open the control channel");
+        fcntl(ctl_fd[0], F_SETFL, fcntl(ctl_fd[0], F_GETFL, 0) | O_NONBLOCK);
+    }
+    std::vector<float> rates(n_ch);
+    for (int k = 0; k < n_ch; k++) if (sscanf(argv[5 + 2 * k], "%g", &rates[k]) != 1) return badsyntax("every rate must be a number");
+    const size_t T = bank_block() / 1024 * 1024;
+    Owned<csdr_amd_shiftbank, csdr_amd_shiftbank_destroy> bank(csdr_amd_shiftbank_create(c, variant, n_ch, rates.data(), 1024, aux, CSDR_AMD_SHIFTBANK_IN_CF32, T));
+    if (!bank) die("shiftbank create");
+    Fds out_fd(n_ch, -1);
+    for (int k = 0; k < n_ch; k++) {
+        out_fd[k] = open_spec(argv[4 + 2 * k], O_WRONLY | O_CREAT | O_TRUNC);
+        if (out_fd[k] < 0) { fprintf(stderr, "csdr %s: cannot open output %s\n", g_cmd, argv[4 + 2 * k]); return -1; }
+    }
+    const auto h_in = pinned_alloc<csdr_complexf>(T * 8), h_out = pinned_alloc<csdr_complexf>((size_t)n_ch * T * 8);
+    const auto d_in = ctx_alloc<csdr_complexf>(c, T * 8 + 64), d_out = ctx_alloc<csdr_complexf>(c, (size_t)n_ch * T * 8 + 64);
+    fprintf(stderr, "csdr %s: %d channels, %zu samples per block\n", g_cmd, n_ch, T);
+    for (bool eof = false; !eof;) {
+        size_t got = 0;
+        if (!read_full(h_in.get(), T * 8, &got)) eof = true;
+        const size_t n = got / 8;
+        if (ctl_fd[0] >= 0)
+            while (lines.feed(ctl_fd[0])) while (const char *line = lines.next()) {
+                int ch = -1; float rate = 0;
+                if (sscanf(line, "%d %g", &ch, &rate) != 2 || ch < 0 || ch >= n_ch) continue;
+                MUST(csdr_amd_shiftbank_set_rate(bank.get(), ch, rate));
+                fprintf(stderr, "csdr %s: channel %d reinitialized to %g\n", g_cmd, ch, rate);
+            }
+        if (!n) continue;
+        MUST(csdr_amd_h2d(c, d_in.get(), h_in.get(), n * 8));
+        MUST(csdr_amd_shiftbank_process(bank.get(), d_in.get(), 0, d_out.get(), T, n));
+        MUST(csdr_amd_d2h(c, h_out.get(), d_out.get(), (size_t)n_ch * T * 8));
+        for (int k = 0; k < n_ch; k++)
+            if (out_fd[k] >= 0 && !write_fully(out_fd[k], h_out.get() + (size_t)k * T, n * 8)) { close(out_fd[k]); out_fd[k] = -1; }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ f4, first half: N-stream host ingest into the batch API
 // nmux / ddcd fan one source out to N clients, each client = one `csdr ... | csdr ...` pipeline of processes (nmux.cpp:177-283, ddcd_old.cpp:474-492).
 // The device batch API wants the opposite shape: N streams side by side in ONE call.  These commands are that producer:

@@ -669,6 +669,57 @@ void csdr_amd_carrier_destroy(csdr_amd_carrier *p);
 long long csdr_amd_debug_carrier_walk(const csdr_amd_carrier_params *params, const csdr_complexf *in, long long n, const long long *cuts, int n_cuts,
                                       csdr_complexf *out, float *error, float *dphase, csdr_complexf *nco, csdr_amd_carrier_chan *state_io);
 
+/* ------------------------------------------------------------------ the shifter bank: a shift rate and a phase per stream (shiftbank.hip)
+ * shift_addition_cc / shift_addition_fc (libcsdr_gpl.c:27-52, 54-79; the CLI's 1024-blocks csdr.c:896-923), shift_math_cc (libcsdr.c:186-207) and
+ * shift_table_cc (libcsdr.c:229-265) for n_streams streams, each with its own rate and its own state on the device: one shifter per client on one wideband
+ * stream (csdr.c:881-923, ddcd_old.h:51-61) is one object and one call.  csdr_amd_shift_cc keeps one rate per call; CSDR_SHIFT_UNROLL and CSDR_SHIFT_ADDFAST
+ * exist there only and are refused here.
+ * variant: CSDR_SHIFT_ADDITION (chunk: samples per phasor restart, 1024 in the CLI), CSDR_SHIFT_MATH or CSDR_SHIFT_TABLE (aux: table size, 0 = 65536).
+ * in_format F32 (real input, shift_addition_fc) goes with ADDITION only.
+ * Semantics: the reference's, independent of how calls cut the stream.  ADDITION: chunks count from the STREAM's start (reset), a call may end inside a chunk
+ * and (pos, c, s) carry it on; chunk start c = (float)cos(phase), s = (float)sin(phase); chunk end phase = wrap(phase + (2 rate) PI chunk) in float.
+ * MATH / TABLE: phase = wrap(phase + (2 rate) PI) per sample.
+ * Retune: set_rate takes effect at the first sample of the next process call that has samples.  MATH / TABLE: the phase carries over.  ADDITION: the open
+ * chunk ends where it stands -- pos > 0: phase = wrap(phase + (2 old_rate) PI pos), what the reference returns for a block of pos samples -- and a new chunk
+ * starts at the call's first sample: the reference called on blocks that end at the retune (pos == 0: the CLI's own behaviour).
+ * process: in (device; in_pitch elements apart, in_pitch == 0: ONE input row shared by every stream), out (device, out_pitch samples apart), n samples per
+ * stream, 0 <= n <= max_samples_per_call.  Asynchronous on the context's stream.
+ * MATH / TABLE scan each stream's n phase steps with one lane per stream, and the scan of the NEXT call (same n, from this call's end phases) is queued on
+ * a side stream at once: a call that finds it ready (same n, no set_rate / set_channel / reset since) uses it; scans_ahead counts those calls.
+ * kernel_name: "k_shiftbank_addition" / "k_shiftbank_math" / "k_shiftbank_table", or "k_shiftbank_generic" (force_generic(1), or a chunk below 32). */
+typedef struct csdr_amd_shiftbank csdr_amd_shiftbank;
+enum { CSDR_AMD_SHIFTBANK_IN_CF32 = 0, CSDR_AMD_SHIFTBANK_IN_F32 = 1 };
+typedef struct csdr_amd_shiftbank_chan {   /* one stream's state */
+    float rate;            /* as the caller gave it (the reference's argument, before its own *2) */
+    float phase;           /* ADDITION: phase at the start of the current chunk; MATH / TABLE: phase of the next sample */
+    float c, s;            /* ADDITION: the phasor of the next sample (cosphi, sinphi); MATH / TABLE: 1, 0 */
+    int   pos;             /* ADDITION: samples of the current chunk already done, 0 .. chunk - 1; 0 otherwise */
+    int   pending;         /* 1: `rate` changed since the last call with samples */
+    float old_rate;        /* the rate the open chunk was started with (ADDITION: for the phase advance that closes it) */
+    int   pad;
+} csdr_amd_shiftbank_chan;
+csdr_amd_shiftbank *csdr_amd_shiftbank_create(csdr_amd_ctx *ctx, int variant, int n_streams, const float *rates /* host, n_streams */, int chunk, int aux,
+                                              int in_format, size_t max_samples_per_call);
+int  csdr_amd_shiftbank_process(csdr_amd_shiftbank *p, const void *in, size_t in_pitch, csdr_complexf *out, size_t out_pitch, size_t n);
+int  csdr_amd_shiftbank_set_rate(csdr_amd_shiftbank *p, int stream, float rate);      /* asynchronous, in order with the calls */
+int  csdr_amd_shiftbank_get_rate(csdr_amd_shiftbank *p, int stream, float *rate);
+int  csdr_amd_shiftbank_reset(csdr_amd_shiftbank *p);                                 /* every stream: phase 0, pos 0, its current rate */
+int  csdr_amd_shiftbank_reset_channel(csdr_amd_shiftbank *p, int stream);
+int  csdr_amd_shiftbank_get_channel(csdr_amd_shiftbank *p, int stream, csdr_amd_shiftbank_chan *out);
+int  csdr_amd_shiftbank_set_channel(csdr_amd_shiftbank *p, int stream, const csdr_amd_shiftbank_chan *state);   /* finite, |phase| <= 1024, 0 <= pos < chunk */
+int  csdr_amd_shiftbank_force_generic(csdr_amd_shiftbank *p, int on);
+const char *csdr_amd_shiftbank_kernel_name(const csdr_amd_shiftbank *p);
+long long csdr_amd_shiftbank_scans_ahead(csdr_amd_shiftbank *p);                      /* calls whose phase scan was found ready (MATH / TABLE) */
+void csdr_amd_shiftbank_destroy(csdr_amd_shiftbank *p);
+/* the kernels' step functions on the host for one stream, the stream cut into calls of cuts[0], cuts[1], ... samples and the rest.  call_rates (may be NULL):
+ * n_cuts + 1 floats, a set_rate in front of call k where call_rates[k] is not NaN.  state_io (may be NULL: a fresh stream of rate `rate`) carries the state
+ * in and out.  Returns n or a negative code. */
+long long csdr_amd_debug_shiftbank_walk(int variant, float rate, int chunk, int aux, int in_format, const void *in, long long n, const long long *cuts, int n_cuts,
+                                        const float *call_rates, csdr_complexf *out, csdr_amd_shiftbank_chan *state_io);
+/* ADDITION's chunk start phases as the pre-pass kernel steps them (seeds.hpp's plan where it covers the step, the wrap loop beyond): out[k] = the phase
+ * after k + 1 chunks from `phase`, host build */
+void csdr_amd_debug_shiftbank_chunk_phases(float rate, float phase, int chunk, int n, float *out);
+
 /* ------------------------------------------------------------------ the transmit side: analog modulators and the up-converter bank (txmod.hip)
  * fmmod_fc libcsdr.c:1180-1192 for n_streams rows.  phase_io: device float[n_streams], last_phase in and out.  Bit-equal phases for every cut into calls. */
 int csdr_amd_fmmod_fc(csdr_amd_ctx *ctx, const float *in, csdr_complexf *out, int n_streams, size_t n, size_t in_pitch, size_t out_pitch, float *phase_io);
