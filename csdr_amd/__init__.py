@@ -110,7 +110,7 @@ def lib():
                "reset_channel": (i, [vp, i]), "get_channel": (i, [vp, i, vp]), "set_channel": (i, [vp, i, vp]), "set_lanes": (i, [vp, i]), "lanes": (i, [vp])}
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
-                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("shiftbank", chan), ("amssb", max_out + chan + lanes),
+                       ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("shiftbank", chan), ("framesync", max_out + chan[:1] + lanes), ("amssb", max_out + chan + lanes),
                        ("txbank", max_out)):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
@@ -142,6 +142,14 @@ def lib():
     L.csdr_amd_pulserx_create.restype = vp; L.csdr_amd_pulserx_create.argtypes = [vp, vp, i, i, i]
     L.csdr_amd_pulserx_process.argtypes = [vp, vp, ll, sz, vp, sz, vp, vp, vp]
     L.csdr_amd_debug_pulserx_walk.restype = ll; L.csdr_amd_debug_pulserx_walk.argtypes = [vp, i, i, vp, ll, vp, i, vp, vp, vp, vp]
+    L.csdr_amd_framesync_create.argtypes = [vp, i, vp, i, i, i, vp]
+    L.csdr_amd_framesync_process.argtypes = [vp, vp, sz, ll, vp, vp, sz, vp, vp, sz, vp]
+    L.csdr_amd_framesync_max_frames.restype = ll; L.csdr_amd_framesync_max_frames.argtypes = [vp, ll]
+    L.csdr_amd_framesync_tile.argtypes = []
+    L.csdr_amd_framesync_get_channel.argtypes = [vp, i, vp, vp]
+    L.csdr_amd_framesync_set_channel.argtypes = [vp, i, vp, vp]
+    L.csdr_amd_pattern_search_u8_u8.argtypes = [vp, vp, ll, vp, i, i, vp, vp]
+    L.csdr_amd_debug_framesync_walk.restype = ll; L.csdr_amd_debug_framesync_walk.argtypes = [vp, i, i, i, vp, ll, vp, i, vp, vp, vp, vp, vp]
     L.csdr_amd_generic_slicer_f_u8.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
     L.csdr_amd_plain_interpolate_cc.argtypes = [vp, vp, vp, i, ll, sz, sz, i]
     L.csdr_amd_pack_bits_1to8_u8_u8.argtypes = [vp, vp, vp, i, ll, sz, sz]
@@ -998,6 +1006,113 @@ class PulseRx(_Handle, _MaxOut, _ChannelState, _Lanes):
             res = _counted_calls(self, x, calls, (("d_err", f32), ("d_idx", np.uint32)))
         else:
             res = [r[0] for r in _counted_calls(self, x, calls)]
+        return res[0] if squeeze else res
+
+
+class FrameSyncChan(C.Structure):
+    """csdr_amd_framesync_chan: one channel's record (its ring of pattern_length bytes travels beside it)"""
+    _fields_ = [("fill", C.c_int), ("index", C.c_int), ("remain", C.c_int), ("reserved", C.c_int), ("base", C.c_longlong), ("frames", C.c_longlong)]
+
+    def astuple(self):
+        return (self.fill, self.index, self.remain, self.base, self.frames)
+
+
+def framesync_debug_walk(pattern, values_after, x, max_mismatch=0, cuts=(), state=None, window=None):
+    """CPU run of the frame synchroniser's step function for one channel (csdr_amd_debug_framesync_walk): x cut into calls of `cuts` bytes and the rest ->
+    (payload bytes, the index of each payload's first byte).  state: a FrameSyncChan carried in and out, with `window` (pattern_length bytes, updated in
+    place) holding its ring."""
+    pat = np.ascontiguousarray(pattern, np.uint32)
+    x = np.ascontiguousarray(x, np.uint8)
+    out = np.zeros(max(x.size, 1), np.uint8)
+    pos = np.zeros(x.size + 1, np.int64)
+    nf = C.c_longlong(0)
+    cu = np.ascontiguousarray(cuts, np.int64)
+    if window is not None and (window.dtype != np.uint8 or window.size != pat.size or not window.flags.c_contiguous):
+        raise ValueError("window: a contiguous uint8 array of pattern_length bytes")
+    k = lib().csdr_amd_debug_framesync_walk(_hp(pat), pat.size, int(values_after), int(max_mismatch), _hp(x), x.size, _hp(cu) if cu.size else None, cu.size,
+                                            _hp(out), _hp(pos), C.byref(nf), C.byref(state) if state is not None else None,
+                                            _hp(window) if window is not None else None)
+    if k < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return out[:k], pos[:nf.value]
+
+
+def framesync_tile():
+    """bytes of a row that k_framesync_tiled stages per step"""
+    return int(lib().csdr_amd_framesync_tile())
+
+
+class FrameSync(_Handle, _MaxOut, _PerChannel, _Lanes):
+    """csdr_amd_framesync: pattern_search_u8_u8 (csdr.c:3532-3597) for n_channels byte streams: behind every match of `pattern` (at most max_mismatch
+    positions differing) the next values_after bytes come out; state kept on the device between calls."""
+    in_dtype = out_dtype = np.uint8
+
+    def __init__(self, ctx, pattern, values_after, n_channels=1, max_mismatch=0):
+        self.pattern = np.ascontiguousarray(pattern, np.int64)
+        if self.pattern.size and (self.pattern.min() < 0 or self.pattern.max() > 0xffffffff):
+            raise ValueError("pattern values are unsigned")
+        self.n_channels, self.values_after, self.max_mismatch = int(n_channels), int(values_after), int(max_mismatch)
+        pat, h = self.pattern.astype(np.uint32), C.c_void_p(None)
+        rc = ctx.L.csdr_amd_framesync_create(ctx.h, self.n_channels, _hp(pat), pat.size, self.values_after, self.max_mismatch, C.byref(h))
+        _Handle.__init__(self, ctx, "framesync", h.value if rc == 0 else None)
+
+    def max_frames(self, n_in):
+        return int(self._fn("max_frames")(self.h, int(n_in)))
+
+    def get_channel(self, ch):
+        """-> (FrameSyncChan, the channel's ring bytes)"""
+        st, w = FrameSyncChan(), np.zeros(self.pattern.size, np.uint8)
+        self._call("get_channel", int(ch), C.byref(st), _hp(w))
+        return st, w
+
+    def set_channel(self, ch, st, window=None):
+        w = None if window is None else np.ascontiguousarray(window, np.uint8)
+        if w is not None and w.size != self.pattern.size:
+            raise ValueError("window holds pattern_length bytes")
+        self._call("set_channel", int(ch), C.byref(st), _hp(w) if w is not None else None)
+
+    def process_dev(self, d_in, n_in, in_pitch, d_out, out_pitch, d_counts, d_in_counts=None, d_pos=None, pos_pitch=0, d_frame_counts=None):
+        """device pointers; d_counts (n_channels int32) receives each channel's payload bytes of this call, d_in_counts (or None: n_in) gives each
+        channel's input bytes, d_pos (int64 rows, pos_pitch apart) and d_frame_counts receive the matches.  Asynchronous."""
+        self._call("process", d_in, in_pitch, n_in, d_in_counts, d_out, out_pitch, d_counts, d_pos, pos_pitch, d_frame_counts)
+
+    def process(self, x, counts=None, with_positions=False, calls=None, pitch=None):
+        """x: [n_channels, n] (or [n]) host bytes of which channel c takes counts[c] (default n); calls: per-call byte counts (default one call; with counts a
+        channel takes what is left of its bytes in each call); pitch: bytes between the rows on the device (default n) -> a list of per-channel payload arrays
+        (or one array for 1-D x); with_positions: (payload, positions) per channel."""
+        x = np.ascontiguousarray(x, np.uint8)
+        squeeze = x.ndim == 1
+        if squeeze:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        ctx = self.ctx
+        left = np.full(s, n, np.int64) if counts is None else np.clip(np.asarray(counts, np.int64), 0, n)
+        calls = [n] if calls is None else list(calls)
+        pitch = max(n, 1) if pitch is None else int(pitch)
+        if pitch < n:
+            raise ValueError("pitch below the row length")
+        rows = np.zeros((s, pitch), np.uint8); rows[:, :n] = x
+        di = ctx.upload(rows)
+        most = max(calls) if calls else 0
+        opitch, fpitch = max(most, 1), self.max_frames(most)
+        do, dp = ctx.alloc(opitch * s + 256), ctx.alloc(8 * fpitch * s + 256)
+        dc, dfc, dn = ctx.alloc(4 * s + 256), ctx.alloc(4 * s + 256), ctx.alloc(4 * s + 256)
+        outs, poss, at = [[] for _ in range(s)], [[] for _ in range(s)], 0
+        for k in calls:
+            take = np.clip(left - at, 0, k).astype(np.int32)
+            self.ctx.check(ctx.L.csdr_amd_h2d(ctx.h, dn.ptr, _hp(take), take.nbytes), "h2d")
+            self.process_dev(di.at(at), k, pitch, do.ptr, opitch, dc.ptr, dn.ptr, dp.ptr, fpitch, dfc.ptr)
+            cnt, fc = ctx.download(dc, np.int32, s), ctx.download(dfc, np.int32, s)
+            y = ctx.download(do, np.uint8, opitch * s).reshape(s, opitch)
+            q = ctx.download(dp, np.int64, fpitch * s).reshape(s, fpitch)
+            for c in range(s):
+                outs[c].append(y[c, :cnt[c]].copy()); poss[c].append(q[c, :fc[c]].copy())
+            at += k
+        res = [(np.concatenate(o) if o else np.zeros(0, np.uint8), np.concatenate(p) if p else np.zeros(0, np.int64)) for o, p in zip(outs, poss)]
+        if not with_positions:
+            res = [r[0] for r in res]
         return res[0] if squeeze else res
 
 
@@ -2331,6 +2446,22 @@ class Context:
     def pulse_rx(self, params, n_channels=1, first="filter", last="slice"):
         """A batched pulse-shaped receive object (PulseRx); params from pulserx_params()"""
         return PulseRx(self, params, n_channels, first, last)
+
+    def frame_sync(self, pattern, values_after, n_channels=1, max_mismatch=0):
+        """A batched frame synchroniser (FrameSync): `pattern_search_u8_u8 values_after pattern...` for n_channels byte streams"""
+        return FrameSync(self, pattern, values_after, n_channels, max_mismatch)
+
+    def pattern_search(self, x, pattern, values_after):
+        """pattern_search_u8_u8 (csdr.c:3532-3597) on one stream of bytes with fresh state -> the payload bytes"""
+        x, pat = np.ascontiguousarray(x, np.uint8).ravel(), np.ascontiguousarray(pattern, np.uint32)
+        di, do, dc = self.upload(x), self.alloc(x.size + 256), self.alloc(256)
+        self.check(self.L.csdr_amd_pattern_search_u8_u8(self.h, di.ptr, x.size, _hp(pat), pat.size, int(values_after), do.ptr, dc.ptr), "pattern_search_u8_u8")
+        return self.download(do, np.uint8, int(self.download(dc, np.int32, 1)[0]))
+
+    @staticmethod
+    def framesync_debug_walk(pattern, values_after, x, max_mismatch=0, cuts=(), state=None, window=None):
+        """framesync_debug_walk: the CPU run of the frame synchroniser's step function for one channel"""
+        return framesync_debug_walk(pattern, values_after, x, max_mismatch, cuts, state, window)
 
     @staticmethod
     def pulserx_debug_walk(params, first="filter", last="slice", x=None, cuts=(), state=None, with_extras=False):

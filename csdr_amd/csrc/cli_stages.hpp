@@ -422,6 +422,27 @@ struct PulseRx : Stage {   // pulse_shaping_filter_cc ... | timing_recovery_cc .
         return k;
     }
 };
+struct FrameSync : Stage {   // pattern_search_u8_u8 csdr.c:3532-3597: one device searcher for the run; ring, index and the open payload live on the device between passes.
+                            // Everything handed in is consumed; what comes out is the payload bytes that arrived (no stale block, no end-of-file byte at EOF).
+    Owned<csdr_amd_framesync, csdr_amd_framesync_destroy> p; CtxBuf<int> d_count;
+    FrameSync(csdr_amd_ctx *c, const std::vector<unsigned> &pattern, int values_after, int max_mismatch)
+    {
+        csdr_amd_framesync *h = nullptr;
+        if (csdr_amd_framesync_create(c, 1, pattern.data(), (int)pattern.size(), values_after, max_mismatch, &h) < 0) { badsyntax(csdr_amd_last_error()); exit(255); }
+        p.reset(h);
+        in_elem = 1; out_elem = 1;
+        d_count = ctx_alloc<int>(c, 64, "malloc");
+        fprintf(stderr, "csdr pattern_search_u8_u8: one device frame synchroniser (%d pattern values, %d after, %d may differ)\n", (int)pattern.size(), values_after, max_mismatch);
+    }
+    int next_bufsize(int) override { return 1; }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        MUST(csdr_amd_framesync_process(p.get(), (const uint8_t *)i, n, (long long)n, nullptr, (uint8_t *)o, cap, d_count.get(), nullptr, 0, nullptr));
+        int k = 0; MUST(csdr_amd_d2h(c, &k, d_count.get(), sizeof k));
+        return k;
+    }
+};
 struct GenericSlicer : Stage {   // generic_slicer_f_u8 csdr.c:3221-3236
     int n_symbols;
     GenericSlicer(int n) : n_symbols(n) { in_elem = 4; out_elem = 1; }
@@ -1313,6 +1334,23 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         if (n_symbols < 2 || n_symbols > 256) { badsyntax("n_symbols should be between 2 and 256"); return nullptr; }
         g_cmd = keep;
         return new GenericSlicer(n_symbols);
+    }
+    if (!strcmp(argv[1], "pattern_search_u8_u8")) {                                 // csdr.c:3532-3546, its checks in its order; [--mismatch <m>] in front is ours
+        const char *keep = g_cmd; g_cmd = argv[1];
+        int a = 2, values_after = 0, mismatch = 0;
+        if (argc > 3 && !strcmp(argv[2], "--mismatch")) { sscanf(argv[3], "%d", &mismatch); a = 4; }
+        if (argc <= a) { badsyntax("need required parameter (values_after)"); return nullptr; }
+        sscanf(argv[a], "%d", &values_after);
+        if (argc <= a + 1) { badsyntax("need required parameter (pattern_values × N)"); return nullptr; }
+        std::vector<unsigned> pattern(argc - a - 1, 0u);
+        for (size_t k = 0; k < pattern.size(); k++) sscanf(argv[a + 1 + k], "%u", &pattern[k]);
+        fprintf(stderr, "csdr %s: pattern values: ", g_cmd);
+        for (unsigned v : pattern) fprintf(stderr, "%x ", v);
+        fprintf(stderr, "\n");
+        for (unsigned v : pattern) if (v > 255) { badsyntax("a pattern value above 255 cannot match a byte (the reference would output nothing)"); return nullptr; }
+        Stage *s = new FrameSync(c, pattern, values_after, mismatch);
+        g_cmd = keep;
+        return s;
     }
     if (!strcmp(argv[1], "pack_bits_1to8_u8_u8")) return new PackBits(true);
     if (!strcmp(argv[1], "pack_bits_8to1_u8_u8")) return new PackBits(false);

@@ -212,7 +212,7 @@ int main(int argc, char **argv)
                         "psk31_varicode_encoder_u8_u8 differential_encoder_u8_u8 differential_decoder_u8_u8 psk_modulator_u8_c (<n_psk>) psk31_interpolate_sine_cc (<interpolation>) "
                         "duplicate_samples_ntimes_u8_u8 (<sample_size_bytes> <ntimes>) "
                         "plain_interpolate_cc (<interpolation>) pulse_shaping_filter_cc / firdes_pulse_shaping_filter_f (RRC <samples_per_symbol> <num_taps> <beta> | COSINE <samples_per_symbol>) "
-                        "generic_slicer_f_u8 (<n_symbols>) pack_bits_1to8_u8_u8 pack_bits_8to1_u8_u8 "
+                        "generic_slicer_f_u8 (<n_symbols>) pack_bits_1to8_u8_u8 pack_bits_8to1_u8_u8 pattern_search_u8_u8 ([--mismatch <m>] <values_after> <pattern_values x N>) "
                         "bfsk_demod_cf serial_line_decoder_f_u8 rtty_baudot2ascii_u8_u8 rtty_line_decoder_u8_u8 binary_slicer_f_u8 firdes_peak_c peaks_fir_cc (<taps_length> <peak_rate> [<peak_rate> ...]) "
                         "squelch_and_smeter_cc (--fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>) bpsk_costas_loop_cc (<loop_bandwidth> <damping_factor> [--dd | --decision_directed] [--output_error | --output_dphase | --output_nco | --output_combined <error_file> <dphase_file> <nco_file>]) pll_cc (1 [alpha] | 2 [bandwidth [damping_factor [ko [kd]]]]) amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf dsb_fc ([q_value]) fmmod_fc add_dcoffset_cc fixed_amplitude_cc (<new_amplitude>) convert_f_samplerf (<wait_for_this_sample>) fft_cc fft_fc (<fft_out_size> <out_of_every_n_samples> [window]) fft_one_side_ff logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "awgn_cc (<snr_db> [--awgnfile <file>] [--snrshow] [--seed <seed>]) uniform_noise_f ([--seed <seed>]) gaussian_noise_c ([--seed <seed>]) normalized_timing_variance_u32_f (<samples_per_symbol> <initial_sample_offset>) "

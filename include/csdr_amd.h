@@ -419,6 +419,57 @@ int  csdr_amd_apply_real_fir_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr
 int  csdr_amd_firdes_rrc_f(float *taps, int taps_length, int samples_per_symbol, float beta);
 int  csdr_amd_firdes_cosine_f(float *taps, int taps_length, int samples_per_symbol);
 
+/* ------------------------------------------------------------------ the frame synchroniser (framesync.hip, framesync_dev.hpp)
+ * pattern_search_u8_u8 <values_after> <pattern values> (csdr.c:3532-3597) for n_channels byte streams with the same pattern: behind every place where the last
+ * pattern_length bytes equal the pattern, the next values_after bytes are output and the search starts over behind them.  It is the reference's loop byte by byte
+ * (DESIGN section 4u): a ring of pattern_length bytes, a write index and a fill count; a match restarts the fill count and leaves the index where it stands,
+ * so that the bytes which would land past the ring's end are dropped (one byte after a reset; the reference writes them beyond its buffer).  max_mismatch > 0
+ * (not in the reference) accepts a window of which at most that many positions differ.  The result does not depend on how calls cut a stream, 0- and 1-byte
+ * calls included, nor on the kernel.
+ * create: pattern_length 1 .. 1024, values_after 0 .. 2^30, 0 <= max_mismatch < pattern_length, pattern values 0 .. 255 (a larger value cannot match a byte).
+ * process: channel ch takes in_counts[ch] (DEVICE, clamped to 0 .. n_in; NULL: n_in) bytes from in + ch * in_pitch (device).  out (device, out_pitch >= max_out(n_in)
+ * = n_in apart) receives the payload bytes of this call and out_counts[ch] (device) their number; frame_pos (device, may be NULL; frame_pitch >=
+ * max_frames(n_in) = n_in / (pattern_length + 1) + 1 apart) receives per match of this call the absolute index, counted from the channel's last reset, of
+ * the payload's first byte, and frame_counts[ch] (device, may be NULL) the matches.  A short pitch is an error that consumes nothing.  Asynchronous on the
+ * context's stream.
+ * kernel_name: "k_framesync_tiled" (one wave per channel, tiles of csdr_amd_framesync_tile() bytes staged in LDS) or "k_framesync_generic" (one lane per
+ * channel on global memory; force_generic(1)).  set_lanes(n): channels per wave of k_framesync_generic (1 .. 64; 0: automatic); k_framesync_tiled always runs
+ * one channel per wave, so lanes() is 1 for it.  get_channel / set_channel: one channel's record and, where `window` is not NULL, its pattern_length ring bytes (synchronous). */
+typedef struct csdr_amd_framesync_chan {
+    int fill;                            /* bytes since the (re)start, pattern_length at most */
+    int index;                           /* where the next byte is stored: below pattern_length while checking, up to 2 pattern_length - 1 while filling */
+    int remain;                          /* payload bytes left to copy */
+    int reserved;
+    long long base;                      /* bytes taken since the last reset */
+    long long frames;                    /* matches since the last reset */
+} csdr_amd_framesync_chan;
+typedef struct csdr_amd_framesync csdr_amd_framesync;
+int  csdr_amd_framesync_create(csdr_amd_ctx *ctx, int n_channels, const unsigned *pattern, int pattern_length, int values_after, int max_mismatch,
+                               csdr_amd_framesync **out);
+int  csdr_amd_framesync_process(csdr_amd_framesync *p, const unsigned char *in, size_t in_pitch, long long n_in, const int *in_counts, unsigned char *out,
+                                size_t out_pitch, int *out_counts, long long *frame_pos, size_t frame_pitch, int *frame_counts);
+long long csdr_amd_framesync_max_out(const csdr_amd_framesync *p, long long n_in);
+long long csdr_amd_framesync_max_frames(const csdr_amd_framesync *p, long long n_in);
+int  csdr_amd_framesync_tile(void);
+int  csdr_amd_framesync_reset(csdr_amd_framesync *p);
+int  csdr_amd_framesync_reset_channel(csdr_amd_framesync *p, int channel);
+int  csdr_amd_framesync_get_channel(csdr_amd_framesync *p, int channel, csdr_amd_framesync_chan *state, unsigned char *window);
+int  csdr_amd_framesync_set_channel(csdr_amd_framesync *p, int channel, const csdr_amd_framesync_chan *state, const unsigned char *window);
+int  csdr_amd_framesync_set_lanes(csdr_amd_framesync *p, int lanes);
+int  csdr_amd_framesync_lanes(const csdr_amd_framesync *p);
+int  csdr_amd_framesync_force_generic(csdr_amd_framesync *p, int on);
+const char *csdr_amd_framesync_kernel_name(const csdr_amd_framesync *p);
+void csdr_amd_framesync_destroy(csdr_amd_framesync *p);
+/* One stream with fresh state (all pointers device): *out_count (device) receives the payload bytes written to out (n at most). */
+int  csdr_amd_pattern_search_u8_u8(csdr_amd_ctx *ctx, const unsigned char *in, long long n, const unsigned *pattern, int pattern_length, int values_after,
+                                   unsigned char *out, int *out_count);
+/* CPU run of the kernels' step function for one channel (host pointers), the n bytes cut into calls of cuts[0..n_cuts) bytes and the rest; payloads and
+ * positions (may be NULL) concatenated.  state_io (may be NULL: a fresh channel) carries the record and window_io (pattern_length bytes, may be NULL with a
+ * fresh channel) the ring in and out.  Returns the payload count; *n_frames (may be NULL) the matches. */
+long long csdr_amd_debug_framesync_walk(const unsigned *pattern, int pattern_length, int values_after, int max_mismatch, const unsigned char *in, long long n,
+                                        const long long *cuts, int n_cuts, unsigned char *out, long long *pos, long long *n_frames,
+                                        csdr_amd_framesync_chan *state_io, unsigned char *window_io);
+
 /* ------------------------------------------------------------------ RTTY receive chain (rtty.hip)
  * bfsk_demod_cf libcsdr.c:2335-2350 (csdr.c:3271-3300) | serial_line_decoder_f_u8 libcsdr.c:1662-1728 (csdr.c:2490-2528) | rtty_baudot2ascii_u8_u8 csdr.c:2461-2473,
  * for n_channels channels, all with the same parameters.  The object runs the stages first_stage .. last_stage (CSDR_AMD_RTTY_*) and keeps each channel's
