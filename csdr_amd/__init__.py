@@ -111,7 +111,7 @@ def lib():
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
                        ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("shiftbank", chan), ("framesync", max_out + chan[:1] + lanes), ("amssb", max_out + chan + lanes),
-                       ("txbank", max_out)):
+                       ("txbank", max_out), ("fmrx", max_out + chan[:1])):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
             f.restype, f.argtypes = members[m]
@@ -402,6 +402,11 @@ def lib():
     L.csdr_amd_nfm_reset.argtypes = [vp]
     L.csdr_amd_nfm_process.restype = C.c_long; L.csdr_amd_nfm_process.argtypes = [vp, vp, sz, sz, vp, vp, sz]
     L.csdr_amd_nfm_front_end.restype = vp; L.csdr_amd_nfm_front_end.argtypes = [vp]
+    L.csdr_amd_fmrx_create.restype = vp; L.csdr_amd_fmrx_create.argtypes = [vp, i, i, i, fl, fl, sz]
+    L.csdr_amd_fmrx_process.restype = ll; L.csdr_amd_fmrx_process.argtypes = [vp, vp, sz, ll, vp, vp, sz]
+    L.csdr_amd_fmrx_max_output.restype = ll; L.csdr_amd_fmrx_max_output.argtypes = [vp, ll]
+    L.csdr_amd_fmrx_plan.argtypes = [i, ll, i, i, C.POINTER(ll), C.POINTER(i)]
+    L.csdr_amd_fmrx_fill.argtypes = [vp]
     _lib = L
     return L
 
@@ -1907,6 +1912,59 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
         return cat(outs, np.int16), (cat(pres, f32) if with_pre else None), counts
 
 
+def fmrx_plan(fill, n_in, taps_length, agc_block):
+    """csdr_amd_fmrx_plan (a host function): a call of n_in samples on an object that holds `fill` -> (samples written per channel, samples held afterwards)"""
+    ne, nf = C.c_longlong(), C.c_int()
+    if lib().csdr_amd_fmrx_plan(int(fill), int(n_in), int(taps_length), int(agc_block), C.byref(ne), C.byref(nf)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return ne.value, nf.value
+
+
+class FmRx(_Handle, _MaxOut, _PerChannel):
+    """csdr_amd_fmrx: fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 for n_channels rows of complex baseband on the device;
+    the filter's unconsumed input, the previous sample and the AGC's two blocks stay in the object between calls."""
+
+    def __init__(self, ctx, n_channels, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16):
+        self.n_channels, self.agc_block, self.taps_length = n_channels, agc_block, ctx.nfm_taps(audio_rate).size
+        _Handle.__init__(self, ctx, "fmrx", ctx.L.csdr_amd_fmrx_create(ctx.h, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call))
+
+    def max_output(self, n_in):
+        return int(self._fn("max_output")(self.h, int(n_in)))
+
+    def fill(self):
+        """the filter input the object holds, per channel"""
+        return int(self._fn("fill")(self.h))
+
+    def process_dev(self, d_in, in_pitch, n_in, d_s16, d_f, out_pitch):
+        """device pointers (d_s16 / d_f may be None), pitches in elements -> the audio samples written per channel.  Asynchronous."""
+        return self._call("process", d_in, in_pitch, n_in, d_s16, d_f, out_pitch)
+
+    def process(self, x, with_float=False, in_pitch=None, out_pitch=None, in_offset=0, with_s16=True):
+        """One call.  x: [n_channels, n] (or [n]) complex samples; in_pitch / out_pitch: row pitches in samples (default: the row, the input's rounded up to even); in_offset: bytes by which the input's base is
+        moved off its allocation -> (s16 [n_channels, count], count), with the float audio [n_channels, count] in between when with_float; with_s16=False:
+        no s16 row is asked for and the first entry is None."""
+        x = np.ascontiguousarray(x, c64)
+        if x.ndim == 1:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        ip = max((n + 1) & ~1, 2) if in_pitch is None else int(in_pitch)      # (default: the row, rounded up to the even pitch the one-kernel path needs)
+        xin = np.zeros((s, ip), c64)
+        xin[:, :n] = x
+        raw = np.zeros(xin.nbytes + in_offset + 16, np.uint8)
+        raw[in_offset:in_offset + xin.nbytes] = xin.view(np.uint8).ravel()
+        di = self.ctx.upload(raw)
+        op = max(self.max_output(n), 1) if out_pitch is None else int(out_pitch)
+        ds = self.ctx.alloc(2 * op * s + 256) if with_s16 else None
+        df = self.ctx.alloc(4 * op * s + 256) if with_float else None
+        got = self.process_dev(di.at(in_offset), ip, n, ds.ptr if ds else None, df.ptr if df else None, op)
+        pcm = self.ctx.download(ds, np.int16, op * s).reshape(s, op)[:, :got].copy() if ds else None
+        if with_float:
+            return pcm, self.ctx.download(df, f32, op * s).reshape(s, op)[:, :got].copy(), got
+        return pcm, got
+
+
 TX_MODES = {"fm": 0, "am": 1, "dsb": 2}
 TX_FORMATS = {"cf32": 0, "u8": 1}
 
@@ -2602,6 +2660,11 @@ class Context:
     def squelch(self, n_channels=1, block_size=1024, use_every_nth=1, levels=None, max_samples_per_call=1 << 22):
         """A batched squelch_and_smeter_cc object (Squelch)"""
         return Squelch(self, n_channels, block_size, use_every_nth, levels, max_samples_per_call)
+
+    # ---- the NFM receive bank on baseband (fmrx.hip)
+    def fm_rx(self, n_channels=1, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16):
+        """A batched fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 object on complex baseband (FmRx)"""
+        return FmRx(self, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call)
 
     # ---- the AM and SSB receive chains (amssb.hip)
     def am_bank(self, n_channels=1, block=1024, agc=None, limit_max=None, **kw):

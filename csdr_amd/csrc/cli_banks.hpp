@@ -125,6 +125,87 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
     return 0;
 }
 
+// ------------------------------------------------------------------ the ddcd topology for FM clients: channelizer and NFM demodulators in one process
+// Behind its `csdr fastddc_inv_cc` a ddcd / OpenWebRX client runs `fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff <audio_rate> | fastagc_ff | convert_f_s16`
+// (README.md:87's tail).  Here: fastddc_bank_cc's loop with ONE csdr_amd_fmrx behind the bank; the N decimated channels stay in HBM and out_k receives s16 audio:
+//   csdr fastddc_nfm_bank_s16 <decimation> <transition_bw> <window> <audio_rate> <ctl | -> <out_0> <shift_rate_0> [<out_1> <shift_rate_1> ...]
+// out_k and ctl as in fastddc_bank_cc; a control line "<channel> <shift_rate>\n" retunes that channel from the next batch on, "<channel> reset\n" starts its
+// demodulator, de-emphasis filter and AGC over (csdr_amd_fmrx_reset_channel).  The FM bank gives every channel the same number of samples per call; the
+// channelizer's per-channel counts are equal by construction (its residual-shift bookkeeping does not depend on the rate), which is checked for every batch.
+// One GPU only: with CSDR_AMD_WORLD set the command ends (fastddc_bank_cc is the one that shards a bank).
+int run_nfm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
+{
+    if (argc < 9 || (argc - 7) % 2) return badsyntax("usage: fastddc_nfm_bank_s16 <decimation> <transition_bw> <window> <audio_rate> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]");
+    if (getenv("CSDR_AMD_WORLD")) return badsyntax("runs on one GPU only: CSDR_AMD_WORLD is set (fastddc_bank_cc is the command that shards a bank over several)");
+    int D = 0, audio_rate = 0; float tbw = 0.05f; sscanf(argv[2], "%d", &D); sscanf(argv[3], "%g", &tbw); sscanf(argv[5], "%d", &audio_rate);
+    const int window = window_from(argv[4]);
+    const int n_ch = (argc - 7) / 2;
+    Fds ctl_fd(1, -1); LineSplitter lines;
+    if (strcmp(argv[6], "-")) {
+        ctl_fd[0] = open_spec(argv[6], O_RDONLY | O_NONBLOCK);
+        if (ctl_fd[0] < 0) return badsyntax("cannot open the control channel");
+        fcntl(ctl_fd[0], F_SETFL, fcntl(ctl_fd[0], F_GETFL, 0) | O_NONBLOCK);
+    }
+    std::vector<float> rates(n_ch);
+    for (int k = 0; k < n_ch; k++) if (sscanf(argv[8 + 2 * k], "%g", &rates[k]) != 1) return badsyntax("every rate must be a number");
+    csdr_fastddc_t ddc;
+    if (csdr_amd_fastddc_init(&ddc, tbw, D, 0)) return badsyntax("error in fastddc_init()");
+    int nb_max = (int)(block / ddc.input_size); if (nb_max < 1) nb_max = 1;
+    Owned<csdr_amd_fastddc_bank, csdr_amd_fastddc_bank_destroy> bank(csdr_amd_fastddc_bank_create(c, tbw, D, rates.data(), n_ch, window, nb_max));
+    if (!bank) die("fastddc_bank create");
+    const size_t pitch = ((size_t)csdr_amd_fastddc_bank_max_output(bank.get(), nb_max) + 9) & ~(size_t)1;      // even: the FM bank's one-kernel path reads two samples a lane
+    Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> fm(csdr_amd_fmrx_create(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
+    if (!fm) return badsyntax(csdr_amd_last_error());
+    const size_t a_pitch = ((size_t)csdr_amd_fmrx_max_output(fm.get(), (long long)pitch) + 15) & ~(size_t)7;
+    Fds out_fd(n_ch, -1);
+    for (int k = 0; k < n_ch; k++) {
+        out_fd[k] = open_spec(argv[7 + 2 * k], O_WRONLY | O_CREAT | O_TRUNC);
+        if (out_fd[k] < 0) { fprintf(stderr, "csdr %s: cannot open output %s\n", g_cmd, argv[7 + 2 * k]); return -1; }
+    }
+    const size_t in_elems = (size_t)nb_max * ddc.input_size;
+    const auto h_in = pinned_alloc<csdr_complexf>(in_elems * 8);
+    const auto h_out = pinned_alloc<int16_t>((size_t)n_ch * a_pitch * 2);
+    const auto d_in = ctx_alloc<csdr_complexf>(c, in_elems * 8 + 64), d_bb = ctx_alloc<csdr_complexf>(c, (size_t)n_ch * pitch * 8 + 64);
+    const auto d_out = ctx_alloc<int16_t>(c, (size_t)n_ch * a_pitch * 2 + 64);
+    std::vector<int> counts(n_ch);
+    fprintf(stderr, "csdr %s: %d channels, fft_size = %d, input_size = %d, %d blocks per call, audio rate %d\n", g_cmd, n_ch, ddc.fft_size, ddc.input_size, nb_max, audio_rate);
+    size_t have = 0;
+    for (bool eof = false; !eof;) {
+        size_t got = 0;
+        if (!read_full((char *)h_in.get() + have * 8, (in_elems - have) * 8, &got)) eof = true;
+        have += got / 8;
+        if (ctl_fd[0] >= 0)
+            while (lines.feed(ctl_fd[0])) while (const char *line = lines.next()) {
+                int ch = -1; char what[32] = "";
+                if (sscanf(line, "%d %31s", &ch, what) != 2 || ch < 0 || ch >= n_ch) continue;
+                float rate = 0;
+                if (!strcmp(what, "reset")) {
+                    MUST(csdr_amd_fmrx_reset_channel(fm.get(), ch));
+                    fprintf(stderr, "csdr %s: channel %d reset\n", g_cmd, ch);
+                } else if (sscanf(what, "%g", &rate) == 1) {
+                    MUST(csdr_amd_fastddc_bank_set_rate(bank.get(), ch, rate));
+                    fprintf(stderr, "csdr %s: channel %d retuned to %g\n", g_cmd, ch, rate);
+                }
+            }
+        const int nb = (int)(have / ddc.input_size);
+        if (nb == 0) continue;
+        const size_t used = (size_t)nb * ddc.input_size;
+        MUST(csdr_amd_h2d(c, d_in.get(), h_in.get(), used * 8));
+        MUST(csdr_amd_fastddc_bank_process(bank.get(), d_in.get(), nb, d_bb.get(), pitch, counts.data()));
+        for (int k = 1; k < n_ch; k++)
+            if (counts[k] != counts[0]) { fprintf(stderr, "csdr %s: the channelizer wrote %d samples for channel %d and %d for channel 0: the FM bank advances its channels in lockstep\n", g_cmd, counts[k], k, counts[0]); return -1; }
+        const long long na = csdr_amd_fmrx_process(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch);
+        MUST(na);
+        if (na > 0) {
+            MUST(csdr_amd_d2h(c, h_out.get(), d_out.get(), (size_t)n_ch * a_pitch * 2));
+            for (int k = 0; k < n_ch; k++)
+                if (out_fd[k] >= 0 && !write_fully(out_fd[k], h_out.get() + (size_t)k * a_pitch, (size_t)na * 2)) { close(out_fd[k]); out_fd[k] = -1; }
+        }
+        memmove(h_in.get(), h_in.get() + used, (have - used) * 8); have -= used;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ one shifter per client on one wideband stream (csdr.c:881-923, ddcd_old.h:51-61) in one process
 //   csdr shift_bank_cc <addition|math|table[:size]> <ctl | -> <out_0> <rate_0> [<out_1> <rate_1> ...]
 // reads ONE complexf stream from stdin and writes N shifted streams through one csdr_amd_shiftbank (the input row shared by all streams).  out_k and ctl as in

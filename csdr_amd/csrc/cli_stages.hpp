@@ -752,6 +752,30 @@ struct NfmChain : Stage {   // the README.md:87 chain as ONE command (extension)
     bool noted = false;
 };
 
+struct NfmRx : Stage {   // fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff <audio_rate> | fastagc_ff | convert_f_s16 as ONE command (extension): the stage behind one fastddc_inv_cc,
+                        // one channel of csdr_amd_fmrx; the filter's unconsumed input, the previous sample and the AGC's blocks stay in the object between passes
+    Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> p; size_t max_n;
+    NfmRx(csdr_amd_ctx *c, int audio_rate, size_t block) : max_n(block + 1024)
+    {
+        in_elem = 8; out_elem = 2;
+        p.reset(csdr_amd_fmrx_create(c, 1, audio_rate, 1024, 1.0f, 1.0f, max_n));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
+        if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+    }
+    size_t out_capacity(size_t n) override { return n + 4096; }
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        long total = 0;
+        for (size_t at = 0; at < n; at += max_n) {                     // (inside `chain` a pass may hand over more than the command's own block)
+            const size_t m = std::min(max_n, n - at);
+            const long long na = csdr_amd_fmrx_process(p.get(), (const csdr_complexf *)i + at, 0, (long long)m, (int16_t *)o + total, nullptr, cap - total);
+            MUST(na);
+            total += (long)na;
+        }
+        return total;
+    }
+};
+
 struct DecimatingShift : Stage {   // csdr.c:851-875: one libcsdr call per the_bufsize samples, status carried between calls
     int dec, bufsize; float dsa[3]; void *d_dsa, *d_status;
     DecimatingShift(csdr_amd_ctx *c, float rate, int decimation, int the_bufsize) : dec(decimation), bufsize(the_bufsize)
@@ -1617,6 +1641,11 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         if (csdr_amd_log2n(fft) < 1 || every <= 0 || avg <= 0) { badsyntax("fft_size must be a power of two >= 2, every_n and avgnumber positive"); return nullptr; }
         const int in_format = cmd == "waterfall_u8" ? CSDR_AMD_WF_IN_U8 : cmd == "waterfall_cc" ? CSDR_AMD_WF_IN_CF32 : cmd == "waterfall_ff" ? CSDR_AMD_WF_IN_F32 : CSDR_AMD_WF_IN_S16;
         return new WaterfallStage(c, in_format, fft, every, window_from(argv[4]), add_db, avg, !strcmp(argv[7], "adpcm"), block);
+    }
+    if (cmd == "nfm_rx_cc_s16") {
+        int rate = 48000;
+        if (argc > 2 && sscanf(argv[2], "%d", &rate) != 1) { badsyntax("the audio rate must be a number"); return nullptr; }
+        return new NfmRx(c, rate, block);
     }
     // the fused commands: `--fifo <path>` / `--fd <n>` stand where the shift rate stands, as in shift_addition_cc (csdr.c:881-893); the first rate is waited for
     if (cmd == "ddc_u8_cc" || cmd == "nfm_chain_u8_s16" || cmd == "wfm_chain_u8_s16") {

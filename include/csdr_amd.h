@@ -1239,6 +1239,38 @@ long csdr_amd_nfm_process(csdr_amd_nfm *w, const uint8_t *in, size_t in_pitch, s
 /* the chain's front end object (kernel name / profiling: csdr_amd_ddc_kernel_name, csdr_amd_ddc_set_profiling, csdr_amd_ddc_kernel_time) */
 csdr_amd_ddc *csdr_amd_nfm_front_end(csdr_amd_nfm *w);
 
+/* ------------------------------------------------------------------ the NFM receive bank on baseband (fmrx.hip)
+ *   fmdemod_quadri_cf | limit_ff [max_amp] | deemphasis_nfm_ff <audio_rate> | fastagc_ff [block [reference]] | convert_f_s16
+ * for n_channels rows of decimated complex baseband on the device (the output of csdr_amd_fastddc_bank, csdr_amd_ddc_process, csdr_amd_fir_decimate_cc): the tail of
+ * csdr_amd_nfm without its u8 front end, in the same stream model and with the same arithmetic.  Per channel: the demodulator starts from the sample (0, 0) and a
+ * zero denominator gives 0; the de-emphasis FIR runs over (1024 zeros ++ limited stream), as `csdr deemphasis_nfm_ff` does at the default buffer size, as an exact
+ * integer product on three base-256 digits per sample; fastagc_ff works on whole blocks of agc_block samples from a zeroed state, so the first two blocks are 0.
+ * The channels advance in lockstep: a call gives every channel n_in samples.  With `fill` the filter input the object holds (1024 after a reset) and Ld the taps of
+ * csdr_amd_nfm_deemph_taps(audio_rate), a call writes ne = ((fill + n_in - Ld) / agc_block) * agc_block samples per channel (0 when that is not positive) and then
+ * holds fill + n_in - ne: csdr_amd_fmrx_plan, a host function.  The audio has the same bits however the stream is cut into calls, on either kernel path, and fed with
+ * the rows of csdr_amd_ddc_process it has the bits of csdr_amd_nfm on the same u8 input.  Inputs are finite; Inf and NaN behave as they do in csdr_amd_nfm.
+ * create: NULL with a message when audio_rate has no table, the taps exceed the matrix-core tile (241), agc_block is not a multiple of 16 in 16 .. 1536, limit_max <= 0,
+ * n_channels < 1 (or > 65535) or max_samples_per_call is not in 1 .. 2^30.
+ * process: in (device) [n_channels][in_pitch complexf]; audio_s16 and audio_f (the float audio in front of convert_f_s16), both device, [n_channels][out_pitch], either
+ * may be NULL.  Returns the samples written per channel; -3 when n_in > max_samples_per_call, or when out_pitch < ne with more than one channel (nothing has changed
+ * then).  n_in = 0 does nothing.  Asynchronous on the context's stream.
+ * max_output: the largest ne of a call of n_in samples whatever the object holds (max_out: the same, the name the other banks use).
+ * reset_channel: one channel's held input, previous sample and AGC state to zero; `fill` is the bank's and stays, the other channels carry on.
+ * kernel_name: the path of the last call: "k_fmrx_front" (agc_block 1024, 16-byte aligned rows, even in_pitch: the rows are read, demodulated and filtered in one
+ * kernel) or "k_nfm_deemph_mfma" (csdr_amd_nfm's separate launches; every shape; force_generic(1)).  Both give the same bits, and a stream may change between them. */
+typedef struct csdr_amd_fmrx csdr_amd_fmrx;
+csdr_amd_fmrx *csdr_amd_fmrx_create(csdr_amd_ctx *ctx, int n_channels, int audio_rate, int agc_block, float agc_reference, float limit_max, size_t max_samples_per_call);
+long long csdr_amd_fmrx_process(csdr_amd_fmrx *o, const csdr_complexf *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *audio_f, size_t out_pitch);
+long long csdr_amd_fmrx_max_output(const csdr_amd_fmrx *o, long long n_in);
+long long csdr_amd_fmrx_max_out(const csdr_amd_fmrx *o, long long n_in);
+int  csdr_amd_fmrx_plan(int fill, long long n_in, int taps_length, int agc_block, long long *ne, int *new_fill);
+int  csdr_amd_fmrx_fill(const csdr_amd_fmrx *o);
+int  csdr_amd_fmrx_reset(csdr_amd_fmrx *o);
+int  csdr_amd_fmrx_reset_channel(csdr_amd_fmrx *o, int channel);
+int  csdr_amd_fmrx_force_generic(csdr_amd_fmrx *o, int on);
+const char *csdr_amd_fmrx_kernel_name(const csdr_amd_fmrx *o);
+void csdr_amd_fmrx_destroy(csdr_amd_fmrx *o);
+
 /* ------------------------------------------------------------------ the AM and SSB receive chains (amssb.hip)
  * README.md:95   ... | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16
  * README.md:110  ... | bandpass_fir_fft_cc lo hi tbw | realpart_cf | agc_ff | limit_ff | convert_f_s16
