@@ -395,6 +395,8 @@ def lib():
     L.csdr_amd_ddc_reset.argtypes = [vp]
     L.csdr_amd_ddc_process.restype = C.c_long; L.csdr_amd_ddc_process.argtypes = [vp, vp, sz, sz, vp, sz]
     L.csdr_amd_ddc_kernel_name.restype = C.c_char_p; L.csdr_amd_ddc_kernel_name.argtypes = [vp]
+    if hasattr(L, "csdr_amd_ddc_last_instance"):         # (absent from older builds selected with CSDR_AMD_LIB for A/B runs)
+        L.csdr_amd_ddc_last_instance.restype = C.c_char_p; L.csdr_amd_ddc_last_instance.argtypes = [vp]
     L.csdr_amd_ddc_set_profiling.argtypes = [vp, i]
     L.csdr_amd_ddc_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     L.csdr_amd_nfm_create.restype = vp; L.csdr_amd_nfm_create.argtypes = [vp, i, fl, i, vp, i, i, i, fl, fl, sz]
@@ -2926,7 +2928,8 @@ class Context:
     def ddc_u8(self, iq_u8, shift_rate, decimation, taps, block=None, pitch_pad=0, retunes=None):
         """Fused front end convert_u8_f | shift_addition_cc | fir_decimate_cc (csdr_amd_ddc_*): iq_u8 [2n] or [streams, 2n] uint8 ->
         complex64 [streams, n_out].  `block` = samples per call; `pitch_pad` = extra bytes of row pitch (a pitch that is not a multiple of
-        128 selects the plain kernel).  The kernel of the last call is left in `self.last_ddc_kernel`, all kernels used in `self.ddc_kernels`.
+        128 selects the plain kernel).  The kernel of the last call is left in `self.last_ddc_kernel`, all kernels used in `self.ddc_kernels`, the set of the
+        calls' dispatch reports (csdr_amd_ddc_last_instance) in `self.ddc_instances`.
         shift_rate: one float, or one per stream (csdr_amd_ddc_create_rates); retunes: {call index: [(stream, rate), ...]} applied in front of that call."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         s, nbytes = x2.shape; n = nbytes // 2
@@ -2944,13 +2947,14 @@ class Context:
             di = self.upload(xx)
             opitch = n // decimation + 64
             do = self.alloc(8 * s * opitch)
-            pos = 0; no = 0; self.ddc_kernels = set(); call = 0
+            pos = 0; no = 0; self.ddc_kernels = set(); self.ddc_instances = set(); call = 0
             while pos < n:
                 for st, r in (retunes or {}).get(call, []):
                     d._call("set_rate", st, r)
                 k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
                 got = d._call("process", di.at(2 * pos), pitch, k, do.at(8 * no), opitch)
                 self.ddc_kernels.add(d.kernel_name())
+                self.ddc_instances.add(self.L.csdr_amd_ddc_last_instance(d.h).decode())
                 pos += k; no += got
             y = self.download(do, c64, s * opitch).reshape(s, opitch)[:, :no]
             self.last_ddc_kernel = d.kernel_name()
@@ -3007,7 +3011,8 @@ class Context:
     def nfm_chain(self, iq_u8, shift_rate, decimation=50, tbw=0.005, audio_rate=48000, agc_block=1024, block=None, retunes=None):
         """BASELINE config 5 / README.md:87 through the chain object csdr_amd_nfm_* (matrix-core front end + audio-rate back end):
         iq_u8 [streams, 2n] uint8 -> (s16 [streams, na], float audio [streams, na]); `block` = samples per call.
-        shift_rate: one float, or one per stream (csdr_amd_nfm_create_rates); retunes: {call index: [(stream, rate), ...]}."""
+        shift_rate: one float, or one per stream (csdr_amd_nfm_create_rates); retunes: {call index: [(stream, rate), ...]}.  The set of the front end's
+        dispatch reports (csdr_amd_ddc_last_instance) is left in `self.ddc_instances`."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         S, nbytes = x2.shape; n = nbytes // 2
         pitch = (nbytes + 127) // 128 * 128
@@ -3025,12 +3030,13 @@ class Context:
             di = self.upload(xx)
             apitch = n // decimation + 1024 + 64
             ds = self.alloc(2 * S * apitch); df = self.alloc(4 * S * apitch)
-            pos = 0; na = 0; call = 0
+            pos = 0; na = 0; call = 0; self.ddc_instances = set()
             while pos < n:
                 for st, r in (retunes or {}).get(call, []):
                     w._call("set_rate", st, r)
                 k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
                 got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na), apitch)
+                self.ddc_instances.add(self.L.csdr_amd_ddc_last_instance(w._fn("front_end")(w.h)).decode())
                 pos += k; na += got
             pcm = self.download(ds, np.int16, S * apitch).reshape(S, apitch)[:, :na]
             af = self.download(df, f32, S * apitch).reshape(S, apitch)[:, :na]

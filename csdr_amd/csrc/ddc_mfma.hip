@@ -32,6 +32,7 @@
 #include "nfm_demod.hpp"
 #include "seeds.hpp"
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <complex>
@@ -57,6 +58,12 @@ constexpr int DDC_WIN = 64 * DDC_NKT;       // 2304 bytes
 constexpr int DDC_HIST = 1024;              // complex samples of input history kept per stream between blocks (>= L - 1; one chunk, so that history has ONE phasor seed)
 constexpr int DDC_DTAB = 3072;              // D^k for k in [-2048, 1024)
 constexpr int DDC_NGRAN = 2 * DDC_NKT + 1;  // prefix sums of the weights at 32-byte granules
+// A rate per stream: the matrix-core kernel applies a drifting stream's correction once per K-range part (its role waves fold it into the post factor table), sampled at
+// the part's centre.  An output with few taps can have all of them up to (288 - L) / 2 samples away from there, where the drift differs by up to 3.2e-8 per sample
+// (rates 0.05, 0.2, 1e-4): 4.6e-6 of the output for 4 taps, 1.8 times its per-sample float32 bound (tests/ddc_reference.py; measured at D = 164, 4 taps).  The bound
+// (4 ceil(sqrt(L)) + 4) 2^-24 grows with L while the distance shrinks: from 100 taps on the worst case is inside it.  Below, objects with a drifting stream run on
+// k_ddc_direct, which corrects every tap with its own granule's value.  (The shared-rate kernel samples per output and has no such limit.)
+constexpr int DDC_PS_DRIFT_MIN_TAPS = 100;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -277,6 +284,7 @@ struct DdcParams {
     long long tile_first; int n_tiles, tiles_per_seg;
     long long k_out0;                 // output index stored at out[stream][0]
     int D, nk_used;                   // decimation; K-steps of the window that hold weights at all
+    int L;                            // taps (where an output's taps lie inside a K-range: the drift corrections' sampling points)
     float scale;
     int n_out;                        // outputs of this call: only k_out0 <= 8 tile + o < k_out0 + n_out are stored (the first / last tile of a call may be partial)
     const uint8_t *hist_in;           // != nullptr: the tiles start in the previous blocks' tail (2 KiB per stream in front of the block: ring positions < 0)
@@ -608,24 +616,38 @@ __global__ __launch_bounds__(64 * DDC_WPT * NT) void k_ddc_mfma(const uint8_t *_
             }
             // ---- this wave's share of rows 4q .. 4q+3 = (Re, Im) of outputs 2q and 2q+1, after the post factors
             const float2 *pt = ptab + (gi & 1) * PTN + ((team * WPT + w) * 2) * 16 + col;      // PS: prepared by the role waves
-            float2 P0;
+            float2 P0, P0b;                                                          // post factors of side 0 for the lane's outputs 2q and 2q + 1
             const int off = (int)((n0 + 32LL * DDC_NKW * w) & 1023);
-            if constexpr (PS) P0 = pt[0];
+            // optional per-chunk correction (rates for which the reference's float recurrence drifts away from C_m D^k).  The drift moves by up to 5e-6 over the 144
+            // samples between a K-range's centre and its ends, so the correction is sampled per OUTPUT, at the centre of the stretch of the K-range's part in each
+            // chunk that the output's taps cover ([D o, D o + L) of the window): with few taps and a large D an output's taps are a short stretch anywhere in the
+            // K-range (4 taps at D = 164 missed the per-sample gate by 1.7 with one sample at the part's centre).  Where the taps cover the whole part this is
+            // the part's centre, as before.  cen(o, a, b): the sampling point for output o in the part [a, b) of the K-range (samples from the K-range's start).
+            const int len0 = two ? 1024 - off : 32 * DDC_NKW;                        // samples of side 0
+            auto cen = [&](int o, int a, int b) {
+                const int lo = max(p.D * o - 32 * DDC_NKW * w, a), hi = min(p.D * o + p.L - 32 * DDC_NKW * w, b);
+                return hi > lo ? (lo + hi) >> 1 : (a + b) >> 1;                      // (no tap inside: the share is an exact zero)
+            };
+            if constexpr (PS) P0b = P0 = pt[0];                                      // (a rate per stream: one correction per part, folded into the table by the role waves)
             else {
-                P0 = cmulf(ctab[ci0], dtab[g.e0 + 2048]);
-                // optional per-chunk correction (rates for which the reference's float recurrence drifts away from C_m D^k): sampled at the
-                // centre of the K-range's part in each chunk
-                if (corr) P0 = cmulf(P0, corr[ci0 * 32 + ((off + (two ? (1024 - off) / 2 : 16 * DDC_NKW)) >> 5)]);
+                P0b = P0 = cmulf(ctab[ci0], dtab[g.e0 + 2048]);
+                if (corr) {
+                    P0b = cmulf(P0, corr[ci0 * 32 + ((off + cen(2 * q + 1, 0, len0)) >> 5)]);
+                    P0 = cmulf(P0, corr[ci0 * 32 + ((off + cen(2 * q, 0, len0)) >> 5)]);
+                }
             }
             float u[4];
             if (two) {
                 const float4 cb = *reinterpret_cast<const float4 *>(lcum + g.gb * 16 + 4 * q);
                 const float cbv[4] = {cb.x, cb.y, cb.z, cb.w};
-                float2 P1;
-                if constexpr (PS) P1 = pt[16];
+                float2 P1, P1b;
+                if constexpr (PS) P1b = P1 = pt[16];
                 else {
-                    P1 = cmulf(ctab[chunk_rel + 2], dtab[g.e0 - 1024 + 2048]);
-                    if (corr) P1 = cmulf(P1, corr[(chunk_rel + 2) * 32 + (((off + 32 * DDC_NKW - 1024) / 2) >> 5)]);
+                    P1b = P1 = cmulf(ctab[chunk_rel + 2], dtab[g.e0 - 1024 + 2048]);
+                    if (corr) {
+                        P1b = cmulf(P1, corr[(chunk_rel + 2) * 32 + ((cen(2 * q + 1, len0, 32 * DDC_NKW) - len0) >> 5)]);
+                        P1 = cmulf(P1, corr[(chunk_rel + 2) * 32 + ((cen(2 * q, len0, 32 * DDC_NKW) - len0) >> 5)]);
+                    }
                 }
                 float v[4];
 #pragma unroll
@@ -634,12 +656,12 @@ __global__ __launch_bounds__(64 * DDC_WPT * NT) void k_ddc_mfma(const uint8_t *_
                     v[r] = fmaf(combine_digits(acc[0][r] - snap[0][r], acc[1][r] - snap[1][r], acc[2][r] - snap[2][r]), scale, cg1[r] - cbv[r]);
                 }
                 part.x = P0.x * u[0] - P0.y * u[1] + (P1.x * v[0] - P1.y * v[1]); part.y = P0.x * u[1] + P0.y * u[0] + (P1.x * v[1] + P1.y * v[0]);
-                part.z = P0.x * u[2] - P0.y * u[3] + (P1.x * v[2] - P1.y * v[3]); part.w = P0.x * u[3] + P0.y * u[2] + (P1.x * v[3] + P1.y * v[2]);
+                part.z = P0b.x * u[2] - P0b.y * u[3] + (P1b.x * v[2] - P1b.y * v[3]); part.w = P0b.x * u[3] + P0b.y * u[2] + (P1b.x * v[3] + P1b.y * v[2]);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; r++) u[r] = fmaf(combine_digits(acc[0][r], acc[1][r], acc[2][r]), scale, cfull[r]);
                 part.x = P0.x * u[0] - P0.y * u[1]; part.y = P0.x * u[1] + P0.y * u[0];
-                part.z = P0.x * u[2] - P0.y * u[3]; part.w = P0.x * u[3] + P0.y * u[2];
+                part.z = P0b.x * u[2] - P0b.y * u[3]; part.w = P0b.x * u[3] + P0b.y * u[2];
             }
         }
 #endif
@@ -825,10 +847,11 @@ struct csdr_amd_ddc {
     float phase; float2 c_prev;
     long long tab_first; bool tab_valid;      // the device tables of chunk seeds (and drift corrections) cover chunks [tab_first, tab_first + ctab_cap)
     long long B, next_k;
-    std::string kernel_name;
+    std::string kernel_name, last_instance;   // last_instance: csdr_amd_ddc_last_instance
     bool profiling; KernelTimer timer; double prof_ms; long prof_launches;
     // a shift rate per stream (csdr_amd_ddc_create_rates)
     bool ps; std::vector<float> rates, h_taps; DevBuf<float> d_scales;
+    std::vector<char> drifting;                                       // per stream: its rate's recurrence drifts (corrections apply)
     DevBuf<float2> d_dtab_old, d_corr_old; DevBuf<int> d_list; std::vector<int> retuned;      // streams retuned since the last call: their first outputs straddle two rates (lead fix-up)
     int fallback;                                                     // 1: the last call ran outside the matrix-core kernel (csdr_amd_ddc_fallback)
     Owned<csdr_amd::SeedTables, seeds_destroy> seeds;                 // (reads d_dtab on its side stream)
@@ -900,6 +923,7 @@ static csdr_amd_ddc *ddc_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
             std::vector<char> dr(n_streams);
             for (int s = 0; s < n_streams; s++) dr[s] = drifts(rates[s]) ? 1 : 0;
             if (seeds_set_drift(d->seeds.get(), dr)) return nullptr;
+            d->drifting = dr;
         }
     } else if (d->use_mfma) {
         DdcTable t;
@@ -959,7 +983,9 @@ int csdr_amd_ddc_set_rate(csdr_amd_ddc *d, int stream, float shift_rate)
     const int rc = ddc_upload_stream_tables(d, stream, shift_rate); if (rc) return rc;
     d->rates[stream] = shift_rate;
     const char *ce = getenv("CSDR_AMD_DDC_CORR");
-    return seeds_set_rate(d->seeds.get(), stream, shift_rate, ce ? atoi(ce) != 0 : ddc_rotator_model_rms(shift_rate) > 2e-6);
+    const bool drifts = ce ? atoi(ce) != 0 : ddc_rotator_model_rms(shift_rate) > 2e-6;
+    d->drifting[stream] = drifts ? 1 : 0;
+    return seeds_set_rate(d->seeds.get(), stream, shift_rate, drifts);
 }
 
 float csdr_amd_ddc_get_rate(const csdr_amd_ddc *d, int stream)
@@ -988,6 +1014,7 @@ int csdr_amd_ddc_reset(csdr_amd_ddc *d)
 }
 
 const char *csdr_amd_ddc_kernel_name(const csdr_amd_ddc *d) { return d->kernel_name.c_str(); }
+const char *csdr_amd_ddc_last_instance(const csdr_amd_ddc *d) { return d->last_instance.c_str(); }
 
 int csdr_amd_ddc_set_profiling(csdr_amd_ddc *d, int on)
 {
@@ -1077,6 +1104,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
     const long long n_out_ll = k_hi - d->next_k + 1;
     const long n_out = n_out_ll > 0 ? (long)n_out_ll : 0;
     bool hist_saved = false;
+    d->last_instance.clear();
     if (n_out > 0) {
         if ((size_t)n_out > out_pitch && d->n_streams > 1) return fail_msg(-3, "ddc: out_pitch %zu smaller than the %ld outputs of this block", out_pitch, n_out);
         const long long k_first = d->next_k;
@@ -1099,14 +1127,16 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             }
         }
         const int n_cu = current_device_cu_count();
-        if (d->ps && !whole) { ta = 0; tb = -1; }                     // a rate per stream: the matrix-core kernel takes whole calls only, everything else is k_ddc_direct's
+        bool coarse = false;                                          // few taps and a drifting stream: DDC_PS_DRIFT_MIN_TAPS
+        if (d->ps && d->L < DDC_PS_DRIFT_MIN_TAPS) for (const char c : d->drifting) coarse |= c != 0;
+        if (d->ps && (!whole || coarse)) { ta = 0; tb = -1; whole = false; }      // a rate per stream: the matrix-core kernel takes whole calls only, everything else is k_ddc_direct's
         // retuned streams: their outputs with D k < B reach into samples that were rotated at the old rate
         long n_fix = 0;
         if (d->ps && !d->retuned.empty()) { n_fix = (long)((d->B + d->D - 1) / d->D - k_first); if (n_fix < 0) n_fix = 0; if (n_fix > n_out) n_fix = n_out; }
         if (tb >= ta) {
             DdcParams p;
             memset(&p, 0, sizeof p);
-            p.n_streams = d->n_streams; p.B = d->B; p.tile_first = ta; p.n_tiles = (int)(tb - ta + 1); p.k_out0 = k_first; p.D = d->D; p.nk_used = d->nk_used; p.scale = d->scale;
+            p.n_streams = d->n_streams; p.B = d->B; p.tile_first = ta; p.n_tiles = (int)(tb - ta + 1); p.k_out0 = k_first; p.D = d->D; p.L = d->L; p.nk_used = d->nk_used; p.scale = d->scale;
             p.two_T = 2LL * T; p.hist_out = (T >= DDC_HIST && (T & 7) == 0) ? d->d_hist[d->hflip ^ 1].get() : nullptr; hist_saved = p.hist_out != nullptr;
             p.n_out = (int)n_out; p.hist_in = whole ? d->d_hist[d->hflip].get() : nullptr;
             const int n_wsb = (d->n_streams + 15) / 16;
@@ -1162,6 +1192,9 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             }
             if (e1) CSDR_HIP(hipEventRecord(e1, st));
             d->kernel_name = "k_ddc_mfma";
+            char inst[64];
+            snprintf(inst, sizeof inst, "k_ddc_mfma<%d,%d,%s,%s> %s", rbl, nt, fuse ? "true" : "false", d->ps ? "true" : "false", whole ? "whole" : "tiles");
+            d->last_instance = inst;
         } else d->kernel_name = "k_ddc_direct";
         // everything else: leading outputs (history), trailing outputs of the last partial tile, or the whole block
         DirectParams q;
@@ -1179,6 +1212,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             if (tb < ta && e1) CSDR_HIP(hipEventRecord(e1, st));
         }
         d->fallback = tb >= ta ? 0 : 1;
+        if (q.na + q.nb > 0 || n_fix > 0) d->last_instance += d->last_instance.empty() ? "k_ddc_direct" : " + k_ddc_direct";
         if (n_fix > 0) {
             // the first outputs of the streams retuned since the last call, with the old rate's table for the samples in front of the block
             const int nr = (int)d->retuned.size();

@@ -1200,7 +1200,8 @@ csdr_amd_ddc *csdr_amd_ddc_create_rates(csdr_amd_ctx *ctx, int n_streams, const 
 int   csdr_amd_ddc_set_rate(csdr_amd_ddc *d, int stream, float shift_rate);
 float csdr_amd_ddc_get_rate(const csdr_amd_ddc *d, int stream);
 /* 1 when the last process() call ran outside the matrix-core kernel (k_ddc_direct: odd decimation, windows beyond 2304 bytes, input pitch not a multiple of 128 bytes,
- * ragged or very short blocks): same results, a fraction of the rate */
+ * ragged or very short blocks; a rate per stream with fewer than 100 taps while a stream's rate needs drift corrections: the matrix-core kernel applies those once per
+ * 288-sample stretch of the window, too coarse for a few taps at its end): same results, a fraction of the rate */
 int   csdr_amd_ddc_fallback(const csdr_amd_ddc *d);
 void csdr_amd_ddc_destroy(csdr_amd_ddc *d);
 int  csdr_amd_ddc_reset(csdr_amd_ddc *d);
@@ -1209,6 +1210,10 @@ int  csdr_amd_ddc_reset(csdr_amd_ddc *d);
 long csdr_amd_ddc_process(csdr_amd_ddc *d, const uint8_t *in, size_t in_pitch, size_t block_samples,
                           csdr_complexf *out, size_t out_pitch);
 const char *csdr_amd_ddc_kernel_name(const csdr_amd_ddc *d);
+/* what the last process() call launched: "k_ddc_mfma<13,NT,FUSE,PS> whole" (the matrix-core kernel took the whole call) or "... tiles" (its whole tiles inside the
+ * block), followed by " + k_ddc_direct" when the plain kernel ran beside it (edge outputs, the first outputs of retuned streams); "k_ddc_direct" when it ran alone;
+ * "" when the call produced no output.  NT: teams per workgroup, FUSE: the NFM chain's demodulating epilogue, PS: a rate per stream. */
+const char *csdr_amd_ddc_last_instance(const csdr_amd_ddc *d);
 int csdr_amd_ddc_set_profiling(csdr_amd_ddc *d, int on);
 int csdr_amd_ddc_kernel_time(csdr_amd_ddc *d, double *total_ms, long *launches);
 /* Test hook: CPU evaluation of one tile of the front end's matrix-core kernel with its own weight table, K-range split and chunk-boundary

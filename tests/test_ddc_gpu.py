@@ -110,5 +110,7 @@ def test_ddc_and_nfm_random_call_sizes(gpu, port, seed):
     if seed == 21:
         pcm1, af1 = gpu.nfm_chain(u8[:5], -rate)
         pcm2, af2 = gpu.nfm_chain(u8[:5], -rate, block=sizes + [1024 * 3])
+        print("INSTANCES nfm D=50 L=801 in calls:", sorted(gpu.ddc_instances))
+        assert "k_ddc_mfma<13,2,true,false> whole" in gpu.ddc_instances
         m = min(pcm1.shape[1], pcm2.shape[1])
         assert m >= pcm1.shape[1] - 2048 and np.array_equal(pcm1[:, :m], pcm2[:, :m])

@@ -112,6 +112,8 @@ def test_nfm_rates_and_retune(gpu, port):
     nfm_taps = gpu.nfm_taps(48000)
     pcm, _ = gpu.nfm_chain(u8, rates)
     assert gpu.last_ddc_kernel == "k_ddc_mfma"
+    print("INSTANCES nfm rates D=50 L=801:", sorted(gpu.ddc_instances))
+    assert gpu.ddc_instances == {"k_ddc_mfma<13,2,true,true> whole"}
     for s in range(S):
         ps, _ = port.nfm_chain(u8[s], float(rates[s]), nfm_taps, D, 0.005, 1024)
         assert pcm.shape[1] == ps.size and vc.s16_diff(pcm[s], ps).max() <= 1, "channel %d" % s
