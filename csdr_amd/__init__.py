@@ -266,6 +266,7 @@ def lib():
     L.csdr_amd_convert_f_s24.argtypes = [vp, vp, vp, sz, i]
     L.csdr_amd_convert_s24_f.argtypes = [vp, vp, vp, sz, i]
     L.csdr_amd_rotator_generate.argtypes = [vp, i, fl, C.POINTER(fl), vp, sz, i, i]
+    L.csdr_amd_debug_shift_scans_ahead.restype = ll; L.csdr_amd_debug_shift_scans_ahead.argtypes = [vp]
     L.csdr_amd_mix_cc.argtypes = [vp, vp, vp, vp, i, sz, sz, sz]
     L.csdr_amd_mix_fc.argtypes = [vp, vp, vp, vp, i, sz, sz, sz]
     L.csdr_amd_shift_cc.argtypes = [vp, i, fl, C.POINTER(fl), vp, vp, i, sz, sz, sz, i, i]
@@ -2150,15 +2151,62 @@ class Context:
         x = np.ascontiguousarray(x, dt)
         return (x[None, :], True) if x.ndim == 1 else (x, False)
 
-    def shift_cc(self, x, rate, variant="addition", phase=0.0, chunk=1024, aux=0):
-        """x: [n] or [streams, n] complex64 -> (shifted, new_phase)"""
+    PAD = -7.5                                           # what _rows writes between and around the rows: a call must leave it alone
+
+    def _rows(self, x2, pitch, offset, dt):
+        """x2 [streams, n] as rows of `pitch` elements that start `offset` elements into a buffer filled with PAD -> (DevBuf, elements)"""
+        s, n = x2.shape
+        assert pitch >= n and offset >= 0
+        flat = np.full(offset + s * pitch + 8, self.PAD, dt)
+        flat[offset:offset + s * pitch].reshape(s, pitch)[:, :n] = x2
+        return self.upload(flat), flat.size
+
+    def shift_cc(self, x, rate, variant="addition", phase=0.0, chunk=1024, aux=0, in_pitch=None, out_pitch=None, in_offset=0, out_offset=0,
+                 in_place=False, full=False):
+        """x: [n] or [streams, n] complex64 -> (shifted, new_phase).  in_pitch / out_pitch: elements from row to row (default n); in_offset / out_offset:
+        elements the first row starts into its buffer (an odd one takes the pointer off 16 bytes); in_place: the output over the input, at its pitch and
+        offset.  full: returns the whole output buffer instead, flat, PAD wherever the call wrote nothing."""
         x2, squeeze = self._2d(x, c64)
         s, n = x2.shape
-        di = self.upload(x2); do = self.alloc(x2.nbytes + 64)
+        ip = n if in_pitch is None else int(in_pitch)
+        op, oo = (ip, in_offset) if in_place else (n if out_pitch is None else int(out_pitch), out_offset)
+        di = self._rows(x2, ip, in_offset, c64)[0]
+        total =oo + s * op + 8
+        do = di if in_place else self.upload(np.full(total, self.PAD, c64)) if full else self.alloc(8 * total)
         ph = C.c_float(phase)
-        self.check(self.L.csdr_amd_shift_cc(self.h, SHIFT[variant], rate, C.byref(ph), di.ptr, do.ptr, s, n, n, n, chunk, aux), "shift_cc")
-        y = self.download(do, c64, s * n).reshape(s, n)
+        self.check(self.L.csdr_amd_shift_cc(self.h, SHIFT[variant], rate, C.byref(ph), di.at(8 * in_offset), do.at(8 * oo), s, n, ip, op, chunk, aux), "shift_cc")
+        flat = self.download(do, c64, total)
+        if full:
+            return flat, ph.value
+        y = flat[oo:oo + s * op].reshape(s, op)[:, :n].copy()
         return (y[0] if squeeze else y), ph.value
+
+    def rotator(self, variant, rate, phase, n, chunk=1024, aux=0):
+        """csdr_amd_rotator_generate -> (rot [n] complex64 as the device wrote it, the phase after n samples)"""
+        rot = self.upload(np.full(n + 8, self.PAD, c64))
+        ph = C.c_float(phase)
+        self.check(self.L.csdr_amd_rotator_generate(self.h, SHIFT[variant], rate, C.byref(ph), rot.ptr, n, chunk, aux), "rotator")
+        got = self.download(rot, c64, n + 8)
+        assert np.all(got[n:] == c64(self.PAD)), "rotator_generate wrote past n"
+        return got[:n].copy(), ph.value
+
+    def shift_scans_ahead(self):
+        """the calls of shift_math_cc / shift_table_cc on this context that found their phase scan done (csdr_amd_debug_shift_scans_ahead)"""
+        return int(self.L.csdr_amd_debug_shift_scans_ahead(self.h))
+
+    def mix_fc(self, x, rot, in_pitch=None, out_pitch=None, full=False):
+        """csdr_amd_mix_fc: x [n] or [streams, n] float32 times rot [n] complex64 -> [streams, n] complex64 (full: the whole output buffer, flat)"""
+        x2, squeeze = self._2d(x, f32); rot = np.ascontiguousarray(rot, c64)
+        s, n = x2.shape; assert rot.size == n
+        ip, op = n if in_pitch is None else int(in_pitch), n if out_pitch is None else int(out_pitch)
+        total = s * op + 8
+        di = self._rows(x2, ip, 0, f32)[0]; do = self.upload(np.full(total, self.PAD, c64)); dr = self.upload(rot)
+        self.check(self.L.csdr_amd_mix_fc(self.h, di.ptr, do.ptr, dr.ptr, s, n, ip, op), "mix_fc")
+        flat = self.download(do, c64, total)
+        if full:
+            return flat
+        y = flat[:s * op].reshape(s, op)[:, :n].copy()
+        return y[0] if squeeze else y
 
     # the reference's own names for the five shifter variants (libcsdr.h:108, 185-207; libcsdr_gpl.h:32-35), CLI chunking included
     def shift_addition_cc(self, x, rate, chunk=1024, phase=0.0): return self.shift_cc(x, rate, "addition", phase, chunk)
@@ -2175,7 +2223,25 @@ class Context:
         self.check(self.L.csdr_amd_mix_fc(self.h, di.ptr, do.ptr, rot.ptr, 1, n, n, n), "mix_fc")
         return self.download(do, c64, n), ph.value
 
-    def decimating_shift_addition_cc(self, x, rate, decimation, status=(0, 0.0, 0)):
+    def decimating_shift_addition_cc(self, x, rate, decimation, status=(0, 0.0, 0), in_pitch=None, out_pitch=None, full=False):
+        """x [n] complex64, one rate, one status (remain, phase, produced) -> (y, status); or x [streams, n], a rate and a status per stream ->
+        ([streams] arrays, [streams] statuses), with in_pitch / out_pitch elements from row to row (full: the whole output buffer as well, flat)"""
+        if np.ndim(x) == 2:
+            x2 = np.ascontiguousarray(x, c64); s, n = x2.shape
+            rates = np.ascontiguousarray(rate, f32); assert rates.size == s and len(status) == s
+            ip, op = n if in_pitch is None else int(in_pitch), n // decimation + 4 if out_pitch is None else int(out_pitch)
+            assert op >= (n + decimation - 1) // decimation
+            dsa = np.zeros((s, 3), f32); st = np.zeros((s, 3), np.int32)
+            for k in range(s):
+                self.L.csdr_amd_shift_addition_init(rates[k] * f32(decimation), _hp(dsa[k]))
+                st[k] = (status[k][0], np.array([status[k][1]], f32).view(np.int32)[0], status[k][2])
+            total = s * op + 8
+            di = self._rows(x2, ip, 0, c64)[0]; do = self.upload(np.full(total, self.PAD, c64)); dd = self.upload(dsa); ds = self.upload(st)
+            self.check(self.L.csdr_amd_decimating_shift_addition_cc(self.h, di.ptr, do.ptr, s, n, ip, op, dd.ptr, decimation, ds.ptr), "dsa")
+            st = self.download(ds, np.int32, 3 * s).reshape(s, 3); flat = self.download(do, c64, total)
+            ys = [flat[k * op:k * op + int(st[k, 2])].copy() for k in range(s)]
+            sts = [(int(st[k, 0]), float(st[k, 1:2].view(f32)[0]), int(st[k, 2])) for k in range(s)]
+            return (ys, sts, flat) if full else (ys, sts)
         x = np.ascontiguousarray(x, c64); n = x.size
         dsa = np.zeros(3, f32); self.L.csdr_amd_shift_addition_init(np.float32(rate) * np.float32(decimation), _hp(dsa))
         st = np.zeros(3, np.int32); st[0] = status[0]; st[1] = np.array([status[1]], f32).view(np.int32)[0]; st[2] = status[2]

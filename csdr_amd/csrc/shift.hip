@@ -224,14 +224,24 @@ static int shift_slot_reserve(ShiftAheadSlot &s, size_t n_tiles)
     return 0;
 }
 
+// grid.y carries the stream index in both mixing launches: more streams than a grid has rows are refused here, in front of any launch
+constexpr int MIX_MAX_STREAMS = 65535;
+static int mix_streams_check(const char *who, int n_streams)
+{
+    if (n_streams > MIX_MAX_STREAMS) return fail_msg(-3, "%s: n_streams %d exceeds %d (one grid row per stream)", who, n_streams, MIX_MAX_STREAMS);
+    return 0;
+}
+
 } // namespace
 
 namespace csdr_amd {
-struct ShiftAhead { ShiftAheadSlot slot[2]; int cur = 0; };
+struct ShiftAhead { ShiftAheadSlot slot[2]; int cur = 0; long long hits = 0; };      // hits: calls that found their scan done (csdr_amd_debug_shift_scans_ahead)
 void ShiftAheadDel::operator()(ShiftAhead *a) const { delete a; }
 }
 
 extern "C" {
+
+long long csdr_amd_debug_shift_scans_ahead(csdr_amd_ctx *c) { return c && c->shift_ahead ? c->shift_ahead->hits : 0; }
 
 int csdr_amd_rotator_generate(csdr_amd_ctx *c, int variant, float rate, float *phase_io, csdr_complexf *rot, size_t n, int chunk, int aux)
 {
@@ -282,7 +292,7 @@ int csdr_amd_rotator_generate(csdr_amd_ctx *c, int variant, float rate, float *p
         ShiftAheadSlot *use = nullptr;
         {   // the scan a previous call started for exactly this (rate, phase, n)?
             ShiftAheadSlot &pr = sa->slot[sa->cur ^ 1];
-            if (pr.predicted && pr.rate == rate && pr.n == n && pr.phase_in == p) { pr.fut.wait(); use = &pr; sa->cur ^= 1; }
+            if (pr.predicted && pr.rate == rate && pr.n == n && pr.phase_in == p) { pr.fut.wait(); use = &pr; sa->cur ^= 1; sa->hits++; }
         }
         int rc;
         if (!use) {                                                       // no: scan now, in the call
@@ -320,6 +330,7 @@ int csdr_amd_mix_cc(csdr_amd_ctx *c, const csdr_complexf *in, csdr_complexf *out
                     int n_streams, size_t n, size_t in_pitch, size_t out_pitch)
 {
     if (!n || n_streams <= 0) return 0;
+    if (int rc = mix_streams_check("mix_cc", n_streams)) return rc;
     const bool vec = !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)rot) & 15) && !(in_pitch & 1) && !(out_pitch & 1);
     size_t gx = (n / 2 + 255) / 256; if (gx < 1) gx = 1;
     const size_t cap = (size_t)(4096 / (n_streams < 4096 ? n_streams : 4096)); if (gx > (cap ? cap : 1) * 8) gx = (cap ? cap : 1) * 8;
@@ -334,6 +345,7 @@ int csdr_amd_mix_fc(csdr_amd_ctx *c, const float *in, csdr_complexf *out, const 
                     int n_streams, size_t n, size_t in_pitch, size_t out_pitch)
 {
     if (!n || n_streams <= 0) return 0;
+    if (int rc = mix_streams_check("mix_fc", n_streams)) return rc;
     size_t gx = (n + 255) / 256; if (gx > 512) gx = 512;
     hipLaunchKernelGGL(k_mix_fc, dim3((unsigned)gx, (unsigned)n_streams), dim3(256), 0, c->stream, in, out, rot, n, in_pitch, out_pitch);
     CSDR_LAUNCH_CHECK();
@@ -344,9 +356,10 @@ int csdr_amd_shift_cc(csdr_amd_ctx *c, int variant, float rate, float *phase_io,
                       int n_streams, size_t n, size_t in_pitch, size_t out_pitch, int chunk, int aux)
 {
     if (!n) return 0;
+    int rc = mix_streams_check("shift_cc", n_streams); if (rc) return rc;    // in front of the generator: a refused call launches nothing
     csdr_complexf *rot = (csdr_complexf *)c->get_scratch(2, sizeof(csdr_complexf) * (n + 2));
     if (!rot) return -2;
-    int rc = csdr_amd_rotator_generate(c, variant, rate, phase_io, rot, n, chunk, aux);
+    rc = csdr_amd_rotator_generate(c, variant, rate, phase_io, rot, n, chunk, aux);
     if (rc) return rc;
     return csdr_amd_mix_cc(c, in, out, rot, n_streams, n, in_pitch, out_pitch);
 }

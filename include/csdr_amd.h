@@ -95,7 +95,11 @@ enum {
 };
 int csdr_amd_rotator_generate(csdr_amd_ctx *ctx, int variant, float rate, float *phase_io,
                               csdr_complexf *rot, size_t n, int chunk, int aux);
-/* out[s][k] = in[s][k] * rot[k]   (four float products, two sums, no FMA contraction) */
+/* MATH / TABLE: the number of calls on this context that found their phase scan done by the call before (same rate, same n, the
+ * phase that call handed back; either of the two variants); the twin of csdr_amd_shiftbank_scans_ahead */
+long long csdr_amd_debug_shift_scans_ahead(csdr_amd_ctx *ctx);
+/* out[s][k] = in[s][k] * rot[k]   (four float products, two sums, no FMA contraction).  csdr_amd_mix_cc, csdr_amd_mix_fc and
+ * csdr_amd_shift_cc take at most 65535 streams a call (one grid row each): more is refused with -3 and nothing is launched */
 int csdr_amd_mix_cc(csdr_amd_ctx *ctx, const csdr_complexf *in, csdr_complexf *out, const csdr_complexf *rot,
                     int n_streams, size_t n, size_t in_pitch, size_t out_pitch);
 /* real input variant: shift_addition_fc libcsdr_gpl.c:54-79 */
