@@ -398,6 +398,10 @@ def lib():
     L.csdr_amd_ddc_kernel_name.restype = C.c_char_p; L.csdr_amd_ddc_kernel_name.argtypes = [vp]
     if hasattr(L, "csdr_amd_ddc_last_instance"):         # (absent from older builds selected with CSDR_AMD_LIB for A/B runs)
         L.csdr_amd_ddc_last_instance.restype = C.c_char_p; L.csdr_amd_ddc_last_instance.argtypes = [vp]
+    if hasattr(L, "csdr_amd_ddc_seed_stats"):            # (absent from older builds selected with CSDR_AMD_LIB for A/B runs)
+        L.csdr_amd_ddc_seed_stats.argtypes = [vp, C.POINTER(C.c_long)]; L.csdr_amd_wfm_seed_stats.argtypes = [vp, C.POINTER(C.c_long)]
+        L.csdr_amd_ddc_tables_built.restype = C.c_long; L.csdr_amd_ddc_tables_built.argtypes = [vp]
+        L.csdr_amd_wfm_tables_built.restype = C.c_long; L.csdr_amd_wfm_tables_built.argtypes = [vp]
     L.csdr_amd_ddc_set_profiling.argtypes = [vp, i]
     L.csdr_amd_ddc_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     L.csdr_amd_nfm_create.restype = vp; L.csdr_amd_nfm_create.argtypes = [vp, i, fl, i, vp, i, i, i, fl, fl, sz]
@@ -2946,14 +2950,33 @@ class Context:
 
     # (the multi-rank form of the bank on ONE GPU: sharded_bank_loopback below, module level -- one Context per rank thread)
 
+    def _seed_stats(self, pre, h, per_stream, seen=None, call=0):
+        """csdr_amd_<pre>_seed_stats (pre: "ddc" / "wfm") of object h as a dict: a rate per stream -> generated, takeovers, refits, dirty, regrowths (seeds.hip's
+        counters) and takeover_calls / refit_calls, the indexes of the calls in front of which those counters moved (`seen`: the dict of the call before);
+        a shared rate -> tables_built alone.  None with an older build selected with CSDR_AMD_LIB."""
+        if not hasattr(self.L, "csdr_amd_%s_seed_stats" % pre):
+            return None
+        if not per_stream:
+            return {"tables_built": int(getattr(self.L, "csdr_amd_%s_tables_built" % pre)(h))}
+        out = (C.c_long * 5)()
+        self.check(getattr(self.L, "csdr_amd_%s_seed_stats" % pre)(h, out), "%s_seed_stats" % pre)
+        st = dict(zip(("generated", "takeovers", "refits", "dirty", "regrowths"), (int(v) for v in out)))
+        st["tables_built"] = st["generated"]
+        for key, calls in (("takeovers", "takeover_calls"), ("refits", "refit_calls")):
+            st[calls] = list(seen[calls]) if seen else []
+            if st[key] > (seen[key] if seen else 0):
+                st[calls].append(call)
+        return st
+
     def wfm_chain(self, iq_u8, shift_rate, decimation, taps, frac_rate=5, tau=50e-6, audio_rate=48000, block=None, pitch_pad=0, retunes=None, want_float=True,
-                  out_per_call=False):
+                  out_per_call=False, max_block=None):
         """iq_u8: [2n] or [streams, 2n] uint8 -> (s16 [streams, na], float audio [streams, na]); `block` = samples per call (or a list of call sizes);
         `pitch_pad` = extra bytes of row pitch (multiple of 16).  shift_rate: one float, or one per stream (csdr_amd_wfm_create_rates);
         retunes: {call index: [(stream, rate), ...]} applied in front of that call.  want_float=False: s16 only (the kernel's line-collecting store path).
         out_per_call: every call writes at the START of the (16-byte aligned) output rows, as a streaming caller with one output buffer does -- the kernel's
         aligned store path on every call (otherwise call k's audio follows call k - 1's in one row: aligned only by chance).
-        The front-end kernel of the last call is left in `self.last_wfm_kernel`."""
+        max_block: the object's max_block_samples (default: the largest call) -- it sizes the chunk-seed tables, nothing else of the matrix-core chain.
+        The front-end kernel of the last call is left in `self.last_wfm_kernel`, the seed tables' counters (_seed_stats) in `self.wfm_seed_stats`."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         s, nbytes = x2.shape; n = nbytes // 2
         pitch = (nbytes + 15) // 16 * 16 + pitch_pad
@@ -2961,16 +2984,18 @@ class Context:
         taps = np.ascontiguousarray(taps, f32)
         sched = list(block) if isinstance(block, (list, tuple)) else None
         block = n if block is None else (max(sched) if sched else block)
-        if np.ndim(shift_rate) == 0:
-            w = self.L.csdr_amd_wfm_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, max(block, 1024))
+        cap = max(block, 1024) if max_block is None else int(max_block)
+        ps = np.ndim(shift_rate) != 0
+        if not ps:
+            w = self.L.csdr_amd_wfm_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, cap)
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == s
-            w = self.L.csdr_amd_wfm_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, max(block, 1024))
+            w = self.L.csdr_amd_wfm_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, frac_rate, tau, audio_rate, cap)
         with _Handle(self, "wfm", w) as w:
             di = self.upload(xx)
             apitch = (n // (decimation * frac_rate) + 64 + 63) // 64 * 64
             ds = self.alloc(2 * s * apitch); df = self.alloc(4 * s * apitch) if want_float else None
-            pos = 0; na = 0; call = 0; parts_s = []; parts_f = []
+            pos = 0; na = 0; call = 0; parts_s = []; parts_f = []; stats = None
             while pos < n:
                 for st, r in (retunes or {}).get(call, []):
                     w._call("set_rate", st, r)
@@ -2981,6 +3006,7 @@ class Context:
                     if want_float: parts_f.append(self.download(df, f32, s * apitch).reshape(s, apitch)[:, :got].copy())
                 else:
                     got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na) if want_float else None, apitch)
+                stats = self._seed_stats("wfm", w.h, ps, stats, call - 1)
                 pos += k; na += got
             if out_per_call:
                 s16 = np.concatenate(parts_s, axis=1) if parts_s else np.zeros((s, 0), np.int16)
@@ -2988,15 +3014,18 @@ class Context:
             else:
                 s16 = self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :na]
                 af = self.download(df, f32, s * apitch).reshape(s, apitch)[:, :na] if want_float else np.zeros((s, 0), f32)
-            self.last_wfm_kernel = w.kernel_name()
+            self.last_wfm_kernel = w.kernel_name(); self.wfm_seed_stats = stats
         return (s16[0].copy(), af[0].copy()) if squeeze else (s16.copy(), af.copy())
 
-    def ddc_u8(self, iq_u8, shift_rate, decimation, taps, block=None, pitch_pad=0, retunes=None):
+    def ddc_u8(self, iq_u8, shift_rate, decimation, taps, block=None, pitch_pad=0, retunes=None, max_block=None, reset_at=None):
         """Fused front end convert_u8_f | shift_addition_cc | fir_decimate_cc (csdr_amd_ddc_*): iq_u8 [2n] or [streams, 2n] uint8 ->
         complex64 [streams, n_out].  `block` = samples per call; `pitch_pad` = extra bytes of row pitch (a pitch that is not a multiple of
         128 selects the plain kernel).  The kernel of the last call is left in `self.last_ddc_kernel`, all kernels used in `self.ddc_kernels`, the set of the
         calls' dispatch reports (csdr_amd_ddc_last_instance) in `self.ddc_instances`.
-        shift_rate: one float, or one per stream (csdr_amd_ddc_create_rates); retunes: {call index: [(stream, rate), ...]} applied in front of that call."""
+        shift_rate: one float, or one per stream (csdr_amd_ddc_create_rates); retunes: {call index: [(stream, rate), ...]} applied in front of that call.
+        max_block: the object's max_block_samples (default: the largest call) -- it sizes the chunk-seed tables, nothing else.  reset_at: csdr_amd_ddc_reset in front of
+        that call (the outputs of the stream that starts there follow the others; their first index is left in `self.ddc_reset_out`).
+        The seed tables' counters (_seed_stats) are left in `self.ddc_seed_stats`, the position of every call's first output in `self.ddc_call_out`."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         s, nbytes = x2.shape; n = nbytes // 2
         pitch = (nbytes + 127) // 128 * 128 + pitch_pad
@@ -3004,26 +3033,32 @@ class Context:
         taps = np.ascontiguousarray(taps, f32)
         sched = list(block) if isinstance(block, (list, tuple)) else None          # `block` may be a list of call sizes (the rest of the stream follows in one call)
         block = n if block is None else (max(sched) if sched else block)
-        if np.ndim(shift_rate) == 0:
-            d = self.L.csdr_amd_ddc_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, max(block, 1024))
+        cap = max(block, 1024) if max_block is None else int(max_block)
+        ps = np.ndim(shift_rate) != 0
+        if not ps:
+            d = self.L.csdr_amd_ddc_create(self.h, s, shift_rate, decimation, _hp(taps), taps.size, cap)
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == s
-            d = self.L.csdr_amd_ddc_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, max(block, 1024))
+            d = self.L.csdr_amd_ddc_create_rates(self.h, s, _hp(rates), decimation, _hp(taps), taps.size, cap)
         with _Handle(self, "ddc", d) as d:
             di = self.upload(xx)
             opitch = n // decimation + 64
             do = self.alloc(8 * s * opitch)
-            pos = 0; no = 0; self.ddc_kernels = set(); self.ddc_instances = set(); call = 0
+            pos = 0; no = 0; self.ddc_kernels = set(); self.ddc_instances = set(); call = 0; stats = None; self.ddc_call_out = []; self.ddc_reset_out = None
             while pos < n:
+                if reset_at is not None and call == reset_at:
+                    d.reset(); self.ddc_reset_out = no
                 for st, r in (retunes or {}).get(call, []):
                     d._call("set_rate", st, r)
                 k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
                 got = d._call("process", di.at(2 * pos), pitch, k, do.at(8 * no), opitch)
                 self.ddc_kernels.add(d.kernel_name())
                 self.ddc_instances.add(self.L.csdr_amd_ddc_last_instance(d.h).decode())
+                stats = self._seed_stats("ddc", d.h, ps, stats, call - 1)
+                self.ddc_call_out.append(no)
                 pos += k; no += got
             y = self.download(do, c64, s * opitch).reshape(s, opitch)[:, :no]
-            self.last_ddc_kernel = d.kernel_name()
+            self.last_ddc_kernel = d.kernel_name(); self.ddc_seed_stats = stats
         return y[0].copy() if squeeze else y.copy()
 
     def wfm_ring_chain(self, iq_u8, shift_rate, decimation, taps, block=16384, n_slots=8, frac_rate=5, tau=50e-6, audio_rate=48000, retunes=None, in_flight=None,
@@ -3074,11 +3109,12 @@ class Context:
         y = np.concatenate(outs, axis=1)
         return y[0].copy() if squeeze else y
 
-    def nfm_chain(self, iq_u8, shift_rate, decimation=50, tbw=0.005, audio_rate=48000, agc_block=1024, block=None, retunes=None):
+    def nfm_chain(self, iq_u8, shift_rate, decimation=50, tbw=0.005, audio_rate=48000, agc_block=1024, block=None, retunes=None, max_block=None):
         """BASELINE config 5 / README.md:87 through the chain object csdr_amd_nfm_* (matrix-core front end + audio-rate back end):
         iq_u8 [streams, 2n] uint8 -> (s16 [streams, na], float audio [streams, na]); `block` = samples per call.
         shift_rate: one float, or one per stream (csdr_amd_nfm_create_rates); retunes: {call index: [(stream, rate), ...]}.  The set of the front end's
-        dispatch reports (csdr_amd_ddc_last_instance) is left in `self.ddc_instances`."""
+        dispatch reports (csdr_amd_ddc_last_instance) is left in `self.ddc_instances`, its seed tables' counters (_seed_stats) in `self.ddc_seed_stats`.
+        max_block: the object's max_block_samples (default: the largest call) -- it sizes the chunk-seed tables and the back end's buffers."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         S, nbytes = x2.shape; n = nbytes // 2
         pitch = (nbytes + 127) // 128 * 128
@@ -3087,26 +3123,29 @@ class Context:
         taps = np.ascontiguousarray(self.firdes_lowpass_f(nt, 0.5 / decimation), f32)
         sched = list(block) if isinstance(block, (list, tuple)) else None
         block = n if block is None else (max(sched) if sched else block)
-        if np.ndim(shift_rate) == 0:
-            w = self.L.csdr_amd_nfm_create(self.h, S, shift_rate, decimation, _hp(taps), taps.size, audio_rate, agc_block, 1.0, 1.0, max(block, 1024))
+        cap = max(block, 1024) if max_block is None else int(max_block)
+        ps = np.ndim(shift_rate) != 0
+        if not ps:
+            w = self.L.csdr_amd_nfm_create(self.h, S, shift_rate, decimation, _hp(taps), taps.size, audio_rate, agc_block, 1.0, 1.0, cap)
         else:
             rates = np.ascontiguousarray(shift_rate, f32); assert rates.size == S
-            w = self.L.csdr_amd_nfm_create_rates(self.h, S, _hp(rates), decimation, _hp(taps), taps.size, audio_rate, agc_block, 1.0, 1.0, max(block, 1024))
+            w = self.L.csdr_amd_nfm_create_rates(self.h, S, _hp(rates), decimation, _hp(taps), taps.size, audio_rate, agc_block, 1.0, 1.0, cap)
         with _Handle(self, "nfm", w) as w:
             di = self.upload(xx)
             apitch = n // decimation + 1024 + 64
             ds = self.alloc(2 * S * apitch); df = self.alloc(4 * S * apitch)
-            pos = 0; na = 0; call = 0; self.ddc_instances = set()
+            pos = 0; na = 0; call = 0; self.ddc_instances = set(); stats = None
             while pos < n:
                 for st, r in (retunes or {}).get(call, []):
                     w._call("set_rate", st, r)
                 k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
                 got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na), apitch)
                 self.ddc_instances.add(self.L.csdr_amd_ddc_last_instance(w._fn("front_end")(w.h)).decode())
+                stats = self._seed_stats("ddc", w._fn("front_end")(w.h), ps, stats, call - 1)
                 pos += k; na += got
             pcm = self.download(ds, np.int16, S * apitch).reshape(S, apitch)[:, :na]
             af = self.download(df, f32, S * apitch).reshape(S, apitch)[:, :na]
-            self.last_ddc_kernel = self.L.csdr_amd_ddc_kernel_name(w._fn("front_end")(w.h)).decode()
+            self.last_ddc_kernel = self.L.csdr_amd_ddc_kernel_name(w._fn("front_end")(w.h)).decode(); self.ddc_seed_stats = stats
         return (pcm[0].copy(), af[0].copy()) if squeeze else (pcm.copy(), af.copy())
 
     def nfm_chain_unfused(self, iq_u8, shift_rate, decimation=50, tbw=0.005, audio_rate=48000, agc_block=1024):

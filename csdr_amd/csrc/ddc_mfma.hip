@@ -846,6 +846,7 @@ struct csdr_amd_ddc {
     bool use_mfma, ended, whole_off;
     float phase; float2 c_prev;
     long long tab_first; bool tab_valid;      // the device tables of chunk seeds (and drift corrections) cover chunks [tab_first, tab_first + ctab_cap)
+    long tabs_built;                          // host-built tables since create (csdr_amd_ddc_tables_built)
     long long B, next_k;
     std::string kernel_name, last_instance;   // last_instance: csdr_amd_ddc_last_instance
     bool profiling; KernelTimer timer; double prof_ms; long prof_launches;
@@ -996,6 +997,22 @@ float csdr_amd_ddc_get_rate(const csdr_amd_ddc *d, int stream)
 
 int csdr_amd_ddc_fallback(const csdr_amd_ddc *d) { return d->fallback; }
 
+int csdr_amd_ddc_seed_stats(const csdr_amd_ddc *d, long out[5])
+{
+    if (!d || !out) return fail_msg(-3, "ddc_seed_stats: bad arguments");
+    if (!d->ps) return fail_msg(-3, "ddc_seed_stats: the object shares one rate, it has no per-stream seed tables (csdr_amd_ddc_tables_built counts its host-built table)");
+    seeds_stats(d->seeds.get(), out);
+    return 0;
+}
+
+long csdr_amd_ddc_tables_built(const csdr_amd_ddc *d)
+{
+    if (!d) return fail_msg(-3, "ddc_tables_built: bad arguments");
+    if (!d->ps) return d->tabs_built;
+    long st[5]; seeds_stats(d->seeds.get(), st);
+    return st[0];
+}
+
 void csdr_amd_ddc_destroy(csdr_amd_ddc *d)
 {
     if (!d) return;
@@ -1081,7 +1098,7 @@ long csdr_amd::ddc_process_fused(csdr_amd_ddc *d, const uint8_t *in, size_t in_p
             hipLaunchKernelGGL(k_ddc_corr, dim3(cdiv(d->ctab_cap, 64)), dim3(64), 0, st, d->d_ctab.get(), d->d_dtab.get(), d->d_corr.get(), (int)d->ctab_cap, (float)cos((double)inc), (float)sin((double)inc));
             CSDR_LAUNCH_CHECK();
         }
-        d->tab_first = first; d->tab_valid = true;
+        d->tab_first = first; d->tab_valid = true; d->tabs_built++;
     }
     const float2 *ctab = d->ps ? sv.ctab : d->d_ctab.get() + (first - d->tab_first);
     const float2 *corr = d->ps ? sv.corr : d->need_corr ? d->d_corr.get() + (first - d->tab_first) * 32 : nullptr;

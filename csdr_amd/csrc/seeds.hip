@@ -105,6 +105,9 @@ struct csdr_amd::SeedTables {
     // few streams (the CLI's one): the phase chain runs on the HOST (the same wrap_plan code, host build: ~25 ns per chunk step against ~130 ns for a lane of
     // k_seed_phases, whose one wave leaves 63 lanes idle) into pinned shadows of the two tables, uploaded on the side stream
     bool host_chain; HostBuf<float> h_ph[2]; bool h_used[2];
+    // which path ran, since create (seeds_stats; read-only, they survive a reset): tables generated, takeovers of a prepared table, regenerations because the
+    // prepared table did not fit the call, regenerations because of `dirty`, regrowths of the correction buffers in mid-stream
+    long n_generated = 0, n_takeover = 0, n_refit = 0, n_dirty = 0, n_regrow = 0;
 };
 
 namespace {
@@ -119,6 +122,28 @@ int alloc_corr(SeedTables *t, int rows)
     if (rows > 0) CSDR_HIP(dev_alloc(t->d_row_stream, sizeof(int) * rows));
     t->corr_rows = rows;
     t->row_stream.assign(rows, -1);
+    return 0;
+}
+
+// More correction rows in mid-stream (everything is synchronised): the rows in use keep their place AND their contents -- a retune of another, drifting stream in
+// front of the same call still reads the current table's corrections of the chunk in front of the next block (seeds_corr_entry).  corr is [row][cap][32]: the old
+// buffer is the head of the new one.
+int grow_corr(SeedTables *t, int rows)
+{
+    CSDR_HIP(hipStreamSynchronize(t->side.get())); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
+    const size_t old_bytes = sizeof(float2) * 32 * (size_t)t->corr_rows * t->cap;
+    for (int b = 0; b < 2; b++) {
+        DevBuf<float2> nb;
+        CSDR_HIP(dev_alloc(nb, sizeof(float2) * 32 * (size_t)rows * t->cap));
+        if (old_bytes) CSDR_HIP(hipMemcpy(nb.get(), t->d_corr[b].get(), old_bytes, hipMemcpyDeviceToDevice));
+        t->d_corr[b] = std::move(nb);
+    }
+    t->row_stream.resize(rows, -1);
+    DevBuf<int> nr;
+    CSDR_HIP(dev_alloc(nr, sizeof(int) * rows));
+    CSDR_HIP(hipMemcpy(nr.get(), t->row_stream.data(), sizeof(int) * rows, hipMemcpyHostToDevice));
+    t->d_row_stream = std::move(nr);
+    t->corr_rows = rows;
     return 0;
 }
 
@@ -156,6 +181,7 @@ int generate(SeedTables *t, int dst, int src, long idx, long long first)
     }
     CSDR_HIP(hipEventRecord(t->ev_ready[dst].get(), ss));
     t->first[dst] = first; t->valid[dst] = true;
+    t->n_generated++;
     return 0;
 }
 
@@ -204,7 +230,7 @@ void seeds_destroy(SeedTables *t)
     delete t;
 }
 
-// the drift rows of all streams at once (create / reset time and when the rows run out): everything is synchronised
+// the drift rows of all streams at once (create time: the correction buffers' contents are dropped, the tables are generated afresh): everything is synchronised
 int seeds_set_drift(SeedTables *t, const std::vector<char> &drift)
 {
     CSDR_HIP(hipStreamSynchronize(t->side.get())); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
@@ -236,15 +262,11 @@ int seeds_set_rate(SeedTables *t, int stream, float rate, bool drift)
         row = old_row;
         if (row < 0) {
             for (int r = 0; r < t->corr_rows && row < 0; r++) if (t->row_stream[r] < 0) row = r;
-            if (row < 0) {                                            // no row left: grow (rare: everything is synchronised and the tables are rebuilt)
-                std::vector<char> dr(t->n, 0);
-                for (int s = 0; s < t->n; s++) dr[s] = t->corr_row[s] >= 0;
-                dr[stream] = 1;
-                t->rates[stream] = rate;
-                CSDR_HIP(hipStreamSynchronize(t->side.get())); CSDR_HIP(hipStreamSynchronize(t->ctx->stream));
-                CSDR_HIP(hipMemcpy(t->d_rates.get() + stream, &rate, sizeof(float), hipMemcpyHostToDevice));
-                // the current table's phases must survive: only the correction buffers are reallocated
-                return seeds_set_drift(t, dr);
+            if (row < 0) {                                            // no row left: grow (rare: everything is synchronised; the tables are rebuilt as after any retune)
+                row = t->corr_rows;
+                const int rc = grow_corr(t, t->corr_rows + 1 + 8);    // (spare rows as seeds_set_drift leaves them)
+                if (rc) return rc;
+                t->n_regrow++;
             }
         }
     }
@@ -256,6 +278,11 @@ int seeds_set_rate(SeedTables *t, int stream, float rate, bool drift)
     CSDR_LAUNCH_CHECK();
     t->dirty = true;
     return 0;
+}
+
+void seeds_stats(const SeedTables *t, long out[5])
+{
+    out[0] = t->n_generated; out[1] = t->n_takeover; out[2] = t->n_refit; out[3] = t->n_dirty; out[4] = t->n_regrow;
 }
 
 const float2 *seeds_corr_entry(SeedTables *t, int stream, long long chunk)
@@ -283,6 +310,7 @@ int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, 
         if (!t->dirty && covers(o)) {                                 // the prepared table takes over
             CSDR_HIP(hipEventRecord(t->ev_free[t->cur].get(), st)); t->free_pending[t->cur] = true;
             t->cur = o;
+            t->n_takeover++;
         } else {
             // regenerate from the phases some table holds for chunks first, first + 1 (a retune, or a call the prepared table does not fit): the history chunk and
             // the call's first chunk were reached under the rate that was valid then
@@ -290,6 +318,7 @@ int seeds_acquire(SeedTables *t, long long first, size_t n, size_t n_next_hint, 
             for (int b : {t->cur, o}) if (src < 0 && t->valid[b] && first >= t->first[b] && first + 1 < t->first[b] + t->cap) src = b;
             if (src < 0) return fail_msg(-3, "seed table: cannot continue at chunk %lld", first);
             const int dst = src ^ 1;
+            if (t->dirty) t->n_dirty++; else t->n_refit++;
             CSDR_HIP(hipEventRecord(t->ev_free[dst].get(), st)); t->free_pending[dst] = true;      // whatever was queued so far may still read it
             t->valid[dst] = false;
             int rc = generate(t, dst, src, (long)(first - t->first[src]), first); if (rc) return rc;

@@ -89,6 +89,10 @@ int seeds_set_rate(SeedTables *t, int stream, float rate, bool drift); // from t
 // not in the table): what a retune has to keep for the samples in front of the next block
 const float2 *seeds_corr_entry(SeedTables *t, int stream, long long chunk);
 
+// Which path ran since create (read-only; a reset does not clear them): out[0] tables generated, [1] takeovers of a prepared table, [2] regenerations because the
+// prepared table did not fit the call, [3] regenerations because of a retune (`dirty`), [4] regrowths of the correction buffers in mid-stream.
+void seeds_stats(const SeedTables *t, long out[5]);
+
 struct SeedView {
     const float2 *ctab;      // seed of chunk (first + k) of stream s: ctab[k * pitch + s]
     size_t pitch;

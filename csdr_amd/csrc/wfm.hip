@@ -221,6 +221,7 @@ struct csdr_amd_wfm {
     DevBuf<float2> d_ctab; size_t ctab_cap;
     float2 c_prev;                   // phasor seed of the previous block's last chunk (history windows)
     long long tab_first; bool tab_valid;      // the device table of seeds covers chunks [tab_first, tab_first + ctab_cap)
+    long tabs_built;                          // host-built tables since create (csdr_amd_wfm_tables_built)
     // a shift rate per stream (csdr_amd_wfm_create_rates): one table set per stream in mfma.*, chunk seeds from a seed table (seeds.hip)
     bool ps; std::vector<float> rates, h_taps; DevBuf<float> d_scales;
     DevBuf<float2> d_dtab_old; DevBuf<int> d_lead_n; int *d_list; DevBuf<float> d_lead_d; std::vector<int> retuned;      // streams retuned since the last call: their first samples straddle two rates
@@ -374,6 +375,22 @@ int csdr_amd_wfm_reset(csdr_amd_wfm *w)
 const char *csdr_amd_wfm_kernel_name(const csdr_amd_wfm *w) { return w->kernel_name.c_str(); }
 int csdr_amd_wfm_fallback(const csdr_amd_wfm *w) { return w->use_mfma ? 0 : 1; }
 
+int csdr_amd_wfm_seed_stats(const csdr_amd_wfm *w, long out[5])
+{
+    if (!w || !out) return fail_msg(-3, "wfm_seed_stats: bad arguments");
+    if (!w->ps) return fail_msg(-3, "wfm_seed_stats: the object shares one rate, it has no per-stream seed tables (csdr_amd_wfm_tables_built counts its host-built table)");
+    seeds_stats(w->seeds.get(), out);
+    return 0;
+}
+
+long csdr_amd_wfm_tables_built(const csdr_amd_wfm *w)
+{
+    if (!w) return fail_msg(-3, "wfm_tables_built: bad arguments");
+    if (!w->ps) return w->tabs_built;
+    long st[5]; seeds_stats(w->seeds.get(), st);
+    return st[0];
+}
+
 int csdr_amd_wfm_set_profiling(csdr_amd_wfm *w, int on)
 {
     w->profiling = on != 0; w->timer.reset(); w->prof_ms = 0; w->prof_launches = 0;
@@ -429,7 +446,7 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
                 ph = nx;
             }
             rc = c->pinned_upload(w->d_ctab.get(), sizeof(float2) * w->ctab_cap); if (rc) return rc;
-            w->tab_first = first; w->tab_valid = true;
+            w->tab_first = first; w->tab_valid = true; w->tabs_built++;
         }
         ctab_call = w->d_ctab.get() + (first - w->tab_first);
         // the stream's phase behind this block (and the seed of its last chunk, for a table rebuilt at the next call)

@@ -1132,6 +1132,9 @@ const char *csdr_amd_wfm_kernel_name(const csdr_amd_wfm *w);
 /* 1 when the object runs outside the matrix-core chain kernel (k_wfm_front + k_wfm_back: decimation x audio decimation odd, filters beyond the 256-sample window;
  * CSDR_AMD_WFM_PATH=valu): same results at about a sixth of the rate.  The CLI prints a one-line note on stderr. */
 int csdr_amd_wfm_fallback(const csdr_amd_wfm *w);
+/* as csdr_amd_ddc_seed_stats / csdr_amd_ddc_tables_built (the WFM chain has no drift corrections: out[4] stays 0) */
+int  csdr_amd_wfm_seed_stats(const csdr_amd_wfm *w, long out[5]);
+long csdr_amd_wfm_tables_built(const csdr_amd_wfm *w);
 /* HIP-event timing of that kernel, on the context's stream: enable, run, then read the accumulated time. */
 int csdr_amd_wfm_set_profiling(csdr_amd_wfm *w, int on);
 int csdr_amd_wfm_kernel_time(csdr_amd_wfm *w, double *total_ms, long *launches);
@@ -1207,6 +1210,12 @@ float csdr_amd_ddc_get_rate(const csdr_amd_ddc *d, int stream);
  * ragged or very short blocks; a rate per stream with fewer than 100 taps while a stream's rate needs drift corrections: the matrix-core kernel applies those once per
  * 288-sample stretch of the window, too coarse for a few taps at its end): same results, a fraction of the rate */
 int   csdr_amd_ddc_fallback(const csdr_amd_ddc *d);
+/* Which path the per-stream seed tables took since create (read-only, no effect on the stream; a reset does not clear them): out[0] tables generated, out[1] takeovers of
+ * a prepared table, out[2] regenerations because the prepared table did not fit the call, out[3] regenerations after a retune, out[4] regrowths of the drift-correction
+ * rows in mid-stream.  A negative error on an object that shares one rate.  The NFM and AM/SSB chains: through their *_front_end.
+ * csdr_amd_ddc_tables_built: chunk-seed tables built since create -- the host-built table of a shared-rate object (rebuilt 16 calls ahead), out[0] otherwise. */
+int   csdr_amd_ddc_seed_stats(const csdr_amd_ddc *d, long out[5]);
+long  csdr_amd_ddc_tables_built(const csdr_amd_ddc *d);
 void csdr_amd_ddc_destroy(csdr_amd_ddc *d);
 int  csdr_amd_ddc_reset(csdr_amd_ddc *d);
 /* in: u8 IQ, [n_streams][in_pitch bytes], block_samples complex samples per stream (multiple of 1024 except for the last block of a
