@@ -111,7 +111,7 @@ def lib():
     common, max_out, chan, lanes = ("reset", "force_generic", "kernel_name", "destroy"), ("max_out",), ("reset_channel", "get_channel", "set_channel"), ("set_lanes", "lanes")
     for pre, extra in (("waterfall", ()), ("resampler", max_out), ("interp", max_out), ("psk31", max_out + chan + lanes), ("psk31tx", max_out + chan),
                        ("pulsetx", max_out), ("pulserx", max_out + chan + lanes), ("rtty", max_out + chan[:1]), ("cfir", max_out + chan[:1]), ("squelch", chan[:1]), ("carrier", chan + lanes), ("shiftbank", chan), ("framesync", max_out + chan[:1] + lanes), ("amssb", max_out + chan + lanes),
-                       ("txbank", max_out), ("fmrx", max_out + chan[:1])):
+                       ("txbank", max_out), ("fmrx", max_out + chan[:1]), ("wfmrx", max_out + chan[:1])):
         for m in common + extra:
             f = getattr(L, "csdr_amd_%s_%s" % (pre, m))
             f.restype, f.argtypes = members[m]
@@ -414,6 +414,12 @@ def lib():
     L.csdr_amd_fmrx_max_output.restype = ll; L.csdr_amd_fmrx_max_output.argtypes = [vp, ll]
     L.csdr_amd_fmrx_plan.argtypes = [i, ll, i, i, C.POINTER(ll), C.POINTER(i)]
     L.csdr_amd_fmrx_fill.argtypes = [vp]
+    L.csdr_amd_wfmrx_create.restype = vp; L.csdr_amd_wfmrx_create.argtypes = [vp, i, fl, i, vp, i, i, fl, i, sz]
+    L.csdr_amd_wfmrx_process.restype = ll; L.csdr_amd_wfmrx_process.argtypes = [vp, vp, sz, ll, vp, vp, sz]
+    L.csdr_amd_wfmrx_max_output.restype = ll; L.csdr_amd_wfmrx_max_output.argtypes = [vp, ll]
+    L.csdr_amd_wfmrx_plan.argtypes = [fl, i, i, i, fl, i, ll, C.POINTER(ll), C.POINTER(fl), C.POINTER(i)]
+    L.csdr_amd_wfmrx_held.argtypes = [vp]
+    L.csdr_amd_wfmrx_where.restype = fl; L.csdr_amd_wfmrx_where.argtypes = [vp]
     _lib = L
     return L
 
@@ -1972,6 +1978,71 @@ class FmRx(_Handle, _MaxOut, _PerChannel):
         return pcm, got
 
 
+def wfmrx_plan(rate, num_poly_points, taps_length, window, where, held, n_in):
+    """csdr_amd_wfmrx_plan (a host function): a call of n_in samples on an object that holds `held` demodulated samples at position `where`
+    -> (samples written per channel, where afterwards, samples held afterwards)"""
+    no, nw, nh = C.c_longlong(), C.c_float(), C.c_int()
+    if lib().csdr_amd_wfmrx_plan(float(rate), int(num_poly_points), int(taps_length), int(window), float(where), int(held), int(n_in), C.byref(no), C.byref(nw), C.byref(nh)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return no.value, nw.value, nh.value
+
+
+class WfmRx(_Handle, _MaxOut, _PerChannel):
+    """csdr_amd_wfmrx: fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 for n_channels rows of complex baseband on the device;
+    the decimator's unprocessed samples and position, the previous sample and the de-emphasis state stay in the object between calls."""
+
+    def __init__(self, ctx, n_channels, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16):
+        taps = None if prefilter_taps is None else np.ascontiguousarray(prefilter_taps, f32)
+        self.n_channels, self.rate, self.num_poly_points, self.window = n_channels, float(f32(rate)), num_poly_points, window or 1024
+        self.taps_length = 0 if taps is None else taps.size
+        _Handle.__init__(self, ctx, "wfmrx", ctx.L.csdr_amd_wfmrx_create(ctx.h, n_channels, rate, num_poly_points, taps.ctypes.data if taps is not None else None,
+                                                                         self.taps_length, window, tau, audio_rate, max_samples_per_call))
+
+    def max_output(self, n_in):
+        return int(self._fn("max_output")(self.h, int(n_in)))
+
+    def held(self):
+        """the demodulated samples the object holds, per channel"""
+        return int(self._fn("held")(self.h))
+
+    def where(self):
+        """the decimator's position in front of the first held sample"""
+        return float(self._fn("where")(self.h))
+
+    def plan(self, n_in):
+        """wfmrx_plan for the next call of n_in samples"""
+        return wfmrx_plan(self.rate, self.num_poly_points, self.taps_length, self.window, self.where(), self.held(), n_in)
+
+    def process_dev(self, d_in, in_pitch, n_in, d_s16, d_f, out_pitch):
+        """device pointers (d_s16 / d_f may be None), pitches in elements -> the audio samples written per channel.  Asynchronous."""
+        return self._call("process", d_in, in_pitch, n_in, d_s16, d_f, out_pitch)
+
+    def process(self, x, with_float=False, in_pitch=None, out_pitch=None, in_offset=0, with_s16=True):
+        """One call.  x: [n_channels, n] (or [n]) complex samples; in_pitch / out_pitch: row pitches in samples (default: the row, the input's rounded up to even);
+        in_offset: bytes by which the input's base is moved off its allocation -> (s16 [n_channels, count], count), with the float audio [n_channels, count] in
+        between when with_float; with_s16=False: no s16 row is asked for and the first entry is None."""
+        x = np.ascontiguousarray(x, c64)
+        if x.ndim == 1:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        ip = max((n + 1) & ~1, 2) if in_pitch is None else int(in_pitch)
+        xin = np.zeros((s, ip), c64)
+        xin[:, :n] = x
+        raw = np.zeros(xin.nbytes + in_offset + 16, np.uint8)
+        raw[in_offset:in_offset + xin.nbytes] = xin.view(np.uint8).ravel()
+        di = self.ctx.upload(raw)
+        op = max(self.max_output(n), 1) if out_pitch is None else int(out_pitch)
+        ds = self.ctx.alloc(2 * op * s + 256) if with_s16 else None
+        df = self.ctx.alloc(4 * op * s + 256) if with_float else None
+        got = self.process_dev(di.at(in_offset), ip, n, ds.ptr if ds else None, df.ptr if df else None, op)
+        pcm = self.ctx.download(ds, np.int16, op * s).reshape(s, op)[:, :got].copy() if ds else None
+        if with_float:
+            return pcm, self.ctx.download(df, f32, op * s).reshape(s, op)[:, :got].copy(), got
+        return pcm, got
+
+
 TX_MODES = {"fm": 0, "am": 1, "dsb": 2}
 TX_FORMATS = {"cf32": 0, "u8": 1}
 
@@ -2737,6 +2808,11 @@ class Context:
     def fm_rx(self, n_channels=1, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16):
         """A batched fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 object on complex baseband (FmRx)"""
         return FmRx(self, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call)
+
+    # ---- the WFM receive bank on baseband (wfmrx.hip)
+    def wfm_rx(self, n_channels=1, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16):
+        """A batched fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 object on complex baseband (WfmRx)"""
+        return WfmRx(self, n_channels, rate, num_poly_points, prefilter_taps, window, tau, audio_rate, max_samples_per_call)
 
     # ---- the AM and SSB receive chains (amssb.hip)
     def am_bank(self, n_channels=1, block=1024, agc=None, limit_max=None, **kw):

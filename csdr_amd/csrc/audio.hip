@@ -5,7 +5,7 @@
 //   fastagc_ff              libcsdr.c:946-991
 //   fractional_decimator_ff libcsdr.c:715-793
 // File is built with -ffp-contract=off: products and sums round separately like the reference's SSE code.
-#include "common.hpp"
+#include "audio_dev.hpp"
 #include <math.h>
 #include <vector>
 #include <string.h>
@@ -17,30 +17,13 @@ namespace {
 __global__ __launch_bounds__(256) void k_fmdemod(const cf32 *__restrict__ in, float *__restrict__ out, size_t n,
                                                  size_t in_pitch, size_t out_pitch, const cf32 *__restrict__ last)
 {
-    const float Kf = 0.340447550238101026565118445432744920253753662109375f;   // libcsdr.c:1021
     const cf32 *src = in + (size_t)blockIdx.y * in_pitch;
     float *dst = out + (size_t)blockIdx.y * out_pitch;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
         const cf32 x = src[k];
         const cf32 p = k ? src[k - 1] : last[blockIdx.y];
-        const float dq = x.q - p.q, di = x.i - p.i;
-        const float num = x.i * dq - x.q * di;
-        const float den = x.i * x.i + x.q * x.q;
-        // the reference scales and divides in double (:1067) and rounds once; a float product with a Newton-refined reciprocal is within a few ulp of
-        // that (tests/audio_model.py derives the gate) and avoids the ~25-instruction fp64 division sequence that made this kernel arithmetic bound.
-        // v_rcp_f32 takes a subnormal den as 0 (-> inf, and the refinement then gives NaN) and flushes 1 / den to 0 above den = 2^126, and Kf * num
-        // loses bits once it is subnormal: outside a window that leaves all three (and the refinement's residual) far inside the normal range the
-        // reference's own expression runs instead.  Signals at |x| ~ 1 never leave the window; the compare is the only cost there.
-        const float an = fabsf(num);
-        float v;
-        if (den >= 0x1p-60f && den <= 0x1p60f && (an >= 0x1p-100f || an == 0.f)) {
-            float rd = __builtin_amdgcn_rcpf(den);
-            rd = fmaf(fmaf(-den, rd, 1.0f), rd, rd);
-            v = (Kf * num) * rd;
-        } else
-            v = (den != 0.f) ? (float)(0.340447550238101026565118445432744920253753662109375 * (double)num / (double)den) : 0.f;
-        dst[k] = v;
+        dst[k] = fmdemod_quadri(x.i, x.q, p.i, p.q);                  // (audio_dev.hpp)
     }
 }
 __global__ void k_store_last(const cf32 *__restrict__ in, size_t n, size_t in_pitch, cf32 *__restrict__ last, int n_streams)
@@ -97,7 +80,7 @@ __global__ __launch_bounds__(64) void k_deemph_wfm(const float *__restrict__ in,
         const int cols = (int)((n - t0 < 64) ? (n - t0) : 64);
         for (int r = 0; r < rows; r++) if (lane < cols) tile[r * 65 + lane] = in[(size_t)(s0 + r) * in_pitch + t0 + lane];
         __syncthreads();
-        if (lane < rows) for (int k = 0; k < cols; k++) { y = alpha * tile[lane * 65 + k] + one_minus * y; tile[lane * 65 + k] = y; }
+        if (lane < rows) for (int k = 0; k < cols; k++) { y = deemph_wfm_step(alpha, one_minus, tile[lane * 65 + k], y); tile[lane * 65 + k] = y; }
         __syncthreads();
         for (int r = 0; r < rows; r++) if (lane < cols) out[(size_t)(s0 + r) * out_pitch + t0 + lane] = tile[r * 65 + lane];
         __syncthreads();
@@ -285,10 +268,7 @@ __global__ __launch_bounds__(256) void k_fracdec(const float *__restrict__ in, f
         float y;
         if (ntaps) { y = 0.f; for (int t = 0; t < ntaps; t++) y += taps[t] * x[w + t]; }   // fir_one_pass_ff libcsdr.c:675-680
         else y = x[w];
-        const int a = xifirst + w;
-        float prod = 1;
-        for (int b = xifirst; b < xifirst + P; b++) if (a != b) prod *= (fx - b);
-        acc += (prod / denom[w]) * y;
+        acc += fracdec_coeff(fx, w, P, xifirst, denom[w]) * y;
     }
     out[(size_t)blockIdx.y * out_pitch + k] = acc;
 }
@@ -298,7 +278,6 @@ __global__ __launch_bounds__(256) void k_fracdec(const float *__restrict__ in, f
 // and half-integer rate (5, 5.5, 2.5 ...) at the block sizes in use -- each of those adds is EXACT, so position k of a window is where_0 + k rate with no rounding: a
 // lane evaluates it directly.  The host then only walks the WINDOWS (closed form per window; one window without the CLI's loop), uploads 16 bytes per window instead of
 // 8 bytes per output, and the call no longer waits for the stream.  Rates that are not exact in float (3.3 ...) keep the host walk: their positions are the recurrence's.
-struct FdWin { int base; float w0; int first_out; int count; };
 __global__ __launch_bounds__(256) void k_fracdec_plan(const FdWin *__restrict__ win, int n_win, int n_out, float rate, int *__restrict__ lo_idx, float *__restrict__ frac)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -317,17 +296,6 @@ __global__ __launch_bounds__(256) void k_fracdec_plan(const FdWin *__restrict__ 
 // the kernel path the calling thread's last deemphasis_wfm_ff / agc_ff / fractional_decimator_ff call took (host side only; f2blocks.hip sets it for agc_ff)
 static thread_local const char *g_audio_last_path = "";
 void csdr_amd::set_audio_last_path(const char *path) { g_audio_last_path = path; }
-
-struct csdr_amd_fracdec {
-    float where, rate; int input_processed, num_poly_points, xifirst, xilast, taps_length;
-    std::vector<float> denom, taps;
-    // cached plan
-    float plan_where; int plan_n; bool plan_valid; int plan_outputs, plan_processed; float plan_where_after;
-    int cli_bufsize, plan_bufsize;   // > 0: replay the CLI's loop over the_bufsize-sample windows (csdr.c:1511-1524) instead of one call over the whole array
-    std::vector<int> lo; std::vector<float> frac;      // per output: first input sample of its window, fractional position (the coefficients are the kernel's)
-    DevBuf<int> d_lo; DevBuf<float> d_frac, d_denom, d_taps; size_t d_cap;
-    DevBuf<FdWin> d_win; size_t win_cap;                      // exact rates: the windows of the plan (the outputs' positions are evaluated on the device)
-};
 
 extern "C" {
 
@@ -455,8 +423,9 @@ void csdr_amd_fracdec_destroy(csdr_amd_fracdec *d)
     delete d;
 }
 
-int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const float *in, float *out, int n_streams, int input_size,
-                                     size_t in_pitch, size_t out_pitch, int *input_processed)
+} // extern "C"
+
+int csdr_amd::fracdec_plan(csdr_amd_ctx *c, csdr_amd_fracdec *d, int input_size)
 {
     const int P = d->num_poly_points;
     const bool cached = d->plan_valid && d->plan_where == d->where && d->plan_n == input_size && d->plan_bufsize == d->cli_bufsize;
@@ -556,13 +525,22 @@ int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const
         }
         d->plan_valid = true;
     }
+    return 0;
+}
+
+extern "C" {
+
+int csdr_amd_fractional_decimator_ff(csdr_amd_ctx *c, csdr_amd_fracdec *d, const float *in, float *out, int n_streams, int input_size,
+                                     size_t in_pitch, size_t out_pitch, int *input_processed)
+{
+    const int P = d->num_poly_points;
+    if (const int rc = csdr_amd::fracdec_plan(c, d, input_size)) return rc;
     if (d->plan_outputs && n_streams > 0) {
         hipLaunchKernelGGL(k_fracdec, dim3(cdiv(d->plan_outputs, 256), n_streams), dim3(256), 0, c->stream, in, out, d->plan_outputs,
                            in_pitch, out_pitch, d->d_lo.get(), d->d_frac.get(), P, d->xifirst, d->d_denom.get(), d->d_taps.get(), d->taps_length);
         CSDR_LAUNCH_CHECK();
     }
-    d->input_processed = d->plan_processed;
-    d->where = d->plan_where_after;
+    csdr_amd::fracdec_commit(d);
     if (input_processed) *input_processed = d->input_processed;
     return d->plan_outputs;
 }

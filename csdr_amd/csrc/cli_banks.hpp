@@ -133,34 +133,44 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
 // demodulator, de-emphasis filter and AGC over (csdr_amd_fmrx_reset_channel).  The FM bank gives every channel the same number of samples per call; the
 // channelizer's per-channel counts are equal by construction (its residual-shift bookkeeping does not depend on the rate), which is checked for every batch.
 // One GPU only: with CSDR_AMD_WORLD set the command ends (fastddc_bank_cc is the one that shards a bank).
-int run_nfm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
+// The same loop with ONE csdr_amd_wfmrx behind the bank, for broadcast FM clients (`fmdemod_quadri_cf | fractional_decimator_ff <frac_rate> | deemphasis_wfm_ff
+// <audio_rate> <tau> | convert_f_s16`, the reference README's first receive line behind the channelizer):
+//   csdr fastddc_wfm_bank_s16 <decimation> <transition_bw> <window> <frac_rate> <audio_rate> <tau> <ctl | -> <out_0> <shift_rate_0> [<out_1> <shift_rate_1> ...]
+// with the same control lines; "<channel> reset\n" starts that channel's demodulator, held decimator input and de-emphasis over (csdr_amd_wfmrx_reset_channel).
+int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
 {
-    if (argc < 9 || (argc - 7) % 2) return badsyntax("usage: fastddc_nfm_bank_s16 <decimation> <transition_bw> <window> <audio_rate> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]");
+    const int a0 = wfm ? 8 : 6;                                        // argv index of the control channel; the <out_k> <rate_k> pairs follow it
+    if (argc < a0 + 3 || (argc - a0 - 1) % 2)
+        return badsyntax(wfm ? "usage: fastddc_wfm_bank_s16 <decimation> <transition_bw> <window> <frac_rate> <audio_rate> <tau> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]"
+                             : "usage: fastddc_nfm_bank_s16 <decimation> <transition_bw> <window> <audio_rate> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]");
     if (getenv("CSDR_AMD_WORLD")) return badsyntax("runs on one GPU only: CSDR_AMD_WORLD is set (fastddc_bank_cc is the command that shards a bank over several)");
-    int D = 0, audio_rate = 0; float tbw = 0.05f; sscanf(argv[2], "%d", &D); sscanf(argv[3], "%g", &tbw); sscanf(argv[5], "%d", &audio_rate);
+    int D = 0, audio_rate = 0; float tbw = 0.05f, frac_rate = 0, tau = 0; sscanf(argv[2], "%d", &D); sscanf(argv[3], "%g", &tbw); sscanf(argv[wfm ? 6 : 5], "%d", &audio_rate);
+    if (wfm && (sscanf(argv[5], "%g", &frac_rate) != 1 || sscanf(argv[7], "%g", &tau) != 1)) return badsyntax("frac_rate and tau must be numbers");
     const int window = window_from(argv[4]);
-    const int n_ch = (argc - 7) / 2;
+    const int n_ch = (argc - a0 - 1) / 2;
     Fds ctl_fd(1, -1); LineSplitter lines;
-    if (strcmp(argv[6], "-")) {
-        ctl_fd[0] = open_spec(argv[6], O_RDONLY | O_NONBLOCK);
+    if (strcmp(argv[a0], "-")) {
+        ctl_fd[0] = open_spec(argv[a0], O_RDONLY | O_NONBLOCK);
         if (ctl_fd[0] < 0) return badsyntax("cannot open the control channel");
         fcntl(ctl_fd[0], F_SETFL, fcntl(ctl_fd[0], F_GETFL, 0) | O_NONBLOCK);
     }
     std::vector<float> rates(n_ch);
-    for (int k = 0; k < n_ch; k++) if (sscanf(argv[8 + 2 * k], "%g", &rates[k]) != 1) return badsyntax("every rate must be a number");
+    for (int k = 0; k < n_ch; k++) if (sscanf(argv[a0 + 2 + 2 * k], "%g", &rates[k]) != 1) return badsyntax("every rate must be a number");
     csdr_fastddc_t ddc;
     if (csdr_amd_fastddc_init(&ddc, tbw, D, 0)) return badsyntax("error in fastddc_init()");
     int nb_max = (int)(block / ddc.input_size); if (nb_max < 1) nb_max = 1;
     Owned<csdr_amd_fastddc_bank, csdr_amd_fastddc_bank_destroy> bank(csdr_amd_fastddc_bank_create(c, tbw, D, rates.data(), n_ch, window, nb_max));
     if (!bank) die("fastddc_bank create");
     const size_t pitch = ((size_t)csdr_amd_fastddc_bank_max_output(bank.get(), nb_max) + 9) & ~(size_t)1;      // even: the FM bank's one-kernel path reads two samples a lane
-    Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> fm(csdr_amd_fmrx_create(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
-    if (!fm) return badsyntax(csdr_amd_last_error());
-    const size_t a_pitch = ((size_t)csdr_amd_fmrx_max_output(fm.get(), (long long)pitch) + 15) & ~(size_t)7;
+    Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> fm; Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> wf;
+    if (wfm) wf.reset(csdr_amd_wfmrx_create(c, n_ch, frac_rate, 12, nullptr, 0, 1024, tau, audio_rate, pitch));          // fractional_decimator_ff's defaults (csdr.c:1470-1472)
+    else fm.reset(csdr_amd_fmrx_create(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
+    if (!fm && !wf) return badsyntax(csdr_amd_last_error());
+    const size_t a_pitch = ((size_t)(wfm ? csdr_amd_wfmrx_max_output(wf.get(), (long long)pitch) : csdr_amd_fmrx_max_output(fm.get(), (long long)pitch)) + 15) & ~(size_t)7;
     Fds out_fd(n_ch, -1);
     for (int k = 0; k < n_ch; k++) {
-        out_fd[k] = open_spec(argv[7 + 2 * k], O_WRONLY | O_CREAT | O_TRUNC);
-        if (out_fd[k] < 0) { fprintf(stderr, "csdr %s: cannot open output %s\n", g_cmd, argv[7 + 2 * k]); return -1; }
+        out_fd[k] = open_spec(argv[a0 + 1 + 2 * k], O_WRONLY | O_CREAT | O_TRUNC);
+        if (out_fd[k] < 0) { fprintf(stderr, "csdr %s: cannot open output %s\n", g_cmd, argv[a0 + 1 + 2 * k]); return -1; }
     }
     const size_t in_elems = (size_t)nb_max * ddc.input_size;
     const auto h_in = pinned_alloc<csdr_complexf>(in_elems * 8);
@@ -180,7 +190,7 @@ int run_nfm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
                 if (sscanf(line, "%d %31s", &ch, what) != 2 || ch < 0 || ch >= n_ch) continue;
                 float rate = 0;
                 if (!strcmp(what, "reset")) {
-                    MUST(csdr_amd_fmrx_reset_channel(fm.get(), ch));
+                    MUST(wfm ? csdr_amd_wfmrx_reset_channel(wf.get(), ch) : csdr_amd_fmrx_reset_channel(fm.get(), ch));
                     fprintf(stderr, "csdr %s: channel %d reset\n", g_cmd, ch);
                 } else if (sscanf(what, "%g", &rate) == 1) {
                     MUST(csdr_amd_fastddc_bank_set_rate(bank.get(), ch, rate));
@@ -194,7 +204,8 @@ int run_nfm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
         MUST(csdr_amd_fastddc_bank_process(bank.get(), d_in.get(), nb, d_bb.get(), pitch, counts.data()));
         for (int k = 1; k < n_ch; k++)
             if (counts[k] != counts[0]) { fprintf(stderr, "csdr %s: the channelizer wrote %d samples for channel %d and %d for channel 0: the FM bank advances its channels in lockstep\n", g_cmd, counts[k], k, counts[0]); return -1; }
-        const long long na = csdr_amd_fmrx_process(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch);
+        const long long na = wfm ? csdr_amd_wfmrx_process(wf.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch)
+                                 : csdr_amd_fmrx_process(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch);
         MUST(na);
         if (na > 0) {
             MUST(csdr_amd_d2h(c, h_out.get(), d_out.get(), (size_t)n_ch * a_pitch * 2));

@@ -776,6 +776,31 @@ struct NfmRx : Stage {   // fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff <au
     }
 };
 
+struct WfmRxStage : Stage {   // fmdemod_quadri_cf | fractional_decimator_ff <rate> | deemphasis_wfm_ff <audio_rate> <tau> | convert_f_s16 as ONE command (extension): the stage behind
+                             // one fastddc_inv_cc, one channel of csdr_amd_wfmrx; the decimator's unprocessed samples and position, the previous sample and the de-emphasis
+                             // state stay in the object between passes.  What the four commands write at the default buffer size, without their stale blocks at EOF.
+    Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> p; size_t max_n;
+    WfmRxStage(csdr_amd_ctx *c, float rate, int points, const float *taps, int nt, float tau, int audio_rate, size_t block) : max_n(block + 1024)
+    {
+        in_elem = 8; out_elem = 2;
+        p.reset(csdr_amd_wfmrx_create(c, 1, rate, points, taps, nt, 1024, tau, audio_rate, max_n));
+        if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+    }
+    size_t out_capacity(size_t n) override { return n + 4096; }
+    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    {
+        *cons = n;
+        long total = 0;
+        for (size_t at = 0; at < n; at += max_n) {                     // (inside `chain` a pass may hand over more than the command's own block)
+            const size_t m = std::min(max_n, n - at);
+            const long long na = csdr_amd_wfmrx_process(p.get(), (const csdr_complexf *)i + at, 0, (long long)m, (int16_t *)o + total, nullptr, cap - total);
+            MUST(na);
+            total += (long)na;
+        }
+        return total;
+    }
+};
+
 struct DecimatingShift : Stage {   // csdr.c:851-875: one libcsdr call per the_bufsize samples, status carried between calls
     int dec, bufsize; float dsa[3]; void *d_dsa, *d_status;
     DecimatingShift(csdr_amd_ctx *c, float rate, int decimation, int the_bufsize) : dec(decimation), bufsize(the_bufsize)
@@ -1646,6 +1671,22 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         int rate = 48000;
         if (argc > 2 && sscanf(argv[2], "%d", &rate) != 1) { badsyntax("the audio rate must be a number"); return nullptr; }
         return new NfmRx(c, rate, block);
+    }
+    if (cmd == "wfm_rx_cc_s16") {                                       // <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]]
+        if (argc <= 2) { badsyntax("need required parameters (rate)   usage: wfm_rx_cc_s16 <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]]"); return nullptr; }
+        float rate = 0, tau = 50e-6f, tbw = 0.03f; int audio_rate = 48000, points = 12;
+        if (sscanf(argv[2], "%g", &rate) != 1) { badsyntax("the rate must be a number"); return nullptr; }
+        if (argc > 3 && sscanf(argv[3], "%d", &audio_rate) != 1) { badsyntax("the audio rate must be a number"); return nullptr; }
+        if (argc > 4 && sscanf(argv[4], "%g", &tau) != 1) { badsyntax("tau must be a number"); return nullptr; }
+        if (argc > 5 && sscanf(argv[5], "%d", &points) != 1) { badsyntax("num_poly_points must be a number"); return nullptr; }
+        std::vector<float> taps;
+        if (argc > 6) {
+            if (strcmp(argv[6], "--prefilter")) { badsyntax("the argument behind num_poly_points is --prefilter"); return nullptr; }
+            if (argc > 7 && (sscanf(argv[7], "%g", &tbw) != 1 || !(tbw > 0))) { badsyntax("transition_bw must be a positive number"); return nullptr; }
+            const int nt = csdr_amd_firdes_filter_len(tbw); taps.resize(nt);                        // csdr.c:1506-1509
+            csdr_amd_firdes_lowpass_f(taps.data(), nt, 0.5f / (rate - tbw), window_arg(argc, argv, 8, g_cmd));
+        }
+        return new WfmRxStage(c, rate, points, taps.empty() ? nullptr : taps.data(), (int)taps.size(), tau, audio_rate, block);
     }
     // the fused commands: `--fifo <path>` / `--fd <n>` stand where the shift rate stands, as in shift_addition_cc (csdr.c:881-893); the first rate is waited for
     if (cmd == "ddc_u8_cc" || cmd == "nfm_chain_u8_s16" || cmd == "wfm_chain_u8_s16") {

@@ -1289,6 +1289,46 @@ int  csdr_amd_fmrx_force_generic(csdr_amd_fmrx *o, int on);
 const char *csdr_amd_fmrx_kernel_name(const csdr_amd_fmrx *o);
 void csdr_amd_fmrx_destroy(csdr_amd_fmrx *o);
 
+/* ------------------------------------------------------------------ the WFM receive bank on baseband (wfmrx.hip)
+ *   fmdemod_quadri_cf | fractional_decimator_ff <rate> [num_poly_points] [--prefilter] | deemphasis_wfm_ff <audio_rate> <tau> | convert_f_s16
+ * for n_channels rows of decimated complex baseband on the device: the tail of the reference README's first receive line behind csdr_amd_fastddc_bank,
+ * csdr_amd_ddc_process or csdr_amd_fir_decimate_cc.  The stream model is the four commands' at the default buffer size.  Per channel: the demodulator starts
+ * from the sample (0, 0) and a zero denominator gives 0; the decimator is called on windows of `window` demodulated samples from the first unprocessed one
+ * (csdr.c:1513-1524), the unprocessed tail is presented again and `where` is carried; the de-emphasis is the reference's recurrence from state 0 (a NaN state
+ * restarts at 0); convert_f_s16 truncates.  The channels advance in lockstep: `where`, the count of held samples and the plan are the bank's; a channel has its
+ * previous sample, its held floats (at most window - 1) and its de-emphasis state.  A window is processed once `window` samples from the first unprocessed one are
+ * there, so a fresh object writes its first outputs in the call that completes sample number `window`.  What a call writes and keeps depends on
+ * (rate, num_poly_points, taps_length, window, where, held, n_in) only: csdr_amd_wfmrx_plan, a host function (window 0: 1024).  The audio has the same bits
+ * however the stream is cut into calls and on either kernel path.  Inputs are finite.
+ * create: NULL with a message "wfmrx: ..." when rate <= 1, num_poly_points is odd or outside 2 .. 64, n_channels < 1 (or > 65535), max_samples_per_call is not in
+ * 1 .. 2^30, tau <= 0, or the window and the rate do not fit: a window call advances by (ceilf(where) - 1) + xifirst samples, which is at least 1 and at most
+ * `window` when   window >= 3 * num_poly_points / 2 + taps_length + 1   and   ceil(rate) <= 3 * num_poly_points / 2 + taps_length + 1   (sufficient; both are
+ * checked, by plan as well).  host_prefilter_taps NULL: no prefilter (taps_length is not read).
+ * process: in (device) [n_channels][in_pitch complexf]; audio_s16 and audio_f (the float audio in front of convert_f_s16), both device, [n_channels][out_pitch],
+ * either may be NULL.  Returns the samples written per channel; -3 when n_in > max_samples_per_call, or when out_pitch is below that count with more than one
+ * channel (nothing has changed then).  n_in = 0 does nothing.  Asynchronous on the context's stream, except that a rate which is not exact in float uploads its
+ * positions synchronously, as csdr_amd_fractional_decimator_ff does.
+ * max_output: a bound on what a call of n_in samples writes whatever the object holds (max_out: the same, the name the other banks use).
+ * reset_channel: one channel's previous sample, held floats and de-emphasis state to zero, which is a fresh object's channel whose earlier input was all zeros;
+ * `where` and `held` are the bank's and stay, the other channels carry on.
+ * kernel_name: the path of the last call: "k_wfmrx_front" (no prefilter, num_poly_points <= 16, 16-byte aligned rows, even in_pitch: the rows
+ * are read, demodulated and interpolated in one kernel, k_wfmrx_tail de-emphasises and converts) or "k_fracdec" (the stand-alone entry points composed; every shape;
+ * force_generic(1)).  Both give the same bits, and a stream may change between them. */
+typedef struct csdr_amd_wfmrx csdr_amd_wfmrx;
+csdr_amd_wfmrx *csdr_amd_wfmrx_create(csdr_amd_ctx *ctx, int n_channels, float rate, int num_poly_points, const float *host_prefilter_taps, int taps_length, int window,
+                                      float tau, int audio_rate, size_t max_samples_per_call);
+long long csdr_amd_wfmrx_process(csdr_amd_wfmrx *o, const csdr_complexf *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *audio_f, size_t out_pitch);
+long long csdr_amd_wfmrx_max_output(const csdr_amd_wfmrx *o, long long n_in);
+long long csdr_amd_wfmrx_max_out(const csdr_amd_wfmrx *o, long long n_in);
+int  csdr_amd_wfmrx_plan(float rate, int num_poly_points, int taps_length, int window, float where, int held, long long n_in, long long *n_out, float *new_where, int *new_held);
+int  csdr_amd_wfmrx_held(const csdr_amd_wfmrx *o);
+float csdr_amd_wfmrx_where(const csdr_amd_wfmrx *o);
+int  csdr_amd_wfmrx_reset(csdr_amd_wfmrx *o);
+int  csdr_amd_wfmrx_reset_channel(csdr_amd_wfmrx *o, int channel);
+int  csdr_amd_wfmrx_force_generic(csdr_amd_wfmrx *o, int on);
+const char *csdr_amd_wfmrx_kernel_name(const csdr_amd_wfmrx *o);
+void csdr_amd_wfmrx_destroy(csdr_amd_wfmrx *o);
+
 /* ------------------------------------------------------------------ the AM and SSB receive chains (amssb.hip)
  * README.md:95   ... | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16
  * README.md:110  ... | bandpass_fir_fft_cc lo hi tbw | realpart_cf | agc_ff | limit_ff | convert_f_s16
