@@ -414,6 +414,13 @@ def lib():
     L.csdr_amd_fmrx_max_output.restype = ll; L.csdr_amd_fmrx_max_output.argtypes = [vp, ll]
     L.csdr_amd_fmrx_plan.argtypes = [i, ll, i, i, C.POINTER(ll), C.POINTER(i)]
     L.csdr_amd_fmrx_fill.argtypes = [vp]
+    L.csdr_amd_fmrx_create_squelched.restype = vp; L.csdr_amd_fmrx_create_squelched.argtypes = [vp, i, i, i, fl, fl, sz, i, i, vp]
+    L.csdr_amd_fmrx_process_squelched.restype = ll; L.csdr_amd_fmrx_process_squelched.argtypes = [vp, vp, sz, ll, vp, vp, sz, vp, sz, vp, C.POINTER(i)]
+    L.csdr_amd_fmrx_squelch_plan.argtypes = [i, ll, i, C.POINTER(ll), C.POINTER(i)]
+    L.csdr_amd_fmrx_set_squelch_level.argtypes = [vp, i, fl]
+    L.csdr_amd_fmrx_get_squelch_level.argtypes = [vp, i, C.POINTER(fl)]
+    L.csdr_amd_fmrx_squelch_held.argtypes = [vp]
+    L.csdr_amd_fmrx_squelch_block_index.restype = ll; L.csdr_amd_fmrx_squelch_block_index.argtypes = [vp]
     L.csdr_amd_wfmrx_create.restype = vp; L.csdr_amd_wfmrx_create.argtypes = [vp, i, fl, i, vp, i, i, fl, i, sz]
     L.csdr_amd_wfmrx_process.restype = ll; L.csdr_amd_wfmrx_process.argtypes = [vp, vp, sz, ll, vp, vp, sz]
     L.csdr_amd_wfmrx_max_output.restype = ll; L.csdr_amd_wfmrx_max_output.argtypes = [vp, ll]
@@ -1933,13 +1940,30 @@ def fmrx_plan(fill, n_in, taps_length, agc_block):
     return ne.value, nf.value
 
 
+def fmrx_squelch_plan(held, n_in, block):
+    """csdr_amd_fmrx_squelch_plan (a host function): a call of n_in samples on a squelched object that holds `held` -> (gated samples handed to the demodulator,
+    samples held afterwards)"""
+    m, nh = C.c_longlong(), C.c_int()
+    if lib().csdr_amd_fmrx_squelch_plan(int(held), int(n_in), int(block), C.byref(m), C.byref(nh)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return m.value, nh.value
+
+
 class FmRx(_Handle, _MaxOut, _PerChannel):
     """csdr_amd_fmrx: fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 for n_channels rows of complex baseband on the device;
-    the filter's unconsumed input, the previous sample and the AGC's two blocks stay in the object between calls."""
+    the filter's unconsumed input, the previous sample and the AGC's two blocks stay in the object between calls.  squelch_block > 0: squelch_and_smeter_cc
+    in blocks of squelch_block samples in front of every channel (csdr_amd_fmrx_create_squelched); levels: one level or n_channels (None: 0, always open)."""
 
-    def __init__(self, ctx, n_channels, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16):
-        self.n_channels, self.agc_block, self.taps_length = n_channels, agc_block, ctx.nfm_taps(audio_rate).size
-        _Handle.__init__(self, ctx, "fmrx", ctx.L.csdr_amd_fmrx_create(ctx.h, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call))
+    def __init__(self, ctx, n_channels, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16, squelch_block=0, use_every_nth=1,
+                 levels=None):
+        self.n_channels, self.agc_block, self.taps_length, self.squelch_block = n_channels, agc_block, ctx.nfm_taps(audio_rate).size, squelch_block
+        if squelch_block == 0 and use_every_nth == 1 and levels is None:
+            h = ctx.L.csdr_amd_fmrx_create(ctx.h, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call)
+        else:
+            lv = None if levels is None else np.ascontiguousarray(np.broadcast_to(np.asarray(levels, f32), (max(n_channels, 0),)))
+            h = ctx.L.csdr_amd_fmrx_create_squelched(ctx.h, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call, squelch_block, use_every_nth,
+                                                     None if lv is None else _hp(lv))
+        _Handle.__init__(self, ctx, "fmrx", h)
 
     def max_output(self, n_in):
         return int(self._fn("max_output")(self.h, int(n_in)))
@@ -1976,6 +2000,59 @@ class FmRx(_Handle, _MaxOut, _PerChannel):
         if with_float:
             return pcm, self.ctx.download(df, f32, op * s).reshape(s, op)[:, :got].copy(), got
         return pcm, got
+
+    # ---- the squelch in front (squelch_block > 0)
+    def set_squelch_level(self, ch, level):
+        """takes effect from the next block that starts; ch = -1: all channels"""
+        self._call("set_squelch_level", int(ch), float(level))
+
+    def get_squelch_level(self, ch):
+        v = C.c_float()
+        self._call("get_squelch_level", int(ch), C.byref(v))
+        return float(v.value)
+
+    def squelch_held(self):
+        """the samples per channel that wait for their squelch block to complete"""
+        return self._call("squelch_held")
+
+    def squelch_block_index(self):
+        """the squelch blocks completed since the reset"""
+        return int(self._call("squelch_block_index"))
+
+    def process_squelched_dev(self, d_in, in_pitch, n_in, d_s16, d_f, out_pitch, d_power=None, power_pitch=0, d_flags=None):
+        """device pointers (d_s16 / d_f / d_power / d_flags may be None), pitches in elements -> (audio samples written per channel, squelch blocks completed).
+        Asynchronous."""
+        nb = C.c_int()
+        got = self._call("process_squelched", d_in, in_pitch, n_in, d_s16, d_f, out_pitch, d_power, power_pitch, d_flags, C.byref(nb))
+        return got, nb.value
+
+    def process_squelched(self, x, with_float=False, in_pitch=None, out_pitch=None, in_offset=0, with_s16=True, power_pitch=None):
+        """One call, as process -> (s16 [n_channels, count], [float audio,] count, power [n_channels, blocks], flags [n_channels, blocks]): the powers and the open
+        flags of the squelch blocks the call completed."""
+        x = np.ascontiguousarray(x, c64)
+        if x.ndim == 1:
+            x = x[None]
+        s, n = x.shape
+        if s != self.n_channels:
+            raise ValueError("x has %d rows for %d channels" % (s, self.n_channels))
+        ip = max((n + 1) & ~1, 2) if in_pitch is None else int(in_pitch)
+        xin = np.zeros((s, ip), c64)
+        xin[:, :n] = x
+        raw = np.zeros(xin.nbytes + in_offset + 16, np.uint8)
+        raw[in_offset:in_offset + xin.nbytes] = xin.view(np.uint8).ravel()
+        di = self.ctx.upload(raw)
+        op = max(self.max_output(n), 1) if out_pitch is None else int(out_pitch)
+        pp = n // max(self.squelch_block, 1) + 1 if power_pitch is None else int(power_pitch)
+        ds = self.ctx.alloc(2 * op * s + 256) if with_s16 else None
+        df = self.ctx.alloc(4 * op * s + 256) if with_float else None
+        dp, dg = self.ctx.alloc(4 * pp * s + 256), self.ctx.alloc(pp * s + 256)
+        got, nb = self.process_squelched_dev(di.at(in_offset), ip, n, ds.ptr if ds else None, df.ptr if df else None, op, dp.ptr, pp, dg.ptr)
+        pcm = self.ctx.download(ds, np.int16, op * s).reshape(s, op)[:, :got].copy() if ds else None
+        power = self.ctx.download(dp, f32, pp * s).reshape(s, pp)[:, :nb].copy()
+        flags = self.ctx.download(dg, np.uint8, pp * s).reshape(s, pp)[:, :nb].copy()
+        if with_float:
+            return pcm, self.ctx.download(df, f32, op * s).reshape(s, op)[:, :got].copy(), got, power, flags
+        return pcm, got, power, flags
 
 
 def wfmrx_plan(rate, num_poly_points, taps_length, window, where, held, n_in):
@@ -2805,9 +2882,10 @@ class Context:
         return Squelch(self, n_channels, block_size, use_every_nth, levels, max_samples_per_call)
 
     # ---- the NFM receive bank on baseband (fmrx.hip)
-    def fm_rx(self, n_channels=1, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16):
-        """A batched fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 object on complex baseband (FmRx)"""
-        return FmRx(self, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call)
+    def fm_rx(self, n_channels=1, audio_rate=48000, agc_block=1024, reference=1.0, limit=1.0, max_samples_per_call=1 << 16, squelch_block=0, use_every_nth=1, levels=None):
+        """A batched fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 object on complex baseband (FmRx), behind a squelch when
+        squelch_block > 0"""
+        return FmRx(self, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call, squelch_block, use_every_nth, levels)
 
     # ---- the WFM receive bank on baseband (wfmrx.hip)
     def wfm_rx(self, n_channels=1, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16):

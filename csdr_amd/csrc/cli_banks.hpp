@@ -133,12 +133,27 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
 // demodulator, de-emphasis filter and AGC over (csdr_amd_fmrx_reset_channel).  The FM bank gives every channel the same number of samples per call; the
 // channelizer's per-channel counts are equal by construction (its residual-shift bookkeeping does not depend on the rate), which is checked for every batch.
 // One GPU only: with CSDR_AMD_WORLD set the command ends (fastddc_bank_cc is the one that shards a bank).
+//   csdr fastddc_nfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ...      (the rest as above)
+// puts squelch_and_smeter_cc (csdr.c:2192-2243) in front of every channel's demodulator, inside the bank object (csdr_amd_fmrx_create_squelched): blocks of <block>
+// decimated samples, every level 0 (open) at the start; a control line "<channel> squelch <level>\n" sets that channel's level from the next block that starts.
+// Every squelch block k with k mod (report_every_nth + 2) == report_every_nth + 1 writes one line "<channel> %g\n" per channel, its power, to <smeter_out>, which is
+// written non-blocking as the reference writes its --outfifo: a line that does not fit is dropped.
 // The same loop with ONE csdr_amd_wfmrx behind the bank, for broadcast FM clients (`fmdemod_quadri_cf | fractional_decimator_ff <frac_rate> | deemphasis_wfm_ff
 // <audio_rate> <tau> | convert_f_s16`, the reference README's first receive line behind the channelizer):
 //   csdr fastddc_wfm_bank_s16 <decimation> <transition_bw> <window> <frac_rate> <audio_rate> <tau> <ctl | -> <out_0> <shift_rate_0> [<out_1> <shift_rate_1> ...]
 // with the same control lines; "<channel> reset\n" starts that channel's demodulator, held decimator input and de-emphasis over (csdr_amd_wfmrx_reset_channel).
 int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
 {
+    int sqB = 0, sq_d = 1, sq_report = 0; const char *smeter_path = nullptr;
+    if (!wfm && argc > 2 && !strcmp(argv[2], "--squelch")) {
+        if (argc < 7 || sscanf(argv[3], "%d", &sqB) != 1 || sscanf(argv[4], "%d", &sq_d) != 1 || sscanf(argv[5], "%d", &sq_report) != 1)
+            return badsyntax("usage: fastddc_nfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ...");
+        if (sqB < 1) return badsyntax("the squelch block must be >= 1");
+        if (sq_d <= 0) return badsyntax("use_every_nth <= 0 is invalid");
+        if (sq_report <= 0) return badsyntax("report_every_nth <= 0 is invalid");
+        smeter_path = argv[6];
+        argv += 5; argc -= 5;                                          // argv[2] is <decimation> again
+    }
     const int a0 = wfm ? 8 : 6;                                        // argv index of the control channel; the <out_k> <rate_k> pairs follow it
     if (argc < a0 + 3 || (argc - a0 - 1) % 2)
         return badsyntax(wfm ? "usage: fastddc_wfm_bank_s16 <decimation> <transition_bw> <window> <frac_rate> <audio_rate> <tau> <ctl|-> <out_0> <rate_0> [<out_k> <rate_k> ...]"
@@ -164,8 +179,18 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
     const size_t pitch = ((size_t)csdr_amd_fastddc_bank_max_output(bank.get(), nb_max) + 9) & ~(size_t)1;      // even: the FM bank's one-kernel path reads two samples a lane
     Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> fm; Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> wf;
     if (wfm) wf.reset(csdr_amd_wfmrx_create(c, n_ch, frac_rate, 12, nullptr, 0, 1024, tau, audio_rate, pitch));          // fractional_decimator_ff's defaults (csdr.c:1470-1472)
+    else if (sqB) fm.reset(csdr_amd_fmrx_create_squelched(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch, sqB, sq_d, nullptr));
     else fm.reset(csdr_amd_fmrx_create(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
     if (!fm && !wf) return badsyntax(csdr_amd_last_error());
+    Fds smeter_fd(1, -1);
+    const size_t p_pitch = sqB ? pitch / (size_t)sqB + 1 : 0;           // the most squelch blocks of a call
+    CtxBuf<float> d_power; std::vector<float> h_power;
+    if (sqB) {
+        smeter_fd[0] = open_spec(smeter_path, O_WRONLY | O_CREAT | O_TRUNC);
+        if (smeter_fd[0] < 0) return badsyntax("cannot open the S-meter output");
+        fcntl(smeter_fd[0], F_SETFL, fcntl(smeter_fd[0], F_GETFL, 0) | O_NONBLOCK);
+        d_power = ctx_alloc<float>(c, (size_t)n_ch * p_pitch * 4 + 64); h_power.resize((size_t)n_ch * p_pitch);
+    }
     const size_t a_pitch = ((size_t)(wfm ? csdr_amd_wfmrx_max_output(wf.get(), (long long)pitch) : csdr_amd_fmrx_max_output(fm.get(), (long long)pitch)) + 15) & ~(size_t)7;
     Fds out_fd(n_ch, -1);
     for (int k = 0; k < n_ch; k++) {
@@ -188,8 +213,12 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
             while (lines.feed(ctl_fd[0])) while (const char *line = lines.next()) {
                 int ch = -1; char what[32] = "";
                 if (sscanf(line, "%d %31s", &ch, what) != 2 || ch < 0 || ch >= n_ch) continue;
-                float rate = 0;
-                if (!strcmp(what, "reset")) {
+                float rate = 0, level = 0;
+                if (sqB && !strcmp(what, "squelch")) {
+                    if (sscanf(line, "%d squelch %g", &ch, &level) != 2) continue;
+                    MUST(csdr_amd_fmrx_set_squelch_level(fm.get(), ch, level));
+                    fprintf(stderr, "csdr %s: channel %d squelch level is %g\n", g_cmd, ch, level);
+                } else if (!strcmp(what, "reset")) {
                     MUST(wfm ? csdr_amd_wfmrx_reset_channel(wf.get(), ch) : csdr_amd_fmrx_reset_channel(fm.get(), ch));
                     fprintf(stderr, "csdr %s: channel %d reset\n", g_cmd, ch);
                 } else if (sscanf(what, "%g", &rate) == 1) {
@@ -204,9 +233,22 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
         MUST(csdr_amd_fastddc_bank_process(bank.get(), d_in.get(), nb, d_bb.get(), pitch, counts.data()));
         for (int k = 1; k < n_ch; k++)
             if (counts[k] != counts[0]) { fprintf(stderr, "csdr %s: the channelizer wrote %d samples for channel %d and %d for channel 0: the FM bank advances its channels in lockstep\n", g_cmd, counts[k], k, counts[0]); return -1; }
+        const long long sq_k0 = sqB ? csdr_amd_fmrx_squelch_block_index(fm.get()) : 0;
+        int sq_nb = 0;
         const long long na = wfm ? csdr_amd_wfmrx_process(wf.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch)
+                           : sqB ? csdr_amd_fmrx_process_squelched(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch, d_power.get(), p_pitch, nullptr, &sq_nb)
                                  : csdr_amd_fmrx_process(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch);
         MUST(na);
+        bool sq_due = false;
+        for (int k = 0; k < sq_nb && !sq_due; k++) sq_due = csdr_amd_squelch_report_due(sq_report, sq_k0 + k) != 0;
+        if (sq_due) {
+            MUST(csdr_amd_d2h(c, h_power.data(), d_power.get(), (size_t)n_ch * p_pitch * 4));
+            for (int k = 0; k < sq_nb; k++) if (csdr_amd_squelch_report_due(sq_report, sq_k0 + k))
+                for (int ch = 0; ch < n_ch; ch++) {
+                    char line[128]; const int len = snprintf(line, sizeof line, "%d %g\n", ch, h_power[(size_t)ch * p_pitch + k]);
+                    (void)!write(smeter_fd[0], line, (size_t)len);       // non-blocking: a line that does not fit is dropped (csdr.c:2211-2228)
+                }
+        }
         if (na > 0) {
             MUST(csdr_amd_d2h(c, h_out.get(), d_out.get(), (size_t)n_ch * a_pitch * 2));
             for (int k = 0; k < n_ch; k++)

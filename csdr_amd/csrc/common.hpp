@@ -101,6 +101,9 @@ int fastagc_ff_s16(struct ::csdr_amd_ctx *c, const float *in, float *out, int16_
 float *fastagc_peaks_buffer(struct ::csdr_amd_ctx *c, int n_streams, int n_blocks);      // [n_streams][n_blocks + 2]; entries 2.. = peak |x| of the call's new blocks
 void set_audio_last_path(const char *path);                          // audio.hip: what csdr_amd_audio_last_path() reports for the calling thread
 void firdes_rrc_below(float *taps, int taps_length, int samples_per_symbol, float beta);   // modem.hip: firdes_rrc_f for any taps_length >= 1, writing indexes < taps_length only
+// squelch.hip, for csdr_amd_fmrx, which serves some calls of a stream itself: every channel of `s` takes the bank's held count, block index and levels
+// (lv, lv_started: n_channels each) -> the object's held samples [n_channels][block_size], which the caller may read and write between calls
+void *squelch_adopt(struct ::csdr_amd_squelch *s, int held, long long block_index, const float *lv, const float *lv_started);
 struct ShiftAhead;                                                   // shift.hip
 struct ShiftAheadDel { void operator()(ShiftAhead *a) const; };
 

@@ -62,18 +62,6 @@ template <int R> __global__ __launch_bounds__(256) void k_squelch_wave(SqArgs a)
     }
 }
 
-// the 512 chains of a workgroup (thread t: chains 2 t, 2 t + 1) -> P in every thread
-__device__ __forceinline__ float wg_tree(float (&acc)[2], float *sh)
-{
-    *reinterpret_cast<float2 *>(sh + 2 * threadIdx.x) = make_float2(acc[0], acc[1]);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    float t[4][2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const float2 u = *reinterpret_cast<const float2 *>(sh + 128 * k + 2 * lane); t[k][0] = u.x; t[k][1] = u.y; }
-    return squelch_wave_tree(t);
-}
-
 // one workgroup per block: thread t holds the samples 512 r + 2 t, + 1 of the rows r < R; same preconditions as k_squelch_wave
 template <int R> __global__ __launch_bounds__(256) void k_squelch_wg(SqArgs a)
 {
@@ -88,7 +76,7 @@ template <int R> __global__ __launch_bounds__(256) void k_squelch_wg(SqArgs a)
     const float fB = (float)a.B;
 #pragma unroll
     for (int r = 0; r < R; r++) { const int p = 256 * r + t; if (p < np) add_pair(acc, v[r], 2 * p, a.d, fB); }
-    const float P = wg_tree(acc, sh);
+    const float P = squelch_wg_tree(acc, sh);
     const bool open = squelch_open(P, a.lv[ch]);
     float4 *y = reinterpret_cast<float4 *>(a.out + (size_t)ch * a.out_pitch + (size_t)k * a.B);
 #pragma unroll
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(256) void k_squelch_generic(SqArgs a)
             const int s = s0 + e;
             if (s < a.B && s % a.d == 0) { const float2 u = V(p0 + s); acc[e] = acc[e] + squelch_term_c(u.x, u.y, fB); }
         }
-    const float P = wg_tree(acc, sh);
+    const float P = squelch_wg_tree(acc, sh);
     const bool open = squelch_open(P, a.lv[(k == 0 && rem > 0 ? a.n_ch : 0) + ch]);
     float2 *y = a.out + (size_t)ch * a.out_pitch + p0;
     for (int s = t; s < a.B; s += 256) y[s] = open ? V(p0 + s) : make_float2(0.f, 0.f);
@@ -163,7 +151,7 @@ template <bool CPLX> __global__ __launch_bounds__(256) void k_get_power(const fl
             const int s = s0 + e;
             if (s < B && s % d == 0) acc[e] = acc[e] + (CPLX ? squelch_term_c(x[2 * (size_t)s], x[2 * (size_t)s + 1], fB) : squelch_term_f(x[s], fB));
         }
-    const float P = wg_tree(acc, sh);
+    const float P = squelch_wg_tree(acc, sh);
     if (t == 0) out[(size_t)st * n_blocks + k] = P;
 }
 
@@ -191,6 +179,17 @@ struct csdr_amd_squelch : Bank {
     bool uniform;                    // every channel holds rem[0] samples: the kernels need no per-channel counts
     DevBuf<float2> d_carry; DevBuf<float> d_lv; DevBuf<int> d_rem;
 };
+
+// common.hpp: the bank's state as csdr_amd_fmrx keeps it, for the calls it hands to this object
+void *csdr_amd::squelch_adopt(csdr_amd_squelch *p, int held, long long block_index, const float *lv, const float *lv_started)
+{
+    const size_t bytes = sizeof(float) * p->n_ch;
+    if (memcmp(p->lv.data(), lv, bytes) || memcmp(p->lv_started.data(), lv_started, bytes)) {
+        p->lv.assign(lv, lv + p->n_ch); p->lv_started.assign(lv_started, lv_started + p->n_ch); p->lv_dirty = true;
+    }
+    p->rem.assign(p->n_ch, held); p->blk.assign(p->n_ch, block_index); p->uniform = true;
+    return p->d_carry.get();
+}
 
 extern "C" {
 

@@ -64,6 +64,17 @@ __device__ __forceinline__ float squelch_wave_tree(float (&a)[4][2])
     }
     return __shfl(a[0][0] + a[0][1], 0);                                                            // h = 1
 }
+// Device: the 512 chains of a workgroup of 256 (thread t: chains 2 t, 2 t + 1; sh: SQ_CHAINS floats of LDS) -> P in every thread
+__device__ __forceinline__ float squelch_wg_tree(float (&acc)[2], float *sh)
+{
+    *reinterpret_cast<float2 *>(sh + 2 * threadIdx.x) = make_float2(acc[0], acc[1]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    float t[4][2];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const float2 u = *reinterpret_cast<const float2 *>(sh + 128 * k + 2 * lane); t[k][0] = u.x; t[k][1] = u.y; }
+    return squelch_wave_tree(t);
+}
 #endif
 
 } // namespace csdr_amd
