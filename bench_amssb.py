@@ -11,6 +11,15 @@ sample-serial chain, and the line says how far from the HBM bound that leaves it
 `lanes_sweep_ms` times the channels-per-wave choices of the tiled kernel.  --verify compares sampled channels with the CPU run of the kernels' functions by bits.
 
     python bench_amssb.py [--gpus 1] [--steps K] [--warmup W] [--channels 4096] [--block 131072] [--agc-block 1024] [--verify] [--no-sweep]
+
+--squelch measures the squelch inside the object (csdr_amd_amssb_enable_squelch) instead: per closed fraction and pattern one JSON line with three legs per
+mode on the same buffers, alternating: the gated object on its tiled kernel, csdr_amd.Squelch into a second buffer followed by the unsquelched object, and the
+gated object on its one-lane kernel.  `--pattern channel` closes whole channels drawn at random, `--pattern block` closes (channel, block) pairs drawn at
+random; closed blocks are the signal scaled by 1e-4 under one level for all channels.  Without --closed-fraction / --pattern: 0, 0.5, 0.9 and 1 by channel and
+0.5 by block.  Every line counts the (workgroup, block) pairs whose channels were all closed, from the flags the object returned; --verify compares the s16 of
+sampled channels between the three legs in every bit.
+
+    python bench_amssb.py --squelch [--closed-fraction f] [--pattern channel|block] [--steps 7] [--verify]
 """
 import argparse
 import ctypes as C
@@ -46,6 +55,106 @@ def median(v):
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
+QUIET, SQ_LEVEL = 1e-4, 1e-5             # the loud blocks' power is at least about 1e-3, the scaled ones' at most about 1e-7
+SQ_LEGS = ("gated_tiled", "squelch_then_object", "gated_generic")
+
+
+def squelch_bench(args, ctx, x):
+    """--squelch: one JSON line per (pattern, closed fraction)"""
+    import numpy as np
+    import torch
+    import csdr_amd
+    S, N, B = args.channels, args.block, args.agc_block
+    nblk = N // B
+    configs = [("channel", f) for f in (0.0, 0.5, 0.9, 1.0)] + [("block", 0.5)]
+    if args.closed_fraction is not None or args.pattern is not None:
+        configs = [(args.pattern or "channel", 0.5 if args.closed_fraction is None else args.closed_fraction)]
+    P = {m: csdr_amd.amssb_params(m, B) for m in MODES}
+    lv = np.full(S, SQ_LEVEL, np.float32)
+    xq = torch.empty_like(x)                                                # the input of a configuration
+    gated = torch.empty_like(x)                                             # the composed path's second buffer
+    s16 = {leg: torch.empty((S, N), dtype=torch.int16, device="cuda") for leg in SQ_LEGS}
+    pw = torch.empty((S, nblk), dtype=torch.float32, device="cuda"); fl = torch.empty((S, nblk), dtype=torch.uint8, device="cuda")
+    objs = {}
+    for m in MODES:
+        objs[m, "gated_tiled"] = csdr_amd.AmSsb(ctx, P[m], S, max_samples_per_call=N, squelch=True, levels=lv)
+        objs[m, "gated_generic"] = csdr_amd.AmSsb(ctx, P[m], S, max_samples_per_call=N, squelch=True, levels=lv); objs[m, "gated_generic"].force_generic()
+        objs[m, "squelch_then_object"] = csdr_amd.AmSsb(ctx, P[m], S, max_samples_per_call=N)
+    sq = csdr_amd.Squelch(ctx, S, B, 1, lv, max_samples_per_call=N)
+    cnt = np.zeros(S, np.int32)
+
+    def prepare(m, leg):
+        objs[m, leg].reset()
+        if leg == "squelch_then_object":
+            sq.reset()
+
+    def step(m, leg):
+        if leg == "squelch_then_object":
+            sq.process_dev(xq.data_ptr(), N, N, gated.data_ptr(), N, pw.data_ptr(), nblk, fl.data_ptr(), cnt)
+            got = objs[m, leg].process_dev(gated.data_ptr(), N, N, s16[leg].data_ptr(), None, N)
+        else:
+            got, _ = objs[m, leg].process_squelched_dev(xq.data_ptr(), N, N, s16[leg].data_ptr(), None, N, pw.data_ptr(), nblk, fl.data_ptr())
+        assert got == N
+
+    calls = [(m, leg) for m in MODES for leg in SQ_LEGS]
+    sampled = sorted(set(k for k in (0, 1, 37, 63, S // 2, S - 2, S - 1) if 0 <= k < S))
+    for pattern, frac in configs:
+        rng = np.random.default_rng(int(1000 * frac) + (7 if pattern == "block" else 0))
+        if pattern == "channel":
+            closed = np.zeros((S, nblk), bool); closed[rng.permutation(S)[:int(round(frac * S))]] = True
+        else:
+            closed = rng.random((S, nblk)) < frac
+        scale = torch.from_numpy(np.where(closed, QUIET, 1.0).astype(np.float32)).cuda()
+        torch.mul(x.view(S, nblk, 2 * B), scale[:, :, None], out=xq.view(S, nblk, 2 * B))
+        torch.cuda.synchronize()
+        ver, groups = {}, {}
+        for m in MODES:
+            for leg in SQ_LEGS:
+                prepare(m, leg); step(m, leg); ctx.sync(); torch.cuda.synchronize()
+                if leg == "gated_tiled":
+                    flags = fl.cpu().numpy()
+                    assert np.array_equal(flags == 0, closed), "the flags are not the configuration's"
+                    C_ = objs[m, leg].lanes()
+                    pad = (-S) % C_
+                    allc = np.concatenate([flags == 0, np.ones((pad, nblk), bool)]).reshape(-1, C_, nblk).all(axis=1)
+                    groups[m] = {"channels_per_workgroup": C_, "workgroup_blocks": int(allc.size), "all_closed": int(allc.sum()),
+                                 "all_closed_fraction": round(float(allc.mean()), 4)}
+            if args.verify:
+                rows = {leg: s16[leg][sampled].cpu().numpy() for leg in SQ_LEGS}
+                ver[m] = {"gated_tiled_vs_composed_words_differing": int(np.count_nonzero(rows["gated_tiled"] != rows["squelch_then_object"])),
+                          "gated_generic_vs_composed_words_differing": int(np.count_nonzero(rows["gated_generic"] != rows["squelch_then_object"]))}
+                ver[m]["ok"] = not any(ver[m].values())
+        for _ in range(args.warmup):
+            for m, leg in calls:
+                prepare(m, leg); step(m, leg)
+        ctx.sync(); torch.cuda.synchronize()
+        times = {c: [] for c in calls}
+        for _ in range(args.steps):
+            for m, leg in calls:
+                prepare(m, leg)
+                ctx.timer_start(); step(m, leg); times[m, leg].append(ctx.timer_stop_ms())
+        shapes = {}
+        for m in MODES:
+            shapes[m] = {"kernel": objs[m, "gated_tiled"].kernel_name(), "generic_kernel": objs[m, "gated_generic"].kernel_name(), "workgroups": groups[m]}
+            for leg in SQ_LEGS:
+                shapes[m][leg] = {"ms": round(median(times[m, leg]), 3), "min_ms": round(min(times[m, leg]), 3), "max_ms": round(max(times[m, leg]), 3)}
+            shapes[m]["composed_over_gated"] = round(shapes[m]["squelch_then_object"]["ms"] / shapes[m]["gated_tiled"]["ms"], 2)
+        t = shapes["am"]["gated_tiled"]["ms"]
+        res = {"metric": "MS/s, squelch_and_smeter_cc | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16 x N channels", "value": round(S * N / t / 1e3, 1),
+               "unit": "MS/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "event_ms_per_step": t, "higher_is_better": True, "dtype": "f32",
+               "data": "generated", "library": os.environ.get("CSDR_AMD_LIB") or "this tree",
+               "config": {"workload": "AM and SSB audio tails behind a squelch, batched, CF32 input", "channels": S, "block_samples_per_channel": N, "agc_block": B,
+                          "pattern": pattern, "closed_fraction": frac, "closed_fraction_drawn": round(float(closed.mean()), 4), "use_every_nth": 1},
+               "timer": "HIP events around every leg's calls (the reset in front is not timed), medians over interleaved repeats of the three legs in both modes",
+               "shapes": shapes}
+        if args.verify:
+            ver["sampled_channels"] = sampled; ver["samples_per_channel"] = N; ver["ok"] = bool(all(ver[m]["ok"] for m in MODES))
+            res["verify"] = ver
+        print(json.dumps(res), flush=True)
+    for o in list(objs.values()) + [sq]:
+        o.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -56,6 +165,9 @@ def main():
     ap.add_argument("--agc-block", type=int, default=1024)
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--squelch", action="store_true")
+    ap.add_argument("--closed-fraction", type=float, default=None)
+    ap.add_argument("--pattern", choices=("channel", "block"), default=None)
     args = ap.parse_args()
     if args.gpus != 1:
         raise SystemExit("bench_amssb.py measures one GPU (--gpus 1)")
@@ -72,6 +184,10 @@ def main():
     n_sig = min(64, S)
     X = signals(n_sig, N)
     x = torch.from_numpy(X.view(np.float32)).cuda().repeat((S + n_sig - 1) // n_sig, 1)[:S].contiguous()      # [S, 2 N] floats
+    if args.squelch:
+        squelch_bench(args, ctx, x)
+        ctx.close()
+        return
     s16 = torch.empty((S, N), dtype=torch.int16, device="cuda")
     fa = torch.empty((S, N), dtype=torch.float32, device="cuda")           # the composed path's intermediates
     fb = torch.empty((S, N), dtype=torch.float32, device="cuda")

@@ -237,6 +237,13 @@ def lib():
         L.csdr_amd_amssb_set_passband.argtypes = [vp, i, fl, fl, i]
         L.csdr_amd_amssb_set_channel_taps.argtypes = [vp, i, vp, i]
         L.csdr_amd_amssb_get_passband.argtypes = [vp, i, vp, vp]
+    if hasattr(L, "csdr_amd_amssb_enable_squelch"):
+        L.csdr_amd_amssb_enable_squelch.argtypes = [vp, i, vp]
+        L.csdr_amd_amssb_process_squelched.restype = ll; L.csdr_amd_amssb_process_squelched.argtypes = [vp, vp, sz, ll, vp, vp, sz, vp, sz, vp, C.POINTER(i)]
+        L.csdr_amd_amssb_set_squelch_level.argtypes = [vp, i, fl]
+        L.csdr_amd_amssb_get_squelch_level.argtypes = [vp, i, C.POINTER(fl)]
+        L.csdr_amd_amssb_squelch_block_index.restype = ll; L.csdr_amd_amssb_squelch_block_index.argtypes = [vp]
+        L.csdr_amd_debug_amssb_zero_run.restype = fl; L.csdr_amd_debug_amssb_zero_run.argtypes = [vp, fl, ll, C.POINTER(ll)]
     L.csdr_amd_debug_amssb_walk.restype = ll; L.csdr_amd_debug_amssb_walk.argtypes = [vp, vp, i, vp, vp, vp]
     L.csdr_amd_fmmod_fc.argtypes = [vp, vp, vp, i, sz, sz, sz, vp]
     L.csdr_amd_dsb_fc.argtypes = [vp, vp, vp, sz, fl]
@@ -1824,6 +1831,15 @@ def amssb_debug_walk(params, x, state=None):
     return s16, pre
 
 
+def amssb_zero_run(params, gain, n):
+    """csdr_amd_debug_amssb_zero_run: agc_ff's gain behind n zero samples as the kernels take it -> (gain as float32, the steps taken one by one)"""
+    it = C.c_longlong()
+    g = lib().csdr_amd_debug_amssb_zero_run(C.byref(params), float(gain), int(n), C.byref(it))
+    if n < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return f32(g), it.value
+
+
 def _passband_list(passbands, n_channels):
     """[(low, high)] * n_channels as floats; ValueError on any other shape (before a device is touched)"""
     pb = np.asarray(passbands, np.float64)
@@ -1834,11 +1850,13 @@ def _passband_list(passbands, n_channels):
 
 class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
     """csdr_amd_amssb: the AM / SSB receive chain's demodulator and audio tail for n_channels channels; input "cf32" (decimated complex baseband) or "u8"
-    (wideband u8 IQ through an owned front end: shift_rate one float or one per channel, decimation, ddc_taps); taps / fft_size: SSB's band-pass filter."""
+    (wideband u8 IQ through an owned front end: shift_rate one float or one per channel, decimation, ddc_taps); taps / fft_size: SSB's band-pass filter.
+    squelch=True: squelch_and_smeter_cc at the tail's input in blocks of params.block (csdr_amd_amssb_enable_squelch); levels: one level or n_channels (None: 0,
+    always open)."""
     _chan = AmSsbChan
 
     def __init__(self, ctx, params, n_channels=1, in_format="cf32", taps=None, fft_size=0, max_samples_per_call=1 << 20, shift_rate=0.0, decimation=50,
-                 ddc_taps=None, passbands=None, window=WINDOWS["HAMMING"]):
+                 ddc_taps=None, passbands=None, window=WINDOWS["HAMMING"], squelch=False, use_every_nth=1, levels=None):
         """passbands: [(low, high), ...], one pair per channel, set (set_passband) on the fresh object; taps still give the length and the channels' start"""
         if passbands is not None:
             passbands = _passband_list(passbands, n_channels)
@@ -1859,6 +1877,10 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
         _Handle.__init__(self, ctx, "amssb", h)
         for ch, (lo, hi) in enumerate(passbands or []):
             self.set_passband(ch, lo, hi, window)
+        self.squelch = bool(squelch)
+        if squelch:
+            lv = None if levels is None else np.ascontiguousarray(np.broadcast_to(np.asarray(levels, f32), (n_channels,)))
+            self._call("enable_squelch", int(use_every_nth), None if lv is None else _hp(lv))
 
     def set_passband(self, ch, low, high, window=WINDOWS["HAMMING"]):
         """channel ch's filter becomes firdes_bandpass_c(low, high) at the object's taps length, from the first sample the filter has not consumed yet"""
@@ -1889,7 +1911,33 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
         """device pointers (d_pre may be None) -> the audio samples written per channel.  Asynchronous."""
         return self._call("process", d_in, in_pitch, n_in, d_s16, d_pre, out_pitch)
 
-    def process(self, x, calls=None, with_pre=True, in_pitch=None, out_pitch=None, in_offset=0, retunes=None):
+    # ---- the gate at the tail's input (squelch=True)
+    def set_squelch_level(self, ch, level):
+        """takes effect from the next block that starts; ch = -1: all channels"""
+        self._call("set_squelch_level", int(ch), float(level))
+
+    def get_squelch_level(self, ch):
+        v = C.c_float()
+        self._call("get_squelch_level", int(ch), C.byref(v))
+        return float(v.value)
+
+    def squelch_block_index(self):
+        """the blocks completed since the reset"""
+        return int(self._call("squelch_block_index"))
+
+    def process_squelched_dev(self, d_in, in_pitch, n_in, d_s16, d_pre, out_pitch, d_power=None, power_pitch=0, d_flags=None):
+        """device pointers (d_pre / d_power / d_flags may be None) -> (audio samples written per channel, blocks completed).  Asynchronous."""
+        nb = C.c_int()
+        got = self._call("process_squelched", d_in, in_pitch, n_in, d_s16, d_pre, out_pitch, d_power, power_pitch, d_flags, C.byref(nb))
+        return got, nb.value
+
+    def process_squelched(self, x, calls=None, with_pre=True, in_pitch=None, out_pitch=None, in_offset=0, retunes=None, levels_between=None, generic_calls=None):
+        """process on an object with a squelch; levels_between: {call index: [(channel, level), ...]} applied in front of that call; generic_calls: the call
+        indices that run under force_generic(True) (None: the object's setting stays) -> (s16, pre_agc or None, counts, power [n_channels, blocks],
+        flags [n_channels, blocks], the kernel names of the calls that wrote blocks)"""
+        return self.process(x, calls, with_pre, in_pitch, out_pitch, in_offset, retunes, levels_between, generic_calls, True)
+
+    def process(self, x, calls=None, with_pre=True, in_pitch=None, out_pitch=None, in_offset=0, retunes=None, levels_between=None, generic_calls=None, _squelched=False):
         """x: [n_channels, n] complex samples (or [n_channels, 2n] u8 IQ bytes); calls: per-call sample counts (default one call); in_pitch: row pitch in
         samples (bytes for u8); out_pitch in samples; in_offset: bytes by which the input's base is moved off its allocation; retunes: {call index:
         [(channel, rate) or (channel, "bp", low, high) or (channel, "taps", taps), ...]} -> (s16 [n_channels, na], pre_agc [n_channels, na] or None, the counts of the calls)"""
@@ -1911,15 +1959,31 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
         op = max(self.max_out(max(calls) if calls else 0), 1) if out_pitch is None else int(out_pitch)
         ds = self.ctx.alloc(2 * op * s + 256); dp = self.ctx.alloc(4 * op * s + 256) if with_pre else None
         outs, pres, counts = [], [], []
+        pws, fls, names = [], [], []
+        if _squelched:
+            pp = op // self.params.block + 1
+            dw, dg = self.ctx.alloc(4 * pp * s + 256), self.ctx.alloc(pp * s + 256)
         at = 0
         for ci, k in enumerate(calls):
             self.ctx.check(self.ctx.L.csdr_amd_memset(self.ctx.h, ds.ptr, 0x55, 2 * op * s + 256), "memset")      # (what a call leaves alone is checked below)
+            for ch, lv in (levels_between or {}).get(ci, []):
+                self.set_squelch_level(ch, lv)
+            if generic_calls is not None:
+                self.force_generic(ci in generic_calls)
             for ch, r, *more in (retunes or {}).get(ci, []):
                 if isinstance(r, str):
                     self.set_passband(ch, *more) if r == "bp" else self.set_channel_taps(ch, *more)
                 else:
                     self.set_rate(ch, r)
-            got = self.process_dev(di.at(in_offset + (2 if u8 else 8) * at), ip, k, ds.ptr, dp.ptr if with_pre else None, op)
+            if _squelched:
+                got, nb = self.process_squelched_dev(di.at(in_offset + (2 if u8 else 8) * at), ip, k, ds.ptr, dp.ptr if with_pre else None, op, dw.ptr, pp, dg.ptr)
+                assert nb * self.params.block == got
+                pws.append(self.ctx.download(dw, f32, pp * s).reshape(s, pp)[:, :nb].copy())
+                fls.append(self.ctx.download(dg, np.uint8, pp * s).reshape(s, pp)[:, :nb].copy())
+                if nb:
+                    names.append(self.kernel_name())
+            else:
+                got = self.process_dev(di.at(in_offset + (2 if u8 else 8) * at), ip, k, ds.ptr, dp.ptr if with_pre else None, op)
             counts.append(got)
             y = self.ctx.download(ds, np.int16, op * s).reshape(s, op)
             if np.any(y[:, got:] != 0x5555):
@@ -1929,6 +1993,8 @@ class AmSsb(_Handle, _MaxOut, _ChannelState, _Lanes):
                 pres.append(self.ctx.download(dp, f32, op * s).reshape(s, op)[:, :got].copy())
             at += k
         cat = lambda parts, dt: np.concatenate(parts, axis=1) if parts else np.zeros((s, 0), dt)
+        if _squelched:
+            return cat(outs, np.int16), (cat(pres, f32) if with_pre else None), counts, cat(pws, f32), cat(fls, np.uint8), names
         return cat(outs, np.int16), (cat(pres, f32) if with_pre else None), counts
 
 
@@ -2894,7 +2960,7 @@ class Context:
 
     # ---- the AM and SSB receive chains (amssb.hip)
     def am_bank(self, n_channels=1, block=1024, agc=None, limit_max=None, **kw):
-        """csdr_amd_amssb in AM mode (README.md:95's amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16); kw: AmSsb's in_format, max_samples_per_call
+        """csdr_amd_amssb in AM mode (README.md:95's amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16); kw: AmSsb's squelch, use_every_nth, levels, in_format, max_samples_per_call
         and, for "u8", shift_rate, decimation, ddc_taps"""
         return AmSsb(self, amssb_params("am", block, agc, limit_max), n_channels, **kw)
 

@@ -16,6 +16,7 @@
 // Both run amssb_dev.hpp's functions on the same samples in the same order: the same bits, for every C, every cut into calls and every pitch, as the CPU hook.
 #include "bank.hpp"
 #include "amssb_dev.hpp"
+#include "squelch_dev.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -35,6 +36,9 @@ struct AmSsbArgs {
     int n_blocks;
     int16_t *s16; float *pre; size_t out_pitch;
 };
+// the gate at the tail's input (csdr_amd_amssb_enable_squelch): flags[ch][blk] is 0 where block blk of the call is closed.  Read by the <.., true> instances only
+// zeros: one tile of (0, 0) samples, what the tiled kernel reads in a closed channel's place
+struct AmSsbSq { const uint8_t *flags; size_t fl_pitch; const float2 *zeros; };
 
 __device__ __forceinline__ float2 sample_any(const AmSsbArgs &a, int ch, long long v)      // float by float: any alignment
 {
@@ -42,7 +46,9 @@ __device__ __forceinline__ float2 sample_any(const AmSsbArgs &a, int ch, long lo
     return make_float2(p[0], p[1]);
 }
 
-template <int MODE> __global__ __launch_bounds__(64) void k_amssb_generic(AmSsbArgs a)
+// SQ: a closed block's samples are (0, 0).  Its envelope and mean are +0, so it is walked on the ramp from last_dc to 0 without a load; once last_dc is +-0
+// (SSB: at once) every pre-AGC sample is +0, every s16 is 0 and the walk is amssb_agc_zero_run: a zero block
+template <int MODE, bool SQ> __global__ __launch_bounds__(64) void k_amssb_generic(AmSsbArgs a, AmSsbSq q)
 {
     if ((int)threadIdx.x >= a.lanes) return;
     const int ch = blockIdx.x * a.lanes + threadIdx.x;
@@ -51,13 +57,20 @@ template <int MODE> __global__ __launch_bounds__(64) void k_amssb_generic(AmSsbA
     const int B = a.cfg.block;
     for (int blk = 0; blk < a.n_blocks; blk++) {
         const long long base = (long long)blk * B;
+        const size_t o = (size_t)ch * a.out_pitch + base;
+        const bool open = !SQ || q.flags[(size_t)ch * q.fl_pitch + blk];
+        if (SQ && !open && (MODE == AMSSB_SSB || s.last_dc == 0.f)) {
+            for (int i = 0; i < B; i++) { a.s16[o + i] = 0; if (a.pre) a.pre[o + i] = 0.f; }
+            s.last_gain = amssb_agc_zero_run(a.cfg, s.last_gain, B - 1);
+            if (MODE == AMSSB_AM) s.last_dc = 0.f;
+            continue;
+        }
         float avg = 0.f;
-        if (MODE == AMSSB_AM)
+        if (MODE == AMSSB_AM && open)
             avg = amssb_block_mean(amssb_block_sum(B, [&](int i) { const float2 v = sample_any(a, ch, base + i); return amssb_envelope(v.x, v.y); }), B);
         AgcCall g;
-        const size_t o = (size_t)ch * a.out_pitch + base;
         for (int i = 0; i < B; i++) {
-            const float2 v = sample_any(a, ch, base + i);
+            const float2 v = open ? sample_any(a, ch, base + i) : make_float2(0.f, 0.f);
             const float x = MODE == AMSSB_AM ? amssb_dc_ramp(amssb_envelope(v.x, v.y), s.last_dc, avg, i, B) : v.x;
             const float gn = i == 0 ? agc_call_begin(a.cfg, g, s.last_gain) : agc_call_step(a.cfg, g, x, amssb_agc_ratio(a.cfg, x));
             a.s16[o + i] = amssb_finish(a.cfg, gn, x);
@@ -75,7 +88,12 @@ constexpr int ACMAX = 64;                                // channels per workgro
 constexpr size_t tiled_lds(int C) { return (size_t)C * ATP * 2 * sizeof(float); }      // at most 33 280 bytes
 
 // block % 64 == 0, 8-byte aligned input rows
-template <int MODE> __global__ __launch_bounds__(64) void k_amssb_tiled(AmSsbArgs a, int C)
+// SQ: per block, bit cc of `open` is channel cc's flag, the same in every lane.  A closed channel is never loaded: its tile is (0, 0) in registers and its mean
+// +0, and beside open channels it goes through the stages below like them (the lanes of a wave walk in lockstep: a lane that stood still would save nothing,
+// and a zero run beside the walk would add to it).  A workgroup whose channels are all in zero blocks (k_amssb_generic) skips the mean pass, the tile loop and
+// its barriers: the rows are stored as zeros and every lane takes the zero run.  The flags of the next block are fetched a block ahead, so that the prefetch
+// across the block seam knows them.
+template <int MODE, bool SQ> __global__ __launch_bounds__(64) void k_amssb_tiled(AmSsbArgs a, int C, AmSsbSq q)
 {
     extern __shared__ float lds_f[];
     float *xr = lds_f, *rr = lds_f + (size_t)C * ATP;    // the pre-AGC samples; reference / |x|, then the gains
@@ -88,43 +106,82 @@ template <int MODE> __global__ __launch_bounds__(64) void k_amssb_tiled(AmSsbArg
     auto sample = [&](int cc, long long v) {
         return v < a.fill ? carry[(size_t)(ch0 + cc) * B + v] : in[(size_t)(ch0 + cc) * a.in_pitch + (v - a.fill)];
     };
+    auto sample_at = [&](int cc, long long v) {
+        return v < a.fill ? carry + (size_t)(ch0 + cc) * B + v : in + (size_t)(ch0 + cc) * a.in_pitch + (v - a.fill);
+    };
     AmSsbChan s{0.f, 1.f};
     if (chain) s = a.st[ch0 + lane];
     const int me = lane * ATP;
     float my_avg = 0.f;
     AgcCall g{0.f, 0.f, 0.f, 0, 0};
 
+    typedef unsigned long long mask_t;
+    const mask_t live = nc >= 64 ? ~(mask_t)0 : (((mask_t)1 << nc) - 1);
+    mask_t open = live, open_next = live;
+    const bool wide16 = !(((uintptr_t)a.s16 | (a.out_pitch * 2)) & 15), wide32 = !(((uintptr_t)a.pre | (a.out_pitch * 4)) & 15);
+    auto flags_of = [&](int blk) {
+        bool f = false;
+        if (chain && blk < a.n_blocks) f = q.flags[(size_t)(ch0 + lane) * q.fl_pitch + blk] != 0;
+        return (mask_t)__ballot(f);
+    };
+    if (SQ) open_next = flags_of(0);
+
     float2 nx[ACMAX];                                    // the next tile, loaded while the chain lanes walk this one
-    auto fetch = [&](long long b) {
+    auto fetch = [&](long long b, mask_t m) {
 #pragma unroll
         for (int cc = 0; cc < ACMAX; cc++)
-            if (cc < nc) nx[cc] = sample(cc, b + lane);  // (whole tiles only: b + lane < total)
+            if (cc < nc) {                               // (whole tiles only: b + lane < total)
+                if (!SQ) nx[cc] = sample(cc, b + lane);
+                else nx[cc] = *(((m >> cc) & 1) ? sample_at(cc, b + lane) : q.zeros + lane);      // a closed channel: the zero tile, from cache, never its rows
+            }
     };
-    fetch(0);
-    for (long long base = 0; base < total; base += B) {
-        if (MODE == AMSSB_AM) {                          // 0. the block's mean per channel: lane l sums the samples l, l + 64, ..., then the tree
+    fetch(0, open_next);
+    int blk = 0;
+    for (long long base = 0; base < total; base += B, blk++) {
+        bool skip = false;
+        if (SQ) {
+            open = open_next; open_next = flags_of(blk + 1);
+            // every channel of the workgroup in a zero block: no tile, no barrier; the rows as 16-byte stores where they are aligned so (B is a multiple of 64)
+            skip = open == 0 && (mask_t)__ballot(chain && (MODE == AMSSB_SSB || s.last_dc == 0.f)) == live;
+            if (skip) {
+                for (int cc = 0; cc < nc; cc++) {
+                    const size_t o = (size_t)(ch0 + cc) * a.out_pitch + base;
+                    if (wide16) for (int i = lane; i < B / 8; i += AT) reinterpret_cast<int4 *>(a.s16 + o)[i] = make_int4(0, 0, 0, 0);
+                    else for (int i = lane; i < B; i += AT) a.s16[o + i] = 0;
+                    if (a.pre) {
+                        if (wide32) for (int i = lane; i < B / 4; i += AT) reinterpret_cast<float4 *>(a.pre + o)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        else for (int i = lane; i < B; i += AT) a.pre[o + i] = 0.f;
+                    }
+                }
+            }
+        }
+        if (MODE == AMSSB_AM && !(SQ && skip)) {                         // 0. the block's mean per channel: lane l sums the samples l, l + 64, ..., then the tree
             for (int cc = 0; cc < nc; cc++) {
-                float p = 0.f;
+                float avg = 0.f;                         // (a closed block's mean: +0 / B)
+                if (!SQ || ((open >> cc) & 1)) {
+                    float p = 0.f;
 #pragma unroll 4
-                for (int i = lane; i < B; i += AT) { const float2 v = sample(cc, base + i); p = p + amssb_envelope(v.x, v.y); }
+                    for (int i = lane; i < B; i += AT) { const float2 v = sample(cc, base + i); p = p + amssb_envelope(v.x, v.y); }
 #pragma unroll
-                for (int w = 32; w > 0; w >>= 1) p = p + __shfl_down(p, w);
-                const float avg = amssb_block_mean(__shfl(p, 0), B);
+                    for (int w = 32; w > 0; w >>= 1) p = p + __shfl_down(p, w);
+                    avg = amssb_block_mean(__shfl(p, 0), B);
+                }
                 if (lane == cc) my_avg = avg;
             }
         }
-        for (int t0 = 0; t0 < B; t0 += AT) {
+        for (int t0 = SQ && skip ? B - AT : 0; t0 < B; t0 += AT) {          // (a skipped block: the fetch across its end only)
 #pragma unroll
             for (int cc = 0; cc < ACMAX; cc++) {         // 1. stage: lane j holds sample t0 + j of channel cc's block
-                if (cc < nc) {
+                if (cc < nc && !(SQ && skip)) {
                     float x = nx[cc].x;
                     if (MODE == AMSSB_AM) x = amssb_dc_ramp(amssb_envelope(nx[cc].x, nx[cc].y), __shfl(s.last_dc, cc), __shfl(my_avg, cc), t0 + lane, B);
                     xr[cc * ATP + lane] = x;
                     rr[cc * ATP + lane] = amssb_agc_ratio(a.cfg, x);
                 }
             }
-            __syncthreads();
-            if (base + t0 + AT < total) fetch(base + t0 + AT);
+            if (!(SQ && skip)) __syncthreads();
+            if (base + t0 + AT < total) fetch(base + t0 + AT, t0 + AT < B ? open : open_next);
+            if (SQ && skip) break;
             if (chain) {                                 // 2. lane c walks channel c
                 for (int j0 = 0; j0 < AT; j0 += 8) {
                     float xv[8], rv[8];                  // 8 samples to registers first: the LDS latency stays off the chain
@@ -148,10 +205,55 @@ template <int MODE> __global__ __launch_bounds__(64) void k_amssb_tiled(AmSsbArg
             }
             __syncthreads();                             // (the rows are free for the next tile)
         }
-        s.last_gain = g.gain;
-        if (MODE == AMSSB_AM) s.last_dc = my_avg;
+        if (SQ && skip) {
+            s.last_gain = amssb_agc_zero_run(a.cfg, s.last_gain, B - 1);
+            if (MODE == AMSSB_AM) s.last_dc = 0.f;
+        } else {
+            s.last_gain = g.gain;
+            if (MODE == AMSSB_AM) s.last_dc = my_avg;
+        }
     }
     if (chain) a.st[ch0 + lane] = s;
+}
+
+// The power pass of a gated call: grid (ceil(n_blocks n_ch / 4)), 256 threads, one wave per (channel, block) over (carry ++ call) in squelch_dev.hpp's order: lane l
+// takes the samples 128 r + 2 l, + 1 of the block's rows r of 128, chains 128 (r mod 4) + 2 l, + 1, each added to in increasing sample order.  -> the power
+// and the open flag, to the object's rows (pitch fl_pitch) and to the caller's where given.  lv: n_ch levels of the blocks this call starts, then n_ch of the
+// block begun earlier.  A8: 8-byte aligned input rows, a sample is one load (fmrx.hip's k_fmrx_power asks 16-byte rows of its caller and cannot serve here).
+template <bool A8> __global__ __launch_bounds__(256) void k_amssb_power(AmSsbArgs a, int d, const float *__restrict__ lv, float *__restrict__ own_power,
+                                                                        uint8_t *__restrict__ own_flags, size_t fl_pitch, float *__restrict__ power,
+                                                                        uint8_t *__restrict__ flags, size_t power_pitch)
+{
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (long long)a.n_ch * a.n_blocks) return;                    // (the whole wave)
+    const int ch = (int)(w / a.n_blocks), k = (int)(w % a.n_blocks), B = a.cfg.block;
+    const long long base = (long long)k * B;
+    const float fB = (float)B;
+    const float2 *carry = (const float2 *)a.carry, *in = (const float2 *)a.in;
+    float acc[4][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    for (int s0 = 0; s0 < B; s0 += 512) {
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const int s = s0 + 128 * r + 2 * lane + e;
+                if (s < B && (d == 1 || s % d == 0)) {
+                    const long long v = base + s;
+                    float2 u;
+                    if (A8) u = v < a.fill ? carry[(size_t)ch * B + v] : in[(size_t)ch * a.in_pitch + (v - a.fill)];
+                    else u = sample_any(a, ch, v);
+                    acc[r][e] = acc[r][e] + squelch_term_c(u.x, u.y, fB);
+                }
+            }
+    }
+    const float P = squelch_wave_tree(acc);
+    const bool open = squelch_open(P, lv[(k == 0 && a.fill > 0 ? a.n_ch : 0) + ch]);
+    if (lane == 0) {
+        own_power[(size_t)ch * fl_pitch + k] = P; own_flags[(size_t)ch * fl_pitch + k] = open;
+        if (power) power[(size_t)ch * power_pitch + k] = P;
+        if (flags) flags[(size_t)ch * power_pitch + k] = open;
+    }
 }
 
 // dst[ch][dst_off .. dst_off + count) = src[ch][src_off .. src_off + count), complex samples, float by float
@@ -225,7 +327,15 @@ struct csdr_amd_amssb : ChanBank<AmSsbChan> {
     Owned<csdr_amd_fftfilt, csdr_amd_fftfilt_destroy> filt; int taps_len;
     std::vector<float> band;                             // [n_ch][2]: the edges set_passband gave a channel last (NaN: none, or taps of the caller's own)
     Owned<csdr_amd_ddc, csdr_amd_ddc_destroy> ddc;
+    // the gate at the tail's input (csdr_amd_amssb_enable_squelch; sq false: none).  Its block is cfg.block and its held samples are d_carry's
+    bool fed = false;                                              // a sample has come in since the create or the last reset
+    bool sq = false; int sqd = 1; long long sq_blk = 0;              // use_every_nth, blocks since the reset
+    std::vector<float> lv, lv_started; bool lv_dirty = false;      // csdr_amd_squelch's levels: of the blocks a call starts, of the block begun earlier
+    DevBuf<float2> d_zero;                                         // AT samples of (0, 0)
+    DevBuf<float> d_lv, d_pw; DevBuf<uint8_t> d_fl; size_t fl_pitch = 0;      // [2][n_ch]; the powers and flags of a call's blocks, [n_ch][fl_pitch]
 };
+// what a gated call hands back besides the audio
+struct SqOut { float *power; size_t power_pitch; uint8_t *flags; int *n_blocks; };
 
 namespace {
 
@@ -293,7 +403,7 @@ long long run_filter(csdr_amd_amssb *p, const float *x, size_t xp, long long n, 
 }
 
 // the tail: n new complex samples per channel at x -> the whole blocks that became available
-long long run_tail(csdr_amd_amssb *p, const float *x, size_t xp, long long n, int16_t *s16, float *pre, size_t out_pitch)
+long long run_tail(csdr_amd_amssb *p, const float *x, size_t xp, long long n, int16_t *s16, float *pre, size_t out_pitch, const SqOut *so)
 {
     hipStream_t st = p->c->stream;
     const int B = p->cfg.block;
@@ -305,15 +415,46 @@ long long run_tail(csdr_amd_amssb *p, const float *x, size_t xp, long long n, in
         a.cfg = p->cfg; a.st = p->d_st.get(); a.n_ch = p->n_ch;
         a.carry = p->d_carry.get(); a.fill = p->fill; a.in = x; a.in_pitch = xp; a.n_blocks = (int)nb;
         a.s16 = s16; a.pre = pre; a.out_pitch = out_pitch;
-        const bool am = p->cfg.mode == AMSSB_AM;
-        if (!p->force_generic && B % AT == 0 && !((uintptr_t)x & 7)) {
-            const int C = a.lanes = bank_launch_lanes(p, am ? "k_amssb_tiled<AM>" : "k_amssb_tiled<SSB>", default_lanes(p->n_ch, true), ACMAX);
-            if (am) hipLaunchKernelGGL(k_amssb_tiled<AMSSB_AM>, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C), st, a, C);
-            else hipLaunchKernelGGL(k_amssb_tiled<AMSSB_SSB>, dim3(cdiv(p->n_ch, C)), dim3(64), tiled_lds(C), st, a, C);
+        const bool am = p->cfg.mode == AMSSB_AM, a8 = !((uintptr_t)x & 7);
+        const AmSsbSq q{p->d_fl.get(), p->fl_pitch, p->d_zero.get()};
+        if (p->sq) {                                     // the power pass: every block's power and flag, in front of the kernel that reads the flags
+            if ((size_t)nb > p->fl_pitch) return fail_msg(-4, "amssb: %lld blocks in a call where %zu were planned", nb, p->fl_pitch);
+            if (p->lv_dirty) {
+                const size_t S = (size_t)p->n_ch;
+                float *hl = (float *)p->c->pinned_acquire(sizeof(float) * 2 * S); if (!hl) return -2;
+                memcpy(hl, p->lv.data(), sizeof(float) * S); memcpy(hl + S, p->lv_started.data(), sizeof(float) * S);
+                if (const int rc = p->c->pinned_upload(p->d_lv.get(), sizeof(float) * 2 * S)) return rc;
+                p->lv_dirty = false;
+            }
+            const dim3 pg(cdiv((size_t)nb * p->n_ch, 4));
+            if (a8) hipLaunchKernelGGL(k_amssb_power<true>, pg, dim3(256), 0, st, a, p->sqd, p->d_lv.get(), p->d_pw.get(), p->d_fl.get(), p->fl_pitch, so ? so->power : nullptr,
+                                       so ? so->flags : nullptr, so ? so->power_pitch : 0);
+            else hipLaunchKernelGGL(k_amssb_power<false>, pg, dim3(256), 0, st, a, p->sqd, p->d_lv.get(), p->d_pw.get(), p->d_fl.get(), p->fl_pitch, so ? so->power : nullptr,
+                                    so ? so->flags : nullptr, so ? so->power_pitch : 0);
+            CSDR_LAUNCH_CHECK();
+        }
+        if (!p->force_generic && B % AT == 0 && a8) {
+            static const char *const names[2][2] = {{"k_amssb_tiled<AM>", "k_amssb_tiled<SSB>"}, {"k_amssb_tiled_sq<AM>", "k_amssb_tiled_sq<SSB>"}};
+            const int C = a.lanes = bank_launch_lanes(p, names[p->sq][!am], default_lanes(p->n_ch, true), ACMAX);
+            const dim3 grid(cdiv(p->n_ch, C));
+            if (!p->sq) {
+                if (am) hipLaunchKernelGGL((k_amssb_tiled<AMSSB_AM, false>), grid, dim3(64), tiled_lds(C), st, a, C, q);
+                else hipLaunchKernelGGL((k_amssb_tiled<AMSSB_SSB, false>), grid, dim3(64), tiled_lds(C), st, a, C, q);
+            } else {
+                if (am) hipLaunchKernelGGL((k_amssb_tiled<AMSSB_AM, true>), grid, dim3(64), tiled_lds(C), st, a, C, q);
+                else hipLaunchKernelGGL((k_amssb_tiled<AMSSB_SSB, true>), grid, dim3(64), tiled_lds(C), st, a, C, q);
+            }
         } else {
-            a.lanes = bank_launch_lanes(p, am ? "k_amssb_generic<AM>" : "k_amssb_generic<SSB>", default_lanes(p->n_ch, false));
-            if (am) hipLaunchKernelGGL(k_amssb_generic<AMSSB_AM>, dim3(cdiv(p->n_ch, a.lanes)), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL(k_amssb_generic<AMSSB_SSB>, dim3(cdiv(p->n_ch, a.lanes)), dim3(64), 0, st, a);
+            static const char *const names[2][2] = {{"k_amssb_generic<AM>", "k_amssb_generic<SSB>"}, {"k_amssb_generic_sq<AM>", "k_amssb_generic_sq<SSB>"}};
+            a.lanes = bank_launch_lanes(p, names[p->sq][!am], default_lanes(p->n_ch, false));
+            const dim3 grid(cdiv(p->n_ch, a.lanes));
+            if (!p->sq) {
+                if (am) hipLaunchKernelGGL((k_amssb_generic<AMSSB_AM, false>), grid, dim3(64), 0, st, a, q);
+                else hipLaunchKernelGGL((k_amssb_generic<AMSSB_SSB, false>), grid, dim3(64), 0, st, a, q);
+            } else {
+                if (am) hipLaunchKernelGGL((k_amssb_generic<AMSSB_AM, true>), grid, dim3(64), 0, st, a, q);
+                else hipLaunchKernelGGL((k_amssb_generic<AMSSB_SSB, true>), grid, dim3(64), 0, st, a, q);
+            }
         }
         CSDR_LAUNCH_CHECK();
     }
@@ -324,7 +465,53 @@ long long run_tail(csdr_amd_amssb *p, const float *x, size_t xp, long long n, in
         CSDR_LAUNCH_CHECK();
     }
     p->fill = (int)rem;
+    if (p->sq) {
+        p->sq_blk += nb;
+        // a block that is under way behind this call's whole blocks was started by this call: its level is the one in force now
+        if (nb > 0 && memcmp(p->lv_started.data(), p->lv.data(), sizeof(float) * p->n_ch)) { p->lv_started = p->lv; p->lv_dirty = true; }
+        if (so && so->n_blocks) *so->n_blocks = (int)nb;
+    }
     return nb * B;
+}
+
+// the most blocks a call of n_in samples can complete: exact without a front end, whose output count is known only behind it (there: max_out's bound)
+long long blocks_bound(const csdr_amd_amssb *p, long long n_in)
+{
+    if (p->ddc) return csdr_amd_amssb_max_out(p, n_in) / p->cfg.block;
+    long long n = n_in;
+    if (p->filt) n = (p->f_fill + n) / p->inp * p->inp;
+    return (p->fill + n) / p->cfg.block;
+}
+
+int squelched(const csdr_amd_amssb *p)
+{
+    if (!p) return fail_msg(-3, "amssb: null object");
+    if (!p->sq) return fail_msg(-3, "amssb: the object has no squelch (csdr_amd_amssb_enable_squelch)");
+    return 0;
+}
+
+long long process_impl(csdr_amd_amssb *p, const void *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *pre_agc_f, size_t out_pitch, const SqOut *so)
+{
+    if (n_in < 0 || (size_t)n_in > p->max_in) return fail_msg(-3, "amssb: n_in should be 0 .. the max_samples_per_call given to create (%zu)", p->max_in);
+    if (n_in > 0 && (!in || in_pitch < (size_t)n_in)) return fail_msg(-3, "amssb: need in and in_pitch >= n_in");
+    if (so && (so->power || so->flags) && (long long)so->power_pitch < blocks_bound(p, n_in))
+        return fail_msg(-3, "amssb: power_pitch %zu below the %lld blocks this call may complete", so->power_pitch, blocks_bound(p, n_in));
+    if (so && so->n_blocks) *so->n_blocks = 0;
+    if (n_in > 0) p->fed = true;
+    const float *x = (const float *)in; size_t xp = in_pitch; long long n = n_in;
+    if (p->ddc) {
+        if (n_in > 0) {
+            n = csdr_amd_ddc_process(p->ddc.get(), (const uint8_t *)in, in_pitch, (size_t)n_in, (csdr_complexf *)p->d_y.get(), p->y_pitch);
+            if (n < 0) return n;
+            if ((size_t)n > p->y_pitch) return fail_msg(-3, "amssb: the front end produced more than the planned %zu samples", p->y_pitch);
+        }
+        x = p->d_y.get(); xp = p->y_pitch;
+    } else if (n_in > 0 && ((uintptr_t)in & 3)) return fail_msg(-3, "amssb: in should be 4-byte aligned");
+    if (p->filt) {
+        n = run_filter(p, x, xp, n, &x, &xp);
+        if (n < 0) return n;
+    }
+    return run_tail(p, x, xp, n, audio_s16, pre_agc_f, out_pitch, so);
 }
 
 } // namespace
@@ -416,6 +603,7 @@ int csdr_amd_amssb_reset(csdr_amd_amssb *p)
     hipLaunchKernelGGL(k_amssb_reset, dim3(cdiv(p->n_ch, 256)), dim3(256), 0, p->c->stream, p->d_st.get(), p->n_ch);
     CSDR_LAUNCH_CHECK();
     p->fill = 0; p->f_fill = 0;
+    p->fed = false; p->sq_blk = 0; p->lv_started = p->lv; p->lv_dirty = true;       // (the levels stay)
     if (p->filt && csdr_amd_fftfilt_reset(p->filt.get()) < 0) return -5;
     if (p->ddc && csdr_amd_ddc_reset(p->ddc.get()) < 0) return -5;
     return 0;
@@ -451,22 +639,67 @@ long long csdr_amd_amssb_max_out(const csdr_amd_amssb *p, long long n_in)
 long long csdr_amd_amssb_process(csdr_amd_amssb *p, const void *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *pre_agc_f, size_t out_pitch)
 {
     if (!p) return fail_msg(-3, "amssb: null object");
-    if (n_in < 0 || (size_t)n_in > p->max_in) return fail_msg(-3, "amssb: n_in should be 0 .. the max_samples_per_call given to create (%zu)", p->max_in);
-    if (n_in > 0 && (!in || in_pitch < (size_t)n_in)) return fail_msg(-3, "amssb: need in and in_pitch >= n_in");
-    const float *x = (const float *)in; size_t xp = in_pitch; long long n = n_in;
-    if (p->ddc) {
-        if (n_in > 0) {
-            n = csdr_amd_ddc_process(p->ddc.get(), (const uint8_t *)in, in_pitch, (size_t)n_in, (csdr_complexf *)p->d_y.get(), p->y_pitch);
-            if (n < 0) return n;
-            if ((size_t)n > p->y_pitch) return fail_msg(-3, "amssb: the front end produced more than the planned %zu samples", p->y_pitch);
-        }
-        x = p->d_y.get(); xp = p->y_pitch;
-    } else if (n_in > 0 && ((uintptr_t)in & 3)) return fail_msg(-3, "amssb: in should be 4-byte aligned");
-    if (p->filt) {
-        n = run_filter(p, x, xp, n, &x, &xp);
-        if (n < 0) return n;
+    return process_impl(p, in, in_pitch, n_in, audio_s16, pre_agc_f, out_pitch, nullptr);
+}
+
+// ---- the gate at the tail's input
+int csdr_amd_amssb_enable_squelch(csdr_amd_amssb *p, int use_every_nth, const float *levels)
+{
+    if (!p) return fail_msg(-3, "amssb: null object");
+    if (use_every_nth < 1) return fail_msg(-3, "amssb: use_every_nth should be at least 1");
+    if (p->fed)
+        return fail_msg(-3, "amssb: enable_squelch needs an object that holds no sample (fresh, or after reset)");
+    // a closed block's audio is g * 0 behind limit_ff: 0 for every g only where limit_max is not negative (and not NaN)
+    if (!(p->cfg.limit_max >= 0)) return fail_msg(-3, "amssb: a squelch needs limit_max >= 0");
+    const size_t S = (size_t)p->n_ch, fl_pitch = p->max_tail / p->cfg.block + 2;
+    DevBuf<float> lv, pw; DevBuf<uint8_t> fl; DevBuf<float2> zero;
+    if (dev_alloc(zero, sizeof(float2) * AT) != hipSuccess || dev_alloc(lv, sizeof(float) * 2 * S) != hipSuccess || dev_alloc(pw, sizeof(float) * fl_pitch * S) != hipSuccess || dev_alloc(fl, fl_pitch * S) != hipSuccess)
+        return fail_msg(-2, "amssb: out of device memory");
+    CSDR_HIP(hipMemsetAsync(zero.get(), 0, sizeof(float2) * AT, p->c->stream));
+    p->d_zero = std::move(zero); p->d_lv = std::move(lv); p->d_pw = std::move(pw); p->d_fl = std::move(fl); p->fl_pitch = fl_pitch;
+    p->lv.assign(S, 0.f);
+    if (levels) p->lv.assign(levels, levels + S);
+    p->lv_started = p->lv; p->lv_dirty = true;
+    p->sq = true; p->sqd = use_every_nth; p->sq_blk = 0;
+    return 0;
+}
+
+int csdr_amd_amssb_set_squelch_level(csdr_amd_amssb *p, int ch, float level)
+{
+    if (const int rc = squelched(p)) return rc;
+    if (ch < -1 || ch >= p->n_ch) return fail_msg(-3, "amssb: channel out of range");
+    for (int k = (ch < 0 ? 0 : ch); k < (ch < 0 ? p->n_ch : ch + 1); k++) {
+        p->lv[k] = level;
+        if (p->fill == 0) p->lv_started[k] = level;                    // no block is under way: the next one starts under this level
     }
-    return run_tail(p, x, xp, n, audio_s16, pre_agc_f, out_pitch);
+    p->lv_dirty = true;
+    return 0;
+}
+
+int csdr_amd_amssb_get_squelch_level(const csdr_amd_amssb *p, int ch, float *level)
+{
+    if (const int rc = squelched(p)) return rc;
+    if (ch < 0 || ch >= p->n_ch || !level) return fail_msg(-3, "amssb: channel out of range");
+    *level = p->lv[ch];
+    return 0;
+}
+
+long long csdr_amd_amssb_squelch_block_index(const csdr_amd_amssb *p) { if (const int rc = squelched(p)) return rc; return p->sq_blk; }
+
+long long csdr_amd_amssb_process_squelched(csdr_amd_amssb *p, const void *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *pre_agc_f, size_t out_pitch,
+                                           float *power, size_t power_pitch, uint8_t *open_flags, int *n_blocks_out)
+{
+    if (const int rc = squelched(p)) return rc;
+    const SqOut so{power, power_pitch, open_flags, n_blocks_out};
+    return process_impl(p, in, in_pitch, n_in, audio_s16, pre_agc_f, out_pitch, &so);
+}
+
+// amssb_agc_zero_run on the host, the source the kernels run: the gain after n agc_ff steps on zero samples, and how many of them were taken one by one
+float csdr_amd_debug_amssb_zero_run(const csdr_amd_amssb_params *params, float gain, long long n, long long *steps_iterated)
+{
+    AmSsbCfg cfg;
+    if (check_params(params, &cfg) < 0 || n < 0) { fail_msg(-3, "debug_amssb_zero_run: bad arguments"); return NAN; }
+    return amssb_agc_zero_run(cfg, gain, n, steps_iterated);
 }
 
 // CPU run of the kernels' functions for one channel (params->mode says which chain): in holds n_blocks * params->block complex samples; state_io (may be NULL: a

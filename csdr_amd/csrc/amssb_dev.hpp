@@ -97,6 +97,40 @@ __host__ __device__ inline float agc_call_step(const AmSsbCfg &c, AgcCall &a, fl
     return a.gain;
 }
 
+// agc_call_step for v == 0, as a map of the gain alone: nz is false, so the hang counter, the wait counter and the peak stay, g1 is the gain, and gain ==
+// last_gain holds at every step of a call.  The operations below are agc_call_step's from g2 on, in its order.
+__host__ __device__ inline float amssb_agc_zero_step(const AmSsbCfg &c, float g)
+{
+    float g2 = g > c.max_gain ? c.max_gain : g;
+    g2 = g2 < 0 ? 0.f : g2;
+    return g2 + g - c.alpha * g;
+}
+__host__ __device__ inline uint32_t amssb_float_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+// The gain after n applications of amssb_agc_zero_step.  The map is a pure function of one float, so once a gain repeats one of the four before it, bit
+// for bit, the sequence is periodic from there and the rest is an index into those four.  Without a repeat (none is known: in float32 the map runs into a
+// cycle of period 1 to 3 for every parameter set tried) every step is taken.  *steps_iterated: the applications actually performed.
+__host__ __device__ inline float amssb_agc_zero_run(const AmSsbCfg &c, float g, long long n, long long *steps_iterated = nullptr)
+{
+    float h0 = g, h1 = g, h2 = g, h3 = g;                // the gains 1, 2, 3, 4 steps back (before that many steps exist: the start, which comes first in the search)
+    long long i = 0;
+    float out = g;
+    while (i < n) {
+        const float gn = amssb_agc_zero_step(c, h0);
+        i++;
+        const uint32_t b = amssb_float_bits(gn);
+        const int p = b == amssb_float_bits(h0) ? 1 : b == amssb_float_bits(h1) ? 2 : b == amssb_float_bits(h2) ? 3 : b == amssb_float_bits(h3) ? 4 : 0;
+        if (p) {                                         // step i equals step i - p: step i + r is step i - p + (r mod p), the gain p - (r mod p) steps back
+            const int k = p - (int)((n - i) % p);
+            out = k == 1 ? h0 : k == 2 ? h1 : k == 3 ? h2 : h3;
+            break;
+        }
+        h3 = h2; h2 = h1; h1 = h0; h0 = gn;
+        out = gn;
+    }
+    if (steps_iterated) *steps_iterated = i;
+    return out;
+}
+
 // agc_ff's scaling, limit_ff and convert_f_s16 of one sample: x the pre-AGC sample, g its gain
 __host__ __device__ inline int16_t amssb_finish(const AmSsbCfg &c, float g, float x)
 {

@@ -331,6 +331,11 @@ int run_shift_bank(csdr_amd_ctx *c, int argc, char **argv)
 //   --ctl <fifo | fd:<n>> in front of it: control lines "<stream> <rate>\n", applied between two passes exactly as `shift_addition_cc --fifo` applies a new rate
 //   between two reads (csdr.c:881-923: the phase carries over).  ssb_bank_u8_s16 also takes "<stream> bp <low> <high>\n": that stream's passband, as a retuned
 //   `bandpass_fir_fft_cc --fifo` (csdr.c:1817-1881), from the first sample the bank's filter has not consumed yet.
+//   csdr am_bank_u8_s16 --squelch <use_every_nth> <report_every_nth> <smeter_out> ...   and the same for ssb_bank_u8_s16 (the rest as above, --lsb, --passbands and
+//   --ctl included): squelch_and_smeter_cc (csdr.c:2192-2243) between every stream's channel filter and its demodulator, inside the bank object
+//   (csdr_amd_amssb_enable_squelch): blocks of the chain's 1024 decimated samples, every level 0 (open) at the start; a control line "<stream> squelch <level>\n"
+//   sets that stream's level from the next block that starts.  Every block k with k mod (report_every_nth + 2) == report_every_nth + 1 writes one line
+//   "<stream> %g\n" per stream, its power, to <smeter_out>, non-blocking as the reference writes its --outfifo: a line that does not fit is dropped.
 size_t bank_block() { size_t T = 262144; if (const char *e = getenv("CSDR_AMD_BANK_BLOCK")) { long v = atol(e); if (v >= 1024) T = (size_t)v; } return T; }
 
 // The lockstep loop of the stream banks.  specs: in_0 out_0 in_1 out_1 ... (S pairs).  Every pass reads T samples of u8 IQ from EVERY input into the rows of one batch
@@ -372,7 +377,16 @@ enum { BANK_WFM, BANK_NFM, BANK_AM, BANK_SSB };
 int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
 {
     const bool nfm = kind == BANK_NFM, amssb = kind == BANK_AM || kind == BANK_SSB;
-    bool lsb = false;
+    bool lsb = false, sq = false;
+    int sq_d = 1, sq_report = 0; const char *smeter_path = nullptr;
+    if (amssb && argc > 2 && !strcmp(argv[2], "--squelch")) {
+        if (argc < 6 || sscanf(argv[3], "%d", &sq_d) != 1 || sscanf(argv[4], "%d", &sq_report) != 1)
+            return badsyntax("usage: --squelch <use_every_nth> <report_every_nth> <smeter_out> [--lsb | --passbands ...] [--ctl <fifo|fd:n>] <shift_rate[,...]> <in_0> <out_0> ...");
+        if (sq_d <= 0) return badsyntax("use_every_nth <= 0 is invalid");
+        if (sq_report <= 0) return badsyntax("report_every_nth <= 0 is invalid");
+        smeter_path = argv[5]; sq = true;
+        argv += 4; argc -= 4;
+    }
     if (kind == BANK_SSB && argc > 2 && !strcmp(argv[2], "--lsb")) { lsb = true; argv += 1; argc -= 1; }
     std::vector<float> bands;                                          // --passbands: low_0, high_0, low_1, ...
     if (kind == BANK_SSB && argc > 2 && !strcmp(argv[2], "--passbands")) {
@@ -434,8 +448,35 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
     if (!w && !n && !a) die("bank create");
     if (bands.size() > 2) for (int k = 0; k < S; k++) MUST(csdr_amd_amssb_set_passband(a.get(), k, bands[2 * k], bands[2 * k + 1], CSDR_WINDOW_HAMMING));
     const size_t in_pitch = 2 * T, out_pitch = ((T / 50 + 4096 + 63) / 64) * 64;      // out_pitch: s16 samples
+    Fds smeter_fd(1, -1);
+    size_t p_pitch = 0; CtxBuf<float> d_power; std::vector<float> h_power;
+    if (sq) {
+        MUST(csdr_amd_amssb_enable_squelch(a.get(), sq_d, nullptr));
+        smeter_fd[0] = open_spec(smeter_path, O_WRONLY | O_CREAT | O_TRUNC);
+        if (smeter_fd[0] < 0) return badsyntax("cannot open the S-meter output");
+        fcntl(smeter_fd[0], F_SETFL, fcntl(smeter_fd[0], F_GETFL, 0) | O_NONBLOCK);
+        p_pitch = (size_t)csdr_amd_amssb_max_out(a.get(), (long long)T) / 1024 + 1;     // the most blocks of a pass (the chain's block is 1024)
+        d_power = ctx_alloc<float>(c, (size_t)S * p_pitch * 4 + 64); h_power.resize((size_t)S * p_pitch);
+    }
     // a short final block: whole 1024-sample chunks of the shortest stream (the chain objects take a ragged LAST block only)
     auto pass = [&](const uint8_t *d_in, uint8_t *d_out, size_t nproc) {
+        if (sq) {
+            const long long k0 = csdr_amd_amssb_squelch_block_index(a.get());
+            int nb = 0;
+            const long long na = csdr_amd_amssb_process_squelched(a.get(), d_in, in_pitch, (long long)nproc, (int16_t *)d_out, nullptr, out_pitch, d_power.get(), p_pitch, nullptr, &nb);
+            MUST(na);
+            bool due = false;
+            for (int k = 0; k < nb && !due; k++) due = csdr_amd_squelch_report_due(sq_report, k0 + k) != 0;
+            if (due) {
+                MUST(csdr_amd_d2h(c, h_power.data(), d_power.get(), (size_t)S * p_pitch * 4));
+                for (int k = 0; k < nb; k++) if (csdr_amd_squelch_report_due(sq_report, k0 + k))
+                    for (int ch = 0; ch < S; ch++) {
+                        char line[128]; const int len = snprintf(line, sizeof line, "%d %g\n", ch, h_power[(size_t)ch * p_pitch + k]);
+                        (void)!write(smeter_fd[0], line, (size_t)len);       // non-blocking: a line that does not fit is dropped (csdr.c:2211-2228)
+                    }
+            }
+            return (size_t)na * 2;
+        }
         const long na = amssb ? (long)csdr_amd_amssb_process(a.get(), d_in, in_pitch, (long long)nproc, (int16_t *)d_out, nullptr, out_pitch) :
                         nfm ? csdr_amd_nfm_process(n.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch) : csdr_amd_wfm_process(w.get(), d_in, in_pitch, nproc, (int16_t *)d_out, nullptr, out_pitch);
         MUST(na);
@@ -450,6 +491,12 @@ int run_stream_bank(csdr_amd_ctx *c, int argc, char **argv, int kind)
                 if (st < 0 || st >= S || !(lo < hi)) continue;
                 MUST(csdr_amd_amssb_set_passband(a.get(), st, lo, hi, CSDR_WINDOW_HAMMING));
                 fprintf(stderr, "csdr %s: stream %d passband reinitialized to %g %g\n", g_cmd, st, lo, hi);
+                continue;
+            }
+            if (sq && sscanf(line, "%d squelch %g", &st, &rv) == 2) {
+                if (st < 0 || st >= S) continue;
+                MUST(csdr_amd_amssb_set_squelch_level(a.get(), st, rv));
+                fprintf(stderr, "csdr %s: stream %d squelch level is %g\n", g_cmd, st, rv);
                 continue;
             }
             if (sscanf(line, "%d %g", &st, &rv) != 2 || st < 0 || st >= S) continue;

@@ -1423,6 +1423,30 @@ void csdr_amd_amssb_destroy(csdr_amd_amssb *p);
  * channel) carries the state in and out; either output may be NULL.  Returns n_blocks * block or a negative code. */
 long long csdr_amd_debug_amssb_walk(const csdr_amd_amssb_params *params, const csdr_complexf *in, int n_blocks, csdr_amd_amssb_chan *state_io, int16_t *s16_out,
                                     float *pre_agc_out);
+/* The squelch and S-meter inside the object: squelch_and_smeter_cc at the tail's input (behind the owned front end and filter), per channel
+ *   squelch_and_smeter_cc | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16          (realpart_cf for amdemod_cf | fastdcblock_ff in SSB)
+ * The squelch block is the object's block and is counted from the reset, for all channels in lockstep; the samples short of a block that the object carries
+ * serve both.  The power of a block is csdr_amd_squelch's, bit for bit (use_every_nth: every n-th sample enters, the divisor is the block); a block passes if
+ * its level is 0 or its power >= the level, else it goes on as (0, 0) samples.  A block's level is the one in force when its first sample reached the tail's
+ * input, so set_squelch_level between calls gives the flags csdr_amd_squelch_set_level gives at the same call boundaries.  The outputs are, in every bit, those
+ * of a csdr_amd_squelch in front of an unsquelched object; closed blocks are not loaded, and once fastdcblock_ff's level has reached 0 they are not walked either.
+ * enable_squelch: levels holds n_channels floats (NULL: 0, open), on any creation form; only while the object has taken no sample since its creation or its last
+ * reset, and only with limit_max >= 0 (-3 otherwise, nothing changed).  There is no way back.  reset clears the block index and the held samples and keeps the
+ * levels; reset_channel and set_channel stay the two state words.
+ * process_squelched: as process; power and open_flags (device, [n_channels][power_pitch], either may be NULL) receive one entry per block the call completed,
+ * *n_blocks_out (may be NULL) their count.  power_pitch must hold the blocks the call can complete: exactly those of this call for CF32 input, max_out(n_in) /
+ * block behind an owned front end (-3 otherwise, nothing changed).  process on such an object is process_squelched without the rows.
+ * set_squelch_level: channel -1 = all.  squelch_block_index: the blocks completed since the reset.  Every squelch call on an object without one returns -3.
+ * kernel_name: "k_amssb_tiled_sq<AM>" / "k_amssb_tiled_sq<SSB>" / "k_amssb_generic_sq<AM>" / "k_amssb_generic_sq<SSB>". */
+int  csdr_amd_amssb_enable_squelch(csdr_amd_amssb *p, int use_every_nth, const float *levels);
+long long csdr_amd_amssb_process_squelched(csdr_amd_amssb *p, const void *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *pre_agc_f, size_t out_pitch,
+                                           float *power, size_t power_pitch, uint8_t *open_flags, int *n_blocks_out);
+int  csdr_amd_amssb_set_squelch_level(csdr_amd_amssb *p, int channel, float level);
+int  csdr_amd_amssb_get_squelch_level(const csdr_amd_amssb *p, int channel, float *level);
+long long csdr_amd_amssb_squelch_block_index(const csdr_amd_amssb *p);
+/* agc_ff over n zero samples, as the kernels take it (amssb_dev.hpp's amssb_agc_zero_run): the gain behind them; *steps_iterated (may be NULL): how many
+ * of the n steps were taken one by one before a cycle of the gain (period <= 4) was found.  NaN and a message on bad arguments. */
+float csdr_amd_debug_amssb_zero_run(const csdr_amd_amssb_params *params, float gain, long long n, long long *steps_iterated);
 
 /* Test hook: one tile of the WFM chain kernel (k_wfm_mfma_seq: phase-independent weight set, post factors, chunk-boundary handling) on the CPU.
  * n0: window base sample (multiple of 8); window: 512 raw bytes; ctab2: (cos, sin) of chunks n0>>10, +1; out16: 16 rows. */
