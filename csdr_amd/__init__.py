@@ -364,6 +364,11 @@ def lib():
     L.csdr_amd_wfm_reset.argtypes = [vp]
     L.csdr_amd_wfm_process.restype = C.c_long; L.csdr_amd_wfm_process.argtypes = [vp, vp, sz, sz, vp, vp, sz]
     L.csdr_amd_wfm_kernel_name.restype = C.c_char_p; L.csdr_amd_wfm_kernel_name.argtypes = [vp]
+    if hasattr(L, "csdr_amd_wfm_deemph_exact"):          # (absent from older builds selected with CSDR_AMD_LIB for A/B runs)
+        L.csdr_amd_wfm_deemph_exact.argtypes = [fl, i, i]
+        L.csdr_amd_wfm_deemph_warm_samples.argtypes = [i]
+        L.csdr_amd_wfm_exact_deemphasis.argtypes = [vp]
+        L.csdr_amd_wfm_set_deemphasis_state.argtypes = [vp, vp]
     ll = C.c_longlong; db = C.c_double
     L.csdr_amd_wfm_ring_create.restype = vp; L.csdr_amd_wfm_ring_create.argtypes = [vp, i, fl, i, vp, i, i, fl, i, sz, i]
     L.csdr_amd_wfm_ring_destroy.argtypes = [vp]; L.csdr_amd_wfm_ring_destroy.restype = None
@@ -3189,14 +3194,17 @@ class Context:
         return st
 
     def wfm_chain(self, iq_u8, shift_rate, decimation, taps, frac_rate=5, tau=50e-6, audio_rate=48000, block=None, pitch_pad=0, retunes=None, want_float=True,
-                  out_per_call=False, max_block=None):
+                  out_per_call=False, max_block=None, deemph_state=None, repeat_after_reset=False):
         """iq_u8: [2n] or [streams, 2n] uint8 -> (s16 [streams, na], float audio [streams, na]); `block` = samples per call (or a list of call sizes);
         `pitch_pad` = extra bytes of row pitch (multiple of 16).  shift_rate: one float, or one per stream (csdr_amd_wfm_create_rates);
         retunes: {call index: [(stream, rate), ...]} applied in front of that call.  want_float=False: s16 only (the kernel's line-collecting store path).
         out_per_call: every call writes at the START of the (16-byte aligned) output rows, as a streaming caller with one output buffer does -- the kernel's
         aligned store path on every call (otherwise call k's audio follows call k - 1's in one row: aligned only by chance).
         max_block: the object's max_block_samples (default: the largest call) -- it sizes the chunk-seed tables, nothing else of the matrix-core chain.
-        The front-end kernel of the last call is left in `self.last_wfm_kernel`, the seed tables' counters (_seed_stats) in `self.wfm_seed_stats`."""
+        deemph_state: float per stream, the de-emphasis state in front of the first call (csdr_amd_wfm_set_deemphasis_state).  repeat_after_reset: the whole
+        schedule runs a second time behind csdr_amd_wfm_reset (rates and state put back as at the start); that run's (s16, float) are left in `self.wfm_repeat`.
+        The front-end kernel of the last call is left in `self.last_wfm_kernel`, the seed tables' counters (_seed_stats) in `self.wfm_seed_stats`, the route of the
+        de-emphasis (csdr_amd_wfm_exact_deemphasis) in `self.last_wfm_exact`."""
         x2, squeeze = self._2d(iq_u8, np.uint8)
         s, nbytes = x2.shape; n = nbytes // 2
         pitch = (nbytes + 15) // 16 * 16 + pitch_pad
@@ -3215,25 +3223,42 @@ class Context:
             di = self.upload(xx)
             apitch = (n // (decimation * frac_rate) + 64 + 63) // 64 * 64
             ds = self.alloc(2 * s * apitch); df = self.alloc(4 * s * apitch) if want_float else None
-            pos = 0; na = 0; call = 0; parts_s = []; parts_f = []; stats = None
-            while pos < n:
-                for st, r in (retunes or {}).get(call, []):
-                    w._call("set_rate", st, r)
-                k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+            stats = None
+
+            def run():
+                nonlocal stats
+                pos = 0; na = 0; call = 0; parts_s = []; parts_f = []
+                if deemph_state is not None:
+                    st0 = np.ascontiguousarray(deemph_state, f32); assert st0.size == s
+                    w._call("set_deemphasis_state", _hp(st0))
+                while pos < n:
+                    for st, r in (retunes or {}).get(call, []):
+                        w._call("set_rate", st, r)
+                    k = min(sched[call] if (sched and call < len(sched)) else block, n - pos); call += 1
+                    if out_per_call:
+                        got = w._call("process", di.at(2 * pos), pitch, k, ds.ptr, df.ptr if want_float else None, apitch)
+                        parts_s.append(self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :got].copy())
+                        if want_float: parts_f.append(self.download(df, f32, s * apitch).reshape(s, apitch)[:, :got].copy())
+                    else:
+                        got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na) if want_float else None, apitch)
+                    stats = self._seed_stats("wfm", w.h, ps, stats, call - 1)
+                    pos += k; na += got
                 if out_per_call:
-                    got = w._call("process", di.at(2 * pos), pitch, k, ds.ptr, df.ptr if want_float else None, apitch)
-                    parts_s.append(self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :got].copy())
-                    if want_float: parts_f.append(self.download(df, f32, s * apitch).reshape(s, apitch)[:, :got].copy())
+                    s16 = np.concatenate(parts_s, axis=1) if parts_s else np.zeros((s, 0), np.int16)
+                    af = np.concatenate(parts_f, axis=1) if parts_f else np.zeros((s, 0), f32)
                 else:
-                    got = w._call("process", di.at(2 * pos), pitch, k, ds.at(2 * na), df.at(4 * na) if want_float else None, apitch)
-                stats = self._seed_stats("wfm", w.h, ps, stats, call - 1)
-                pos += k; na += got
-            if out_per_call:
-                s16 = np.concatenate(parts_s, axis=1) if parts_s else np.zeros((s, 0), np.int16)
-                af = np.concatenate(parts_f, axis=1) if parts_f else np.zeros((s, 0), f32)
-            else:
-                s16 = self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :na]
-                af = self.download(df, f32, s * apitch).reshape(s, apitch)[:, :na] if want_float else np.zeros((s, 0), f32)
+                    s16 = self.download(ds, np.int16, s * apitch).reshape(s, apitch)[:, :na].copy()
+                    af = self.download(df, f32, s * apitch).reshape(s, apitch)[:, :na].copy() if want_float else np.zeros((s, 0), f32)
+                return s16, af
+            s16, af = run()
+            if repeat_after_reset:
+                w.reset()
+                if ps:
+                    for st in range(s):
+                        w._call("set_rate", st, float(rates[st]))
+                self.wfm_repeat = run()
+            if hasattr(self.L, "csdr_amd_wfm_exact_deemphasis"):
+                self.last_wfm_exact = int(self.L.csdr_amd_wfm_exact_deemphasis(w.h))
             self.last_wfm_kernel = w.kernel_name(); self.wfm_seed_stats = stats
         return (s16[0].copy(), af[0].copy()) if squeeze else (s16.copy(), af.copy())
 

@@ -21,10 +21,16 @@
 //   k_wfm_front : (stream, tile of A audio samples) per workgroup.  u8 window -> float -> rotate -> LDS;
 //                 FIR pairs from LDS (two lanes per output, 40 taps each); quadrature demod; writes the
 //                 pre-de-emphasis audio float (4 B per D*F input samples) to a scratch row.
-//   k_wfm_back  : de-emphasis + s16.  The one-pole IIR forgets its state as (1-alpha)^k (0.706^48 = 5.6e-8),
-//                 so every 64-sample segment is started 48 samples early from zero state and is then
-//                 independent of its predecessor to float precision; the first segment of a call uses the
-//                 exact carried state.
+//   k_wfm_back  : de-emphasis + s16.  The one-pole IIR forgets its state as b^k, b = 1 - alpha: every 16-sample
+//                 segment is started WARM = 48 samples early from zero state; the first segment of a call uses
+//                 the exact carried state.  What a seam leaves of the true state is b^48: 5.5e-8 at tau = 50 us
+//                 and 48 kHz, but 1.9e-3 at 75 us / 96 kHz and 0.37 at 1 ms / 48 kHz -- it depends on tau and the
+//                 audio rate, not on the method.
+//
+// The de-emphasis rule (csdr_amd_wfm_deemph_exact): where b^W > 2^-20 for the W samples a path warms up over (both chain kernels: 48), the object takes the EXACT
+// route: the kernels run with alpha = 1 (b = 0: their scans return the demodulated audio unchanged, a seam has nothing to forget) into float scratch rows, and
+// csdr_amd_deemphasis_wfm_ff -- the reference's recurrence, sample by sample, with the object's carried state -- and convert_f_s16 follow.  At every other
+// tau / audio rate, the default 50 us / 48 kHz among them, the kernels get the arguments they always got.
 #include "common.hpp"
 #include "wfm_mfma.hpp"
 #include "seeds.hpp"
@@ -39,7 +45,7 @@ namespace {
 
 constexpr int HIST = WFM_HIST;     // complex samples of input history kept per stream (>= D*(F-1+..)+taps needs 88 for 10/79/5)
 constexpr int TILE_A = 64;         // audio samples per workgroup
-constexpr int WARM = 48;           // de-emphasis warm-up samples
+constexpr int WARM = 48;           // de-emphasis warm-up samples of k_wfm_back (enough where csdr_amd_wfm_deemph_exact says 0)
 
 struct WfmParams {
     int D, L, F;                   // decimation, taps, audio decimation
@@ -124,8 +130,9 @@ __global__ __launch_bounds__(256) void k_wfm_front(const uint8_t *__restrict__ i
 }
 
 // de-emphasis + convert_f_s16.  Block = 256 lanes x 16-sample segments = 4096 audio samples of one stream; every lane starts
-// WARM (48) samples early from zero state (0.706^48 = 5.6e-8: the predecessor's state is forgotten to float precision), the very
-// first segment of a call starts from the exact carried state.  Input staged once through LDS (lane stride 17 floats: conflict free),
+// WARM (48) samples early from zero state (the predecessor's state is forgotten to (1 - alpha)^48: 5.5e-8 at 50 us / 48 kHz; parameters
+// at which that is more than 2^-20 come here with alpha = 1, see the head of this file), the very first segment of a call starts from
+// the exact carried state.  Input staged once through LDS (lane stride 17 floats: conflict free),
 // each lane leaves 16 s16 = 32 contiguous bytes -> fully coalesced 8 KiB per block.
 constexpr int BK_SEG = 16, BK_CHUNK = 256 * BK_SEG;
 __global__ __launch_bounds__(256) void k_wfm_back(const float *__restrict__ demod_base, size_t demod_pitch, int skip, int n_audio, float alpha,
@@ -201,7 +208,9 @@ struct csdr_amd_wfm {
     float shift_rate, tau, alpha;
     size_t max_block;
     DevBuf<float> d_taps, d_demod, d_last[2];
-    float phase;                     // shift_addition_cc starting_phase (host float, like the reference's by-value state)
+    // the exact de-emphasis route (head of this file): scratch rows the kernels write the demodulated audio to, the carried state of csdr_amd_deemphasis_wfm_ff
+    bool exact; DevBuf<float> d_xf, d_state; DevBuf<int16_t> d_xs; size_t x_pitch;
+    float phase;                    // shift_addition_cc starting_phase (host float, like the reference's by-value state)
     DevBuf<cf32> d_rot;
     DevBuf<uint8_t> d_hist;          // VALU front end: 2 * HIST bytes per stream
     DevBuf<uint8_t> d_head[2]; int hflip;   // matrix-core chain kernel: 1 KiB per stream, second half = the previous block's newest 512 bytes (two buffers: wfm_mfma.hip)
@@ -229,6 +238,27 @@ struct csdr_amd_wfm {
 };
 
 extern "C" {
+
+// The de-emphasis rule (host arithmetic only).  A segment that starts warm_samples early from zero state is wrong at its first sample by b^warm_samples times the
+// true state there, b = 1 - alpha in float as the kernels form it (libcsdr.c:1090-1091).  2^-20 of a full-scale state is 0.03 LSB of the s16 audio: below that the
+// seam leaves the chain's +-1 LSB to the front end; above it (1) the fixed warm-up is too short.
+int csdr_amd_wfm_deemph_exact(float tau, int audio_rate, int warm_samples)
+{
+    const float dt = (float)(1.0 / audio_rate);
+    const float alpha = dt / (tau + dt);
+    const float b = 1 - alpha;
+    return pow((double)b, (double)warm_samples) > 0x1p-20 ? 1 : 0;
+}
+
+// the fewest audio samples a path warms up over.  path 0: k_wfm_mfma_seq per call (shared rate and rate per stream), 1: k_wfm_back, 2: the resident ring (a block:
+// the chain kernel's steps; behind a retune: RES_WARM)
+int csdr_amd_wfm_deemph_warm_samples(int path)
+{
+    if (path == 0) return wfm_mfma_warm_samples();
+    if (path == 1) return WARM;
+    if (path == 2) return wfm_mfma_warm_samples() < WFM_RES_WARM ? wfm_mfma_warm_samples() : WFM_RES_WARM;
+    return fail_msg(-3, "wfm_deemph_warm_samples: path %d (0: chain kernel, 1: fallback, 2: ring)", path);
+}
 
 // tables of ONE stream of a per-stream object
 static int wfm_upload_stream_tables(csdr_amd_wfm *w, int s, float rate)
@@ -263,6 +293,13 @@ static csdr_amd_wfm *wfm_create_impl(csdr_amd_ctx *ctx, int n_streams, const flo
         w->use_mfma = !(force && !strcmp(force, "valu")) && wfm_mfma_supported(decimation, taps_length, frac_rate);
     }
     if (per_stream && !w->use_mfma) { fail_msg(-3, "wfm_create_rates: a rate per stream needs the matrix-core chain kernel (decimation x audio decimation even, window <= 256 samples)"); return nullptr; }
+    w->exact = csdr_amd_wfm_deemph_exact(tau, audio_rate, csdr_amd_wfm_deemph_warm_samples(w->use_mfma ? 0 : 1)) != 0;
+    w->x_pitch = w->demod_pitch;                                   // (a multiple of 64 samples: the kernels' aligned store path)
+    if (w->exact) {
+        alloc(w->d_xf, sizeof(float) * w->x_pitch * n_streams);
+        alloc(w->d_xs, sizeof(int16_t) * w->x_pitch * n_streams);
+        alloc(w->d_state, sizeof(float) * n_streams);
+    }
     alloc(w->d_taps, sizeof(float) * taps_length);
     alloc(w->d_last[0], sizeof(float) * n_streams);
     alloc(w->d_last[1], sizeof(float) * n_streams);
@@ -361,6 +398,10 @@ int csdr_amd_wfm_reset(csdr_amd_wfm *w)
     w->phase = 0.f;
     CSDR_HIP(hipMemsetAsync(w->d_last[0].get(), 0, sizeof(float) * w->n_streams, st));
     CSDR_HIP(hipMemsetAsync(w->d_last[1].get(), 0, sizeof(float) * w->n_streams, st));
+    if (w->exact) {
+        CSDR_HIP(hipMemsetAsync(w->d_state.get(), 0, sizeof(float) * w->n_streams, st));
+        CSDR_HIP(hipMemsetAsync(w->d_xf.get(), 0, sizeof(float) * w->x_pitch * w->n_streams, st));      // (convert_f_s16 runs over whole rows)
+    }
     if (w->d_rot) CSDR_HIP(hipMemsetAsync(w->d_rot.get(), 0, sizeof(cf32) * (HIST + w->max_block + 64), st));
     if (w->d_hist) CSDR_HIP(hipMemsetAsync(w->d_hist.get(), 0x80, (size_t)2 * HIST * w->n_streams, st));
     for (int k = 0; k < 2; k++) if (w->d_head[k]) CSDR_HIP(hipMemsetAsync(w->d_head[k].get(), 0x80, wfm_mfma_head_bytes(w->n_streams), st));      // 0x80 = zero samples in front of the stream
@@ -374,6 +415,17 @@ int csdr_amd_wfm_reset(csdr_amd_wfm *w)
 
 const char *csdr_amd_wfm_kernel_name(const csdr_amd_wfm *w) { return w->kernel_name.c_str(); }
 int csdr_amd_wfm_fallback(const csdr_amd_wfm *w) { return w->use_mfma ? 0 : 1; }
+int csdr_amd_wfm_exact_deemphasis(const csdr_amd_wfm *w) { return w->exact ? 1 : 0; }
+
+// the de-emphasis state the next call starts from (libcsdr.c:1081-1097's last_output), one float per stream from host memory
+int csdr_amd_wfm_set_deemphasis_state(csdr_amd_wfm *w, const float *host_state)
+{
+    if (!w || !host_state) return fail_msg(-3, "wfm_set_deemphasis_state: bad arguments");
+    CSDR_HIP(hipStreamSynchronize(w->ctx->stream));
+    float *dst = w->exact ? w->d_state.get() : w->d_last[w->flip].get();
+    CSDR_HIP(hipMemcpy(dst, host_state, sizeof(float) * w->n_streams, hipMemcpyHostToDevice));
+    return 0;
+}
 
 int csdr_amd_wfm_seed_stats(const csdr_amd_wfm *w, long out[5])
 {
@@ -476,13 +528,20 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
     const long long n_audio_ll = j_hi - w->next_j + 1;
     const int n_audio = n_audio_ll > 0 ? (int)n_audio_ll : 0;
     if (n_audio > 0 && (size_t)n_audio > out_pitch) return fail_msg(-3, "wfm: out_pitch %zu smaller than the %d audio samples of this block", out_pitch, n_audio);
+    // where the kernels write and with which alpha.  The exact route: alpha = 1 into the object's scratch rows; the kernels' carried state stays what reset made it
+    // (d_last[0] = 0 is only read, d_last[1] takes what they leave: flip stays 0), the real state is d_state's
+    int16_t *k_s16 = audio_s16; float *k_af = audio_f; size_t k_pitch = out_pitch; float k_alpha = w->alpha;
+    if (w->exact) {
+        if ((size_t)n_audio > w->x_pitch) return fail_msg(-3, "wfm: internal audio rows too small");
+        k_s16 = w->d_xs.get(); k_af = w->d_xf.get(); k_pitch = w->x_pitch; k_alpha = 1.f;
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (w->profiling && n_audio > 0) { if (const int trc = w->timer.take(&e0, &e1)) return trc; }
     if (w->use_mfma) {
         // the whole chain, the carried de-emphasis state and the next call's history in ONE launch (wfm_mfma.hip)
         WfmBackArgs back;
-        back.alpha = w->alpha; back.last_in = w->d_last[w->flip].get(); back.last_out = w->d_last[w->flip ^ 1].get();
-        back.s16 = audio_s16; back.af = audio_f; back.out_pitch = out_pitch; back.head_in = w->d_head[w->hflip].get(); back.head_out = w->d_head[w->hflip ^ 1].get();
+        back.alpha = k_alpha; back.last_in = w->d_last[w->flip].get(); back.last_out = w->d_last[w->flip ^ 1].get();
+        back.s16 = k_s16; back.af = k_af; back.out_pitch = k_pitch; back.head_in = w->d_head[w->hflip].get(); back.head_out = w->d_head[w->hflip ^ 1].get();
         WfmPerStream psa; memset(&psa, 0, sizeof psa);
         if (w->ps) {
             psa.tab_pitch = sv.pitch; psa.tab_len = sv.n_entries; psa.d_scales = w->d_scales.get();
@@ -513,7 +572,7 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
         if (rc) return rc;
         if (n_audio > 0) w->retuned.clear();
         w->hflip ^= 1;
-        if (n_audio > 0) w->flip ^= 1;
+        if (n_audio > 0 && !w->exact) w->flip ^= 1;
     } else {
         if ((size_t)n_audio + 40 > w->demod_pitch) return fail_msg(-3, "wfm: internal audio buffer too small");
         if (n_audio > 0) {
@@ -527,15 +586,25 @@ long csdr_amd_wfm_process(csdr_amd_wfm *w, const uint8_t *in, size_t in_pitch, s
             CSDR_LAUNCH_CHECK();
             if (e1) CSDR_HIP(hipEventRecord(e1, st));
             hipLaunchKernelGGL(k_wfm_back, dim3(cdiv(n_audio, BK_CHUNK), w->n_streams), dim3(256), 0, st,
-                               w->d_demod.get(), w->demod_pitch, 0, n_audio, w->alpha, w->d_last[w->flip].get(), w->d_last[w->flip ^ 1].get(), audio_s16, audio_f, out_pitch);
+                               w->d_demod.get(), w->demod_pitch, 0, n_audio, k_alpha, w->d_last[w->flip].get(), w->d_last[w->flip ^ 1].get(), k_s16, k_af, k_pitch);
             CSDR_LAUNCH_CHECK();
-            w->flip ^= 1;
+            if (!w->exact) w->flip ^= 1;
         }
         // 3. history for the next block
         if (T >= HIST) {
             hipLaunchKernelGGL(k_wfm_save_hist, dim3(w->n_streams), dim3(256), 0, st, in, in_pitch, T, w->d_hist.get());
             CSDR_LAUNCH_CHECK();
         }
+    }
+    if (w->exact && n_audio > 0) {
+        // the reference's recurrence over the call's samples from the carried state (NaN reset: libcsdr.c:1092), then convert_f_s16, into the caller's rows
+        float *xf = w->d_xf.get();
+        rc = csdr_amd_deemphasis_wfm_ff(c, xf, xf, w->n_streams, (size_t)n_audio, w->x_pitch, w->x_pitch, w->tau, w->audio_rate, w->d_state.get());
+        if (rc) return rc;
+        if (audio_f) CSDR_HIP(hipMemcpy2DAsync(audio_f, sizeof(float) * out_pitch, xf, sizeof(float) * w->x_pitch, sizeof(float) * n_audio, w->n_streams, hipMemcpyDeviceToDevice, st));
+        rc = csdr_amd_convert_f_s16(c, xf, w->d_xs.get(), w->x_pitch * w->n_streams);
+        if (rc) return rc;
+        CSDR_HIP(hipMemcpy2DAsync(audio_s16, sizeof(int16_t) * out_pitch, w->d_xs.get(), sizeof(int16_t) * w->x_pitch, sizeof(int16_t) * n_audio, w->n_streams, hipMemcpyDeviceToDevice, st));
     }
     if (T % 1024) w->ended = true;
     w->B += T; w->next_j += n_audio; w->last_T = T;

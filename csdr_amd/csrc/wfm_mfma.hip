@@ -179,7 +179,8 @@ __device__ __forceinline__ void wfm_chain(const v4i (&A)[WFM_NK * 3], const v4i 
 // steps' samples per stream, done by the loader waves, which hold the s16 lines in registers until 5.5 KiB per stream go out together (see "Stores"
 // in the kernel): the demodulated audio never goes to HBM as floats.  A segment
 // that starts in the middle of a call demodulates two steps (48 audio samples) ahead of its range from zero state without storing them --
-// the filter forgets as 0.706^k --; the first segment starts from the exact state the previous call left, the last one leaves its own.
+// the filter forgets as b^k, b = 1 - alpha: 0.706^k at 50 us / 48 kHz; where b^48 > 2^-20 the object hands alpha = 1 down and runs the filter behind the kernel, wfm.hip --;
+// the first segment starts from the exact state the previous call left, the last one leaves its own.
 //
 // A call's edges, all inside this launch:
 //   * history: the first tiles' windows start up to 512 bytes in front of the block.  Ring coordinates run from -1024: the run [-1024, 0) is
@@ -259,7 +260,9 @@ __device__ unsigned long long g_wfm_life[SEQ_NW][4];      // per wave, summed ov
 // tile is recomputed from there; so a workgroup that leaves can be replaced by a new launch at any block boundary: it leaves when the host says stop, when no block
 // arrived for idle_ticks, or when the launch is older than life_ticks (a stalled host or a bug cannot hold the GPU), by raising `exiting` for all others and storing its
 // next item.  The host relaunches on demand (wfm_ring.hip).
-constexpr int RES_WARM = 48;              // audio samples in front of a block over which a retune's de-emphasis state is rebuilt (0.706^48 = 5e-8)
+constexpr int RES_WARM = 48;              // audio samples in front of a block over which a retune's de-emphasis state is rebuilt.  What is left of the state in front of them
+                                          // is (1 - alpha)^48: 5e-8 at tau = 50 us / 48 kHz, but 2e-3 at 75 us / 96 kHz -- a property of tau and the audio rate, not of the method.
+                                          // csdr_amd_wfm_deemph_exact (wfm.hip) is the rule; the ring refuses parameters at which 48 samples are too few
 struct ResCtl {
     const uint32_t *desc;                  // host: [n_slots][desc_lines][16]: dword 0 = tag of the block, 1 = lead samples (a retune), 2.. = 7 x (cos, sin) of chunks first_chunk - 4 ...
     const uint32_t *ctrl;                  // host: [0] = stop
@@ -1145,6 +1148,9 @@ int wfm_mfma_launch_resident(hipStream_t st, hipEvent_t ev_end, const WfmMfmaDev
     if (ev_end) CSDR_HIP(hipEventRecord(ev_end, st));
     return 0;
 }
+// every segment but a call's first, every column of a per-stream call but its first and every ring block runs n_warm = 2 steps of 4 SEQ_TPG audio samples from zero
+// state in front of its own samples (k_wfm_mfma_seq: n_warm, SPS)
+int wfm_mfma_warm_samples() { return 2 * 4 * SEQ_TPG; }
 int wfm_resident_max_grid() { return current_device_cu_count(); }      // one workgroup per CU: eight waves of up to 256 registers fill a CU's register files
 
 } // namespace csdr_amd

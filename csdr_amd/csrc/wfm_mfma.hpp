@@ -44,6 +44,8 @@ struct WfmResident {
     unsigned long long *stats; int fence_mode;
 };
 constexpr int WFM_RES_WARM = 48;   // = RES_WARM (wfm_mfma.hip)
+// audio samples over which a time segment, a column or a ring block of k_wfm_mfma_seq warms its de-emphasis up from zero state (its n_warm steps of 4 SEQ_TPG samples)
+int wfm_mfma_warm_samples();
 int wfm_mfma_launch_resident(hipStream_t st, hipEvent_t ev_end, const WfmMfmaDevice &dev, int n_streams, size_t in_pitch, float alpha, size_t out_pitch, const WfmResident &rv, int grid);
 int wfm_resident_max_grid();
 int wfm_mfma_lead_shared(hipStream_t st, const uint8_t *in, size_t in_pitch, const uint8_t *prev, size_t two_T, const float *d_taps, const float2 *ctab, const float2 *d_dtab,

@@ -13,7 +13,7 @@
 //
 // A work item is (block k, 16-stream group sb); workgroup w of G takes the items k n_wsb + sb = w (mod G), so consecutive blocks of a stream group run on
 // different workgroups at the same time (1024 streams: 64 groups x 4 blocks in flight fill 256 CUs).  No state passes from block to block on the device -- each
-// block warms its de-emphasis up over the 48 audio samples in front of it, read from the previous slot (the filter forgets as 0.706^k: 5e-8 after 48) -- so
+// block warms its de-emphasis up over the 48 audio samples in front of it, read from the previous slot (the filter forgets as (1 - alpha)^k: 5e-8 after 48 at 50 us / 48 kHz; create refuses a tau / audio rate at which 48 leave more than 2^-20) -- so
 // the grid can leave at any block boundary and a new launch continues: it leaves when told to (stop word), when nothing arrived for idle_us, or when it is
 // older than life_ms.  A stalled host, or a bug in the walk, therefore cannot hold the GPU; a killed host process loses its queues to the driver like any other.
 // submit() / wait() relaunch on demand (hipEventQuery on the event behind the launch).
@@ -156,6 +156,12 @@ csdr_amd_wfm_ring *csdr_amd_wfm_ring_create(csdr_amd_ctx *ctx, int n_streams, fl
     if (n_slots < 3 || n_slots > 64) { fail_msg(-3, "wfm ring: 3 .. 64 slots (got %d)", n_slots); return nullptr; }
     // the two warm-up steps (12 tiles) and the first window in front of a block must lie inside the previous block
     if ((size_t)(12 * 4 * decimation * frac_rate + 2 * WFM_HIST + 1024) > block_samples) { fail_msg(-3, "wfm ring: block of %zu samples shorter than the warm-up reach", block_samples); return nullptr; }
+    // the grid stores s16 straight into the output ring: there is no place for the exact de-emphasis route's second pass (wfm.hip)
+    if (csdr_amd_wfm_deemph_exact(tau, audio_rate, csdr_amd_wfm_deemph_warm_samples(2))) {
+        fail_msg(-3, "wfm ring: de-emphasis tau %g s at audio_rate %d forgets too slowly for the ring's %d-sample warm-up in front of every block; use csdr_amd_wfm_process, which runs it exactly",
+                 (double)tau, audio_rate, csdr_amd_wfm_deemph_warm_samples(2));
+        return nullptr;
+    }
     (void)hipSetDevice(ctx->device);
     Owned<csdr_amd_wfm_ring, csdr_amd_wfm_ring_destroy> r(new csdr_amd_wfm_ring());
     r->ctx = ctx; r->S = n_streams; r->D = decimation; r->L = taps_length; r->F = frac_rate; r->T = (int)block_samples; r->N = n_slots; r->audio_rate = audio_rate;

@@ -1103,7 +1103,22 @@ int  csdr_amd_fastddc_inv_block(csdr_amd_ctx *ctx, const csdr_complexf *d_spectr
  * varying complex factor common to y[k] and y[k-1], which fmdemod_quadri_cf cancels: the audio is within the stated tolerance at every rate
  * (tests/test_edges_gpu.py::test_wfm_other_shift_rates), but the object's INTERNAL complex samples are not a substitute for
  * `convert_u8_f | shift_addition_cc | fir_decimate_cc` at such rates.  The complex front end for that is csdr_amd_ddc_* below, which replays the
- * drift per chunk (k_ddc_corr) and is held to 1e-5 on the complex samples themselves. */
+ * drift per chunk (k_ddc_corr) and is held to 1e-5 on the complex samples themselves.
+ *
+ * De-emphasis, tau and audio_rate.  The chain kernels cut a call's audio into time segments; every segment but the call's first starts its one-pole de-emphasis
+ * from zero state W samples early, and W is fixed by the code: 48 in the matrix-core chain kernel (two steps of 24 samples; shared rate, rate per stream and the
+ * resident ring alike; the ring also rebuilds the state behind a retune over 48), 48 in the fallback's k_wfm_back (csdr_amd_wfm_deemph_warm_samples).  A seam is
+ * wrong by b^W of the true state, b = 1 - alpha, alpha = dt / (tau + dt), dt = (float)(1.0 / audio_rate), all in float (libcsdr.c:1090-1091).  The rule
+ * csdr_amd_wfm_deemph_exact(tau, audio_rate, W) returns 1 when b^W > 2^-20 (2^-20 of a full-scale state is 0.03 LSB of the s16 audio: below it a seam leaves the
+ * chain's +-1 LSB to the front end).  Where it says 1 an object of csdr_amd_wfm_create / _create_rates takes the EXACT route: the same kernels with alpha = 1 (their
+ * de-emphasis is then the identity) write float rows owned by the object, and csdr_amd_deemphasis_wfm_ff with the object's carried state and
+ * csdr_amd_convert_f_s16 follow: three more small launches and two copies per call, results the reference's at every tau and rate.  Where it says 0 -- the default
+ * 50e-6 / 48000 (b^48 = 5.5e-8), 50e-6 / 44100, 5e-6 / 48000 -- nothing changes.  On the exact route at W = 48: 75e-6 / 48000 (7.8e-6), 50e-6 / 96000 (1.1e-4),
+ * 75e-6 / 96000 (1.9e-3), 75e-6 / 192000 (4.0e-2), 1e-3 / 48000 (0.37).  csdr_amd_wfm_exact_deemphasis reports the route an object took;
+ * csdr_amd_wfm_ring_create refuses the parameters of the exact route. */
+int csdr_amd_wfm_deemph_exact(float tau, int audio_rate, int warm_samples);
+/* the fewest audio samples a path warms up over.  path 0: the matrix-core chain kernel per call, 1: the fallback (k_wfm_back), 2: the resident ring */
+int csdr_amd_wfm_deemph_warm_samples(int path);
 typedef struct csdr_amd_wfm csdr_amd_wfm;
 csdr_amd_wfm *csdr_amd_wfm_create(csdr_amd_ctx *ctx, int n_streams, float shift_rate, int decimation,
                                   const float *host_taps, int taps_length, int frac_rate,
@@ -1132,6 +1147,11 @@ const char *csdr_amd_wfm_kernel_name(const csdr_amd_wfm *w);
 /* 1 when the object runs outside the matrix-core chain kernel (k_wfm_front + k_wfm_back: decimation x audio decimation odd, filters beyond the 256-sample window;
  * CSDR_AMD_WFM_PATH=valu): same results at about a sixth of the rate.  The CLI prints a one-line note on stderr. */
 int csdr_amd_wfm_fallback(const csdr_amd_wfm *w);
+/* 1 when the object runs its de-emphasis as a pass of its own behind the chain kernel (the exact route above: csdr_amd_wfm_deemph_exact said 1 for its tau, audio
+ * rate and the warm-up of the kernel it uses) */
+int csdr_amd_wfm_exact_deemphasis(const csdr_amd_wfm *w);
+/* sets the de-emphasis state the next call starts from (the reference's last_output, libcsdr.c:1081-1097; a NaN restarts from 0 as there): host float[n_streams] */
+int csdr_amd_wfm_set_deemphasis_state(csdr_amd_wfm *w, const float *host_state);
 /* as csdr_amd_ddc_seed_stats / csdr_amd_ddc_tables_built (the WFM chain has no drift corrections: out[4] stays 0) */
 int  csdr_amd_wfm_seed_stats(const csdr_amd_wfm *w, long out[5]);
 long csdr_amd_wfm_tables_built(const csdr_amd_wfm *w);
@@ -1156,7 +1176,10 @@ int csdr_amd_wfm_kernel_time(csdr_amd_wfm *w, double *total_ms, long *launches);
  *     n = csdr_amd_wfm_ring_wait(r, seq, 0);                     -- audio samples per stream of that block, in csdr_amd_wfm_ring_output(r, seq, &pitch); valid until
  *                                                                   block seq + n_slots is posted.  Up to n_slots - 2 blocks may be in flight.
  * The grid never holds the GPU against a silent host: it leaves by itself when no block arrived for idle_us (default 200) or when it is older than life_ms (default
- * 250), and is relaunched by the next submit / wait; no state lives in it (every block warms its de-emphasis up over the 48 audio samples in front of it).  While it is
+ * 250), and is relaunched by the next submit / wait; no state lives in it: every block warms its de-emphasis up from zero state over the 48 audio samples in front of
+ * it, which leaves (1 - alpha)^48 of the true state at a block's first sample.  That is 5.5e-8 at tau = 50e-6 / 48000 and grows with tau and the audio rate, so
+ * csdr_amd_wfm_ring_create returns NULL (-3, the message names tau and audio_rate) where csdr_amd_wfm_deemph_exact(tau, audio_rate, 48) is 1 -- e.g. 75e-6 / 48000,
+ * 75e-6 / 96000, 1e-3 / 48000: the grid stores s16 straight into the output ring and has no place for a second pass; use csdr_amd_wfm_process there.  While it is
  * resident it occupies every CU it runs on (one workgroup per CU): other kernels of the process wait for it to leave.
  * block_samples: a multiple of 1024, 4096 .. 65536.  Retune: csdr.c:881-923 semantics (from the next posted block's first sample, phase carried). */
 typedef struct csdr_amd_wfm_ring csdr_amd_wfm_ring;
