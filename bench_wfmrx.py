@@ -9,8 +9,16 @@ alternately in the same process over `--repeats` runs of `--steps` steps each (m
 code, and the fraction of the HBM bound for 8 bytes in + 2 / rate bytes out per input sample at 8 TB/s.  --verify compares sampled channels of the two paths bit
 for bit (s16 and the float tap) over two steps, and with the oracle's four stages under the test suite's gates.
 
+--squelch measures the bank with squelch_and_smeter_cc in front of every channel (csdr_amd_wfmrx_create_squelched: block 1024, use_every_nth 1) instead: the fused
+path (k_fmrx_power, then k_wfmrx_front_sq, which gates the samples as it loads them and does not fetch closed blocks) against the composed path (csdr_amd.Squelch
+into a second row buffer, then csdr_amd.WfmRx on its one-kernel path), same input, same process, alternating runs.  --pattern block: every block of a row has its
+own amplitude and the row's level lies between two of its block powers so that --closed-fraction of its blocks close; --pattern channel: that share of the
+channels is closed throughout and the others are open.  --verify compares sampled channels of the two bit for bit over two steps (s16, float tap), their open
+flags with the float64 block powers, and the fused path with the oracle's four stages on the gated rows under the test suite's gates.
+
 One JSON line:
     python bench_wfmrx.py [--gpus 1] [--steps K] [--warmup W] [--repeats R] [--channels 4096] [--block 49152] [--rate 5] [--verify] [--json-out FILE]
+                          [--squelch [--closed-fraction 0.5] [--pattern channel|block]]
 """
 import argparse
 import json
@@ -58,6 +66,149 @@ def oracle_gates(x_row, rate, s16, af):
         return float("inf"), 1 << 16, 1.0
     d = np.abs(s16.astype(np.int32) - want.astype(np.int32))
     return oracle.relrms(af, e), int(d.max()), float((d > 0).mean())
+
+
+SQ_BLOCK = 1024
+
+
+def squelch_bytes_per_sample(rate, closed):
+    """bytes per input sample, from the kernels' loads and stores:
+      composed  k_squelch_wave 8 in + 8 out; then the fused WFM path on the second buffer, 8 + 10 / rate
+      fused     k_fmrx_power 8 in; k_wfmrx_front_sq 8 in for the samples of open blocks only + 4 / rate out; k_wfmrx_tail (4 + 2) / rate"""
+    return {"composed": 24 + 10 / rate, "fused": 8 + 8 * (1.0 - closed) + 10 / rate}
+
+
+def make_squelch_rows(S, N, closed, pattern):
+    """make_rows and a level per row.  block: every block of SQ_BLOCK samples at an amplitude of its own, the level under which `closed` of the row's blocks
+    close (0: all open).  channel: the rows as they are; the first round(closed * S) channels, spread evenly, at a level above every block power, the others 0"""
+    import numpy as np
+    x = make_rows(S, N)
+    nb = N // SQ_BLOCK
+    if pattern == "channel":
+        c = int(round(closed * S))
+        levels = np.zeros(S, np.float32)
+        if c:
+            levels[np.unique(np.linspace(0, S - 1, c).astype(int))] = 10.0
+        return x, levels
+    distinct = min(DISTINCT, S)
+    levels = np.zeros(distinct, np.float32)
+    for r in range(distinct):
+        rng = np.random.default_rng(900 + r)
+        scale = (0.2 + 0.8 * rng.permutation(nb) / max(nb - 1, 1)).astype(np.float32)     # nb distinct amplitudes: no two block powers close to one another
+        x[r::distinct, :nb * SQ_BLOCK] *= np.repeat(scale, SQ_BLOCK)[None, :]
+        blocks = x[r, :nb * SQ_BLOCK].reshape(nb, SQ_BLOCK).astype(np.complex128)
+        P = np.sort((np.abs(blocks) ** 2).mean(axis=1))
+        c = int(round(closed * nb))
+        levels[r] = 0.0 if c == 0 else 2 * P[-1] if c >= nb else 0.5 * (P[c - 1] + P[c])
+    return x, np.tile(levels, (S + distinct - 1) // distinct)[:S]
+
+
+def run_squelch(ctx, x_host, levels, args):
+    import numpy as np
+    import torch
+    import csdr_amd
+    S, N = x_host.shape
+    x = torch.view_as_real(torch.from_numpy(x_host)).cuda()
+    gated = torch.empty((S, N, 2), dtype=torch.float32, device="cuda")                      # the composed path's second row buffer
+    rows = sorted(set(int(v) for v in np.linspace(0, S - 1, SAMPLED)))
+    fused = csdr_amd.WfmRx(ctx, S, rate=args.rate, max_samples_per_call=N, squelch_block=SQ_BLOCK, use_every_nth=1, levels=levels)
+    sq = csdr_amd.Squelch(ctx, S, SQ_BLOCK, 1, levels, max_samples_per_call=N)
+    rx = csdr_amd.WfmRx(ctx, S, rate=args.rate, max_samples_per_call=N)
+    op = fused.max_output(N)
+    y = torch.empty((S, op), dtype=torch.int16, device="cuda")
+    nb = N // SQ_BLOCK + 1
+    flags = torch.empty((S, nb), dtype=torch.uint8, device="cuda")
+
+    def step_fused(f=None, fl=None):
+        return fused.process_squelched_dev(x.data_ptr(), N, N, y.data_ptr(), f, op, None, nb, fl)[0]
+
+    def step_composed(f=None):
+        k = sq.process_dev(x.data_ptr(), N, N, gated.data_ptr(), N)
+        return rx.process_dev(gated.data_ptr(), N, k * SQ_BLOCK, y.data_ptr(), f, op) if k else 0
+
+    res = {"closed_fraction_asked": args.closed_fraction, "pattern": args.pattern}
+    torch.cuda.synchronize()
+    if args.verify:
+        if N % SQ_BLOCK:
+            raise SystemExit("--squelch --verify needs --block to be a multiple of %d" % SQ_BLOCK)
+        f = torch.empty((S, op), dtype=torch.float32, device="cuda")
+        kept = {"fused": [], "composed": []}
+        for name, step in (("fused", lambda: step_fused(f.data_ptr(), flags.data_ptr())), ("composed", lambda: step_composed(f.data_ptr()))):
+            for _ in range(2):
+                got = step()
+                ctx.sync()
+                kept[name].append((got, y[rows, :got].cpu().numpy(), f[rows, :got].cpu().numpy()))
+        same = all(a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32)) for a, b in zip(kept["fused"], kept["composed"]))
+        fl = flags[:, :N // SQ_BLOCK].cpu().numpy()
+        res["closed_fraction"] = round(1.0 - float(fl.mean()), 4)
+        figures, flags_ok = [], True
+        for i, r in enumerate(rows):                                     # the oracle on the rows gated by the float64 block powers (no block is near its level)
+            blocks = x_host[r].reshape(-1, SQ_BLOCK)
+            P = (np.abs(blocks.astype(np.complex128)) ** 2).mean(axis=1)
+            want_open = (P >= float(levels[r])) | (levels[r] == 0)
+            flags_ok = flags_ok and np.array_equal(fl[r].astype(bool), want_open)
+            g = (blocks * want_open[:, None]).reshape(-1).astype(np.complex64)
+            s16 = np.concatenate([kept["fused"][0][1][i], kept["fused"][1][1][i]])
+            af = np.concatenate([kept["fused"][0][2][i], kept["fused"][1][2][i]])
+            if want_open.any():
+                figures.append(oracle_gates(np.concatenate([g, g]), args.rate, s16, af))
+            else:
+                figures.append((0.0, 0, 0.0) if not s16.any() and not af.any() else (float("inf"), 1 << 16, 1.0))
+        gates = all(rr <= 1e-5 and dmax <= 1 and frac < 0.01 for rr, dmax, frac in figures)
+        res["verify"] = {"rows": rows, "steps": 2, "paths_same_bits": bool(same), "flags_ok": bool(flags_ok), "oracle_relrms_max": max(v[0] for v in figures),
+                         "oracle_s16_max_diff": max(v[1] for v in figures), "oracle_s16_differing_max": max(v[2] for v in figures),
+                         "ok": bool(same and flags_ok and gates and kept["fused"][0][0] > 0)}
+        del f
+        fused.reset(); sq.reset(); rx.reset()
+    steps = {"fused": step_fused, "composed": step_composed}
+    ms = {"fused": [], "composed": []}
+    out = {}
+    for name, step in steps.items():
+        for _ in range(1 + args.warmup):
+            out[name] = step()
+    ctx.sync()
+    for _ in range(args.repeats):                                        # the two paths alternate run by run
+        for name, step in steps.items():
+            ctx.timer_start()
+            for _ in range(args.steps):
+                step()
+            ms[name].append(ctx.timer_stop_ms() / args.steps)
+    bps = squelch_bytes_per_sample(args.rate, res.get("closed_fraction", args.closed_fraction))
+    for name in steps:
+        v = sorted(ms[name])
+        res[name] = {"kernel": (fused if name == "fused" else rx).kernel_name(), "samples_out_per_step": out[name], "event_ms_per_step": round(v[len(v) // 2], 4),
+                     "event_ms_min": round(v[0], 4), "event_ms_max": round(v[-1], 4), "steps": args.steps, "repeats": args.repeats,
+                     "bytes_per_input_sample": round(bps[name], 2), "GBs_moved": round(bps[name] * S * N / (v[len(v) // 2] * 1e-3) / 1e9, 1)}
+    res["composed"]["squelch_kernel"] = sq.kernel_name()
+    res["fused_over_composed"] = round(res["fused"]["event_ms_per_step"] / res["composed"]["event_ms_per_step"], 4)
+    res["fused_faster_beyond_spread"] = bool(res["fused"]["event_ms_max"] < res["composed"]["event_ms_min"])
+    res["fused_slower_beyond_spread"] = bool(res["fused"]["event_ms_min"] > res["composed"]["event_ms_max"])
+    for o in (fused, sq, rx):
+        o.close()
+    return res
+
+
+def main_squelch(ctx, args):
+    S, N = args.channels, args.block
+    x, levels = make_squelch_rows(S, N, args.closed_fraction, args.pattern)
+    r = run_squelch(ctx, x, levels, args)
+    t = r["fused"]
+    res = {"metric": "MS/s in, squelched WFM receive bank on baseband (squelch_and_smeter_cc .. convert_f_s16) x N channels",
+           "value": round(S * N / (t["event_ms_per_step"] * 1e-3) / 1e6, 1), "unit": "complex MS/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": t["event_ms_per_step"], "event_ms_per_step": t["event_ms_per_step"], "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": round(1.0 / r["fused_over_composed"], 3), "dtype": "complexf -> s16", "data": "generated",
+           "config": {"workload": "squelched WFM receive bank on baseband, batched", "channels": S, "block_samples_per_channel": N, "rate": args.rate, "num_poly_points": 12,
+                      "window": 1024, "audio_rate": 48000, "tau": 50e-6, "squelch_block": SQ_BLOCK, "use_every_nth": 1, "closed_fraction": args.closed_fraction,
+                      "pattern": args.pattern,
+                      "baseline": "csdr_amd.Squelch into a second row buffer, then csdr_amd.WfmRx (its one-kernel path), same input, same process, alternating runs",
+                      "hbm_peak_GBs": bc.HBM_PEAK_GBS},
+           "roofline": {"bound": "hbm", "kernel": t["kernel"], "kernel_avg_ms": t["event_ms_per_step"],
+                        "timer": "HIP events on the context's stream around the objects' calls",
+                        "frac": round(t["bytes_per_input_sample"] * S * N / bc.HBM_PEAK_GBS / 1e9 / (t["event_ms_per_step"] * 1e-3), 4)},
+           "result": r}
+    if args.verify:
+        res["verify"] = {"ok": r["verify"]["ok"]}
+    return res
 
 
 def run(ctx, x_host, args):
@@ -142,6 +293,9 @@ def main():
     ap.add_argument("--rate", type=float, default=5.0, help="fractional_decimator_ff's rate")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--json-out", default=None, help="also append the result line to this file")
+    ap.add_argument("--squelch", action="store_true", help="measure the squelched bank: the fused path against csdr_amd.Squelch -> csdr_amd.WfmRx")
+    ap.add_argument("--closed-fraction", type=float, default=0.5, help="--squelch: the share of the squelch blocks that close")
+    ap.add_argument("--pattern", choices=("channel", "block"), default="block", help="--squelch: closed blocks within every row, or whole channels closed")
     args = ap.parse_args()
     if args.gpus != 1:
         raise SystemExit("bench_wfmrx.py measures one GPU (--gpus 1)")
@@ -151,6 +305,17 @@ def main():
     import csdr_amd
     ctx = csdr_amd.Context(0)
     S, N = args.channels, args.block
+    if args.squelch:
+        res = main_squelch(ctx, args)
+        line = json.dumps(res)
+        print(line, flush=True)
+        if args.json_out:
+            with open(args.json_out, "a") as f:
+                f.write(line + "\n")
+        ctx.close()
+        if args.verify and not res["verify"]["ok"]:
+            raise SystemExit(1)
+        return
     r = run(ctx, make_rows(S, N), args)
     t = r["fused"]
     res = {"metric": "MS/s in, WFM receive bank on baseband (fmdemod_quadri_cf .. convert_f_s16) x N channels", "value": round(S * N / (t["event_ms_per_step"] * 1e-3) / 1e6, 1),

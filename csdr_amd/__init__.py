@@ -439,6 +439,13 @@ def lib():
     L.csdr_amd_wfmrx_plan.argtypes = [fl, i, i, i, fl, i, ll, C.POINTER(ll), C.POINTER(fl), C.POINTER(i)]
     L.csdr_amd_wfmrx_held.argtypes = [vp]
     L.csdr_amd_wfmrx_where.restype = fl; L.csdr_amd_wfmrx_where.argtypes = [vp]
+    L.csdr_amd_wfmrx_create_squelched.restype = vp; L.csdr_amd_wfmrx_create_squelched.argtypes = [vp, i, fl, i, vp, i, i, fl, i, sz, i, i, vp]
+    L.csdr_amd_wfmrx_process_squelched.restype = ll; L.csdr_amd_wfmrx_process_squelched.argtypes = [vp, vp, sz, ll, vp, vp, sz, vp, sz, vp, C.POINTER(i)]
+    L.csdr_amd_wfmrx_squelch_plan.argtypes = [i, ll, i, C.POINTER(ll), C.POINTER(i)]
+    L.csdr_amd_wfmrx_set_squelch_level.argtypes = [vp, i, fl]
+    L.csdr_amd_wfmrx_get_squelch_level.argtypes = [vp, i, C.POINTER(fl)]
+    L.csdr_amd_wfmrx_squelch_held.argtypes = [vp]
+    L.csdr_amd_wfmrx_squelch_block_index.restype = ll; L.csdr_amd_wfmrx_squelch_block_index.argtypes = [vp]
     _lib = L
     return L
 
@@ -2135,16 +2142,39 @@ def wfmrx_plan(rate, num_poly_points, taps_length, window, where, held, n_in):
     return no.value, nw.value, nh.value
 
 
+def wfmrx_squelch_plan(held, n_in, block):
+    """csdr_amd_wfmrx_squelch_plan (a host function): a call of n_in samples on a squelched object that holds `held` -> (gated samples handed to the demodulator,
+    samples held afterwards)"""
+    m, nh = C.c_longlong(), C.c_int()
+    if lib().csdr_amd_wfmrx_squelch_plan(int(held), int(n_in), int(block), C.byref(m), C.byref(nh)) < 0:
+        raise CsdrAmdError(lib().csdr_amd_last_error().decode())
+    return m.value, nh.value
+
+
 class WfmRx(_Handle, _MaxOut, _PerChannel):
     """csdr_amd_wfmrx: fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 for n_channels rows of complex baseband on the device;
-    the decimator's unprocessed samples and position, the previous sample and the de-emphasis state stay in the object between calls."""
+    the decimator's unprocessed samples and position, the previous sample and the de-emphasis state stay in the object between calls.  squelch_block > 0:
+    squelch_and_smeter_cc in blocks of squelch_block samples in front of every channel (csdr_amd_wfmrx_create_squelched); levels: one level or n_channels
+    (None: 0, always open).  plan() then applies to the gated samples wfmrx_squelch_plan hands on."""
 
-    def __init__(self, ctx, n_channels, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16):
+    def __init__(self, ctx, n_channels, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16,
+                 squelch_block=0, use_every_nth=1, levels=None):
         taps = None if prefilter_taps is None else np.ascontiguousarray(prefilter_taps, f32)
         self.n_channels, self.rate, self.num_poly_points, self.window = n_channels, float(f32(rate)), num_poly_points, window or 1024
-        self.taps_length = 0 if taps is None else taps.size
-        _Handle.__init__(self, ctx, "wfmrx", ctx.L.csdr_amd_wfmrx_create(ctx.h, n_channels, rate, num_poly_points, taps.ctypes.data if taps is not None else None,
-                                                                         self.taps_length, window, tau, audio_rate, max_samples_per_call))
+        self.taps_length, self.squelch_block = 0 if taps is None else taps.size, squelch_block
+        tp = taps.ctypes.data if taps is not None else None
+        if squelch_block == 0 and use_every_nth == 1 and levels is None:
+            h = ctx.L.csdr_amd_wfmrx_create(ctx.h, n_channels, rate, num_poly_points, tp, self.taps_length, window, tau, audio_rate, max_samples_per_call)
+        else:
+            lv = None if levels is None else np.ascontiguousarray(np.broadcast_to(np.asarray(levels, f32), (max(n_channels, 0),)))
+            h = ctx.L.csdr_amd_wfmrx_create_squelched(ctx.h, n_channels, rate, num_poly_points, tp, self.taps_length, window, tau, audio_rate, max_samples_per_call,
+                                                      squelch_block, use_every_nth, None if lv is None else _hp(lv))
+        _Handle.__init__(self, ctx, "wfmrx", h)
+
+    # ---- the squelch in front (squelch_block > 0): FmRx's methods, which reach the library through the object's own prefix
+    set_squelch_level, get_squelch_level = FmRx.set_squelch_level, FmRx.get_squelch_level
+    squelch_held, squelch_block_index = FmRx.squelch_held, FmRx.squelch_block_index
+    process_squelched_dev, process_squelched = FmRx.process_squelched_dev, FmRx.process_squelched
 
     def max_output(self, n_in):
         return int(self._fn("max_output")(self.h, int(n_in)))
@@ -2959,9 +2989,11 @@ class Context:
         return FmRx(self, n_channels, audio_rate, agc_block, reference, limit, max_samples_per_call, squelch_block, use_every_nth, levels)
 
     # ---- the WFM receive bank on baseband (wfmrx.hip)
-    def wfm_rx(self, n_channels=1, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16):
-        """A batched fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 object on complex baseband (WfmRx)"""
-        return WfmRx(self, n_channels, rate, num_poly_points, prefilter_taps, window, tau, audio_rate, max_samples_per_call)
+    def wfm_rx(self, n_channels=1, rate=5, num_poly_points=12, prefilter_taps=None, window=1024, tau=50e-6, audio_rate=48000, max_samples_per_call=1 << 16,
+               squelch_block=0, use_every_nth=1, levels=None):
+        """A batched fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 object on complex baseband (WfmRx), behind a squelch when
+        squelch_block > 0"""
+        return WfmRx(self, n_channels, rate, num_poly_points, prefilter_taps, window, tau, audio_rate, max_samples_per_call, squelch_block, use_every_nth, levels)
 
     # ---- the AM and SSB receive chains (amssb.hip)
     def am_bank(self, n_channels=1, block=1024, agc=None, limit_max=None, **kw):

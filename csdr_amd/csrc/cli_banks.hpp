@@ -142,12 +142,15 @@ int run_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block)
 // <audio_rate> <tau> | convert_f_s16`, the reference README's first receive line behind the channelizer):
 //   csdr fastddc_wfm_bank_s16 <decimation> <transition_bw> <window> <frac_rate> <audio_rate> <tau> <ctl | -> <out_0> <shift_rate_0> [<out_1> <shift_rate_1> ...]
 // with the same control lines; "<channel> reset\n" starts that channel's demodulator, held decimator input and de-emphasis over (csdr_amd_wfmrx_reset_channel).
+//   csdr fastddc_wfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ...      (the rest as above)
+// is the NFM command's --squelch on csdr_amd_wfmrx_create_squelched: the same control line, the same report lines.
 int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
 {
     int sqB = 0, sq_d = 1, sq_report = 0; const char *smeter_path = nullptr;
-    if (!wfm && argc > 2 && !strcmp(argv[2], "--squelch")) {
+    if (argc > 2 && !strcmp(argv[2], "--squelch")) {
         if (argc < 7 || sscanf(argv[3], "%d", &sqB) != 1 || sscanf(argv[4], "%d", &sq_d) != 1 || sscanf(argv[5], "%d", &sq_report) != 1)
-            return badsyntax("usage: fastddc_nfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ...");
+            return badsyntax(wfm ? "usage: fastddc_wfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ..."
+                                 : "usage: fastddc_nfm_bank_s16 --squelch <block> <use_every_nth> <report_every_nth> <smeter_out> <decimation> ...");
         if (sqB < 1) return badsyntax("the squelch block must be >= 1");
         if (sq_d <= 0) return badsyntax("use_every_nth <= 0 is invalid");
         if (sq_report <= 0) return badsyntax("report_every_nth <= 0 is invalid");
@@ -178,7 +181,8 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
     if (!bank) die("fastddc_bank create");
     const size_t pitch = ((size_t)csdr_amd_fastddc_bank_max_output(bank.get(), nb_max) + 9) & ~(size_t)1;      // even: the FM bank's one-kernel path reads two samples a lane
     Owned<csdr_amd_fmrx, csdr_amd_fmrx_destroy> fm; Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> wf;
-    if (wfm) wf.reset(csdr_amd_wfmrx_create(c, n_ch, frac_rate, 12, nullptr, 0, 1024, tau, audio_rate, pitch));          // fractional_decimator_ff's defaults (csdr.c:1470-1472)
+    if (wfm && sqB) wf.reset(csdr_amd_wfmrx_create_squelched(c, n_ch, frac_rate, 12, nullptr, 0, 1024, tau, audio_rate, pitch, sqB, sq_d, nullptr));
+    else if (wfm) wf.reset(csdr_amd_wfmrx_create(c, n_ch, frac_rate, 12, nullptr, 0, 1024, tau, audio_rate, pitch));     // fractional_decimator_ff's defaults (csdr.c:1470-1472)
     else if (sqB) fm.reset(csdr_amd_fmrx_create_squelched(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch, sqB, sq_d, nullptr));
     else fm.reset(csdr_amd_fmrx_create(c, n_ch, audio_rate, 1024, 1.0f, 1.0f, pitch));      // limit_ff and fastagc_ff defaults (csdr.c:673-686, 1379-1391)
     if (!fm && !wf) return badsyntax(csdr_amd_last_error());
@@ -216,7 +220,7 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
                 float rate = 0, level = 0;
                 if (sqB && !strcmp(what, "squelch")) {
                     if (sscanf(line, "%d squelch %g", &ch, &level) != 2) continue;
-                    MUST(csdr_amd_fmrx_set_squelch_level(fm.get(), ch, level));
+                    MUST(wfm ? csdr_amd_wfmrx_set_squelch_level(wf.get(), ch, level) : csdr_amd_fmrx_set_squelch_level(fm.get(), ch, level));
                     fprintf(stderr, "csdr %s: channel %d squelch level is %g\n", g_cmd, ch, level);
                 } else if (!strcmp(what, "reset")) {
                     MUST(wfm ? csdr_amd_wfmrx_reset_channel(wf.get(), ch) : csdr_amd_fmrx_reset_channel(fm.get(), ch));
@@ -233,9 +237,10 @@ int run_fm_bank(csdr_amd_ctx *c, int argc, char **argv, size_t block, bool wfm)
         MUST(csdr_amd_fastddc_bank_process(bank.get(), d_in.get(), nb, d_bb.get(), pitch, counts.data()));
         for (int k = 1; k < n_ch; k++)
             if (counts[k] != counts[0]) { fprintf(stderr, "csdr %s: the channelizer wrote %d samples for channel %d and %d for channel 0: the FM bank advances its channels in lockstep\n", g_cmd, counts[k], k, counts[0]); return -1; }
-        const long long sq_k0 = sqB ? csdr_amd_fmrx_squelch_block_index(fm.get()) : 0;
+        const long long sq_k0 = !sqB ? 0 : wfm ? csdr_amd_wfmrx_squelch_block_index(wf.get()) : csdr_amd_fmrx_squelch_block_index(fm.get());
         int sq_nb = 0;
-        const long long na = wfm ? csdr_amd_wfmrx_process(wf.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch)
+        const long long na = wfm && sqB ? csdr_amd_wfmrx_process_squelched(wf.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch, d_power.get(), p_pitch, nullptr, &sq_nb)
+                           : wfm ? csdr_amd_wfmrx_process(wf.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch)
                            : sqB ? csdr_amd_fmrx_process_squelched(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch, d_power.get(), p_pitch, nullptr, &sq_nb)
                                  : csdr_amd_fmrx_process(fm.get(), d_bb.get(), pitch, counts[0], d_out.get(), nullptr, a_pitch);
         MUST(na);

@@ -810,23 +810,55 @@ struct NfmRx : Stage {   // fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff <au
 struct WfmRxStage : Stage {   // fmdemod_quadri_cf | fractional_decimator_ff <rate> | deemphasis_wfm_ff <audio_rate> <tau> | convert_f_s16 as ONE command (extension): the stage behind
                              // one fastddc_inv_cc, one channel of csdr_amd_wfmrx; the decimator's unprocessed samples and position, the previous sample and the de-emphasis
                              // state stay in the object between passes.  What the four commands write at the default buffer size, without their stale blocks at EOF.
-    Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> p; size_t max_n;
+                             // --squelch: squelch_and_smeter_cc in front, inside the object (csdr_amd_wfmrx_create_squelched), as NfmRx's: blocks of the_bufsize
+                             // samples, the level protocol and the "%g\n" reports of that command, so `squelch_and_smeter_cc ... | wfm_rx_cc_s16` as one process
+    Owned<csdr_amd_wfmrx, csdr_amd_wfmrx_destroy> p; size_t max_n; int sqB = 0, every = 0, fd_out = -1; size_t max_blocks = 0; CtxBuf<float> d_power; std::vector<float> h_power;
     WfmRxStage(csdr_amd_ctx *c, float rate, int points, const float *taps, int nt, float tau, int audio_rate, size_t block) : max_n(block + 1024)
     {
         in_elem = 8; out_elem = 2;
         p.reset(csdr_amd_wfmrx_create(c, 1, rate, points, taps, nt, 1024, tau, audio_rate, max_n));
         if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
     }
-    size_t out_capacity(size_t n) override { return n + 4096; }
-    long process(csdr_amd_ctx *, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
+    WfmRxStage(csdr_amd_ctx *c, float rate, int points, const float *taps, int nt, float tau, int audio_rate, size_t block, int squelch_block, int use_every_nth,
+               int report_every_nth, float level, int out_fd)
+        : max_n(block + 1024), sqB(squelch_block), every(report_every_nth), fd_out(out_fd)
+    {
+        in_elem = 8; out_elem = 2;
+        p.reset(csdr_amd_wfmrx_create_squelched(c, 1, rate, points, taps, nt, 1024, tau, audio_rate, max_n, squelch_block, use_every_nth, &level));
+        if (!p) { badsyntax(csdr_amd_last_error()); exit(255); }
+        max_blocks = max_n / (size_t)squelch_block + 1;
+        d_power = ctx_alloc<float>(c, 4 * max_blocks + 64, "malloc"); h_power.resize(max_blocks);
+    }
+    size_t out_capacity(size_t n) override { return n + 4096 + (size_t)sqB; }
+    const char *ctl_format() override { return sqB ? "%g\n" : nullptr; }
+    void retune(csdr_amd_ctx *, float level, float) override { MUST(csdr_amd_wfmrx_set_squelch_level(p.get(), 0, level)); fprintf(stderr, "csdr %s: new squelch level is %g\n", g_cmd, level); }
+    long process(csdr_amd_ctx *c, const void *i, size_t n, void *o, size_t cap, size_t *cons) override
     {
         *cons = n;
         long total = 0;
         for (size_t at = 0; at < n; at += max_n) {                     // (inside `chain` a pass may hand over more than the command's own block)
             const size_t m = std::min(max_n, n - at);
-            const long long na = csdr_amd_wfmrx_process(p.get(), (const csdr_complexf *)i + at, 0, (long long)m, (int16_t *)o + total, nullptr, cap - total);
+            if (!sqB) {
+                const long long na = csdr_amd_wfmrx_process(p.get(), (const csdr_complexf *)i + at, 0, (long long)m, (int16_t *)o + total, nullptr, cap - total);
+                MUST(na);
+                total += (long)na;
+                continue;
+            }
+            const long long k0 = csdr_amd_wfmrx_squelch_block_index(p.get());
+            int nb = 0;
+            const long long na = csdr_amd_wfmrx_process_squelched(p.get(), (const csdr_complexf *)i + at, 0, (long long)m, (int16_t *)o + total, nullptr, cap - total, d_power.get(),
+                                                                  max_blocks, nullptr, &nb);
             MUST(na);
             total += (long)na;
+            bool any = false;
+            for (int k = 0; k < nb && !any; k++) any = csdr_amd_squelch_report_due(every, k0 + k) != 0;
+            if (any && fd_out >= 0) {
+                MUST(csdr_amd_d2h(c, h_power.data(), d_power.get(), 4 * (size_t)nb));
+                for (int k = 0; k < nb; k++) if (csdr_amd_squelch_report_due(every, k0 + k)) {
+                    char line[101]; const int len = snprintf(line, 100, "%g\n", h_power[k]);
+                    (void)!write(fd_out, line, (size_t)len);             // non-blocking: a full fifo drops the line (csdr.c:2211-2228)
+                }
+            }
         }
         return total;
     }
@@ -1723,6 +1755,11 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
         return new NfmRx(c, rate, block, g_dynamic ? the_bufsize : unitround(g_fixed), decimation, report_every_nth, level, fd2);   // the squelch command's own block
     }
     if (cmd == "wfm_rx_cc_s16") {                                       // <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]]
+                                                                        // [--squelch --fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>] behind any prefix of them
+        int sq_at = 0;                                                  // argv index of --squelch: it ends the optional arguments
+        for (int k = 3; k < argc && !sq_at; k++) if (!strcmp(argv[k], "--squelch")) sq_at = k;
+        const int all_argc = argc;
+        if (sq_at) argc = sq_at;
         if (argc <= 2) { badsyntax("need required parameters (rate)   usage: wfm_rx_cc_s16 <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]]"); return nullptr; }
         float rate = 0, tau = 50e-6f, tbw = 0.03f; int audio_rate = 48000, points = 12;
         if (sscanf(argv[2], "%g", &rate) != 1) { badsyntax("the rate must be a number"); return nullptr; }
@@ -1736,7 +1773,26 @@ Stage *make_stage(csdr_amd_ctx *c, int argc, char **argv, size_t block, Control 
             const int nt = csdr_amd_firdes_filter_len(tbw); taps.resize(nt);                        // csdr.c:1506-1509
             csdr_amd_firdes_lowpass_f(taps.data(), nt, 0.5f / (rate - tbw), window_arg(argc, argv, 8, g_cmd));
         }
-        return new WfmRxStage(c, rate, points, taps.empty() ? nullptr : taps.data(), (int)taps.size(), tau, audio_rate, block);
+        if (!sq_at) return new WfmRxStage(c, rate, points, taps.empty() ? nullptr : taps.data(), (int)taps.size(), tau, audio_rate, block);
+        // squelch_and_smeter_cc's arguments and checks in its order (csdr.c:2192-2218), behind --squelch, as nfm_rx_cc_s16's
+        char **sv = argv + (sq_at - 1); const int sc = all_argc - (sq_at - 1);       // sv[2] is what follows --squelch
+        float level = 0, unused;
+        if (!ctl || !ctl->open_from(sc, sv)) { badsyntax("need required parameter (--fifo <fifo>)"); return nullptr; }
+        ctl->wait_first("%g\n", &level, &unused);
+        fprintf(stderr, "csdr %s: initial squelch level is %g\n", g_cmd, level);
+        if (sc <= 5 || strcmp(sv[4], "--outfifo")) { badsyntax("need required parameter (--outfifo <fifo>)"); return nullptr; }
+        const int fd2 = open(sv[5], O_WRONLY);
+        if (fd2 == -1) { badsyntax("error while opening --outfifo"); return nullptr; }
+        fcntl(fd2, F_SETFL, fcntl(fd2, F_GETFL, 0) | O_NONBLOCK);
+        if (sc <= 6) { badsyntax("need required parameter (use_every_nth)"); return nullptr; }
+        int decimation = 0, report_every_nth = 0;
+        sscanf(sv[6], "%d", &decimation);
+        if (decimation <= 0) { badsyntax("use_every_nth <= 0 is invalid"); return nullptr; }
+        if (sc <= 7) { badsyntax("need required parameter (report_every_nth)"); return nullptr; }
+        sscanf(sv[7], "%d", &report_every_nth);
+        if (report_every_nth <= 0) { badsyntax("report_every_nth <= 0 is invalid"); return nullptr; }
+        return new WfmRxStage(c, rate, points, taps.empty() ? nullptr : taps.data(), (int)taps.size(), tau, audio_rate, block, g_dynamic ? the_bufsize : unitround(g_fixed),
+                              decimation, report_every_nth, level, fd2);               // the squelch command's own block
     }
     // the fused commands: `--fifo <path>` / `--fd <n>` stand where the shift rate stands, as in shift_addition_cc (csdr.c:881-893); the first rate is waited for
     if (cmd == "ddc_u8_cc" || cmd == "nfm_chain_u8_s16" || cmd == "wfm_chain_u8_s16") {

@@ -216,7 +216,7 @@ int main(int argc, char **argv)
                         "bfsk_demod_cf serial_line_decoder_f_u8 rtty_baudot2ascii_u8_u8 rtty_line_decoder_u8_u8 binary_slicer_f_u8 firdes_peak_c peaks_fir_cc (<taps_length> <peak_rate> [<peak_rate> ...]) "
                         "squelch_and_smeter_cc (--fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>) bpsk_costas_loop_cc (<loop_bandwidth> <damping_factor> [--dd | --decision_directed] [--output_error | --output_dphase | --output_nco | --output_combined <error_file> <dphase_file> <nco_file>]) pll_cc (1 [alpha] | 2 [bandwidth [damping_factor [ko [kd]]]]) amdemod_cf amdemod_estimator_cf fmdemod_atan_cf dcblock_ff fastdcblock_ff agc_ff gain_ff realpart_cf logpower_cf dsb_fc ([q_value]) fmmod_fc add_dcoffset_cc fixed_amplitude_cc (<new_amplitude>) convert_f_samplerf (<wait_for_this_sample>) fft_cc fft_fc (<fft_out_size> <out_of_every_n_samples> [window]) fft_one_side_ff logaveragepower_cf fft_exchange_sides_ff encode_ima_adpcm_i16_u8 decode_ima_adpcm_u8_i16 compress_fft_adpcm_f_u8 "
                         "awgn_cc (<snr_db> [--awgnfile <file>] [--snrshow] [--seed <seed>]) uniform_noise_f ([--seed <seed>]) gaussian_noise_c ([--seed <seed>]) normalized_timing_variance_u32_f (<samples_per_symbol> <initial_sample_offset>) "
-                        "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., fastddc_nfm_bank_s16 [--squelch <block> <use_every_nth> <report_every_nth> <smeter_out>] <decimation> <tbw> <window> <audio_rate> <ctl|-> <out_0> <rate_0> ... (the bank with an NFM demodulator per channel: s16 audio; --squelch: squelch_and_smeter_cc in front of each, control line \"<channel> squelch <level>\", report lines \"<channel> <power>\"), nfm_rx_cc_s16 [audio_rate] [--squelch --fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>] (fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 on one complexf stream; --squelch: squelch_and_smeter_cc in front, its arguments), fastddc_wfm_bank_s16 <decimation> <tbw> <window> <frac_rate> <audio_rate> <tau> <ctl|-> <out_0> <rate_0> ... (the bank with a WFM demodulator per channel: s16 audio), wfm_rx_cc_s16 <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]] (fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 on one complexf stream), shift_bank_cc <addition|math|table[:size]> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 / am_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], ssb_bank_u8_s16 [--lsb | --passbands lo:hi[,lo:hi,...]] <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
+                        "setbuf clone through | extensions: wfm_chain_u8_s16 <shift_rate>, nfm_chain_u8_s16 <shift_rate> [decimation [transition_bw]], ddc_u8_cc <shift_rate> <decimation> [transition_bw [window]], fastddc_bank_cc <decimation> <tbw> <window> <ctl|-> <out_0> <rate_0> ..., fastddc_nfm_bank_s16 [--squelch <block> <use_every_nth> <report_every_nth> <smeter_out>] <decimation> <tbw> <window> <audio_rate> <ctl|-> <out_0> <rate_0> ... (the bank with an NFM demodulator per channel: s16 audio; --squelch: squelch_and_smeter_cc in front of each, control line \"<channel> squelch <level>\", report lines \"<channel> <power>\"), nfm_rx_cc_s16 [audio_rate] [--squelch --fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>] (fmdemod_quadri_cf | limit_ff | deemphasis_nfm_ff | fastagc_ff | convert_f_s16 on one complexf stream; --squelch: squelch_and_smeter_cc in front, its arguments), fastddc_wfm_bank_s16 [--squelch <block> <use_every_nth> <report_every_nth> <smeter_out>] <decimation> <tbw> <window> <frac_rate> <audio_rate> <tau> <ctl|-> <out_0> <rate_0> ... (the bank with a WFM demodulator per channel: s16 audio), wfm_rx_cc_s16 <rate> [audio_rate [tau [num_poly_points [--prefilter [transition_bw [window]]]]]] [--squelch --fifo <ctl> --outfifo <path> <use_every_nth> <report_every_nth>] (fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16 on one complexf stream), shift_bank_cc <addition|math|table[:size]> <ctl|-> <out_0> <rate_0> ..., wfm_bank_u8_s16 / nfm_bank_u8_s16 / am_bank_u8_s16 <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], ssb_bank_u8_s16 [--lsb | --passbands lo:hi[,lo:hi,...]] <shift_rate> <in_0> <out_0> [<in_k> <out_k> ...], "
                         "waterfall_u8 / waterfall_cc <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm>, "
                         "waterfall_ff / waterfall_s16 <fft_out_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm> (real input, one-sided rows), "
                         "waterfall_bank_u8 <fft_size> <every_n> <window> <add_db> <avgnumber> <db|adpcm> <in_0> <out_0> [<in_k> <out_k> ...], chain \"<cmd> <args> | <cmd> <args> ...\"\n");

@@ -1378,6 +1378,39 @@ int  csdr_amd_wfmrx_reset_channel(csdr_amd_wfmrx *o, int channel);
 int  csdr_amd_wfmrx_force_generic(csdr_amd_wfmrx *o, int on);
 const char *csdr_amd_wfmrx_kernel_name(const csdr_amd_wfmrx *o);
 void csdr_amd_wfmrx_destroy(csdr_amd_wfmrx *o);
+/* The same bank with squelch_and_smeter_cc (csdr.c:2192-2243) in front of every channel's demodulator:
+ *   squelch_and_smeter_cc | fmdemod_quadri_cf | fractional_decimator_ff | deemphasis_wfm_ff | convert_f_s16
+ * The interface is csdr_amd_fmrx's squelched one, name for name, and so are the rules.  create_squelched: squelch_block B in 1 .. 65536, use_every_nth >= 1,
+ * levels: n_channels host floats or NULL (all 0: always open); else NULL with a message "wfmrx: ...", as for everything create refuses.
+ * The squelch cuts a channel's input into blocks of B samples counted from the reset.  Only whole blocks go on to the demodulator, a closed block as B samples
+ * (0, 0); what lies behind the last whole block, at most B - 1 complexf per channel, waits in the object.  With `held` waiting, a call of n_in samples advances
+ * the chain by m = (held + n_in) / B * B gated samples and then holds held + n_in - m (csdr_amd_wfmrx_squelch_plan, a host function); csdr_amd_wfmrx_plan
+ * applies to m as it does to n_in without a squelch, and max_output counts B - 1 samples more.  Behind the gate the model above applies to the gated stream: the
+ * demodulator's previous sample is the last gated one, (0, 0) behind a closed block; a zero sample demodulates to 0; the de-emphasis runs on through closed
+ * stretches (it decays, it is not reset).
+ * The power of a block is csdr_amd_squelch's (the same bits), its gate level == 0 || power >= level, its level the one in force when its first sample
+ * arrived: set_squelch_level (channel -1: all) reaches the block under way only when nothing of it is held yet.  squelch_held and squelch_block_index (the
+ * blocks completed since the reset) are the bank's: the channels advance in lockstep.
+ * process_squelched: as process; power (float) and open_flags (u8), both device, [n_channels][power_pitch], either may be NULL, get one entry per block the
+ * call completed, *n_blocks (may be NULL) their number.  -3 and no change when power_pitch is below that number while one of the two is given, when out_pitch
+ * is too small or n_in > max_samples_per_call.  process on a squelched object is this call without the two rows.  The entry points of this paragraph return
+ * -3 on an object created without a squelch.
+ * reset starts the block count and the held samples over and keeps the levels; reset_channel also zeroes the channel's held squelch samples, the block phase
+ * is the bank's and stays.
+ * kernel_name: "k_wfmrx_front_sq" (the shapes of "k_wfmrx_front", any n_in and any B: k_fmrx_power reads the samples once for the block powers, the front
+ * kernel then gates them as it loads them and does not fetch closed blocks; the gated rows never exist in memory) or "k_fracdec" (an internal csdr_amd_squelch
+ * writes gated rows, the generic path runs over them; every shape; force_generic(1)).  Both give the bits of csdr_amd_squelch followed by csdr_amd_wfmrx, and a
+ * stream may change between them. */
+csdr_amd_wfmrx *csdr_amd_wfmrx_create_squelched(csdr_amd_ctx *ctx, int n_channels, float rate, int num_poly_points, const float *host_prefilter_taps, int taps_length,
+                                                int window, float tau, int audio_rate, size_t max_samples_per_call, int squelch_block, int use_every_nth,
+                                                const float *levels);
+long long csdr_amd_wfmrx_process_squelched(csdr_amd_wfmrx *o, const csdr_complexf *in, size_t in_pitch, long long n_in, int16_t *audio_s16, float *audio_f, size_t out_pitch,
+                                           float *power, size_t power_pitch, uint8_t *open_flags, int *n_blocks);
+int  csdr_amd_wfmrx_squelch_plan(int held, long long n_in, int block, long long *m, int *new_held);
+int  csdr_amd_wfmrx_set_squelch_level(csdr_amd_wfmrx *o, int channel, float level);
+int  csdr_amd_wfmrx_get_squelch_level(const csdr_amd_wfmrx *o, int channel, float *level);
+int  csdr_amd_wfmrx_squelch_held(const csdr_amd_wfmrx *o);
+long long csdr_amd_wfmrx_squelch_block_index(const csdr_amd_wfmrx *o);
 
 /* ------------------------------------------------------------------ the AM and SSB receive chains (amssb.hip)
  * README.md:95   ... | amdemod_cf | fastdcblock_ff | agc_ff | limit_ff | convert_f_s16
